@@ -16,9 +16,12 @@ region.  Workload: BASELINE.json configs[1] (X 65536x128x128 f32, Y 65536x16, R=
 the same X is row-sharded over the N ranks, as the metric is quoted ("iters/sec on X 65536x128x128 at
 1/2/4/8 GPU"); per iteration the ranks all-reduce Z (J*K doubles) and Y^T t (M doubles).
 
-Timing (round 3): W warm-up steps, then ``--repeats`` (default 5) windows of EXACTLY K steps each, every window bracketed by a
-barrier + ``torch.cuda.synchronize()`` on both sides and reduced with MAX over ranks; ``value`` = K / the MEDIAN window
-(``value_min`` / ``value_max`` = the slowest / fastest window).  At N = 1 with the default workload the line also carries
+Timing: W warm-up steps, then EXACTLY K timed steps in all, split into ``--repeats`` (default 5; at most K) windows whose
+sizes differ by at most one, every window bracketed by a barrier + ``torch.cuda.synchronize()`` on both sides and reduced
+with MAX over ranks; ``ms_per_step`` = the K windows' total time / K, ``value`` = K / that total (``value_min`` /
+``value_max`` = the slowest / fastest window's rate).  The eager pass that feeds the per-kernel figures runs its own K steps
+the same way before the headline (graph-replay) pass.  ``--dump-outputs DIR`` writes what the last timed step computed
+(``dump_outputs``).  At N = 1 with the default workload the line also carries
 ``north_star``: BASELINE configs[4] (X 262144x256x256 f32 = 68.7 GB, Y 262144x32) formed on the device after the cfg-2 legs,
 direct iterations under graph replay and the component's deflation sweeps (skipped when less than 150 GB of HBM are free).
 
@@ -64,7 +67,7 @@ def parse(argv=None):
     ap.add_argument("--no-ceilings", action="store_true", help="skip the measured streaming ceilings")
     ap.add_argument("--cpu-rows", type=int, default=2048)
     ap.add_argument("--graphs", type=int, default=1, help="replay the iteration's launch sequence as a HIP graph (0 = eager)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows of exactly --steps iterations each; value = median")
+    ap.add_argument("--repeats", type=int, default=5, help="number of windows the --steps timed iterations are split into")
     ap.add_argument("--no-north-star", action="store_true", help="skip the 262144x256x256 leg (BASELINE.json north_star)")
     ap.add_argument("--north-star-steps", type=int, default=10)
     ap.add_argument("--rank1-chain", type=int, default=1,
@@ -72,7 +75,30 @@ def parse(argv=None):
     ap.add_argument("--capture-collectives", type=int, default=0,
                     help="N > 1: capture the two per-iteration all-reduces inside the iteration's HIP graph (EngineOptions.capture_collectives; "
                          "falls back to the segment-wise form when the capture fails)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB)")
     return ap.parse_args(argv)
+
+
+def window_sizes(steps, repeats):
+    """`steps` timed iterations split into min(repeats, steps) windows (at least one) whose sizes differ by at most one."""
+    n = max(1, min(repeats, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write every array as <path>/<name>.npy in float64.  An array larger than its share of `limit` is replaced by a fixed
+    sample of its entries, in index order (the same size and seed always give the same indices)."""
+    os.makedirs(path, exist_ok=True)
+    cap = limit // (8 * len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---- launcher (no GPU call may happen before or inside these two functions) -----------------------
@@ -332,6 +358,8 @@ def measure_ceilings(be, timer, scratch, src, row_bytes):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit(f"--steps must be >= 1, got {args.steps}")
     mode, world = resolve_world(args, os.environ)
     if mode == "launch":
         # nothing above touched the GPU: starting the ranks as children is allowed
@@ -433,21 +461,21 @@ def main():
         return float(tmax.item())
 
     # (1) eager passes with HIP events bracketing every kernel launch (roofline figures come from here;
-    #     events cannot bracket kernels inside a graph replay).  `--repeats` windows of EXACTLY `--steps` iterations
-    #     each; every window contributes its own per-kernel mean, the report carries median / min / max over windows
-    reps = max(1, args.repeats)
+    #     events cannot bracket kernels inside a graph replay).  EXACTLY `--steps` iterations split into `--repeats`
+    #     windows; every window contributes its own per-kernel mean, the report carries median / min / max over windows
+    sizes = window_sizes(args.steps, args.repeats)
     for _ in range(args.warmup):
         run.iterate(state["it"])
         state["it"] += 1
     eager_windows, kernel_windows = [], {n: [] for n in timer.records}
-    for _ in range(reps):
+    for n_steps in sizes:
         for n in timer.records:
             timer.records[n] = []
-        eager_windows.append(timed(args.steps, events=True))
+        eager_windows.append(timed(n_steps, events=True))
         for n in timer.records:
             if timer.records[n]:
                 kernel_windows[n].append(timer.mean_ms(n))
-    eager_elapsed = float(np.median(eager_windows))
+    eager_elapsed = sum(eager_windows)
     elapsed, windows = eager_elapsed, eager_windows
     # (2) the same windows with the launch sequence replayed as a HIP graph (the headline when
     #     capture works: identical kernels, ~1 host call per iteration instead of ~20 launches)
@@ -458,8 +486,8 @@ def main():
                 run.iterate(state["it"])
                 state["it"] += 1
             if run.use_graphs:
-                windows = [timed(args.steps, events=False) for _ in range(reps)]
-                elapsed = float(np.median(windows))
+                windows = [timed(n_steps, events=False) for n_steps in sizes]
+                elapsed = sum(windows)
         except Exception as e:                     # keep the eager figure rather than lose the run
             run.use_graphs = False
             run._graph_error = repr(e)
@@ -467,6 +495,17 @@ def main():
     graphs_used, graph_error = run.use_graphs, run._graph_error
     collectives_in_graph = run._collectives_captured is True
     iter_notes = list(run.notes)
+    if args.dump_outputs:
+        # what the last timed step computed, as a caller of FitRun.iterate holds it: the scores t (row-sharded, so gathered
+        # over the ranks), the loading vectors of modes 1 and 2, and the response weights q
+        t = run.t.cpu().numpy()
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, t)
+            t = np.concatenate(parts)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"t": t, "w_j": run.wA[0].cpu().numpy(), "w_k": run.wB[0].cpu().numpy(),
+                                             "q": run.q.cpu().numpy()})
     run.finish_component(0)                        # exercises the deflation sweep once (timed below by events)
 
     es = X.element_size()
@@ -533,8 +572,8 @@ def main():
         comm_info = {"backend": backend, "ranks": dist.get_world_size(), "forced_single_rank": force_dist,
                      "in_graph": collectives_in_graph, "notes": iter_notes,
                      "allreduce_ms_by_bytes": {str(nb): sum(v) / len(v) for nb, v in sorted(by_size.items())},
-                     "allreduce_ms_per_step": sum(sum(v) for v in by_size.values()) / max(args.steps * reps, 1),
-                     "collectives_per_step": len(comm.pairs) / max(args.steps * reps, 1)}
+                     "allreduce_ms_per_step": sum(sum(v) for v in by_size.values()) / args.steps,
+                     "collectives_per_step": len(comm.pairs) / args.steps}
     # N > 1: what every rank spent where (a scaling record must explain itself): the two sweeps, the rank-1 chain, the Y
     # update and the all-reduces of the eager windows (HIP events), next to the rank's own graph-replay step
     per_rank = None
@@ -626,11 +665,13 @@ def main():
     cfg_name = {(65536, 128, 128, 16): "BASELINE configs[1]", (262144, 256, 256, 32): "BASELINE configs[4]"}.get(
         (I_total, J, K, M), "custom shape")
     if rank == 0:
+        rates = [n / t for n, t in zip(sizes, windows)]
+        eager_ms = [t / n * 1e3 for n, t in zip(sizes, eager_windows)]
         out = {
             "metric": "nipals_iters_per_sec", "value": args.steps / elapsed, "unit": "it/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "repeats": len(windows), "value_min": args.steps / max(windows), "value_max": args.steps / min(windows),
-            "value_is": f"median of {len(windows)} timed windows of exactly {args.steps} iterations each",
+            "repeats": len(windows), "value_min": min(rates), "value_max": max(rates),
+            "value_is": f"{args.steps} timed iterations (in {len(windows)} windows) / their total time",
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{cfg_name}: tPLS direct NIPALS iteration, X {I_total}x{J}x{K} f32 "
@@ -639,7 +680,7 @@ def main():
                        "rccl_ranks": dist.get_world_size() if backend == "nccl" else 0,
                        "x_reads_per_step": 2, "hip_graphs": bool(graphs_used), "graph_error": graph_error,
                        "eager_ms_per_step": eager_elapsed / args.steps * 1e3,
-                       "eager_ms_per_step_min_max": [min(eager_windows) / args.steps * 1e3, max(eager_windows) / args.steps * 1e3]},
+                       "eager_ms_per_step_min_max": [min(eager_ms), max(eager_ms)]},
             "roofline": roofline, "cpu_baseline": cpu, "kernels": kern, "collectives": comm_info, "per_rank": per_rank,
             "mfma": mfma, "fit": fit_info, "north_star": north,
         }

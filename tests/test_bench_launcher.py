@@ -54,3 +54,29 @@ def test_launcher_forwards_a_failing_rank(tmp_path):
                        env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert p.returncode != 0
     assert '"metric"' not in p.stdout
+
+
+@pytest.mark.parametrize("steps,repeats", [(20, 5), (7, 5), (3, 5), (1, 1), (50, 1), (11, 4)])
+def test_window_sizes_add_up_to_exactly_the_timed_steps(steps, repeats):
+    sizes = bench.window_sizes(steps, repeats)
+    assert sum(sizes) == steps and len(sizes) == min(steps, repeats) and max(sizes) - min(sizes) <= 1
+
+
+def test_steps_below_one_are_refused_before_any_gpu_call():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps" in p.stderr and p.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_float64_within_the_limit_and_samples_the_same_entries(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    arrays = {"t": rng.normal(size=5000), "w": rng.normal(size=12).astype(np.float32)}
+    limit = 2 * 8 * 1000                                     # 1000 float64 entries per array
+    bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    t, w = np.load(tmp_path / "a" / "t.npy"), np.load(tmp_path / "a" / "w.npy")
+    assert t.dtype == np.float64 and w.dtype == np.float64
+    assert t.size == 1000 and np.isin(t, arrays["t"]).all()
+    np.testing.assert_array_equal(w, arrays["w"].astype(np.float64))
+    np.testing.assert_array_equal(t, np.load(tmp_path / "b" / "t.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit + 2 * 128   # + the .npy headers

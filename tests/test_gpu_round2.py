@@ -53,6 +53,26 @@ def test_bench_launches_two_ranks_by_itself():
     assert len(out["fit"]["n_iter"]) == 10 and out["fit"]["xcov"]["n_iter"] == out["fit"]["n_iter"]
 
 
+def test_bench_times_exactly_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """--steps K is the number of timed steps (split over --repeats windows), and --dump-outputs writes the last timed step's
+    scores and weights: t = Xc (w_j kron w_k) and q = Yc^T t / |Yc^T t| on the same seeded inputs, regenerated here."""
+    import bench
+    out = _bench(["--gpus", "1"] + SMALL + ["--no-fit", "--dump-outputs", str(tmp_path)], {})
+    assert out["steps"] == 4 and out["repeats"] == 4 and out["ms_per_step"] > 0
+    d = {n: np.load(tmp_path / f"{n}.npy") for n in ("t", "w_j", "w_k", "q")}
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in d.values())
+    assert d["t"].shape == (2048,) and d["w_j"].shape == (128,) and d["w_k"].shape == (128,) and d["q"].shape == (16,)
+    X, Y = bench.synth_shard(2048, 128, 128, 16, 10, 0.1, 0, 2048, torch.device("cuda", 0))
+    Xc = X.double().view(2048, -1)
+    Xc = (Xc - Xc.mean(0)).cpu().numpy()
+    Yc = Y.double().cpu().numpy()
+    Yc = Yc - Yc.mean(0)
+    t = Xc @ np.kron(d["w_j"], d["w_k"])
+    np.testing.assert_allclose(d["t"], t, rtol=0, atol=1e-5 * np.abs(t).max())
+    q = Yc.T @ d["t"]
+    np.testing.assert_allclose(d["q"], q / np.linalg.norm(q), rtol=0, atol=1e-9)
+
+
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_matrix_block_wider_than_the_lds(dtype):
     """An order-2 X has A = 1, B = P: with P > 12286 the loadings do not fit the 96 KB LDS staging area and the
