@@ -20,6 +20,13 @@ class XcovBlock(ctypes.Structure):
                 ("n_squarings", c_int), ("Z", _P), ("wA", _P), ("wB", _P), ("info", _P)]
 
 
+class KfoldState(ctypes.Structure):
+    """cmtfpls_kfold_state (include/cmtfpls.h): the device buffers of a K-fold run (cmtfpls_kfold_inner_f64 / _epilogue_f64)."""
+    _fields_ = [("I", c_int), ("A", c_int), ("B", c_int), ("M", c_int), ("K", c_int), ("R", c_int)] + [
+        (name, _P) for name in ("fold_of", "S", "mean", "Yk", "Gy", "WA", "WB", "Q", "Wa", "Wb", "T", "Gt", "coef", "Rm", "tm",
+                                "Tout", "vec", "n_iter", "status", "part")]
+
+
 # name -> (restype, argtypes); mirrors include/cmtfpls.h one to one
 SIGNATURES = {
     "cmtfpls_xcov_iterate_blocks_f64": (c_int, [ctypes.POINTER(XcovBlock), c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
@@ -117,6 +124,14 @@ SIGNATURES = {
     "cmtfpls_loo_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_tpls_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "cmtfpls_kfold_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "cmtfpls_kfold_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_xcov_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_row_tiles": (c_int, [c_int64]),
+    "cmtfpls_kfold_part_stride": (c_int, []),
+    "cmtfpls_kfold_inner_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cmtfpls_kfold_inner_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_double, c_int, _P, c_size_t, _P]),
+    "cmtfpls_kfold_epilogue_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, _P, _P]),
     "cmtfpls_loo_xcov_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_fit_small_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cmtfpls_fit_small_f64": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int] + [_P] * 11 + [_P, c_size_t, _P]),

@@ -6,6 +6,7 @@ path: constructing the backend without a GPU or without the library raises.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -629,6 +630,49 @@ class HipBackend:
             if not declined:
                 return Ypred, n_iter, form
         return None
+
+    # -- K-fold cross-validation (validate.kfold_predictions, kfold.py): every fold from the same reads of X ----------------
+    def kfold_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,
+                   ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:
+        """Every fold's training cross-covariance S[k] (K x M x P) and training means (K x P) from ONE read of the uncentred X2
+        (cmtfpls_kfold_xcov_*); returns the column sums / sums of squares of all rows (2 P), or None when the shape is outside
+        the device form.  The partial-sum workspace is local to the call."""
+        I, P = X2.shape
+        M = Y.shape[1]
+        assert Y.dtype == torch.float64 and Y.is_contiguous() and order.dtype == torch.int32 and fold_off.dtype == torch.int32 and P == A * B
+        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K)), 256), dtype=torch.uint8, device=self.device)
+        stats = self.empty(2 * P)
+        rc = self._fn("kfold_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), M, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S), _ptr(mean),
+                                        _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_xcov")
+        return stats
+
+    def kfold_inner(self, state, a: int, tol: float, max_iter: int, ws: torch.Tensor) -> Optional[bool]:
+        """Component a's inner loop for every fold, a workgroup per fold (cmtfpls_kfold_inner_f64); `state` is a
+        _lib.KfoldState, `ws` at least kfold_inner_workspace_bytes.  None when the shape is outside the device form."""
+        rc = self.lib.cmtfpls_kfold_inner_f64(ctypes.byref(state), int(a), float(tol), int(max_iter), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner")
+        return True
+
+    def kfold_inner_workspace_bytes(self, A: int, B: int, K: int) -> int:
+        return int(self.lib.cmtfpls_kfold_inner_workspace_bytes(A, B, K))
+
+    def kfold_row_tiles(self, I: int) -> Tuple[int, int]:
+        """(row tiles of the K-fold epilogue's grid, doubles of partial sums per tile)."""
+        return int(self.lib.cmtfpls_kfold_row_tiles(I)), int(self.lib.cmtfpls_kfold_part_stride())
+
+    def kfold_epilogue(self, state, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
+        """Stage 0: every fold's Gy; 1: component a's epilogue from the MTTKRP scores (I x K); 2: the down-date of S from the
+        contraction (K x P) -- cmtfpls_kfold_epilogue_f64.  None when the shape is outside the device form."""
+        rc = self.lib.cmtfpls_kfold_epilogue_f64(ctypes.byref(state), int(stage), int(a), _ptr(src), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_epilogue")
+        return True
 
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):

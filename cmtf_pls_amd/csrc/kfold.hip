@@ -1,0 +1,508 @@
+// K-fold cross-validation of a tPLS model with every fold served by the same reads of X (validate.kfold_predictions).
+//
+// The folds of a K-fold split differ only in which rows are training rows, their means and their loadings; X_0 (the caller's
+// uncentred tensor) is the same for all of them.  The no-write cross-covariance fit (fitrun_xcov.FitRun._finish_xcov_nowrite)
+// needs X_0 only linearly in w (scores: X_0 w - (mu^T w) 1 - T g) and in t (down-date of S: X_0^T t - (1^T t) mu), so one pass
+// over X with K columns serves all K folds:
+//   kfold_xcov      S_f = X[rows_f]^T Y[rows_f] and the column sums / sums of squares per fold, ONE read of X; the training
+//                   cross-covariance of fold k is the all-minus-own sum_f S_f - S_k, centred by a rank-one correction
+//   kfold_inner     the whole inner loop of one component for every fold (a 1024-thread workgroup per fold, fold_loop.hpp)
+//   (score pass)    X_0 [w_1 .. w_K] through cmtfpls_mttkrp_*                                       ONE read of X
+//   kfold_epilogue  stage 1: the scores of every row under every fold (held-out rows: the prediction's projection), the row sums
+//                   of the inner regression, the Y-side deflation and G_y on a grid of row tiles x folds, the R x R solve per
+//                   fold; stage 2: the down-date of S_k from r = X_c^T t
+//   (contraction)   X_0^T [t_1 * train_1 .. t_K * train_K] through cmtfpls_xcov_*                    ONE read of X
+// 2R reads of X for all K folds; nothing is written to X and no copy of it is made.  Arithmetic: float64 (an f32 X is widened
+// on load).  No workgroup waits on another.
+#include "fold_loop.hpp"
+
+namespace cmtfpls {
+
+constexpr int kKfMaxK = 32, kKfMaxM = 64, kKfMaxR = 64, kKfMaxN = 256;
+constexpr int kKfCols = 256;          // columns per workgroup of the column-owner kernels (one per thread)
+
+// ---- kfold_xcov ------------------------------------------------------------------------------------------------------------
+// Row chunks per fold so that the partial-sum grid has >= ~2048 workgroups (a thread per column, rows sequential: the rows of a
+// workgroup are all of one fold, in the host's fold-sorted order); <= 64.
+static int kf_chunks(int64_t I, int64_t P, int K) {
+  const int64_t cb = (P + kKfCols - 1) / kKfCols;
+  int64_t ch = (2048 + cb * K - 1) / (cb * K);
+  const int64_t per_fold = I / K;
+  if (ch > per_fold / 64) ch = per_fold / 64;
+  if (ch > 64) ch = 64;
+  return ch < 1 ? 1 : (int)ch;
+}
+
+template <typename T, int MT>
+__global__ __launch_bounds__(kKfCols) void kfold_partials_kernel(const T* __restrict__ X, int64_t P, const double* __restrict__ Y, int M,
+                                                                 const int* __restrict__ order, const int* __restrict__ off, int nch,
+                                                                 double* __restrict__ part) {
+  const int64_t c = (int64_t)blockIdx.x * kKfCols + threadIdx.x;
+  const int k = blockIdx.y, ch = blockIdx.z;
+  if (c >= P) return;
+  const int lo0 = off[k], n = off[k + 1] - lo0, len = (n + nch - 1) / nch;
+  const int lo = lo0 + min(n, ch * len), hi = lo0 + min(n, (ch + 1) * len);
+  double acc[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) acc[j] = 0.0;
+  double s1 = 0.0, s2 = 0.0;
+  int r = lo;
+  for (; r + 4 <= hi; r += 4) {                                   // four rows in flight
+    int i4[4];
+    double x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) i4[u] = order[r + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = (double)X[(int64_t)i4[u] * P + c];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double* y = Y + (int64_t)i4[u] * M;
+#pragma unroll
+      for (int j = 0; j < MT; ++j)
+        if (j < M) acc[j] = fma(y[j], x[u], acc[j]);
+      s1 += x[u];
+      s2 = fma(x[u], x[u], s2);
+    }
+  }
+  for (; r < hi; ++r) {
+    const int i = order[r];
+    const double xv = (double)X[(int64_t)i * P + c];
+    const double* y = Y + (int64_t)i * M;
+#pragma unroll
+    for (int j = 0; j < MT; ++j)
+      if (j < M) acc[j] = fma(y[j], xv, acc[j]);
+    s1 += xv;
+    s2 = fma(xv, xv, s2);
+  }
+  double* o = part + (int64_t)(k * nch + ch) * (M + 2) * P + c;
+#pragma unroll
+  for (int j = 0; j < MT; ++j)
+    if (j < M) o[(int64_t)j * P] = acc[j];
+  o[(int64_t)M * P] = s1;
+  o[(int64_t)(M + 1) * P] = s2;
+}
+
+// all-minus-own: S_k = sum_f S_f - S_own(k) - n_k mu_k ydev_k^T (the centring of the training rows as a rank-one correction),
+// mu_k = (colsum - colsum_own(k)) / n_k (n_k: training rows of fold k)
+__global__ __launch_bounds__(kKfCols) void kfold_finish_kernel(int64_t P, int M, int K, int nch, int I, const int* __restrict__ off,
+                                                               const double* __restrict__ part, const double* __restrict__ ydev,
+                                                               double* __restrict__ S, double* __restrict__ mean, double* __restrict__ stats) {
+  const int64_t c = (int64_t)blockIdx.x * kKfCols + threadIdx.x;
+  if (c >= P) return;
+  double own[kKfMaxK], mu[kKfMaxK];
+  auto fold_sum = [&](int k, int j) {
+    double s = 0.0;
+    for (int ch = 0; ch < nch; ++ch) s += part[((int64_t)(k * nch + ch) * (M + 2) + j) * P + c];
+    return s;
+  };
+  double tot = 0.0, totq = 0.0;
+  for (int k = 0; k < K; ++k) { own[k] = fold_sum(k, M); tot += own[k]; totq += fold_sum(k, M + 1); }
+  stats[c] = tot;
+  stats[P + c] = totq;
+  for (int k = 0; k < K; ++k) {
+    const double ntr = (double)(I - (off[k + 1] - off[k]));
+    mu[k] = (tot - own[k]) / ntr;
+    mean[(int64_t)k * P + c] = mu[k];
+  }
+  for (int m = 0; m < M; ++m) {
+    double t = 0.0;
+    for (int k = 0; k < K; ++k) { own[k] = fold_sum(k, m); t += own[k]; }
+    for (int k = 0; k < K; ++k) {
+      const double ntr = (double)(I - (off[k + 1] - off[k]));
+      S[((int64_t)k * M + m) * P + c] = (t - own[k]) - ntr * mu[k] * ydev[k * M + m];
+    }
+  }
+}
+
+// ---- row tiles of the epilogue ------------------------------------------------------------------------------------------------
+// The row work of a component (scores, the training Gram row, T^T u, Y^T t, the Y deflation, Y^T Y) runs on a grid of row tiles x
+// folds; each tile writes its partial sums, which are added in tile order (fixed order: the same bits on every run).
+constexpr int kKfRowThreads = 256, kKfMaxTiles = 128, kKfChunk = 32;
+
+__host__ __device__ inline int kf_tiles(int64_t I) {
+  int64_t nt = (I + kKfRowThreads - 1) / kKfRowThreads;
+  return (int)(nt > kKfMaxTiles ? kKfMaxTiles : (nt < 1 ? 1 : nt));
+}
+
+__device__ __forceinline__ void kf_tile_rows(int I, int NT, int tile, int* lo, int* hi) {
+  const int len = (I + NT - 1) / NT;
+  *lo = min(I, tile * len);
+  *hi = min(I, (tile + 1) * len);
+}
+
+// vec of fold k: b (R) | c (R) | ya (M) | 1^T t (1) | g (R) | mu^T w (1)
+__host__ __device__ inline int kf_vec_len(int R, int M) { return 3 * R + M + 2; }
+
+// ---- kfold_inner ------------------------------------------------------------------------------------------------------------
+static size_t kf_inner_lds_bytes(int A, int B, int M) {
+  const size_t n = (size_t)(A < B ? A : B), k = (size_t)(A < B ? B : A);
+  return ((size_t)A + B + 3 * (size_t)M + (size_t)M * M + n + k) * sizeof(double);
+}
+
+// a workgroup per fold: G_y from the row tiles' partials, the inner loop, then what the row pass needs of the new loadings:
+// mu_k^T w and g_j = w_j^T w_a (Gram of a Khatri-Rao product = product of the mode Grams)
+__global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state st, int a, double tol, int max_iter, double* ws,
+                                                            int64_t ws_per_fold) {
+  extern __shared__ double sm[];
+  __shared__ double red[kLxWaves];
+  __shared__ double bestv[kLxWaves];
+  __shared__ int besti[kLxWaves];
+  const int tid = threadIdx.x, fold = blockIdx.x;
+  const int A = st.A, B = st.B, M = st.M, K = st.K, R = st.R;
+  const int64_t P = (int64_t)A * B;
+  const int n = A < B ? A : B, NT = kf_tiles(st.I);
+  double* Z = ws + (int64_t)fold * ws_per_fold;                  // P
+  double* Zt = Z + P;                                             // P
+  double* wk = Zt + P;                                            // P
+  double* G0 = wk + P;                                            // n x n
+  double* G1 = G0 + (int64_t)n * n;                               // n x n
+  double* wA = sm;
+  double* wB = wA + A;
+  double* q = wB + B;
+  double* qn = q + M;
+  double* tq = qn + M;
+  double* Gy = tq + M;
+  double* xs = Gy + M * M;
+  double* ys = xs + n;
+  for (int o = tid; o < M * M; o += kLxNT) {
+    double s = 0.0;
+    for (int t = 0; t < NT; ++t) s += st.Gy[((int64_t)fold * NT + t) * M * M + o];
+    Gy[o] = s;
+  }
+  __syncthreads();
+  const int it = lx_inner_loop(st.S + (int64_t)fold * M * P, Gy, P, M, A, B, tol, max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs,
+                               ys, red, bestv, besti);
+  bool bad = false;
+  for (int j = tid; j < A; j += kLxNT) {
+    st.WA[(int64_t)j * K + fold] = wA[j];
+    st.Wa[((int64_t)fold * R + a) * A + j] = wA[j];
+    bad |= !isfinite(wA[j]);
+  }
+  for (int j = tid; j < B; j += kLxNT) {
+    st.WB[(int64_t)j * K + fold] = wB[j];
+    st.Wb[((int64_t)fold * R + a) * B + j] = wB[j];
+    bad |= !isfinite(wB[j]);
+  }
+  for (int m = tid; m < M; m += kLxNT) { st.Q[((int64_t)fold * R + a) * M + m] = q[m]; bad |= !isfinite(q[m]); }
+  if (bad) atomicOr(st.status + fold, 1);
+  if (tid == 0) st.n_iter[fold * R + a] = it;
+  double* vec = st.vec + (int64_t)fold * kf_vec_len(R, M);
+  const double* mean = st.mean + (int64_t)fold * P;
+  double s = 0.0;
+  for (int64_t c = tid; c < P; c += kLxNT) s = fma(mean[c], wk[c], s);     // (wk: the converged loadings' Kronecker product)
+  s = lx_sum(s, red);
+  if (tid == 0) vec[3 * R + M + 1] = s;
+  for (int j = 0; j < a; ++j) {
+    double sa = 0.0, sb = 0.0;
+    for (int i = tid; i < A; i += kLxNT) sa = fma(st.Wa[((int64_t)fold * R + j) * A + i], wA[i], sa);
+    for (int i = tid; i < B; i += kLxNT) sb = fma(st.Wb[((int64_t)fold * R + j) * B + i], wB[i], sb);
+    sa = lx_sum(sa, red);
+    sb = lx_sum(sb, red);
+    if (tid == 0) vec[2 * R + M + 1 + j] = sa * sb;
+  }
+}
+
+// ---- kfold_epilogue ---------------------------------------------------------------------------------------------------------
+// stage 1a, grid (row tiles, folds): t_k = X_0 w_k - (mu_k^T w_k) 1 - T_k[:, :a] g_k for every row of the tile (held-out rows: the
+// projection predict makes, tpls.py:133-142), the training-masked score, u = Y_k q, and the tile's partial sums of
+// T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t
+__global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ sc) {
+  constexpr int NW = kKfRowThreads / 64;
+  __shared__ double acc[NW][2 * kKfMaxR + 1 + kKfMaxM];
+  __shared__ double q[kKfMaxM], g[kKfMaxR];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, tile = blockIdx.x, k = blockIdx.y;
+  const int I = st.I, M = st.M, K = st.K, R = st.R, kk = a + 1, NT = kf_tiles(I), nv = 2 * kk + 1 + M;
+  const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
+  const double mw = vec[3 * R + M + 1];
+  for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
+  for (int j = tid; j < a; j += kKfRowThreads) g[j] = vec[2 * R + M + 1 + j];
+  for (int v = tid; v < NW * (2 * kKfMaxR + 1 + kKfMaxM); v += kKfRowThreads) (&acc[0][0])[v] = 0.0;
+  __syncthreads();
+  double* T = st.T + (int64_t)k * I * R;
+  const double* Yk = st.Yk + (int64_t)k * I * M;
+  int lo, hi;
+  kf_tile_rows(I, NT, tile, &lo, &hi);
+  for (int i0 = lo; i0 < hi; i0 += kKfRowThreads) {
+    const int i = i0 + tid;
+    const bool ok = i < hi;
+    bool train = false;
+    double t = 0.0, u = 0.0;
+    if (ok) {
+      t = sc[(int64_t)i * K + k] - mw;
+      for (int j = 0; j < a; ++j) t = fma(-T[(int64_t)i * R + j], g[j], t);
+      T[(int64_t)i * R + a] = t;
+      train = st.fold_of[i] != k;
+      if (!train) st.Tout[(int64_t)i * R + a] = t;
+      st.tm[(int64_t)i * K + k] = train ? t : 0.0;
+      if (train)
+        for (int m = 0; m < M; ++m) u = fma(Yk[(int64_t)i * M + m], q[m], u);
+    }
+    const double tt = train ? t : 0.0;
+    for (int p = 0; p < kk; ++p) {
+      const double tp = train ? (p == a ? t : T[(int64_t)i * R + p]) : 0.0;
+      const double s1 = wave_sum(tp * tt), s2 = wave_sum(tp * u);
+      if (lane == 0) { acc[wv][p] += s1; acc[wv][kk + p] += s2; }
+    }
+    const double s3 = wave_sum(tt);
+    if (lane == 0) acc[wv][2 * kk] += s3;
+    for (int m = 0; m < M; ++m) {                                  // (held-out rows of Y_k are 0)
+      const double s4 = wave_sum(ok ? Yk[(int64_t)i * M + m] * t : 0.0);
+      if (lane == 0) acc[wv][2 * kk + 1 + m] += s4;
+    }
+  }
+  __syncthreads();
+  for (int v = tid; v < nv; v += kKfRowThreads) {
+    double s = 0.0;
+    for (int w = 0; w < NW; ++w) s += acc[w][v];
+    st.part[((int64_t)k * NT + tile) * (2 * kKfMaxR + 1 + kKfMaxM) + v] = s;
+  }
+}
+
+// stage 1b, a workgroup per fold: the tiles' sums in tile order; coef_[:a+1, a] = lstsq(T_train, u) (tpls.py:110-112: normal
+// equations, equilibrated Cholesky, a column with a pivot below (a+1) eps dropped); c = T^T T b for the down-date
+__global__ __launch_bounds__(64) void kfold_solve_kernel(cmtfpls_kfold_state st, int a) {
+  __shared__ double tot[2 * kKfMaxR + 1 + kKfMaxM];
+  __shared__ double Gn[kKfMaxR * kKfMaxR];
+  __shared__ double bb[kKfMaxR], dd[kKfMaxR];
+  const int tid = threadIdx.x, k = blockIdx.x;
+  const int M = st.M, R = st.R, kk = a + 1, NT = kf_tiles(st.I), nv = 2 * kk + 1 + M;
+  double* Gt = st.Gt + (int64_t)k * R * R;
+  double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
+  for (int v = tid; v < nv; v += 64) {
+    double s = 0.0;
+    for (int t = 0; t < NT; ++t) s += st.part[((int64_t)k * NT + t) * (2 * kKfMaxR + 1 + kKfMaxM) + v];
+    tot[v] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int p = 0; p < kk; ++p) { Gt[a * R + p] = tot[p]; Gt[p * R + a] = tot[p]; }
+  for (int i = 0; i < kk; ++i)
+    for (int j = 0; j < kk; ++j) Gn[i * kk + j] = Gt[i * R + j];
+  const double tiny = (double)kk * 2.220446049250313e-16;
+  for (int i = 0; i < kk; ++i) { const double gi = Gn[i * kk + i]; dd[i] = (gi > 0.0 && isfinite(gi)) ? 1.0 / sqrt(gi) : 0.0; }
+  for (int i = 0; i < kk; ++i) {
+    for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
+    bb[i] = tot[kk + i] * dd[i];
+  }
+  bool dep[kKfMaxR];
+  for (int c = 0; c < kk; ++c) {
+    const double piv = Gn[c * kk + c];
+    dep[c] = !(piv > tiny);
+    if (dep[c]) { Gn[c * kk + c] = 1.0; for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0; continue; }
+    const double l = sqrt(piv);
+    Gn[c * kk + c] = l;
+    for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
+    for (int i = c + 1; i < kk; ++i)
+      for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
+  }
+  for (int r = 0; r < kk; ++r) {
+    double v = bb[r];
+    for (int j = 0; j < r; ++j) v -= Gn[r * kk + j] * bb[j];
+    bb[r] = dep[r] ? 0.0 : v / Gn[r * kk + r];
+  }
+  for (int r = kk - 1; r >= 0; --r) {
+    double v = bb[r];
+    for (int j = r + 1; j < kk; ++j) v -= Gn[j * kk + r] * bb[j];
+    bb[r] = dep[r] ? 0.0 : v / Gn[r * kk + r];
+  }
+  for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; st.coef[((int64_t)k * R + r) * R + a] = bb[r]; vec[r] = bb[r]; }
+  for (int r = 0; r < kk; ++r) {                                  // c = T^T yhat = (T^T T) b, the training Gram
+    double v = 0.0;
+    for (int j = 0; j < kk; ++j) v = fma(Gt[r * R + j], bb[j], v);
+    vec[R + r] = v;
+  }
+  for (int m = 0; m < M; ++m) vec[2 * R + m] = tot[2 * kk + 1 + m];
+  vec[2 * R + M] = tot[2 * kk];
+  if (!isfinite(bb[a]) || !isfinite(tot[2 * kk])) st.status[k] |= 2;
+}
+
+// stage 0 / 1c, grid (row tiles, folds): (deflate: Y_k -= (T b) q^T on the training rows, tpls.py:113) and the tile's partial
+// Y_k^T Y_k for the next component's convergence test, rows staged through LDS a chunk at a time
+__global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfold_state st, int a, int deflate) {
+  constexpr int EPT = kKfMaxM * kKfMaxM / kKfRowThreads;          // Gram entries per thread
+  __shared__ double Ys[kKfChunk][kKfMaxM + 1];
+  __shared__ double q[kKfMaxM], b[kKfMaxR];
+  const int tid = threadIdx.x, tile = blockIdx.x, k = blockIdx.y;
+  const int I = st.I, M = st.M, R = st.R, kk = a + 1, NT = kf_tiles(I);
+  const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
+  if (deflate) {
+    for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
+    for (int j = tid; j < kk; j += kKfRowThreads) b[j] = vec[j];
+  }
+  __syncthreads();
+  const double* T = st.T + (int64_t)k * I * R;
+  double* Yk = st.Yk + (int64_t)k * I * M;
+  double accg[EPT];
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) accg[e] = 0.0;
+  int lo, hi;
+  kf_tile_rows(I, NT, tile, &lo, &hi);
+  for (int i0 = lo; i0 < hi; i0 += kKfChunk) {
+    for (int idx = tid; idx < kKfChunk * M; idx += kKfRowThreads) {
+      const int r = idx / M, m = idx % M, i = i0 + r;
+      double y = 0.0;
+      if (i < hi) {
+        y = Yk[(int64_t)i * M + m];
+        if (deflate && st.fold_of[i] != k) {
+          double yh = 0.0;
+          for (int j = 0; j < kk; ++j) yh = fma(T[(int64_t)i * R + j], b[j], yh);
+          y = fma(-yh, q[m], y);
+          Yk[(int64_t)i * M + m] = y;
+        }
+      }
+      Ys[r][m] = y;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      const int o = tid + e * kKfRowThreads;
+      if (o < M * M) {
+        const int m1 = o / M, m2 = o % M;
+        double s = accg[e];
+        for (int r = 0; r < kKfChunk; ++r) s = fma(Ys[r][m1], Ys[r][m2], s);
+        accg[e] = s;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) {
+    const int o = tid + e * kKfRowThreads;
+    if (o < M * M) st.Gy[((int64_t)k * NT + tile) * M * M + o] = accg[e];
+  }
+}
+
+// stage 2, a thread per column and fold: r_a = X_c^T t_a = rs - (1^T t) mu (rs = X_0^T (t * train) from the contraction pass), kept
+// for later components; X_{a+1}^T yhat = sum_{j<=a} b_j r_j - sum_{j<=a} c_j w_j; S -= w ya^T + (X_{a+1}^T yhat) q^T
+// (fitrun_xcov._finish_xcov_nowrite, cmtfpls_s_downdate_f64)
+__global__ __launch_bounds__(kKfCols) void kfold_downdate_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ rs) {
+  const int64_t c = (int64_t)blockIdx.x * kKfCols + threadIdx.x;
+  const int k = blockIdx.y;
+  const int A = st.A, B = st.B, M = st.M, R = st.R;
+  const int64_t P = (int64_t)A * B;
+  if (c >= P) return;
+  const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
+  const int ia = (int)(c / B), ib = (int)(c % B);
+  const double r = rs[(int64_t)k * P + c] - vec[2 * R + M] * st.mean[(int64_t)k * P + c];
+  st.Rm[((int64_t)k * R + a) * P + c] = r;
+  double v = 0.0;
+  for (int j = 0; j < a; ++j) v = fma(vec[j], st.Rm[((int64_t)k * R + j) * P + c], v);
+  v = fma(vec[a], r, v);
+  for (int j = 0; j <= a; ++j) v = fma(-vec[R + j], st.Wa[((int64_t)k * R + j) * A + ia] * st.Wb[((int64_t)k * R + j) * B + ib], v);
+  const double w = st.Wa[((int64_t)k * R + a) * A + ia] * st.Wb[((int64_t)k * R + a) * B + ib];
+  const double* q = st.Q + ((int64_t)k * R + a) * M;
+  double* S = st.S + (int64_t)k * M * P + c;
+  for (int m = 0; m < M; ++m) S[(int64_t)m * P] -= fma(w, vec[2 * R + m], v * q[m]);
+}
+
+static bool kf_shape_ok(int64_t I, int A, int B, int M, int K, int R) {
+  const int n = A < B ? A : B;
+  return K >= 2 && K <= kKfMaxK && M >= 1 && M <= kKfMaxM && R >= 1 && R <= kKfMaxR && n <= kKfMaxN && I >= K &&
+         I <= (int64_t)1 << 30 && (int64_t)A * B <= (int64_t)1 << 24 && kf_inner_lds_bytes(A, B, M) <= 150 * 1024;
+}
+
+template <typename T>
+static int run_kfold_xcov(const T* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                          const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!X || !Y || !order || !fold_off || !ydev || !S || !mean || !stats || I <= 0 || A <= 0 || B <= 0 || M <= 0 || K <= 0) {
+    set_error("kfold_xcov: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if (!kf_shape_ok(I, A, B, M, K, 1)) {
+    set_error("kfold_xcov: shape outside the device form (2 <= K <= 32, M <= 64, min(A, B) <= 256); refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const int64_t P = (int64_t)A * B;
+  const size_t need = cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K);
+  if (!ws || ws_bytes < need) { set_error("kfold_xcov: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const int nch = kf_chunks(I, P, K);
+  double* part = static_cast<double*>(ws);
+  const dim3 g((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)K, (unsigned)nch);
+  if (M <= 8) hipLaunchKernelGGL((kfold_partials_kernel<T, 8>), g, dim3(kKfCols), 0, st, X, P, Y, M, order, fold_off, nch, part);
+  else if (M <= 16) hipLaunchKernelGGL((kfold_partials_kernel<T, 16>), g, dim3(kKfCols), 0, st, X, P, Y, M, order, fold_off, nch, part);
+  else if (M <= 32) hipLaunchKernelGGL((kfold_partials_kernel<T, 32>), g, dim3(kKfCols), 0, st, X, P, Y, M, order, fold_off, nch, part);
+  else hipLaunchKernelGGL((kfold_partials_kernel<T, 64>), g, dim3(kKfCols), 0, st, X, P, Y, M, order, fold_off, nch, part);
+  int rc = check_launch("kfold_xcov");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kfold_finish_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols)), dim3(kKfCols), 0, st, P, M, K, nch, (int)I,
+                     fold_off, part, ydev, S, mean, stats);
+  return check_launch("kfold_xcov");
+}
+
+static bool kf_state_ok(const cmtfpls_kfold_state* s) {
+  return s && s->fold_of && s->S && s->mean && s->Yk && s->Gy && s->WA && s->WB && s->Q && s->Wa && s->Wb && s->T && s->Gt && s->coef &&
+         s->Rm && s->tm && s->Tout && s->vec && s->n_iter && s->status && s->part;
+}
+
+}  // namespace cmtfpls
+
+using namespace cmtfpls;
+
+extern "C" {
+
+size_t cmtfpls_kfold_xcov_workspace_bytes(int64_t I, int64_t P, int M, int K) {
+  if (I <= 0 || P <= 0 || M <= 0 || K <= 0) return 0;
+  return (size_t)K * kf_chunks(I, P, K) * (size_t)(M + 2) * (size_t)P * sizeof(double);
+}
+
+int cmtfpls_kfold_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_xcov<float>(X, I, A, B, Y, M, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_xcov<double>(X, I, A, B, Y, M, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_row_tiles(int64_t I) { return I > 0 ? kf_tiles(I) : 0; }
+
+int cmtfpls_kfold_part_stride(void) { return 2 * kKfMaxR + 1 + kKfMaxM; }
+
+size_t cmtfpls_kfold_inner_workspace_bytes(int A, int B, int K) {
+  if (A <= 0 || B <= 0 || K <= 0) return 0;
+  const size_t P = (size_t)A * B, n = (size_t)(A < B ? A : B);
+  return (size_t)K * (3 * P + 2 * n * n) * sizeof(double);
+}
+
+int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, int max_iter, void* ws, size_t ws_bytes, void* stream) {
+  if (!kf_state_ok(st) || a < 0 || a >= st->R || max_iter <= 0) { set_error("kfold_inner: bad argument"); return CMTFPLS_EINVAL; }
+  if (!kf_shape_ok(st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold_inner: shape outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256); refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
+  if (!ws || ws_bytes < need) { set_error("kfold_inner: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfold_inner_kernel, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
+                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)));
+  return check_launch("kfold_inner");
+}
+
+int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {
+  if (!kf_state_ok(st) || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+    set_error("kfold_epilogue: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if (!kf_shape_ok(st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold_epilogue: shape outside the device form; refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
+  if (stage == 0) {
+    hipLaunchKernelGGL(kfold_ydefl_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, 0);
+  } else if (stage == 1) {
+    hipLaunchKernelGGL(kfold_rows_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, in);
+    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, 1);
+  } else {
+    const int64_t P = (int64_t)st->A * st->B;
+    hipLaunchKernelGGL(kfold_downdate_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st, a, in);
+  }
+  return check_launch("kfold_epilogue");
+}
+
+}  // extern "C"

@@ -20,14 +20,9 @@
 // Arithmetic: float64 throughout, the reference's operation order outside the re-association above.
 // Limits: X of order 2 or 3 without missing values, min(A, B) <= 256, M <= 128, R <= 64, the workgroup's small vectors in
 // 150 KB of LDS; per resident fold a workspace of I P + M P + 3 P + 2 n^2 + I (M + R + 2) + R (A + B) doubles (cmtfpls_loo_xcov_fold_workspace_bytes).
-#include "common.hpp"
+#include "fold_loop.hpp"
 
 namespace cmtfpls {
-
-constexpr int kLxNT = 1024, kLxWaves = kLxNT / 64;
-constexpr int kLxMaxN = 256, kLxMaxM = 128, kLxMaxR = 64;     // (M: as far as the M x M Gram of the responses fits the LDS next to the rest)
-
-typedef double lx_d4_t __attribute__((ext_vector_type(4)));
 
 struct LooXArgs {
   const double* X;        // (I, P) original, uncentred
@@ -41,182 +36,6 @@ struct LooXArgs {
   int I, A, B, M, R, max_iter, fold0, nfolds;
   double tol;
 };
-
-// sum over the workgroup; every thread gets the same value; two barriers, so back-to-back calls may share `red`
-__device__ __forceinline__ double lx_sum(double v, double* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kLxWaves; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
-// C (n x n) = scale2 * Mx Mx^T for row-major Mx (n x k, leading dimension ld), C_keep (nullable) a second copy.
-// Lower-triangular 16 x 16 tiles dealt round-robin to the 16 wavefronts, each on the f64 matrix cores:
-//   v_mfma_f64_16x16x4_f64: lane l supplies A[i = l & 15][kq = l >> 4] and B[kq][j = l & 15] and holds D[(l >> 4) + 4 e][l & 15];
-//   lane group kq takes the 8 consecutive columns c0 + 8 kq + (0..7) of a 32-column chunk, MFMA s multiplies column
-//   c0 + 8 kq + s of row i0 + (l & 15) with the same column of row j0 + (l & 15) (B = Mx^T).
-// The mirrored tile is written from the same registers (C is bitwise symmetric).  Returns tr(C) and |C|_F^2 to every thread.
-__device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, double* C_keep, double scale2, double* red,
-                        double* tr_out, double* fro_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, ri = lane & 15, kq = lane >> 4;
-  const int nt = (n + 15) / 16;
-  double trp = 0.0, frp = 0.0;
-  int idx = 0;
-  for (int ti = 0; ti < nt; ++ti)
-    for (int tj = 0; tj <= ti; ++tj, ++idx) {
-      if ((idx % kLxWaves) != wv) continue;
-      const int i0 = ti * 16, j0 = tj * 16;
-      const bool ra = (i0 + ri) < n, rb = (j0 + ri) < n;
-      const double* rowa = Mx + (int64_t)(ra ? i0 + ri : 0) * ld;
-      const double* rowb = Mx + (int64_t)(rb ? j0 + ri : 0) * ld;
-      lx_d4_t acc = lx_d4_t{0.0, 0.0, 0.0, 0.0};
-      for (int kk = 0; kk < k; kk += 32) {
-        double a[8], b[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          const int c = kk + 8 * kq + s;
-          const int cc = (c < k) ? c : 0;
-          a[s] = rowa[cc];
-          b[s] = rowb[cc];
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          const bool cok = (kk + 8 * kq + s) < k;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64((ra && cok) ? a[s] : 0.0, (rb && cok) ? b[s] : 0.0, acc, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = i0 + kq + 4 * e, c = j0 + ri;
-        if (r < n && c < n) {
-          const double v = acc[e] * scale2;
-          C[(int64_t)r * n + c] = v;
-          if (C_keep) C_keep[(int64_t)r * n + c] = v;
-          if (ti != tj) {
-            C[(int64_t)c * n + r] = v;
-            if (C_keep) C_keep[(int64_t)c * n + r] = v;
-            frp = fma(2.0 * v, v, frp);
-          } else {
-            frp = fma(v, v, frp);
-            if (r == c) trp += v;
-          }
-        }
-      }
-    }
-  *tr_out = lx_sum(trp, red);        // (the barriers inside also publish C to the whole workgroup)
-  *fro_out = lx_sum(frp, red);
-}
-
-// Leading singular pair of Z (A x B row-major, global): wA (A), wB (B) unit norm, largest-|.| entry of wB positive.
-// Zt: P doubles of scratch (the transpose when B < A); G0 / G1: n x n each (ping-pong); xs (n), ys (k) in LDS.
-__device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, double* wB, double* G0, double* G1,
-                         double* xs, double* ys, double* red, double* bestv, int* besti) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const bool rowsA = A <= B;                        // Mx = Z (n = A) or Z^T (n = B)
-  const int n = rowsA ? A : B, k = rowsA ? B : A;
-  const double* Mx = Z;
-  if (!rowsA) {
-    for (int idx = tid; idx < A * B; idx += kLxNT) { const int b = idx / A, a = idx % A; Zt[idx] = Z[(int64_t)a * B + b]; }
-    __syncthreads();
-    Mx = Zt;
-  }
-  double tr, fro;
-  lx_syrk(Mx, n, k, k, G0, nullptr, 1.0, red, &tr, &fro);                              // G_0 = Mx Mx^T
-  double* G = G0;
-  double* Gn = G1;
-  for (int step = 0; step < 64; ++step) {
-    if (!(tr > 0.0) || !isfinite(tr) || fro / (tr * tr) >= 1.0 - 1e-13) break;         // uniform: numerically rank one
-    int e;
-    frexp(tr, &e);
-    const double sc = ldexp(1.0, -e);                                                 // exact power of two
-    lx_syrk(G, n, n, n, Gn, nullptr, sc * sc, red, &tr, &fro);                         // G <- (sc G)^2   (G symmetric: G G = G G^T)
-    double* tmp = G; G = Gn; Gn = tmp;
-  }
-  // seed = dominant column of G (first index on ties), normalised
-  double bv = -1.0;
-  int bi = 0;
-  for (int i = tid; i < n; i += kLxNT) { const double d = G[(int64_t)i * n + i]; if (d > bv) { bv = d; bi = i; } }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const double ov = __shfl_xor(bv, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
-  __syncthreads();
-  bv = bestv[0];
-  bi = besti[0];
-  for (int w = 1; w < kLxWaves; ++w)
-    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
-  __syncthreads();
-  double ss = 0.0;
-  for (int i = tid; i < n; i += kLxNT) { const double g = G[(int64_t)bi * n + i]; ss = fma(g, g, ss); }
-  const double snrm = sqrt(lx_sum(ss, red));
-  for (int i = tid; i < n; i += kLxNT) xs[i] = G[(int64_t)bi * n + i] / snrm;
-  __syncthreads();
-  for (int l = tid; l < k; l += kLxNT) {                                               // y = Mx^T seed
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s = fma(Mx[(int64_t)i * k + l], xs[i], s);
-    ys[l] = s;
-  }
-  __syncthreads();
-  for (int i = wv; i < n; i += kLxWaves) {                                             // x = Mx y: a wavefront per row
-    double s = 0.0;
-    for (int l = lane; l < k; l += 64) s = fma(Mx[(int64_t)i * k + l], ys[l], s);
-    s = wave_sum(s);
-    if (lane == 0) xs[i] = s;                 // (the seed is dead: every wavefront finished y before the barrier above)
-  }
-  __syncthreads();
-  double sx = 0.0, sy = 0.0;
-  for (int i = tid; i < n; i += kLxNT) sx = fma(xs[i], xs[i], sx);
-  for (int l = tid; l < k; l += kLxNT) sy = fma(ys[l], ys[l], sy);
-  const double nx = sqrt(lx_sum(sx, red)), ny = sqrt(lx_sum(sy, red));
-  // sign rule on the LAST mode's vector wB: its largest-|.| entry is positive (first index on ties)
-  const double* vb = rowsA ? ys : xs;
-  const int nb = rowsA ? k : n;
-  bv = -1.0;
-  bi = 0;
-  for (int i = tid; i < nb; i += kLxNT) { const double d = fabs(vb[i]); if (d > bv) { bv = d; bi = i; } }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const double ov = __shfl_xor(bv, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
-  __syncthreads();
-  bv = bestv[0];
-  bi = besti[0];
-  for (int w = 1; w < kLxWaves; ++w)
-    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
-  const double sgn = (vb[bi] < 0.0) ? -1.0 : 1.0;
-  double* ox = rowsA ? wA : wB;
-  double* oy = rowsA ? wB : wA;
-  __syncthreads();
-  for (int i = tid; i < n; i += kLxNT) ox[i] = sgn * (xs[i] / nx);
-  for (int l = tid; l < k; l += kLxNT) oy[l] = sgn * (ys[l] / ny);
-  __syncthreads();
-}
-
-// sum_c row[c] * wk[c] over one wavefront's columns c = lane, lane + 64, ...: one fma chain per lane in column order (the order of the
-// plain loop), eight loads of each operand in flight per trip
-__device__ __forceinline__ double lx_wave_dot(const double* row, const double* wk, int64_t P, int lane) {
-  double s = 0.0;
-  int64_t c = lane;
-  for (; c + 7 * 64 < P; c += 8 * 64) {
-    double xv[8], wv8[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { xv[j] = row[c + 64 * j]; wv8[j] = wk[c + 64 * j]; }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s = fma(xv[j], wv8[j], s);
-  }
-  for (; c < P; c += 64) s = fma(row[c], wk[c], s);
-  return wave_sum(s);
-}
 
 __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
   extern __shared__ double sm[];
@@ -320,53 +139,7 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
       for (int r = 0; r < I; ++r) s = fma(Yf[(int64_t)r * M + m1], Yf[(int64_t)r * M + m2], s);
       Gy[o] = s;
     }
-    for (int m = tid; m < M; m += kLxNT) q[m] = (m == 0) ? 1.0 : 0.0;                 // u_0 = Y_f[:, 0] = Y_f e_0 (tpls.py:78)
-    __syncthreads();
-    int it = 0;
-    for (; it < a.max_iter; ++it) {                                                    // tpls.py:79
-      for (int64_t c = tid; c < P; c += kLxNT) {                                       // Z = X x_0 u = S^T q (tpls.py:83)
-        double s = 0.0;
-        int m = 0;
-        for (; m + 4 <= M; m += 4) {                                                   // (four rows of S in flight; same order of the sum)
-          const double s0 = S[(int64_t)m * P + c], s1 = S[(int64_t)(m + 1) * P + c], s2 = S[(int64_t)(m + 2) * P + c], s3 = S[(int64_t)(m + 3) * P + c];
-          s = fma(q[m], s0, s);
-          s = fma(q[m + 1], s1, s);
-          s = fma(q[m + 2], s2, s);
-          s = fma(q[m + 3], s3, s);
-        }
-        for (; m < M; ++m) s = fma(q[m], S[(int64_t)m * P + c], s);
-        Z[c] = s;
-      }
-      __syncthreads();
-      if (A == 1) {                                                                    // tpls.py:84: Z / norm(Z)
-        double s = 0.0;
-        for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
-        const double nz = sqrt(lx_sum(s, red));
-        for (int64_t c = tid; c < P; c += kLxNT) wB[c] = Z[c] / nz;
-        if (tid == 0) wA[0] = 1.0;
-        __syncthreads();
-      } else {
-        lx_rank1(Z, Zt, A, B, wA, wB, G0, G1, xs, ys, red, bestv, besti);          // tpls.py:86-88
-      }
-      for (int64_t c = tid; c < P; c += kLxNT) wk[c] = wA[c / B] * wB[c % B];          // the Kronecker loading, once per extraction
-      __syncthreads();
-      for (int m = wv; m < M; m += kLxWaves) {                                         // Y^T t = S (wA (x) wB) (tpls.py:97-100)
-        const double s = lx_wave_dot(S + (int64_t)m * P, wk, P, lane);
-        if (lane == 0) tq[m] = s;
-      }
-      __syncthreads();
-      double qs = 0.0;
-      for (int m = tid; m < M; m += kLxNT) qs = fma(tq[m], tq[m], qs);
-      const double qnrm = sqrt(lx_sum(qs, red));
-      for (int m = tid; m < M; m += kLxNT) qn[m] = tq[m] / qnrm;                       // tpls.py:101
-      __syncthreads();
-      double d2 = 0.0;                                                                 // |u_old - u|^2 = dq^T G_y dq (tpls.py:102-103)
-      for (int o = tid; o < M * M; o += kLxNT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
-      d2 = lx_sum(d2, red);
-      for (int m = tid; m < M; m += kLxNT) q[m] = qn[m];
-      __syncthreads();
-      if (it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < a.tol) { ++it; break; }              // first pass: oldU = inf (tpls.py:77)
-    }
+    const int it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti);
     if (a.n_iter && tid == 0) a.n_iter[(int64_t)fold * R + comp] = it;
     // ---- the component's score and Y score with the converged loadings (tpls.py:97-102) ----
     for (int r = wv; r < I; r += kLxWaves) {                                             // (wk holds the converged loadings' Kronecker product)

@@ -65,3 +65,26 @@ def get_q2y(pls_tensor, device_folds: bool = True):
     numerator = (Y_pred - Y_actual) ** 2                     # validate.py:35-37
     denominator = Y_actual ** 2
     return 1 - numerator.sum() / denominator.sum()
+
+
+def kfold_predictions(pls_tensor, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100,
+                      device_folds: bool = True) -> np.ndarray:
+    """K-fold cross-validated predictions, (R, *Y.shape): entry [r - 1, i] is the prediction for sample i by the model
+    fitted without sample i's fold, using its first r components.  folds=None: contiguous folds with the sizes of sklearn's
+    KFold(n_splits, shuffle=False); otherwise an int array of fold ids 0..K-1, one per sample.  On the GPU every fold is served
+    by the same reads of X (2R in all, X never copied or written: kfold.py); anything outside that form refits once per fold.
+    Which form ran is recorded on the model (``q2y_report_``)."""
+    from .kfold import kfold_run
+
+    return kfold_run(pls_tensor, n_splits, folds, tol, max_iter, device_folds)
+
+
+def get_q2y_kfold(pls_tensor, n_splits: int = 5, folds=None, per_component: bool = False, device_folds: bool = True):
+    """Q2Y (validate.py:35-37: 1 - sum (pred - y)^2 / sum y^2) of K-fold cross-validated predictions; per_component=True:
+    the (R,) array of Q2Y with the first r = 1..R components, all from the same run."""
+    pred = kfold_predictions(pls_tensor, n_splits, folds, device_folds=device_folds)
+    Y = np.asarray(pls_tensor.original_Y) if not hasattr(pls_tensor.original_Y, "cpu") else pls_tensor.original_Y.cpu().numpy()
+    Y_actual = Y.astype(float)
+    numerator = ((pred - Y_actual) ** 2).reshape(pred.shape[0], -1).sum(axis=1)
+    q = 1 - numerator / (Y_actual ** 2).sum()
+    return q if per_component else float(q[-1])

@@ -467,6 +467,58 @@ size_t cmtfpls_loo_xcov_fold_workspace_bytes(int I, int A, int B, int M, int R);
 int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
                          int B, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
                          int* n_iter, void* ws, size_t ws_bytes, void* stream);
+/* ---- K-fold cross-validation with every fold served by the same reads of X (validate.kfold_predictions) ------------------------
+ * The folds of a K-fold split share X_0 (the caller's uncentred tensor, never written); a fold differs only in its training rows,
+ * their means and its loadings.  Per component: kfold_inner (the inner loop of every fold on its training cross-covariance, a
+ * workgroup per fold), one MTTKRP of X_0 with the K folds' loadings (cmtfpls_mttkrp_*: every row's score under every fold),
+ * kfold_epilogue stage 1 (scores, inner regression, Y side), one contraction X_0^T [t_k * train_k] (cmtfpls_xcov_*, all but the
+ * last component) and kfold_epilogue stage 2 (the down-date of each fold's S).  Before the first component kfold_xcov builds the
+ * training cross-covariances from ONE read and kfold_epilogue stage 0 the Grams of the folds' training Y.  2R reads of X for all
+ * folds.  Limits: X of order 2 (A = 1) or 3 without missing values, 2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256
+ * (CMTFPLS_EUNSUPPORTED otherwise: refit per fold).  All device buffers below are float64, row-major, owned by the caller. */
+typedef struct {
+  int I, A, B, M, K, R;
+  const int* fold_of;     /* I: fold id of each row */
+  double* S;              /* K x M x A*B: each fold's training cross-covariance (centred; down-dated per component) */
+  double* mean;           /* K x A*B: each fold's training column means */
+  double* Yk;             /* K x I x M: each fold's training Y, centred by its mean and deflated; held-out rows 0 */
+  double* Gy;             /* K x NT x M x M: per row tile the partial Yk^T Yk of the current component (NT = cmtfpls_kfold_row_tiles(I)) */
+  double* WA;             /* A x K: the current component's loadings, column k = fold k (the MTTKRP operands) */
+  double* WB;             /* B x K */
+  double* Q;              /* K x R x M: q of every component */
+  double* Wa;             /* K x R x A: loadings of every component */
+  double* Wb;             /* K x R x B */
+  double* T;              /* K x I x R: the score of every row under each fold's model */
+  double* Gt;             /* K x R x R: Gram of the training scores */
+  double* coef;           /* K x R x R: coef_ of each fold's model (upper triangular) */
+  double* Rm;             /* K x R x A*B: X_c^T t_j of each fold's training rows */
+  double* tm;             /* I x K: the current component's scores, 0 on each fold's held-out rows (contraction operand) */
+  double* Tout;           /* I x R: each row's scores under the model of its own fold (the held-out projection) */
+  double* vec;            /* K x (3 R + M + 2) scratch */
+  int* n_iter;            /* K x R: inner iterations executed */
+  int* status;            /* K: zeroed by the caller; nonzero = a non-finite loading or coefficient */
+  double* part;           /* K x NT x cmtfpls_kfold_part_stride() scratch: the row tiles' partial sums */
+} cmtfpls_kfold_state;
+/* Row tiles of the epilogue's grid (partial sums added in tile order) and the stride of a tile's partials in `part`. */
+int cmtfpls_kfold_row_tiles(int64_t I);
+int cmtfpls_kfold_part_stride(void);
+/* kfold_xcov: S[k] = X_c[train_k]^T (Y[train_k] - nu_k) for every fold from ONE read of X: the fold-grouped partials
+ * X[rows_f]^T Y[rows_f] and column sums (rows in the order `order`, fold f = rows order[fold_off[f] .. fold_off[f+1])), then the
+ * all-minus-own identity and a rank-one centring correction.  Y (I x M): the responses minus any constant shift c; ydev (K x M):
+ * nu_k - c.  mean (K x A*B): the training means; stats (2 A*B): column sums and sums of squares of all rows.
+ * ws >= cmtfpls_kfold_xcov_workspace_bytes(I, A * B, M, K). */
+size_t cmtfpls_kfold_xcov_workspace_bytes(int64_t I, int64_t P, int M, int K);
+int cmtfpls_kfold_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+/* kfold_inner: component a's inner loop (tpls.py:78-107 on S, as cmtfpls_loo_xcov_f64) for every fold, a 1024-thread workgroup per
+ * fold: writes WA / WB (columns k), Q[k, a], n_iter[k, a].  ws >= cmtfpls_kfold_inner_workspace_bytes(A, B, K). */
+size_t cmtfpls_kfold_inner_workspace_bytes(int A, int B, int K);
+int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, int max_iter, void* ws, size_t ws_bytes, void* stream);
+/* kfold_epilogue: stage 0 = the partial Gy of every fold (before component 0; `in` unused); stage 1 = component a's epilogue from
+ * `in` = the MTTKRP X_0 WA (.) WB (I x K): a grid of row tiles x folds for the row work, a small solve per fold; stage 2 = the down-date of S from `in` = X_0^T tm (K x A*B), not after the last component. */
+int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
