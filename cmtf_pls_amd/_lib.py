@@ -21,7 +21,8 @@ class XcovBlock(ctypes.Structure):
 
 
 class KfoldState(ctypes.Structure):
-    """cmtfpls_kfold_state (include/cmtfpls.h): the device buffers of a K-fold run (cmtfpls_kfold_inner_f64 / _epilogue_f64)."""
+    """cmtfpls_kfold_state (include/cmtfpls.h): the device buffers of a K-fold run (cmtfpls_kfold_inner_f64 / _epilogue_f64); for a
+    coupled model one per block (cmtfpls_kfold_inner_coupled_f64)."""
     _fields_ = [("I", c_int), ("A", c_int), ("B", c_int), ("M", c_int), ("K", c_int), ("R", c_int)] + [
         (name, _P) for name in ("fold_of", "S", "mean", "Yk", "Gy", "WA", "WB", "Q", "Wa", "Wb", "T", "Gt", "coef", "Rm", "tm",
                                 "Tout", "vec", "n_iter", "status", "part")]
@@ -132,6 +133,9 @@ SIGNATURES = {
     "cmtfpls_kfold_inner_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cmtfpls_kfold_inner_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_double, c_int, _P, c_size_t, _P]),
     "cmtfpls_kfold_epilogue_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, _P, _P]),
+    "cmtfpls_kfold_inner_coupled_workspace_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int]),
+    "cmtfpls_kfold_inner_coupled_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, c_double, c_int, _P, c_size_t, _P]),
+    "cmtfpls_kfold_combine_scores_f64": (c_int, [_P, c_int, c_int64, _P, _P]),
     "cmtfpls_loo_xcov_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_fit_small_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cmtfpls_fit_small_f64": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int] + [_P] * 11 + [_P, c_size_t, _P]),

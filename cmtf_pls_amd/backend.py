@@ -674,6 +674,27 @@ class HipBackend:
         _lib.check(rc, "kfold_epilogue")
         return True
 
+    def kfold_inner_coupled(self, views, a: int, tol: float, max_iter: int, ws: torch.Tensor) -> Optional[bool]:
+        """Component a's inner loop for every fold of a coupled model, a workgroup per fold going through the blocks
+        (cmtfpls_kfold_inner_coupled_f64); `views` is a ctypes array of _lib.KfoldState, one per block, `ws` at least
+        kfold_inner_coupled_workspace_bytes(views).  None when a block or the LDS is outside the device form."""
+        rc = self.lib.cmtfpls_kfold_inner_coupled_f64(views, len(views), int(a), float(tol), int(max_iter), _ptr(ws), ws.numel(),
+                                                      self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner_coupled")
+        return True
+
+    def kfold_inner_coupled_workspace_bytes(self, views) -> int:
+        return int(self.lib.cmtfpls_kfold_inner_coupled_workspace_bytes(views, len(views)))
+
+    def kfold_combine_scores(self, sc: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """out = the average of sc's nb leading slices (nb x I x K), added in block order (cmtfpls_kfold_combine_scores_f64)."""
+        assert sc.is_contiguous() and out.is_contiguous() and sc[0].numel() == out.numel()
+        _lib.check(self.lib.cmtfpls_kfold_combine_scores_f64(_ptr(sc), sc.shape[0], out.numel(), _ptr(out), self._stream()),
+                   "kfold_combine_scores")
+        return out
+
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
         returns a dict of device tensors (T, U, WA, WB, Q, x_mean, y_mean) and host arrays (coef, ssq, n_iter), or None

@@ -4,6 +4,8 @@ matrix (reference cmtf_pls/cmtf.py:15-237), fitted by the MI355X NIPALS engine.
 Same surface as the reference: ``fit(Xs, Y) / predict(Xs) / transform(Xs, Y=None) /
 Xs_reconstructed / copy``, Mapping ``[0], [1], [2]`` -> Xs_factors, Y_factors, coef_.
 ``Xs_factors[ti][0]`` is the one shared ``factor_T`` array for every block (cmtf.py:61-65).
+``original_Xs / original_Y`` (the training blocks and Y as passed, by reference) are what K-fold cross-validation refits from
+(validate.kfold_predictions / get_q2y_kfold).
 """
 from __future__ import annotations
 
@@ -33,6 +35,9 @@ class ctPLS(_EstimatorBase):
         assert Y.ndim <= 2, "Only a matrix (2-mode tensor) Y is acceptable."
         eng = self._get_engine()
         dev = eng.be.device
+        # kept BY REFERENCE (not copied) for validate.kfold_predictions / get_q2y_kfold; with copy_X=False the fit centres and
+        # deflates the caller's blocks in place, so nothing usable is left to keep and their assertion fires
+        self.original_Xs, self.original_Y = (Xs, Y) if self._copy_X else (None, None)
         Y2 = Y.reshape(-1, 1) if Y.ndim == 1 else Y
         self.Xs_len = len(Xs)
         self.Xs_dim = [X.ndim for X in Xs]

@@ -13,7 +13,8 @@
 //                   fold; stage 2: the down-date of S_k from r = X_c^T t
 //   (contraction)   X_0^T [t_1 * train_1 .. t_K * train_K] through cmtfpls_xcov_*                    ONE read of X
 // 2R reads of X for all K folds; nothing is written to X and no copy of it is made.  Arithmetic: float64 (an f32 X is widened
-// on load).  No workgroup waits on another.
+// on load).  No workgroup waits on another.  Coupled models (ctPLS): the same steps per block with the score shared, see the
+// section "coupled models" below.
 #include "fold_loop.hpp"
 
 namespace cmtfpls {
@@ -434,6 +435,209 @@ static bool kf_state_ok(const cmtfpls_kfold_state* s) {
          s->Rm && s->tm && s->Tout && s->vec && s->n_iter && s->status && s->part;
 }
 
+// ---- coupled models (ctPLS) -------------------------------------------------------------------------------------------------
+// nb blocks share the sample mode and one score, t = (1/nb) sum_b X_b^(a) w_b (cmtf.py:95-126); each block is deflated by that t.
+// Each block has a state view of its own: S, mean, WA, WB, Wa, Wb, Rm, A and B are the block's, every other field is the same
+// buffer in all views (the Y side, the scores, the solve).  Per component:
+//   kfold_inner_coupled  every fold's inner loop over all blocks (a workgroup per fold, the blocks in turn):
+//                        Z_b = S_b^T q, rank-1 of Z_b -> w_b, q ∝ (1/nb) sum_b S_b w_b; then the block-averaged mu^T w and g
+//   (score pass)         X_b [w_b,1 .. w_b,K] per block through cmtfpls_mttkrp_*                          ONE read of each block
+//   kfold_combine        the average of the blocks' scores; then kfold_epilogue stage 1 on the first view (t = that average
+//                        - mean(mu_b^T w_b) - T mean(g_b): the tPLS epilogue on the shared t)
+//   (contraction)        X_b^T [t_1 * train_1 .. t_K * train_K] per block through cmtfpls_xcov_*          ONE read of each block
+//   kfold_epilogue 2     per block on its own view: S_b -= w_b ya^T + (X_b,(a+1)^T yhat) q^T, the tPLS down-date with the
+//                        block's w, r = X_b,c^T t and mean (X_b,(a+1) = X_b,c - sum_j t_j w_b,j^T)
+// Sums over blocks are added in block order.
+constexpr int kKfMaxBlocks = 8;
+
+struct KfBlocks {
+  cmtfpls_kfold_state b[kKfMaxBlocks];
+  int nb;
+};
+
+struct KfCoupledDims {
+  int64_t pmax, psum;                 // largest A * B, sum of A * B over the blocks
+  int amax, bmax, nmax, kmax;         // largest A, B, min(A, B), max(A, B)
+};
+
+static KfCoupledDims kf_coupled_dims(const cmtfpls_kfold_state* v, int nb) {
+  KfCoupledDims d{0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < nb; ++b) {
+    const int64_t P = (int64_t)v[b].A * v[b].B;
+    d.pmax = P > d.pmax ? P : d.pmax;
+    d.psum += P;
+    d.amax = v[b].A > d.amax ? v[b].A : d.amax;
+    d.bmax = v[b].B > d.bmax ? v[b].B : d.bmax;
+    const int n = v[b].A < v[b].B ? v[b].A : v[b].B, k = v[b].A < v[b].B ? v[b].B : v[b].A;
+    d.nmax = n > d.nmax ? n : d.nmax;
+    d.kmax = k > d.kmax ? k : d.kmax;
+  }
+  return d;
+}
+
+// LDS: wA (amax), wB (bmax), q, qn, tq (M each), G_y (M x M), xs (nmax), ys (kmax)
+static size_t kf_coupled_lds_bytes(const KfCoupledDims& d, int M) {
+  return ((size_t)d.amax + d.bmax + 3 * (size_t)M + (size_t)M * M + d.nmax + d.kmax) * sizeof(double);
+}
+
+// per fold: Z, Zt (pmax each), G0, G1 (nmax x nmax each), then every block's Kronecker loading wk_b (A_b * B_b), one after another
+static int64_t kf_coupled_ws_per_fold(const KfCoupledDims& d) { return 2 * d.pmax + 2 * (int64_t)d.nmax * d.nmax + d.psum; }
+
+// a workgroup per fold.  With one block every step is the one of kfold_inner_kernel (lx_inner_loop) in the same order, so the
+// result is bitwise that of the tPLS kernel.
+__global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl, int a, double tol, int max_iter, double* ws,
+                                                                    int64_t ws_per_fold, int64_t pmax, int nmax, int amax, int bmax) {
+  extern __shared__ double sm[];
+  __shared__ double red[kLxWaves];
+  __shared__ double bestv[kLxWaves];
+  __shared__ int besti[kLxWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fold = blockIdx.x;
+  const int nb = bl.nb, M = bl.b[0].M, K = bl.b[0].K, R = bl.b[0].R, NT = kf_tiles(bl.b[0].I);
+  double* Z = ws + (int64_t)fold * ws_per_fold;                  // pmax
+  double* Zt = Z + pmax;                                          // pmax
+  double* G0 = Zt + pmax;                                         // nmax x nmax
+  double* G1 = G0 + (int64_t)nmax * nmax;                         // nmax x nmax
+  double* wk0 = G1 + (int64_t)nmax * nmax;                        // sum_b A_b B_b
+  double* wA = sm;
+  double* wB = wA + amax;
+  double* q = wB + bmax;
+  double* qn = q + M;
+  double* tq = qn + M;
+  double* Gy = tq + M;
+  double* xs = Gy + M * M;
+  double* ys = xs + nmax;                                         // kmax
+  for (int o = tid; o < M * M; o += kLxNT) {
+    double s = 0.0;
+    for (int t = 0; t < NT; ++t) s += bl.b[0].Gy[((int64_t)fold * NT + t) * M * M + o];
+    Gy[o] = s;
+  }
+  for (int m = tid; m < M; m += kLxNT) q[m] = (m == 0) ? 1.0 : 0.0;                 // u_0 = Y_f[:, 0] (cmtf.py:88)
+  __syncthreads();
+  int it = 0;
+  for (; it < max_iter; ++it) {                                                    // cmtf.py:89
+    for (int m = tid; m < M; m += kLxNT) tq[m] = 0.0;
+    double* wk = wk0;
+    for (int b = 0; b < nb; ++b) {                                                 // cmtf.py:90-103, block by block
+      const int A = bl.b[b].A, B = bl.b[b].B;
+      const int64_t P = (int64_t)A * B;
+      const double* S = bl.b[b].S + (int64_t)fold * M * P;
+      for (int64_t c = tid; c < P; c += kLxNT) {                                     // Z_b = X_b x_0 u = S_b^T q
+        double s = 0.0;
+        int m = 0;
+        for (; m + 4 <= M; m += 4) {
+          const double s0 = S[(int64_t)m * P + c], s1 = S[(int64_t)(m + 1) * P + c], s2 = S[(int64_t)(m + 2) * P + c], s3 = S[(int64_t)(m + 3) * P + c];
+          s = fma(q[m], s0, s);
+          s = fma(q[m + 1], s1, s);
+          s = fma(q[m + 2], s2, s);
+          s = fma(q[m + 3], s3, s);
+        }
+        for (; m < M; ++m) s = fma(q[m], S[(int64_t)m * P + c], s);
+        Z[c] = s;
+      }
+      __syncthreads();
+      if (A == 1) {                                                                  // order 2: Z / norm(Z)
+        double s = 0.0;
+        for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
+        const double nz = sqrt(lx_sum(s, red));
+        for (int64_t c = tid; c < P; c += kLxNT) wB[c] = Z[c] / nz;
+        if (tid == 0) wA[0] = 1.0;
+        __syncthreads();
+      } else {
+        lx_rank1(Z, Zt, A, B, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+      }
+      for (int64_t c = tid; c < P; c += kLxNT) wk[c] = wA[c / B] * wB[c % B];
+      double* oa = bl.b[b].Wa + ((int64_t)fold * R + a) * A;                         // (the last pass's loadings stay)
+      double* ob = bl.b[b].Wb + ((int64_t)fold * R + a) * B;
+      for (int j = tid; j < A; j += kLxNT) oa[j] = wA[j];
+      for (int j = tid; j < B; j += kLxNT) ob[j] = wB[j];
+      __syncthreads();
+      for (int m = wv; m < M; m += kLxWaves) {                                       // Y^T t_b = S_b w_b, added in block order
+        const double s = lx_wave_dot(S + (int64_t)m * P, wk, P, lane);
+        if (lane == 0) tq[m] += s;
+      }
+      __syncthreads();
+      wk += P;
+    }
+    for (int m = tid; m < M; m += kLxNT) tq[m] /= (double)nb;                        // Y^T t, t the blocks' average (cmtf.py:126-127)
+    double qs = 0.0;
+    for (int m = tid; m < M; m += kLxNT) qs = fma(tq[m], tq[m], qs);
+    const double qnrm = sqrt(lx_sum(qs, red));
+    for (int m = tid; m < M; m += kLxNT) qn[m] = tq[m] / qnrm;                       // cmtf.py:128
+    __syncthreads();
+    double d2 = 0.0;                                                                 // |u_old - u|^2 = dq^T G_y dq (cmtf.py:129-130)
+    for (int o = tid; o < M * M; o += kLxNT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
+    d2 = lx_sum(d2, red);
+    for (int m = tid; m < M; m += kLxNT) q[m] = qn[m];
+    __syncthreads();
+    if (it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < tol) { ++it; break; }              // first pass: oldU = inf
+  }
+  bool bad = false;
+  for (int m = tid; m < M; m += kLxNT) { bl.b[0].Q[((int64_t)fold * R + a) * M + m] = q[m]; bad |= !isfinite(q[m]); }
+  if (tid == 0) bl.b[0].n_iter[fold * R + a] = it;
+  double mw = 0.0;
+  double* wk = wk0;
+  for (int b = 0; b < nb; ++b) {                                                   // the MTTKRP operands and mu_b^T w_b
+    const cmtfpls_kfold_state& v = bl.b[b];
+    const int64_t P = (int64_t)v.A * v.B;
+    const double* wa = v.Wa + ((int64_t)fold * R + a) * v.A;
+    const double* wb = v.Wb + ((int64_t)fold * R + a) * v.B;
+    for (int j = tid; j < v.A; j += kLxNT) { v.WA[(int64_t)j * K + fold] = wa[j]; bad |= !isfinite(wa[j]); }
+    for (int j = tid; j < v.B; j += kLxNT) { v.WB[(int64_t)j * K + fold] = wb[j]; bad |= !isfinite(wb[j]); }
+    const double* mean = v.mean + (int64_t)fold * P;
+    double s = 0.0;
+    for (int64_t c = tid; c < P; c += kLxNT) s = fma(mean[c], wk[c], s);
+    mw += lx_sum(s, red);
+    wk += P;
+  }
+  if (bad) atomicOr(bl.b[0].status + fold, 1);
+  double* vec = bl.b[0].vec + (int64_t)fold * kf_vec_len(R, M);
+  if (tid == 0) vec[3 * R + M + 1] = mw / (double)nb;
+  for (int j = 0; j < a; ++j) {                                                    // g_j = mean over blocks of w_b,j^T w_b,a
+    double g = 0.0;
+    for (int b = 0; b < nb; ++b) {
+      const cmtfpls_kfold_state& v = bl.b[b];
+      const double* wa = v.Wa + (int64_t)fold * R * v.A;
+      const double* wb = v.Wb + (int64_t)fold * R * v.B;
+      double sa = 0.0, sb = 0.0;
+      for (int i = tid; i < v.A; i += kLxNT) sa = fma(wa[(int64_t)j * v.A + i], wa[(int64_t)a * v.A + i], sa);
+      for (int i = tid; i < v.B; i += kLxNT) sb = fma(wb[(int64_t)j * v.B + i], wb[(int64_t)a * v.B + i], sb);
+      sa = lx_sum(sa, red);
+      sb = lx_sum(sb, red);
+      g += sa * sb;
+    }
+    if (tid == 0) vec[2 * R + M + 1 + j] = g / (double)nb;
+  }
+}
+
+// out = (1/nb) sum_b sc[b] (n entries each), added in block order
+__global__ __launch_bounds__(256) void kfold_combine_kernel(const double* __restrict__ sc, int nb, int64_t n, double* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += sc[(int64_t)b * n + i];
+    out[i] = s / (double)nb;
+  }
+}
+
+// every view valid, inside the device form, and sharing every field that is not the block's own
+static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* what) {
+  if (!v || nb < 1 || nb > kKfMaxBlocks) { set_error("kfold coupled: 1 <= nb <= 8 block views"); return CMTFPLS_EINVAL; }
+  const cmtfpls_kfold_state& s = v[0];
+  for (int b = 0; b < nb; ++b) {
+    const cmtfpls_kfold_state& o = v[b];
+    if (!kf_state_ok(&o) || o.I != s.I || o.M != s.M || o.K != s.K || o.R != s.R || o.fold_of != s.fold_of || o.Yk != s.Yk ||
+        o.Gy != s.Gy || o.Q != s.Q || o.T != s.T || o.Gt != s.Gt || o.coef != s.coef || o.tm != s.tm || o.Tout != s.Tout ||
+        o.vec != s.vec || o.n_iter != s.n_iter || o.status != s.status || o.part != s.part) {
+      set_error(what);
+      return CMTFPLS_EINVAL;
+    }
+    if (!kf_shape_ok(o.I, o.A, o.B, o.M, o.K, o.R)) {
+      set_error("kfold coupled: a block outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256); refit per fold");
+      return CMTFPLS_EUNSUPPORTED;
+    }
+  }
+  return CMTFPLS_OK;
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -503,6 +707,44 @@ int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, 
     hipLaunchKernelGGL(kfold_downdate_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st, a, in);
   }
   return check_launch("kfold_epilogue");
+}
+
+size_t cmtfpls_kfold_inner_coupled_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb) {
+  if (!blocks || nb < 1 || nb > kKfMaxBlocks || blocks[0].K <= 0) return 0;
+  for (int b = 0; b < nb; ++b)
+    if (blocks[b].A <= 0 || blocks[b].B <= 0) return 0;
+  return (size_t)blocks[0].K * (size_t)kf_coupled_ws_per_fold(kf_coupled_dims(blocks, nb)) * sizeof(double);
+}
+
+int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, int a, double tol, int max_iter, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled: bad block views (the shared fields must be the same in every view)");
+  if (rc) return rc;
+  if (a < 0 || a >= blocks[0].R || max_iter <= 0) { set_error("kfold_inner_coupled: bad argument"); return CMTFPLS_EINVAL; }
+  const KfCoupledDims d = kf_coupled_dims(blocks, nb);
+  const size_t lds = kf_coupled_lds_bytes(d, blocks[0].M);
+  if (lds > 150 * 1024) {
+    set_error("kfold_inner_coupled: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t need = cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb);
+  if (!ws || ws_bytes < need) { set_error("kfold_inner_coupled: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  KfBlocks bl;
+  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
+  bl.nb = nb;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfold_inner_coupled_kernel, dim3(blocks[0].K), dim3(kLxNT), lds, (hipStream_t)stream, bl, a, tol, max_iter,
+                     static_cast<double*>(ws), kf_coupled_ws_per_fold(d), d.pmax, d.nmax, d.amax, d.bmax);
+  return check_launch("kfold_inner_coupled");
+}
+
+int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream) {
+  if (!sc || !out || nb < 1 || nb > kKfMaxBlocks || n <= 0) { set_error("kfold_combine_scores: bad argument"); return CMTFPLS_EINVAL; }
+  int64_t g = (n + 255) / 256;
+  if (g > 65536) g = 65536;
+  hipLaunchKernelGGL(kfold_combine_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sc, nb, n, out);
+  return check_launch("kfold_combine_scores");
 }
 
 }  // extern "C"

@@ -73,6 +73,7 @@ def kfold_predictions(pls_tensor, n_splits: int = 5, folds=None, tol: float = 1e
     fitted without sample i's fold, using its first r components.  folds=None: contiguous folds with the sizes of sklearn's
     KFold(n_splits, shuffle=False); otherwise an int array of fold ids 0..K-1, one per sample.  On the GPU every fold is served
     by the same reads of X (2R in all, X never copied or written: kfold.py); anything outside that form refits once per fold.
+    `pls_tensor` is a fitted tPLS or ctPLS (a coupled model: 2R reads of each block, ``x_reads`` one entry per block).
     Which form ran is recorded on the model (``q2y_report_``)."""
     from .kfold import kfold_run
 

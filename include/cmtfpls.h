@@ -519,6 +519,23 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
 /* kfold_epilogue: stage 0 = the partial Gy of every fold (before component 0; `in` unused); stage 1 = component a's epilogue from
  * `in` = the MTTKRP X_0 WA (.) WB (I x K): a grid of row tiles x folds for the row work, a small solve per fold; stage 2 = the down-date of S from `in` = X_0^T tm (K x A*B), not after the last component. */
 int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream);
+/* K-fold cross-validation of a coupled model (ctPLS: nb blocks sharing the sample mode and one score t, the average of the
+ * blocks' scores).  `blocks` holds nb <= 8 state views, one per block: S, mean, WA, WB, Wa, Wb, Rm, A and B are that block's
+ * (A = 1 for a matrix block); every other field is the same buffer in all views (CMTFPLS_EINVAL otherwise).  Per component a:
+ * kfold_inner_coupled; per block the MTTKRP X_b,0 WA_b (.) WB_b into row b of an nb x I x K stack; kfold_combine_scores of the
+ * stack; kfold_epilogue stage 1 on blocks[0] with the combined scores; and, all but the last component, per block the contraction
+ * X_b,0^T tm and kfold_epilogue stage 2 on blocks[b].  Before component 0: kfold_xcov per block (ydev shared), kfold_epilogue
+ * stage 0 on blocks[0].  2R reads of each block for all folds.  Limits: every block within the limits of kfold_inner and
+ * the blocks' vectors within 150 KB of LDS (CMTFPLS_EUNSUPPORTED otherwise). */
+/* kfold_inner_coupled: component a's inner loop for every fold over all blocks, a 1024-thread workgroup per fold going through the
+ * blocks in turn (Z_b = S_b^T q, rank-1 of Z_b -> w_b, q ∝ sum_b S_b w_b / nb, convergence on dq^T G_y dq): writes every block's
+ * WA / WB (columns k) and Wa / Wb [k, a], the shared Q[k, a], n_iter[k, a], and in vec the block-averaged mu^T w and g.
+ * ws >= cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb) (reads A, B and K of the views). */
+size_t cmtfpls_kfold_inner_coupled_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb);
+int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, int a, double tol, int max_iter, void* ws, size_t ws_bytes,
+                                    void* stream);
+/* kfold_combine_scores: out[i] = (sum_b sc[b * n + i]) / nb for i < n, the blocks added in order; 1 <= nb <= 8. */
+int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
