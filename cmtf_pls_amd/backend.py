@@ -695,6 +695,48 @@ class HipBackend:
                    "kfold_combine_scores")
         return out
 
+    # -- response-permutation test of K-fold Q2Y (validate.permutation_test_q2y, permutation.py): G permutations x K folds per pass --
+    def kfold_wide_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,
+                        ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:
+        """kfold_xcov for a wide centred Y' (I x W, W <= 1024: G permuted responses side by side) on the f64 matrix cores
+        (cmtfpls_kfold_wide_xcov_*): S (K x W x P), the folds' training means (K x P) and, returned, the column sums / sums of
+        squares of all rows (2 P); None when the shape is outside the device form.  The partial-sum workspace is local to the call."""
+        I, P = X2.shape
+        W = Y.shape[1]
+        assert Y.dtype == torch.float64 and Y.is_contiguous() and ydev.is_contiguous() and S.is_contiguous() and P == A * B
+        assert order.dtype == torch.int32 and fold_off.dtype == torch.int32 and S.numel() == K * W * P and mean.numel() == K * P
+        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K)), 256), dtype=torch.uint8, device=self.device)
+        stats = self.empty(2 * P)
+        rc = self._fn("kfold_wide_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), W, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S),
+                                             _ptr(mean), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_wide_xcov")
+        return stats
+
+    def kfold_inner_grouped(self, state, model_fold: torch.Tensor, groups: int, a: int, tol: float, max_iter: int,
+                            ws: torch.Tensor) -> Optional[bool]:
+        """kfold_inner for state.K models in `groups` groups, model m holding out fold model_fold[m] (cmtfpls_kfold_inner_grouped_f64)."""
+        assert model_fold.dtype == torch.int32 and model_fold.numel() == state.K
+        rc = self.lib.cmtfpls_kfold_inner_grouped_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(a), float(tol), int(max_iter),
+                                                      _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner_grouped")
+        return True
+
+    def kfold_epilogue_grouped(self, state, model_fold: torch.Tensor, groups: int, stage: int, a: int,
+                               src: Optional[torch.Tensor]) -> Optional[bool]:
+        """kfold_epilogue for state.K models in `groups` groups (cmtfpls_kfold_epilogue_grouped_f64); held-out scores of group
+        m % groups go to that group's I x R slice of Tout."""
+        assert model_fold.dtype == torch.int32 and model_fold.numel() == state.K
+        rc = self.lib.cmtfpls_kfold_epilogue_grouped_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(stage), int(a), _ptr(src),
+                                                         self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_epilogue_grouped")
+        return True
+
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
         returns a dict of device tensors (T, U, WA, WB, Q, x_mean, y_mean) and host arrays (coef, ssq, n_iter), or None

@@ -141,9 +141,12 @@ static size_t kf_inner_lds_bytes(int A, int B, int M) {
 }
 
 // a workgroup per fold: G_y from the row tiles' partials, the inner loop, then what the row pass needs of the new loadings:
-// mu_k^T w and g_j = w_j^T w_a (Gram of a Khatri-Rao product = product of the mode Grams)
+// mu_k^T w and g_j = w_j^T w_a (Gram of a Khatri-Rao product = product of the mode Grams).
+// GROUPED (permutation test, see "grouped models" below): the "folds" of the state are models, model m holding out fold
+// model_fold[m]; the training means are those of that fold.  Without it model k is fold k and the code is the one it always was.
+template <bool GROUPED>
 __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state st, int a, double tol, int max_iter, double* ws,
-                                                            int64_t ws_per_fold) {
+                                                            int64_t ws_per_fold, const int* __restrict__ model_fold) {
   extern __shared__ double sm[];
   __shared__ double red[kLxWaves];
   __shared__ double bestv[kLxWaves];
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
   if (bad) atomicOr(st.status + fold, 1);
   if (tid == 0) st.n_iter[fold * R + a] = it;
   double* vec = st.vec + (int64_t)fold * kf_vec_len(R, M);
-  const double* mean = st.mean + (int64_t)fold * P;
+  const double* mean = st.mean + (int64_t)(GROUPED ? model_fold[fold] : fold) * P;
   double s = 0.0;
   for (int64_t c = tid; c < P; c += kLxNT) s = fma(mean[c], wk[c], s);     // (wk: the converged loadings' Kronecker product)
   s = lx_sum(s, red);
@@ -206,8 +209,11 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
 // ---- kfold_epilogue ---------------------------------------------------------------------------------------------------------
 // stage 1a, grid (row tiles, folds): t_k = X_0 w_k - (mu_k^T w_k) 1 - T_k[:, :a] g_k for every row of the tile (held-out rows: the
 // projection predict makes, tpls.py:133-142), the training-masked score, u = Y_k q, and the tile's partial sums of
-// T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t
-__global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ sc) {
+// T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t.  GROUPED: model k holds out fold model_fold[k] and writes
+// its held-out scores to group k % groups of Tout (groups x I x R)
+template <bool GROUPED>
+__global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ sc,
+                                                                   const int* __restrict__ model_fold, int groups) {
   constexpr int NW = kKfRowThreads / 64;
   __shared__ double acc[NW][2 * kKfMaxR + 1 + kKfMaxM];
   __shared__ double q[kKfMaxM], g[kKfMaxR];
@@ -215,6 +221,8 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
   const int I = st.I, M = st.M, K = st.K, R = st.R, kk = a + 1, NT = kf_tiles(I), nv = 2 * kk + 1 + M;
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
   const double mw = vec[3 * R + M + 1];
+  const int own = GROUPED ? model_fold[k] : k;
+  double* Tout = GROUPED ? st.Tout + (int64_t)(k % groups) * I * R : st.Tout;
   for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
   for (int j = tid; j < a; j += kKfRowThreads) g[j] = vec[2 * R + M + 1 + j];
   for (int v = tid; v < NW * (2 * kKfMaxR + 1 + kKfMaxM); v += kKfRowThreads) (&acc[0][0])[v] = 0.0;
@@ -232,8 +240,8 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
       t = sc[(int64_t)i * K + k] - mw;
       for (int j = 0; j < a; ++j) t = fma(-T[(int64_t)i * R + j], g[j], t);
       T[(int64_t)i * R + a] = t;
-      train = st.fold_of[i] != k;
-      if (!train) st.Tout[(int64_t)i * R + a] = t;
+      train = st.fold_of[i] != own;
+      if (!train) Tout[(int64_t)i * R + a] = t;
       st.tm[(int64_t)i * K + k] = train ? t : 0.0;
       if (train)
         for (int m = 0; m < M; ++m) u = fma(Yk[(int64_t)i * M + m], q[m], u);
@@ -319,13 +327,16 @@ __global__ __launch_bounds__(64) void kfold_solve_kernel(cmtfpls_kfold_state st,
 
 // stage 0 / 1c, grid (row tiles, folds): (deflate: Y_k -= (T b) q^T on the training rows, tpls.py:113) and the tile's partial
 // Y_k^T Y_k for the next component's convergence test, rows staged through LDS a chunk at a time
-__global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfold_state st, int a, int deflate) {
+template <bool GROUPED>
+__global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfold_state st, int a, int deflate,
+                                                                    const int* __restrict__ model_fold) {
   constexpr int EPT = kKfMaxM * kKfMaxM / kKfRowThreads;          // Gram entries per thread
   __shared__ double Ys[kKfChunk][kKfMaxM + 1];
   __shared__ double q[kKfMaxM], b[kKfMaxR];
   const int tid = threadIdx.x, tile = blockIdx.x, k = blockIdx.y;
   const int I = st.I, M = st.M, R = st.R, kk = a + 1, NT = kf_tiles(I);
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
+  const int own = GROUPED ? model_fold[k] : k;
   if (deflate) {
     for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
     for (int j = tid; j < kk; j += kKfRowThreads) b[j] = vec[j];
@@ -344,7 +355,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
       double y = 0.0;
       if (i < hi) {
         y = Yk[(int64_t)i * M + m];
-        if (deflate && st.fold_of[i] != k) {
+        if (deflate && st.fold_of[i] != own) {
           double yh = 0.0;
           for (int j = 0; j < kk; ++j) yh = fma(T[(int64_t)i * R + j], b[j], yh);
           y = fma(-yh, q[m], y);
@@ -376,7 +387,9 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
 // stage 2, a thread per column and fold: r_a = X_c^T t_a = rs - (1^T t) mu (rs = X_0^T (t * train) from the contraction pass), kept
 // for later components; X_{a+1}^T yhat = sum_{j<=a} b_j r_j - sum_{j<=a} c_j w_j; S -= w ya^T + (X_{a+1}^T yhat) q^T
 // (fitrun_xcov._finish_xcov_nowrite, cmtfpls_s_downdate_f64)
-__global__ __launch_bounds__(kKfCols) void kfold_downdate_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ rs) {
+template <bool GROUPED>
+__global__ __launch_bounds__(kKfCols) void kfold_downdate_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ rs,
+                                                                 const int* __restrict__ model_fold) {
   const int64_t c = (int64_t)blockIdx.x * kKfCols + threadIdx.x;
   const int k = blockIdx.y;
   const int A = st.A, B = st.B, M = st.M, R = st.R;
@@ -384,7 +397,7 @@ __global__ __launch_bounds__(kKfCols) void kfold_downdate_kernel(cmtfpls_kfold_s
   if (c >= P) return;
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
   const int ia = (int)(c / B), ib = (int)(c % B);
-  const double r = rs[(int64_t)k * P + c] - vec[2 * R + M] * st.mean[(int64_t)k * P + c];
+  const double r = rs[(int64_t)k * P + c] - vec[2 * R + M] * st.mean[(int64_t)(GROUPED ? model_fold[k] : k) * P + c];
   st.Rm[((int64_t)k * R + a) * P + c] = r;
   double v = 0.0;
   for (int j = 0; j < a; ++j) v = fma(vec[j], st.Rm[((int64_t)k * R + j) * P + c], v);
@@ -638,6 +651,187 @@ static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* wha
   return CMTFPLS_OK;
 }
 
+// ---- grouped models (permutation test, permutation.py) ---------------------------------------------------------------------
+// A pass of the response-permutation test carries G permuted responses x K folds = n <= kKfMaxK models; model m = k G + p holds
+// out fold k and is fitted to Y[pi_p].  X is never permuted, so every model reads the same X_0 and the models differ only in Y,
+// in which rows train them and in their loadings:
+//   kfold_wide      S_f = X[rows_f]^T Y' for every fold f from ONE pass over X, Y' = [Y[pi_1] - ybar, .., Y[pi_G] - ybar]
+//                   (W = G M <= 1024 columns) on v_mfma_f64_16x16x4_f64; kfold_finish_kernel (the all-minus-own identity, column-
+//                   block-wise) then gives model m's S as the m-th M x P block of K x W x P
+//   the inner loop, the score pass, the epilogue and the contraction are those of the folds above with n columns; the grouped
+//   instantiations (GROUPED = true) read which fold a model holds out from model_fold[m] and write its held-out scores to group
+//   m % groups of Tout (groups x I x R)
+constexpr int kKfWideMaxW = 1024, kKfWideCols = 256, kKfWideUn = 4;
+
+struct KfWidePlan {
+  int nyb, mt, nch;                  // column blocks of Y' (16 mt columns each), row chunks per fold
+};
+
+// Y' column blocks of <= 64 columns (MT <= 4 MFMA tiles per wavefront, so the accumulators stay in registers); row chunks per
+// fold so that the grid has >= ~2048 workgroups; <= 16
+static KfWidePlan kf_wide_plan(int64_t I, int64_t P, int W, int K) {
+  KfWidePlan p;
+  p.nyb = (W + 63) / 64;
+  p.mt = (W + 16 * p.nyb - 1) / (16 * p.nyb);
+  const int64_t ct = (P + kKfWideCols - 1) / kKfWideCols;
+  int64_t ch = (2048 + ct * p.nyb * K - 1) / (ct * p.nyb * K);
+  const int64_t per_fold = I / K;
+  if (ch > per_fold / 64) ch = per_fold / 64;
+  if (ch > 16) ch = 16;
+  p.nch = ch < 1 ? 1 : (int)ch;
+  return p;
+}
+
+// grid (column tiles x Y' blocks, folds x row chunks): a wavefront owns 64 columns of X (4 consecutive per lane) and 16 MT columns
+// of Y', and goes through its chunk's rows in the host's fold-sorted order, four rows per MFMA (tile mapping of xcov.hip):
+//   A = Y'[row(kq)][y0 + 16 mt + nn], B of MFMA e = X[row(kq)][c + e], D tile e register g = S[y0 + 16 mt + kq + 4 g][c + e].
+// The Y' blocks of one column tile are neighbours in the launch order, so X streams from HBM once and the other blocks meet it in
+// the caches.  The first Y' block also sums every column and its squares (the fold's partial column sums: the training means
+// and the NaN / offset statistics).  Partials (W + 2 rows per chunk) go to `part` in the layout of kfold_partials_kernel; every
+// sum runs in a fixed order, so the result is the same bits on every run.
+template <typename T, int MT, bool VEC>
+__global__ __launch_bounds__(kKfWideCols) void kfold_wide_kernel(const T* __restrict__ X, int64_t P, const double* __restrict__ Y, int W,
+                                                                 const int* __restrict__ order, const int* __restrict__ off, int nyb,
+                                                                 int nch, double* __restrict__ part) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, kq = lane >> 4, nn = lane & 15;
+  const int yb = (int)(blockIdx.x % (unsigned)nyb);
+  const int64_t ct = blockIdx.x / (unsigned)nyb;
+  const int k = (int)blockIdx.y / nch, ch = (int)blockIdx.y % nch;
+  const int64_t cb = (ct * 4 + wv) * 64;
+  if (cb >= P) return;                                         // whole wavefront past the last column
+  const int64_t c = cb + 4 * nn;
+  const int lo0 = off[k], n = off[k + 1] - lo0, len = (n + nch - 1) / nch;
+  const int lo = lo0 + min(n, ch * len), hi = lo0 + min(n, (ch + 1) * len);
+  const int y0 = yb * 16 * MT;
+  using XV = Pack<T, 4>;
+  lx_d4_t acc[MT][4];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[mt][e] = lx_d4_t{0.0, 0.0, 0.0, 0.0};
+  bool mok[MT], cok[4];
+  int ycol[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    mok[mt] = y0 + 16 * mt + nn < W;
+    ycol[mt] = mok[mt] ? y0 + 16 * mt + nn : W - 1;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) cok[e] = c + e < P;
+  const int64_t cc = (c < P) ? c : (VEC ? P - 4 : P - 1);     // (VEC: P % 4 == 0, so c < P means c + 3 < P)
+  double cs[4] = {0.0, 0.0, 0.0, 0.0}, cq[4] = {0.0, 0.0, 0.0, 0.0};
+  // loads are unconditional (clamped row and column) and masked in the MFMAs
+  for (int r = lo; r < hi; r += 4 * kKfWideUn) {
+    XV x[kKfWideUn];
+    double a[kKfWideUn][MT];
+#pragma unroll
+    for (int s = 0; s < kKfWideUn; ++s) {
+      const int pos = r + 4 * s + kq;
+      const int64_t i = order[pos < hi ? pos : hi - 1];
+      if (VEC) {
+        x[s] = *reinterpret_cast<const XV*>(X + i * P + cc);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[s].e[e] = X[i * P + (cok[e] ? c + e : P - 1)];
+      }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) a[s][mt] = Y[i * W + ycol[mt]];
+    }
+#pragma unroll
+    for (int s = 0; s < kKfWideUn; ++s) {
+      const bool rok = r + 4 * s + kq < hi;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double b = (rok && cok[e]) ? (double)x[s].e[e] : 0.0;
+        cs[e] += b;
+        cq[e] = fma(b, b, cq[e]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt][e] = __builtin_amdgcn_mfma_f64_16x16x4f64((rok && mok[mt]) ? a[s][mt] : 0.0, b, acc[mt][e], 0, 0, 0);
+      }
+    }
+  }
+  double* base = part + (int64_t)(k * nch + ch) * (W + 2) * P;
+  if (yb == 0) {                                               // the four lane groups hold the same columns for different rows
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double v = cs[e], w = cq[e];
+      v += __shfl_xor(v, 16, kWave);
+      v += __shfl_xor(v, 32, kWave);
+      w += __shfl_xor(w, 16, kWave);
+      w += __shfl_xor(w, 32, kWave);
+      if (kq == 0 && cok[e]) { base[(int64_t)W * P + c + e] = v; base[(int64_t)(W + 1) * P + c + e] = w; }
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int j = y0 + 16 * mt + kq + 4 * g;
+      if (j < W) {
+        double* dst = base + (int64_t)j * P + c;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (cok[e]) dst[e] = acc[mt][e][g];
+      }
+    }
+}
+
+template <typename T, int MT>
+static void kf_wide_launch(dim3 g, hipStream_t st, const T* X, int64_t P, const double* Y, int W, const int* order, const int* off,
+                           int nyb, int nch, double* part) {
+  if (P % 4 == 0)
+    hipLaunchKernelGGL((kfold_wide_kernel<T, MT, true>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);
+  else
+    hipLaunchKernelGGL((kfold_wide_kernel<T, MT, false>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);
+}
+
+template <typename T>
+static int run_kfold_wide(const T* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off, int K,
+                          const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!X || !Y || !order || !fold_off || !ydev || !S || !mean || !stats || I <= 0 || A <= 0 || B <= 0 || W <= 0 || K <= 0) {
+    set_error("kfold_wide_xcov: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  const int64_t P = (int64_t)A * B;
+  if (K < 2 || K > kKfMaxK || W > kKfWideMaxW || I < K || I > (int64_t)1 << 30 || P > (int64_t)1 << 24) {
+    set_error("kfold_wide_xcov: shape outside the device form (2 <= K <= 32, W <= 1024, A * B <= 2^24)");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t need = cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K);
+  if (!ws || ws_bytes < need) { set_error("kfold_wide_xcov: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const KfWidePlan pl = kf_wide_plan(I, P, W, K);
+  double* part = static_cast<double*>(ws);
+  const int64_t ct = (P + kKfWideCols - 1) / kKfWideCols;
+  const dim3 g((unsigned)(ct * pl.nyb), (unsigned)(K * pl.nch));
+  switch (pl.mt) {
+    case 1: kf_wide_launch<T, 1>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
+    case 2: kf_wide_launch<T, 2>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
+    case 3: kf_wide_launch<T, 3>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
+    default: kf_wide_launch<T, 4>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
+  }
+  int rc = check_launch("kfold_wide_xcov");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kfold_finish_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols)), dim3(kKfCols), 0, st, P, W, K, pl.nch, (int)I,
+                     fold_off, part, ydev, S, mean, stats);
+  return check_launch("kfold_wide_xcov");
+}
+
+// the grouped entries: n = st->K models in `groups` groups, model m holding out fold model_fold[m] < n / groups (the folds of
+// st->mean); I >= the number of folds (every model of a fold shares its rows)
+static int kf_grouped_check(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int a, const char* what) {
+  if (!kf_state_ok(st) || !model_fold || groups < 1 || st->K % groups != 0 || a < 0 || a >= st->R) {
+    set_error(what);
+    return CMTFPLS_EINVAL;
+  }
+  const int folds = st->K / groups;
+  if (folds < 2 || st->I < folds || !kf_shape_ok(st->I < st->K ? st->K : st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold grouped: shape outside the device form (n <= 32 models, M <= 64, R <= 64, min(A, B) <= 256); refit");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  return CMTFPLS_OK;
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -679,9 +873,9 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
   if (!ws || ws_bytes < need) { set_error("kfold_inner: workspace too small"); return CMTFPLS_EWORKSPACE; }
   const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
   if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfold_inner_kernel, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
-                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfold_inner_kernel<false>, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
+                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)), nullptr);
   return check_launch("kfold_inner");
 }
 
@@ -697,14 +891,15 @@ int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, 
   hipStream_t s = (hipStream_t)stream;
   const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
   if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, 0);
+    hipLaunchKernelGGL(kfold_ydefl_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr);
   } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, in);
+    hipLaunchKernelGGL(kfold_rows_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, 1);
     hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel, rows, dim3(kKfRowThreads), 0, s, *st, a, 1);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr);
   } else {
     const int64_t P = (int64_t)st->A * st->B;
-    hipLaunchKernelGGL(kfold_downdate_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st, a, in);
+    hipLaunchKernelGGL(kfold_downdate_kernel<false>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
+                       a, in, nullptr);
   }
   return check_launch("kfold_epilogue");
 }
@@ -745,6 +940,57 @@ int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double
   if (g > 65536) g = 65536;
   hipLaunchKernelGGL(kfold_combine_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sc, nb, n, out);
   return check_launch("kfold_combine_scores");
+}
+
+size_t cmtfpls_kfold_wide_xcov_workspace_bytes(int64_t I, int64_t P, int W, int K) {
+  if (I <= 0 || P <= 0 || W <= 0 || K <= 0) return 0;
+  return (size_t)K * kf_wide_plan(I, P, W, K).nch * (size_t)(W + 2) * (size_t)P * sizeof(double);
+}
+
+int cmtfpls_kfold_wide_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_wide<float>(X, I, A, B, Y, W, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_wide_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_wide<double>(X, I, A, B, Y, W, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int a, double tol, int max_iter,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_inner_grouped: bad argument");
+  if (rc) return rc;
+  if (max_iter <= 0) { set_error("kfold_inner_grouped: bad argument"); return CMTFPLS_EINVAL; }
+  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
+  if (!ws || ws_bytes < need) { set_error("kfold_inner_grouped: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfold_inner_kernel<true>, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
+                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)), model_fold);
+  return check_launch("kfold_inner_grouped");
+}
+
+int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
+                                       void* stream) {
+  int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_epilogue_grouped: bad argument");
+  if (rc) return rc;
+  if (stage < 0 || stage > 2 || (stage > 0 && !in)) { set_error("kfold_epilogue_grouped: bad argument"); return CMTFPLS_EINVAL; }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
+  if (stage == 0) {
+    hipLaunchKernelGGL(kfold_ydefl_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, model_fold);
+  } else if (stage == 1) {
+    hipLaunchKernelGGL(kfold_rows_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, model_fold, groups);
+    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, model_fold);
+  } else {
+    const int64_t P = (int64_t)st->A * st->B;
+    hipLaunchKernelGGL(kfold_downdate_kernel<true>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
+                       a, in, model_fold);
+  }
+  return check_launch("kfold_epilogue_grouped");
 }
 
 }  // extern "C"

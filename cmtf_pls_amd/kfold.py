@@ -194,8 +194,9 @@ def _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M) -> np.ndarray:
     return pred
 
 
-def device_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
-    """The device form: (pred (R, I, M), report) or (None, why)."""
+def device_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, grouped: bool = False):
+    """The device form: (pred (R, I, M), report) or (None, why).  grouped=True runs the inner loop and the epilogue through the
+    permutation test's grouped entries with model k = fold k in one group (the same bits: tests/test_gpu_permutation.py)."""
     from .tpls import _as_torch_dtype, to_device_copy
 
     eng = pls._get_engine()
@@ -232,17 +233,24 @@ def device_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
         ws = torch.empty(max(be.kfold_inner_workspace_bytes(A, B, K), 256), dtype=torch.uint8, device=dev)
         sc = be.empty(I, K)
         rs = be.empty(K, P)
-        if be.kfold_epilogue(st, 0, 0, None) is None:
+        if grouped:
+            mf = torch.arange(K, dtype=torch.int32, device=dev)
+            inner = lambda a: be.kfold_inner_grouped(st, mf, 1, a, tol, max_iter, ws)
+            epilogue = lambda stage, a, src: be.kfold_epilogue_grouped(st, mf, 1, stage, a, src)
+        else:
+            inner = lambda a: be.kfold_inner(st, a, tol, max_iter, ws)
+            epilogue = lambda stage, a, src: be.kfold_epilogue(st, stage, a, src)
+        if epilogue(0, 0, None) is None:
             return None, "shape outside cmtfpls_kfold_epilogue_f64"
         for a in range(R):
-            if be.kfold_inner(st, a, tol, max_iter, ws) is None:
+            if inner(a) is None:
                 return None, "shape outside cmtfpls_kfold_inner_f64"
             if be.mttkrp(X2, A, B, buf["WA"], buf["WB"], sc) is None:                   # X_0 [w_1 .. w_K]: one read
                 return None, "the folds' loadings outside cmtfpls_mttkrp_*"
-            be.kfold_epilogue(st, 1, a, sc)
+            epilogue(1, a, sc)
             if a + 1 < R:
                 be.xcov(X2, buf["tm"], False, out=rs)                                   # X_0^T [t_k * train_k]: one read
-                be.kfold_epilogue(st, 2, a, rs)
+                epilogue(2, a, rs)
         status = buf["status"].cpu().numpy()
         if status.any():
             return None, f"non-finite loadings or coefficients in folds {np.flatnonzero(status).tolist()} of the device form"

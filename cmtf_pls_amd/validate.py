@@ -89,3 +89,18 @@ def get_q2y_kfold(pls_tensor, n_splits: int = 5, folds=None, per_component: bool
     numerator = ((pred - Y_actual) ** 2).reshape(pred.shape[0], -1).sum(axis=1)
     q = 1 - numerator / (Y_actual ** 2).sum()
     return q if per_component else float(q[-1])
+
+
+def permutation_test_q2y(pls_tensor, n_permutations: int = 99, n_splits: int = 5, folds=None, permutations=None, random_state=0,
+                         per_component: bool = False, device_folds: bool = True) -> dict:
+    """Response-permutation test of K-fold Q2Y: permutation p refits the K folds on Y[pi_p] (X and the folds stay as they are) and
+    scores them with get_q2y_kfold's formula against Y[pi_p].  Permutations: P = n_permutations draws of
+    np.random.default_rng(random_state).permutation(I), in order, or `permutations`, a (P, I) array whose rows are permutations of
+    0..I-1 (ValueError otherwise, or when n_permutations < 1).  Returns {"q2y": get_q2y_kfold(pls_tensor, n_splits, folds,
+    per_component), "null": (P,) or (P, R), "p_value": (1 + #{null >= q2y}) / (P + 1) (per component with per_component),
+    "permutations": (P, I)}.  On the GPU a tPLS runs floor(32 / K) permutations x K folds per pass from shared reads of X (2R reads
+    per pass, permutation.py); anything else refits every fold of every permutation.  Which form ran is recorded on the model
+    (``q2y_report_``)."""
+    from .permutation import permutation_test
+
+    return permutation_test(pls_tensor, n_permutations, n_splits, folds, permutations, random_state, per_component, device_folds)

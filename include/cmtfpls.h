@@ -536,6 +536,30 @@ int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, i
                                     void* stream);
 /* kfold_combine_scores: out[i] = (sum_b sc[b * n + i]) / nb for i < n, the blocks added in order; 1 <= nb <= 8. */
 int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream);
+
+/* ---- Response-permutation test of K-fold Q2Y (validate.permutation_test_q2y) -------------------------------------------------
+ * A pass carries G permuted responses x K folds = n <= 32 models in one cmtfpls_kfold_state (its K = n): model m = k G + p holds
+ * out fold k = model_fold[m] and is fitted to Y[pi_p]; every model shares each read of X.  Per pass: kfold_wide_xcov (every model's
+ * training cross-covariance from ONE pass over X), kfold_epilogue_grouped stage 0, then per component kfold_inner_grouped, the
+ * MTTKRP X_0 WA (.) WB with n columns, kfold_epilogue_grouped stage 1, and (all but the last) the contraction X_0^T tm and stage 2.
+ * The state's mean is K x A*B (per fold) and its Tout is G x I x R (group g = m % G: the held-out scores of permutation g).
+ * With model_fold[m] = m and groups = 1 the grouped entries are bitwise cmtfpls_kfold_inner_f64 / cmtfpls_kfold_epilogue_f64. */
+/* kfold_wide_xcov: S (K x W x A*B) = for every fold k, X_c[train_k]^T (Y'[train_k] - ydev_k) with Y' (I x W, W <= 1024 columns,
+ * already centred by the all-rows mean) and ydev (K x W) the training mean of Y' per fold; the fold-grouped partials on the f64
+ * matrix cores from ONE pass over X in the fold-sorted row order `order`, fold k's rows at positions fold_off[k] .. fold_off[k+1]-1.
+ * Also mean (K x A*B, training column means) and stats (2 A*B: column sums and sums of squares of all rows).  Sums run in a fixed
+ * order (the same bits on every run).  ws >= cmtfpls_kfold_wide_xcov_workspace_bytes(I, A * B, W, K). */
+size_t cmtfpls_kfold_wide_xcov_workspace_bytes(int64_t I, int64_t P, int W, int K);
+int cmtfpls_kfold_wide_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_wide_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+/* kfold_inner_grouped / kfold_epilogue_grouped: cmtfpls_kfold_inner_f64 / cmtfpls_kfold_epilogue_f64 for st->K = n models in
+ * `groups` groups (n % groups == 0), model m holding out fold model_fold[m] (device, n entries, < n / groups). */
+int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int a, double tol, int max_iter,
+                                    void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
+                                       void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
