@@ -737,6 +737,16 @@ class HipBackend:
         _lib.check(rc, "kfold_epilogue_grouped")
         return True
 
+    # -- repeated K-fold Q2Y (validate.get_q2y_repeated_kfold, repeated.py): G shuffled splits x K folds per pass ----------------
+    def kfold_epilogue_splits(self, state, splits: int, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
+        """kfold_epilogue for state.K models in `splits` split-major splits (cmtfpls_kfold_epilogue_splits_f64): fold_of is
+        splits x I, and the held-out scores of split m // (K / splits) go to that split's I x R slice of Tout."""
+        rc = self.lib.cmtfpls_kfold_epilogue_splits_f64(ctypes.byref(state), int(splits), int(stage), int(a), _ptr(src), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_epilogue_splits")
+        return True
+
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
         returns a dict of device tensors (T, U, WA, WB, Q, x_mean, y_mean) and host arrays (coef, ssq, n_iter), or None

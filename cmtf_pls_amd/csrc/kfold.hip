@@ -21,6 +21,9 @@ namespace cmtfpls {
 
 constexpr int kKfMaxK = 32, kKfMaxM = 64, kKfMaxR = 64, kKfMaxN = 256;
 constexpr int kKfCols = 256;          // columns per workgroup of the column-owner kernels (one per thread)
+// which fold a model holds out and where its held-out scores go (kfold_rows_kernel, kfold_ydefl_kernel): model k = fold k
+// (kKfPlain), the grouped models of the permutation test (kKfGrouped) or the split-major models of repeated K-fold (kKfSplits)
+enum KfMode : int { kKfPlain = 0, kKfGrouped = 1, kKfSplits = 2 };
 
 // ---- kfold_xcov ------------------------------------------------------------------------------------------------------------
 // Row chunks per fold so that the partial-sum grid has >= ~2048 workgroups (a thread per column, rows sequential: the rows of a
@@ -209,9 +212,11 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
 // ---- kfold_epilogue ---------------------------------------------------------------------------------------------------------
 // stage 1a, grid (row tiles, folds): t_k = X_0 w_k - (mu_k^T w_k) 1 - T_k[:, :a] g_k for every row of the tile (held-out rows: the
 // projection predict makes, tpls.py:133-142), the training-masked score, u = Y_k q, and the tile's partial sums of
-// T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t.  GROUPED: model k holds out fold model_fold[k] and writes
-// its held-out scores to group k % groups of Tout (groups x I x R)
-template <bool GROUPED>
+// T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t.  kKfGrouped: model k holds out fold model_fold[k] and writes
+// its held-out scores to group k % groups of Tout (groups x I x R).  kKfSplits: `groups` is the folds per split; model k holds out
+// fold k % groups of split k / groups, whose fold map is row k / groups of fold_of, and writes its held-out scores to that split's
+// slot of Tout (splits x I x R)
+template <int MODE>
 __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ sc,
                                                                    const int* __restrict__ model_fold, int groups) {
   constexpr int NW = kKfRowThreads / 64;
@@ -221,8 +226,10 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
   const int I = st.I, M = st.M, K = st.K, R = st.R, kk = a + 1, NT = kf_tiles(I), nv = 2 * kk + 1 + M;
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
   const double mw = vec[3 * R + M + 1];
-  const int own = GROUPED ? model_fold[k] : k;
-  double* Tout = GROUPED ? st.Tout + (int64_t)(k % groups) * I * R : st.Tout;
+  const int own = MODE == kKfGrouped ? model_fold[k] : MODE == kKfSplits ? k % groups : k;
+  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / groups) * I : st.fold_of;
+  double* Tout = MODE == kKfGrouped ? st.Tout + (int64_t)(k % groups) * I * R
+                 : MODE == kKfSplits ? st.Tout + (int64_t)(k / groups) * I * R : st.Tout;
   for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
   for (int j = tid; j < a; j += kKfRowThreads) g[j] = vec[2 * R + M + 1 + j];
   for (int v = tid; v < NW * (2 * kKfMaxR + 1 + kKfMaxM); v += kKfRowThreads) (&acc[0][0])[v] = 0.0;
@@ -240,7 +247,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
       t = sc[(int64_t)i * K + k] - mw;
       for (int j = 0; j < a; ++j) t = fma(-T[(int64_t)i * R + j], g[j], t);
       T[(int64_t)i * R + a] = t;
-      train = st.fold_of[i] != own;
+      train = fold_of[i] != own;
       if (!train) Tout[(int64_t)i * R + a] = t;
       st.tm[(int64_t)i * K + k] = train ? t : 0.0;
       if (train)
@@ -326,17 +333,19 @@ __global__ __launch_bounds__(64) void kfold_solve_kernel(cmtfpls_kfold_state st,
 }
 
 // stage 0 / 1c, grid (row tiles, folds): (deflate: Y_k -= (T b) q^T on the training rows, tpls.py:113) and the tile's partial
-// Y_k^T Y_k for the next component's convergence test, rows staged through LDS a chunk at a time
-template <bool GROUPED>
+// Y_k^T Y_k for the next component's convergence test, rows staged through LDS a chunk at a time.  MODE: the training rows as in
+// kfold_rows_kernel (`folds`: the folds per split of kKfSplits)
+template <int MODE>
 __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfold_state st, int a, int deflate,
-                                                                    const int* __restrict__ model_fold) {
+                                                                    const int* __restrict__ model_fold, int folds) {
   constexpr int EPT = kKfMaxM * kKfMaxM / kKfRowThreads;          // Gram entries per thread
   __shared__ double Ys[kKfChunk][kKfMaxM + 1];
   __shared__ double q[kKfMaxM], b[kKfMaxR];
   const int tid = threadIdx.x, tile = blockIdx.x, k = blockIdx.y;
   const int I = st.I, M = st.M, R = st.R, kk = a + 1, NT = kf_tiles(I);
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
-  const int own = GROUPED ? model_fold[k] : k;
+  const int own = MODE == kKfGrouped ? model_fold[k] : MODE == kKfSplits ? k % folds : k;
+  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / folds) * I : st.fold_of;
   if (deflate) {
     for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
     for (int j = tid; j < kk; j += kKfRowThreads) b[j] = vec[j];
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
       double y = 0.0;
       if (i < hi) {
         y = Yk[(int64_t)i * M + m];
-        if (deflate && st.fold_of[i] != own) {
+        if (deflate && fold_of[i] != own) {
           double yh = 0.0;
           for (int j = 0; j < kk; ++j) yh = fma(T[(int64_t)i * R + j], b[j], yh);
           y = fma(-yh, q[m], y);
@@ -663,6 +672,7 @@ static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* wha
 //   m % groups of Tout (groups x I x R)
 constexpr int kKfWideMaxW = 1024, kKfWideCols = 256, kKfWideUn = 4;
 
+
 struct KfWidePlan {
   int nyb, mt, nch;                  // column blocks of Y' (16 mt columns each), row chunks per fold
 };
@@ -832,6 +842,14 @@ static int kf_grouped_check(const cmtfpls_kfold_state* st, const int* model_fold
   return CMTFPLS_OK;
 }
 
+// ---- split-major models (repeated K-fold, repeated.py) ----------------------------------------------------------------------
+// A pass of repeated K-fold carries G shuffled splits x K folds = n <= kKfMaxK models; model m = g K + k holds out fold k of split
+// g.  Each split's S, mean and Y side are a contiguous K-model slice of the state, built per split by kfold_xcov; the inner loop
+// (kfold_inner, or kfold_inner_coupled on block views), the score pass, the contraction and stages 0 and 2 are those of the folds
+// above with n columns.  Only stage 1 differs (kKfSplits instantiations of kfold_rows_kernel / kfold_ydefl_kernel): fold_of is
+// splits x I, model m reads row m / K of it, and its held-out scores go to slot m / K of Tout (splits x I x R).  The splits are
+// partitions of the rows, so every row of every slot is written exactly once.
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -891,11 +909,11 @@ int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, 
   hipStream_t s = (hipStream_t)stream;
   const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
   if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr);
+    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr, 1);
   } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, 1);
+    hipLaunchKernelGGL(kfold_rows_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, 1);
     hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<false>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr, 1);
   } else {
     const int64_t P = (int64_t)st->A * st->B;
     hipLaunchKernelGGL(kfold_downdate_kernel<false>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
@@ -980,17 +998,43 @@ int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int*
   hipStream_t s = (hipStream_t)stream;
   const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
   if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, model_fold);
+    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, model_fold, 1);
   } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, model_fold, groups);
+    hipLaunchKernelGGL(kfold_rows_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, model_fold, groups);
     hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<true>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, model_fold);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, model_fold, 1);
   } else {
     const int64_t P = (int64_t)st->A * st->B;
     hipLaunchKernelGGL(kfold_downdate_kernel<true>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
                        a, in, model_fold);
   }
   return check_launch("kfold_epilogue_grouped");
+}
+
+int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits, int stage, int a, const double* in, void* stream) {
+  if (!kf_state_ok(st) || splits < 1 || st->K % splits != 0 || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+    set_error("kfold_epilogue_splits: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  const int folds = st->K / splits;
+  if (folds < 2 || !kf_shape_ok(st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold_epilogue_splits: shape outside the device form (2 <= folds, n <= 32 models <= I, M <= 64, R <= 64); refit");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
+  if (stage == 0) {
+    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr, folds);
+  } else if (stage == 1) {
+    hipLaunchKernelGGL(kfold_rows_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, folds);
+    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr, folds);
+  } else {
+    const int64_t P = (int64_t)st->A * st->B;
+    hipLaunchKernelGGL(kfold_downdate_kernel<false>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
+                       a, in, nullptr);
+  }
+  return check_launch("kfold_epilogue_splits");
 }
 
 }  // extern "C"

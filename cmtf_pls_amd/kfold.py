@@ -62,6 +62,34 @@ def fold_ids(n_samples: int, n_splits: int = 5, folds=None) -> Tuple[np.ndarray,
     return f, K
 
 
+def repeated_fold_ids(n_samples: int, n_splits: int = 5, n_repeats: int = 10, random_state=0, folds=None) -> Tuple[np.ndarray, int]:
+    """The (S, n_samples) fold ids of S shuffled K-fold splits and K.  folds=None: the test folds of sklearn's
+    RepeatedKFold(n_splits, n_repeats, random_state=int) in its order (one RandomState(random_state) shuffles arange(n_samples)
+    once per repeat; contiguous blocks of the shuffled index are folds 0..K-1 with KFold's sizes); otherwise `folds` itself, an
+    (S, n_samples) integer array, each row checked as fold_ids checks a split, with the same K in every row."""
+    if folds is None:
+        if isinstance(random_state, bool) or not isinstance(random_state, (int, np.integer)):
+            raise ValueError(f"random_state must be an int (reproducible splits), got {random_state!r}")
+        if int(n_repeats) < 1:
+            raise ValueError(f"n_repeats must be at least 1, got {n_repeats}")
+        base, K = fold_ids(n_samples, n_splits)                   # KFold's contiguous fold of every position
+        rs = np.random.RandomState(int(random_state))
+        ids = np.empty((int(n_repeats), n_samples), dtype=np.int64)
+        for g in range(int(n_repeats)):
+            idx = np.arange(n_samples)
+            rs.shuffle(idx)
+            ids[g, idx] = base                                    # sample idx[j] is in the fold of position j
+        return ids, K
+    f = np.asarray(folds)
+    if f.ndim != 2 or f.shape[1] != n_samples or f.shape[0] < 1:
+        raise ValueError(f"folds must be an (S, {n_samples}) array of fold ids with S >= 1, got shape {f.shape}")
+    rows = [fold_ids(n_samples, folds=row) for row in f]
+    Ks = sorted({K for _, K in rows})
+    if len(Ks) != 1:
+        raise ValueError(f"every split must have the same number of folds, got {Ks}")
+    return np.stack([r for r, _ in rows]), Ks[0]
+
+
 def _host(a) -> np.ndarray:
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
@@ -153,16 +181,22 @@ def _decline(pls, X, Y, ids, K) -> Optional[str]:
     return _decline_blocks(pls, [X], ["X"], Y, K, ("kfold_xcov", "kfold_inner", "kfold_epilogue", "mttkrp", "xcov"))
 
 
-def _fold_y(Yh: np.ndarray, ids: np.ndarray, K: int):
-    """What the folds need of Y: the fold-sorted row order and offsets, the mean of all rows, each fold's training means nu
-    and its centred training Y (held-out rows 0)."""
-    I, M = Yh.shape
+def _fold_means(Yh: np.ndarray, ids: np.ndarray, K: int):
+    """The fold-sorted row order and offsets, the mean of all rows and each fold's training means nu of Y."""
+    I = Yh.shape[0]
     counts = np.bincount(ids, minlength=K)
     order = np.argsort(ids, kind="stable").astype(np.int32)
     off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     ybar = Yh.mean(axis=0)
     colsum = Yh.sum(axis=0)
     nu = np.stack([(colsum - Yh[ids == k].sum(axis=0)) / (I - counts[k]) for k in range(K)])   # training means of Y
+    return order, off, ybar, nu
+
+
+def _fold_y(Yh: np.ndarray, ids: np.ndarray, K: int):
+    """What the folds need of Y: _fold_means and each fold's centred training Y (held-out rows 0)."""
+    I, M = Yh.shape
+    order, off, ybar, nu = _fold_means(Yh, ids, K)
     Yk = np.empty((K, I, M))
     for k in range(K):
         Yk[k] = Yh - nu[k]                                                          # tpls.py:70 on the training rows

@@ -104,3 +104,19 @@ def permutation_test_q2y(pls_tensor, n_permutations: int = 99, n_splits: int = 5
     from .permutation import permutation_test
 
     return permutation_test(pls_tensor, n_permutations, n_splits, folds, permutations, random_state, per_component, device_folds)
+
+
+def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, folds=None, random_state=0, per_component: bool = False,
+                           device_folds: bool = True) -> dict:
+    """Repeated K-fold Q2Y: S shuffled K-fold splits, split g scored exactly as get_q2y_kfold(pls_tensor, folds=ids_g,
+    per_component) scores it.  Splits: the test folds of sklearn's RepeatedKFold(n_splits, n_repeats, random_state) in its order
+    (S = n_repeats; random_state must be an int), or `folds`, an (S, I) integer array with one split per row, each row holding
+    ids 0..K-1 with no empty fold and the same K in every row (ValueError otherwise; n_splits, n_repeats and random_state are
+    then ignored).  Returns {"q2y": (S,) or (S, R), "mean" and "std" (ddof=0) over the splits, "folds": (S, I)}, and with
+    per_component "one_se": the smallest component count r (from 1) whose mean is at least max(mean) - std[argmax] / sqrt(S).
+    On the GPU floor(32 / K) splits x K folds of a tPLS or ctPLS share every MTTKRP and contraction of X (G + 2R - 1 reads
+    per pass and block, repeated.py); anything else refits every fold of every split.  Which form ran is recorded on the model
+    (``q2y_report_``)."""
+    from .repeated import repeated_kfold
+
+    return repeated_kfold(pls_tensor, n_splits, n_repeats, folds, random_state, per_component, device_folds)

@@ -560,6 +560,20 @@ int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* mo
                                     void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
                                        void* stream);
+
+/* ---- Repeated K-fold Q2Y (validate.get_q2y_repeated_kfold) -------------------------------------------------------------------
+ * A pass carries G shuffled splits x K folds = n <= 32 models (n <= I) in one cmtfpls_kfold_state (its K = n), split-major: model
+ * m = g K + k holds out fold k of split g, so each split's S, mean and Y side are a contiguous K-model slice.  Per pass:
+ * cmtfpls_kfold_xcov_* once per split (one read of X each, into that split's slice), kfold_epilogue_splits stage 0, then per
+ * component cmtfpls_kfold_inner_f64 (a ctPLS: cmtfpls_kfold_inner_coupled_f64 on the block views), the MTTKRP with n columns,
+ * kfold_epilogue_splits stage 1, and (all but the last) the contraction X_0^T tm and stage 2.  G + 2R - 1 reads of X per pass.
+ * The state's fold_of is splits x I (row g: split g's fold id of every sample, 0..K-1) and its Tout is splits x I x R (slot g:
+ * split g's held-out scores, every row written once). */
+/* kfold_epilogue_splits: cmtfpls_kfold_epilogue_f64 for st->K = n models in `splits` split-major splits (n % splits == 0,
+ * n / splits >= 2 folds each); stage 1 trains model m on the rows with fold_of[(m / folds) I + i] != m % folds and writes its
+ * held-out scores to Tout slot m / folds.  Stages 0 and 2 are those of cmtfpls_kfold_epilogue_f64; with splits = 1 the entry is
+ * bitwise cmtfpls_kfold_epilogue_f64. */
+int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits, int stage, int a, const double* in, void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
