@@ -842,6 +842,45 @@ static int kf_grouped_check(const cmtfpls_kfold_state* st, const int* model_fold
   return CMTFPLS_OK;
 }
 
+// the launch of the plain and grouped inner entries, after their argument checks
+template <bool GROUPED>
+static int kf_inner_launch(const cmtfpls_kfold_state* st, const int* model_fold, int a, double tol, int max_iter, void* ws,
+                           size_t ws_bytes, hipStream_t s) {
+  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
+  if (!ws || ws_bytes < need) {
+    set_error(GROUPED ? "kfold_inner_grouped: workspace too small" : "kfold_inner: workspace too small");
+    return CMTFPLS_EWORKSPACE;
+  }
+  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfold_inner_kernel<GROUPED>, dim3(st->K), dim3(kLxNT), lds, s, *st, a, tol, max_iter, static_cast<double*>(ws),
+                     (int64_t)(need / st->K / sizeof(double)), model_fold);
+  return check_launch(GROUPED ? "kfold_inner_grouped" : "kfold_inner");
+}
+
+// the stage switch of the three epilogue entries, after their argument checks: stage 0 the Y-side Gram, stage 1 the row work, the
+// solve and (but for the last component) the Y deflation, stage 2 the down-date of S.  kKfGrouped: model_fold and its `groups`;
+// kKfSplits: `groups` is the folds per split; kKfPlain: model_fold null, groups 1
+template <int MODE>
+static int kf_epilogue_launch(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
+                              hipStream_t s, const char* what) {
+  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
+  const int folds = MODE == kKfSplits ? groups : 1;
+  if (stage == 0) {
+    hipLaunchKernelGGL(kfold_ydefl_kernel<MODE>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, model_fold, folds);
+  } else if (stage == 1) {
+    hipLaunchKernelGGL(kfold_rows_kernel<MODE>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, model_fold, groups);
+    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
+    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<MODE>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, model_fold, folds);
+  } else {
+    const int64_t P = (int64_t)st->A * st->B;
+    hipLaunchKernelGGL(kfold_downdate_kernel<MODE == kKfGrouped>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K),
+                       dim3(kKfCols), 0, s, *st, a, in, model_fold);
+  }
+  return check_launch(what);
+}
+
 // ---- split-major models (repeated K-fold, repeated.py) ----------------------------------------------------------------------
 // A pass of repeated K-fold carries G shuffled splits x K folds = n <= kKfMaxK models; model m = g K + k holds out fold k of split
 // g.  Each split's S, mean and Y side are a contiguous K-model slice of the state, built per split by kfold_xcov; the inner loop
@@ -887,14 +926,7 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
     set_error("kfold_inner: shape outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256); refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
-  if (!ws || ws_bytes < need) { set_error("kfold_inner: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfold_inner_kernel<false>, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
-                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)), nullptr);
-  return check_launch("kfold_inner");
+  return kf_inner_launch<false>(st, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {
@@ -906,20 +938,7 @@ int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, 
     set_error("kfold_epilogue: shape outside the device form; refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
-  if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr, 1);
-  } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, 1);
-    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfPlain>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr, 1);
-  } else {
-    const int64_t P = (int64_t)st->A * st->B;
-    hipLaunchKernelGGL(kfold_downdate_kernel<false>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
-                       a, in, nullptr);
-  }
-  return check_launch("kfold_epilogue");
+  return kf_epilogue_launch<kKfPlain>(st, nullptr, 1, stage, a, in, (hipStream_t)stream, "kfold_epilogue");
 }
 
 size_t cmtfpls_kfold_inner_coupled_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb) {
@@ -980,14 +999,7 @@ int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* mo
   int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_inner_grouped: bad argument");
   if (rc) return rc;
   if (max_iter <= 0) { set_error("kfold_inner_grouped: bad argument"); return CMTFPLS_EINVAL; }
-  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
-  if (!ws || ws_bytes < need) { set_error("kfold_inner_grouped: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfold_inner_kernel<true>, dim3(st->K), dim3(kLxNT), lds, (hipStream_t)stream, *st, a, tol, max_iter,
-                     static_cast<double*>(ws), (int64_t)(need / st->K / sizeof(double)), model_fold);
-  return check_launch("kfold_inner_grouped");
+  return kf_inner_launch<true>(st, model_fold, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
@@ -995,20 +1007,7 @@ int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int*
   int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_epilogue_grouped: bad argument");
   if (rc) return rc;
   if (stage < 0 || stage > 2 || (stage > 0 && !in)) { set_error("kfold_epilogue_grouped: bad argument"); return CMTFPLS_EINVAL; }
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
-  if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, model_fold, 1);
-  } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, model_fold, groups);
-    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfGrouped>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, model_fold, 1);
-  } else {
-    const int64_t P = (int64_t)st->A * st->B;
-    hipLaunchKernelGGL(kfold_downdate_kernel<true>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
-                       a, in, model_fold);
-  }
-  return check_launch("kfold_epilogue_grouped");
+  return kf_epilogue_launch<kKfGrouped>(st, model_fold, groups, stage, a, in, (hipStream_t)stream, "kfold_epilogue_grouped");
 }
 
 int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits, int stage, int a, const double* in, void* stream) {
@@ -1021,20 +1020,7 @@ int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits,
     set_error("kfold_epilogue_splits: shape outside the device form (2 <= folds, n <= 32 models <= I, M <= 64, R <= 64); refit");
     return CMTFPLS_EUNSUPPORTED;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 rows((unsigned)kf_tiles(st->I), (unsigned)st->K);
-  if (stage == 0) {
-    hipLaunchKernelGGL(kfold_ydefl_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, 0, nullptr, folds);
-  } else if (stage == 1) {
-    hipLaunchKernelGGL(kfold_rows_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, in, nullptr, folds);
-    hipLaunchKernelGGL(kfold_solve_kernel, dim3(st->K), dim3(64), 0, s, *st, a);
-    if (a + 1 < st->R) hipLaunchKernelGGL(kfold_ydefl_kernel<kKfSplits>, rows, dim3(kKfRowThreads), 0, s, *st, a, 1, nullptr, folds);
-  } else {
-    const int64_t P = (int64_t)st->A * st->B;
-    hipLaunchKernelGGL(kfold_downdate_kernel<false>, dim3((unsigned)((P + kKfCols - 1) / kKfCols), (unsigned)st->K), dim3(kKfCols), 0, s, *st,
-                       a, in, nullptr);
-  }
-  return check_launch("kfold_epilogue_splits");
+  return kf_epilogue_launch<kKfSplits>(st, nullptr, folds, stage, a, in, (hipStream_t)stream, "kfold_epilogue_splits");
 }
 
 }  // extern "C"

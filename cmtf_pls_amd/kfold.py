@@ -11,11 +11,15 @@ Before the first component kfold_xcov builds every S_k from one read (the all-mi
 nothing written to X, no copy of it.  NIPALS components are sequential and coef_ is upper triangular, so the predictions
 with the first r components are those of an r-component model: every component count comes out of one run.
 
-A ctPLS runs the same steps per block with the score shared (device_predictions_coupled): kfold_inner_coupled goes
-through the blocks inside each fold's workgroup, one MTTKRP per block, the blocks' scores averaged (kfold_combine_scores), stage 1
-once on the shared t, one contraction and stage 2 per block: 2R reads of each block.
+A ctPLS runs the same steps per block with the score shared (device_predictions): kfold_inner_coupled goes through
+the blocks inside each fold's workgroup, one MTTKRP per block, the blocks' scores averaged (kfold_combine_scores), stage 1 once on
+the shared t, one contraction and stage 2 per block: 2R reads of each block.
 
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
+
+The permutation test (permutation.py) and repeated K-fold (repeated.py) run the same state with more models per pass: _state
+allocates it (a view per block), _components makes every launch of a pass with the inner and epilogue entries of the form, and
+_device_passes runs the passes and refits whatever they leave.
 """
 from __future__ import annotations
 
@@ -139,6 +143,36 @@ def _dims(X) -> Tuple[int, int]:
     return (1, X.shape[1]) if X.ndim == 2 else (X.shape[1], X.shape[2])
 
 
+def _training_data(pls):
+    """(X, Y) the model was fitted on; a ctPLS's blocks as a list."""
+    from .cmtf import ctPLS
+
+    if isinstance(pls, ctPLS):
+        assert getattr(pls, "original_Xs", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
+        return list(pls.original_Xs), pls.original_Y
+    assert getattr(pls, "original_X", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
+    return pls.original_X, pls.original_Y
+
+
+def _names(Xs, coupled: bool):
+    return [f"block {b}" for b in range(len(Xs))] if coupled else ["X"]
+
+
+def _loadings_fit(A: int, B: int, n: int) -> bool:
+    """Whether n models' loadings of an A x B block fit the LDS of the score pass (cmtfpls_mttkrp_*)."""
+    return (A + B) * 16 * ((n + 15) // 16) * 8 <= 152 * 1024
+
+
+def _groups(X, K: int, P: int) -> int:
+    """Entries (permutations, splits) per pass: floor(32 / K), at most P, fewer while the n models' loadings exceed the LDS of the
+    score pass."""
+    A, B = _dims(X)
+    G = min(MAX_FOLDS // K, P)
+    while G > 1 and not _loadings_fit(A, B, K * G):
+        G -= 1
+    return G
+
+
 def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
     """Why the device form does not take these blocks / this Y (None: it does, as far as can be told before reading them)."""
     eng = pls._get_engine()
@@ -166,7 +200,7 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
         pre = "" if name == "X" else f"{name}: "
         if min(A, B) > MAX_SIDE:
             return f"{pre}min(J, K) = {min(A, B)} > {MAX_SIDE}"
-        if (A + B) * 16 * ((K + 15) // 16) * 8 > 152 * 1024:
+        if not _loadings_fit(A, B, K):
             return f"{pre}the folds' loadings exceed the LDS of the score pass (cmtfpls_mttkrp_*)"
     if np.isnan(_host(Y)).any():
         return "missing values in Y"
@@ -174,11 +208,6 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
         if not isinstance(X, torch.Tensor) and np.isnan(np.asarray(X)).any():
             return f"missing values in {name}"
     return None
-
-
-def _decline(pls, X, Y, ids, K) -> Optional[str]:
-    """Why the device form does not take this model / data (None: it does, as far as can be told before reading X)."""
-    return _decline_blocks(pls, [X], ["X"], Y, K, ("kfold_xcov", "kfold_inner", "kfold_epilogue", "mttkrp", "xcov"))
 
 
 def _fold_means(Yh: np.ndarray, ids: np.ndarray, K: int):
@@ -219,6 +248,81 @@ def _stats_why(stats: torch.Tensor, P: int, I: int, max_offset: float, name: str
     return None
 
 
+def _to_dev(a, dev, dt=torch.float64) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+
+
+def _device_blocks(pls, Xs, dev):
+    """Each block as (X2, A, B): the device tensor of the storage type (the caller's own when it is one: never copied), I x P."""
+    from .tpls import _as_torch_dtype, to_device_copy
+
+    return [(to_device_copy(X, _as_torch_dtype(pls._dtype, X), dev, copy=False).view(X.shape[0], -1), *_dims(X)) for X in Xs]
+
+
+def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: int):
+    """The cmtfpls_kfold_state of n = Yk.shape[0] models: (views, shared, own).  blocks: (A, B, S, mean) each; views: a ctypes array
+    of _lib.KfoldState, one per block; own: each block's S, mean, WA, WB, Wa, Wb and Rm; every other field is in shared, one buffer
+    for every view.  Tout has `slots` slots of held-out scores (slots x I x R)."""
+    n, I, M = Yk.shape
+    dev = be.device
+    NT, stride = be.kfold_row_tiles(I)
+    shared = {
+        "fold_of": fold_of, "Yk": Yk, "Gy": be.empty(n, NT, M, M), "Q": be.zeros(n, R, M), "T": be.zeros(n, I, R), "Gt": be.zeros(n, R, R),
+        "coef": be.zeros(n, R, R), "tm": be.empty(I, n), "Tout": be.zeros(slots, I, R), "vec": be.zeros(n, 3 * R + M + 2),
+        "n_iter": torch.zeros(n, R, dtype=torch.int32, device=dev), "status": torch.zeros(n, dtype=torch.int32, device=dev),
+        "part": be.empty(n, NT, stride),
+    }
+    own = [{"S": S, "mean": mean, "WA": be.empty(A, n), "WB": be.empty(B, n), "Wa": be.zeros(n, R, A), "Wb": be.zeros(n, R, B),
+            "Rm": be.zeros(n, R, A * B)} for A, B, S, mean in blocks]
+    views = [_lib.KfoldState(I, A, B, M, n, R, *[{**shared, **o}[f].data_ptr() for f, _ in _lib.KfoldState._fields_[6:]])
+             for (A, B, _, _), o in zip(blocks, own)]
+    return (_lib.KfoldState * len(views))(*views), shared, own
+
+
+def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0):
+    """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
+    ctPLS, one block included: then the blocks' scores averaged), stage 1 and, but for the last, one contraction and stage 2 per
+    block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled) or kfold_inner_grouped; the epilogue: kfold_epilogue,
+    kfold_epilogue_grouped (grouped = (model_fold, groups)) or kfold_epilogue_splits (splits > 0).  None, or why a kernel declined."""
+    nb, n, I = len(st), st[0].K, st[0].I
+    if coupled:
+        ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
+        inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
+    else:
+        ws = torch.empty(max(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), 256), dtype=torch.uint8, device=be.device)
+        if grouped:
+            inner, inner_name = lambda a: be.kfold_inner_grouped(st[0], *grouped, a, tol, max_iter, ws), "kfold_inner_grouped_f64"
+        else:
+            inner, inner_name = lambda a: be.kfold_inner(st[0], a, tol, max_iter, ws), "kfold_inner_f64"
+    if grouped:
+        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_grouped(st[b], *grouped, *args), "kfold_epilogue_grouped_f64"
+    elif splits:
+        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_splits(st[b], splits, *args), "kfold_epilogue_splits_f64"
+    else:
+        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue(st[b], *args), "kfold_epilogue_f64"
+    scs = be.empty(nb, I, n)
+    sc = be.empty(I, n) if coupled else scs[0]
+    rs = be.empty(n * max(v.A * v.B for v in st))
+    if epilogue(0, 0, 0, None) is None:
+        return f"shape outside cmtfpls_{epilogue_name}"
+    for a in range(R):
+        if inner(a) is None:
+            return f"shape outside cmtfpls_{inner_name}"
+        for b in range(nb):                                                         # X_b,0 [w_1 .. w_n]: one read each
+            if be.mttkrp(X2s[b], st[b].A, st[b].B, own[b]["WA"], own[b]["WB"], scs[b]) is None:
+                return f"{f'block {b}: ' if coupled else ''}the models' loadings outside cmtfpls_mttkrp_*"
+        if coupled:
+            be.kfold_combine_scores(scs, sc)                                        # t: the average of the blocks' scores
+        epilogue(0, 1, a, sc)
+        if a + 1 < R:
+            for b in range(nb):                                                     # X_b,0^T [t_m * train_m]: one read each
+                P = X2s[b].shape[1]
+                r = rs[: n * P].view(n, P)
+                be.xcov(X2s[b], shared["tm"], False, out=r)
+                epilogue(b, 2, a, r)
+    return None
+
+
 def _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M) -> np.ndarray:
     pred = np.empty((R, ids.shape[0], M))
     for k in range(K):
@@ -228,186 +332,73 @@ def _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M) -> np.ndarray:
     return pred
 
 
-def device_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, grouped: bool = False):
-    """The device form: (pred (R, I, M), report) or (None, why).  grouped=True runs the inner loop and the epilogue through the
-    permutation test's grouped entries with model k = fold k in one group (the same bits: tests/test_gpu_permutation.py)."""
-    from .tpls import _as_torch_dtype, to_device_copy
+def _form_entries(build: str, coupled: bool, epilogue: str) -> str:
+    inner = "cmtfpls_kfold_inner_coupled_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64" if coupled else \
+        "cmtfpls_kfold_inner_f64, cmtfpls_mttkrp_*"
+    return f"({build}, {inner}, {epilogue}, cmtfpls_xcov_*)"
 
+
+def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, coupled: bool):
+    """The device form of a tPLS (Xs = [X]) or a ctPLS (coupled, DESIGN 8c: a state view per block): (pred (R, I, M), report) or
+    (None, why)."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
-    I = X.shape[0]
-    A, B = _dims(X)
-    P = A * B
-    Yh = _host(Y).reshape(I, -1).astype(np.float64)
-    M = Yh.shape[1]
-    dev = be.device
-    with eng.device_ctx():
-        Xd = to_device_copy(X, _as_torch_dtype(pls._dtype, X), dev, copy=False)     # a device tensor of the storage type: as it is
-        X2 = Xd.view(I, P)
-        order, off, ybar, nu, Yk = _fold_y(Yh, ids, K)
-        t = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-        S = be.empty(K, M, P)
-        mean = be.empty(K, P)
-        stats = be.kfold_xcov(X2, A, B, t(Yh - ybar), t(order, torch.int32), t(off, torch.int32), K, t(nu - ybar), S, mean)
-        if stats is None:
-            return None, "shape outside cmtfpls_kfold_xcov"
-        why = _stats_why(stats, P, I, eng.opt.xcov_raw_max_offset, "X")
-        if why is not None:
-            return None, why
-        NT, stride = be.kfold_row_tiles(I)
-        buf = {
-            "fold_of": t(ids, torch.int32), "S": S, "mean": mean, "Yk": t(Yk), "Gy": be.empty(K, NT, M, M), "WA": be.empty(A, K),
-            "WB": be.empty(B, K), "Q": be.zeros(K, R, M), "Wa": be.zeros(K, R, A), "Wb": be.zeros(K, R, B), "T": be.zeros(K, I, R),
-            "Gt": be.zeros(K, R, R), "coef": be.zeros(K, R, R), "Rm": be.zeros(K, R, P), "tm": be.empty(I, K), "Tout": be.zeros(I, R),
-            "vec": be.zeros(K, 3 * R + M + 2), "n_iter": torch.zeros(K, R, dtype=torch.int32, device=dev),
-            "status": torch.zeros(K, dtype=torch.int32, device=dev), "part": be.empty(K, NT, stride),
-        }
-        st = _lib.KfoldState(I, A, B, M, K, R, *[b.data_ptr() for b in (buf[f] for f, _ in _lib.KfoldState._fields_[6:])])
-        ws = torch.empty(max(be.kfold_inner_workspace_bytes(A, B, K), 256), dtype=torch.uint8, device=dev)
-        sc = be.empty(I, K)
-        rs = be.empty(K, P)
-        if grouped:
-            mf = torch.arange(K, dtype=torch.int32, device=dev)
-            inner = lambda a: be.kfold_inner_grouped(st, mf, 1, a, tol, max_iter, ws)
-            epilogue = lambda stage, a, src: be.kfold_epilogue_grouped(st, mf, 1, stage, a, src)
-        else:
-            inner = lambda a: be.kfold_inner(st, a, tol, max_iter, ws)
-            epilogue = lambda stage, a, src: be.kfold_epilogue(st, stage, a, src)
-        if epilogue(0, 0, None) is None:
-            return None, "shape outside cmtfpls_kfold_epilogue_f64"
-        for a in range(R):
-            if inner(a) is None:
-                return None, "shape outside cmtfpls_kfold_inner_f64"
-            if be.mttkrp(X2, A, B, buf["WA"], buf["WB"], sc) is None:                   # X_0 [w_1 .. w_K]: one read
-                return None, "the folds' loadings outside cmtfpls_mttkrp_*"
-            epilogue(1, a, sc)
-            if a + 1 < R:
-                be.xcov(X2, buf["tm"], False, out=rs)                                   # X_0^T [t_k * train_k]: one read
-                epilogue(2, a, rs)
-        status = buf["status"].cpu().numpy()
-        if status.any():
-            return None, f"non-finite loadings or coefficients in folds {np.flatnonzero(status).tolist()} of the device form"
-        n_iter = buf["n_iter"].cpu().numpy()
-        Tout = buf["Tout"].cpu().numpy()
-        coef = buf["coef"].cpu().numpy()
-        Qh = buf["Q"].cpu().numpy()
-    pred = _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M)
-    report = {"form": "K folds from shared reads of X (cmtfpls_kfold_xcov_*, cmtfpls_kfold_inner_f64, cmtfpls_mttkrp_*, "
-                      "cmtfpls_kfold_epilogue_f64, cmtfpls_xcov_*)",
-              "folds": int(K), "x_reads": 2 * R, "n_iter": n_iter.tolist()}
-    return pred, report
-
-
-_SHARED = ("fold_of", "Yk", "Gy", "Q", "T", "Gt", "coef", "tm", "Tout", "vec", "n_iter", "status", "part")
-
-
-def device_predictions_coupled(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
-    """The device form of a ctPLS: (pred (R, I, M), report) or (None, why).  Each block has a state view of its own (S, mean,
-    loadings, X_c^T t); the Y side, the scores and the solve are one set of buffers shared by every view.  Per component: the
-    coupled inner loop, one MTTKRP per block, the blocks' scores averaged, stage 1 once, and per block one contraction and its
-    down-date: 2R reads of each block for all folds."""
-    from .tpls import _as_torch_dtype, to_device_copy
-
-    eng = pls._get_engine()
-    be = eng.be
-    R = pls.n_components
-    nb = len(Xs)
     I = Xs[0].shape[0]
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
     dev = be.device
     with eng.device_ctx():
         order, off, ybar, nu, Yk = _fold_y(Yh, ids, K)
-        t = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-        NT, stride = be.kfold_row_tiles(I)
-        shared = {
-            "fold_of": t(ids, torch.int32), "Yk": t(Yk), "Gy": be.empty(K, NT, M, M), "Q": be.zeros(K, R, M), "T": be.zeros(K, I, R),
-            "Gt": be.zeros(K, R, R), "coef": be.zeros(K, R, R), "tm": be.empty(I, K), "Tout": be.zeros(I, R),
-            "vec": be.zeros(K, 3 * R + M + 2), "n_iter": torch.zeros(K, R, dtype=torch.int32, device=dev),
-            "status": torch.zeros(K, dtype=torch.int32, device=dev), "part": be.empty(K, NT, stride),
-        }
-        ydev, order_d, off_d, nudev = t(Yh - ybar), t(order, torch.int32), t(off, torch.int32), t(nu - ybar)
-        X2s, dims, own, views = [], [], [], []
-        for b, X in enumerate(Xs):
-            Xd = to_device_copy(X, _as_torch_dtype(pls._dtype, X), dev, copy=False)  # a device tensor of the storage type: as it is
-            A, B = _dims(X)
-            P = A * B
-            X2 = Xd.view(I, P)
-            S = be.empty(K, M, P)
-            mean = be.empty(K, P)
+        ydev, order_d, off_d, nudev = _to_dev(Yh - ybar, dev), _to_dev(order, dev, torch.int32), _to_dev(off, dev, torch.int32), \
+            _to_dev(nu - ybar, dev)
+        X2s, blocks = [], []
+        for (X2, A, B), name in zip(_device_blocks(pls, Xs, dev), _names(Xs, coupled)):
+            S, mean = be.empty(K, M, A * B), be.empty(K, A * B)
             stats = be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S, mean)
             if stats is None:
-                return None, f"block {b}: shape outside cmtfpls_kfold_xcov"
-            why = _stats_why(stats, P, I, eng.opt.xcov_raw_max_offset, f"block {b}")
+                return None, f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_xcov"
+            why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
             if why is not None:
                 return None, why
-            o = {"S": S, "mean": mean, "WA": be.empty(A, K), "WB": be.empty(B, K), "Wa": be.zeros(K, R, A), "Wb": be.zeros(K, R, B),
-                 "Rm": be.zeros(K, R, P)}
-            views.append(_lib.KfoldState(I, A, B, M, K, R, *[(o[f] if f in o else shared[f]).data_ptr()
-                                                             for f, _ in _lib.KfoldState._fields_[6:]]))
             X2s.append(X2)
-            dims.append((A, B))
-            own.append(o)
-        st = (_lib.KfoldState * nb)(*views)
-        ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=dev)
-        scs = be.empty(nb, I, K)
-        sc = be.empty(I, K)
-        rs = be.empty(K * max(A * B for A, B in dims))
-        if be.kfold_epilogue(st[0], 0, 0, None) is None:
-            return None, "shape outside cmtfpls_kfold_epilogue_f64"
-        for a in range(R):
-            if be.kfold_inner_coupled(st, a, tol, max_iter, ws) is None:
-                return None, "shape outside cmtfpls_kfold_inner_coupled_f64"
-            for b in range(nb):                                                         # X_b,0 [w_b,1 .. w_b,K]: one read each
-                if be.mttkrp(X2s[b], *dims[b], own[b]["WA"], own[b]["WB"], scs[b]) is None:
-                    return None, f"block {b}: the folds' loadings outside cmtfpls_mttkrp_*"
-            be.kfold_combine_scores(scs, sc)                                            # t: the average of the blocks' scores
-            be.kfold_epilogue(st[0], 1, a, sc)
-            if a + 1 < R:
-                for b in range(nb):                                                     # X_b,0^T [t_k * train_k]: one read each
-                    r = rs[: K * X2s[b].shape[1]].view(K, X2s[b].shape[1])
-                    be.xcov(X2s[b], shared["tm"], False, out=r)
-                    be.kfold_epilogue(st[b], 2, a, r)
+            blocks.append((A, B, S, mean))
+        st, shared, own = _state(be, _to_dev(ids, dev, torch.int32), _to_dev(Yk, dev), blocks, R, 1)
+        why = _components(be, X2s, st, shared, own, R, tol, max_iter, coupled)
+        if why is not None:
+            return None, why
         status = shared["status"].cpu().numpy()
         if status.any():
             return None, f"non-finite loadings or coefficients in folds {np.flatnonzero(status).tolist()} of the device form"
         n_iter = shared["n_iter"].cpu().numpy()
-        Tout = shared["Tout"].cpu().numpy()
+        Tout = shared["Tout"][0].cpu().numpy()
         coef = shared["coef"].cpu().numpy()
         Qh = shared["Q"].cpu().numpy()
     pred = _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M)
-    report = {"form": "K folds from shared reads of every block (cmtfpls_kfold_xcov_*, cmtfpls_kfold_inner_coupled_f64, "
-                      "cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64, cmtfpls_kfold_epilogue_f64, cmtfpls_xcov_*)",
-              "folds": int(K), "x_reads": [2 * R] * nb, "n_iter": n_iter.tolist()}
+    source = "every block" if coupled else "X"
+    report = {"form": f"K folds from shared reads of {source} "
+                      + _form_entries("cmtfpls_kfold_xcov_*", coupled, "cmtfpls_kfold_epilogue_f64"),
+              "folds": int(K), "x_reads": [2 * R] * len(Xs) if coupled else 2 * R, "n_iter": n_iter.tolist()}
     return pred, report
 
 
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
     """pred (R, *Y.shape): pred[r - 1, i] = prediction for sample i by the model fitted without sample i's fold, with its first
     r components.  `pls` a fitted tPLS or ctPLS.  Sets pls.q2y_report_."""
-    from .cmtf import ctPLS
-
-    coupled = isinstance(pls, ctPLS)
-    if coupled:
-        assert getattr(pls, "original_Xs", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
-        X, Y = list(pls.original_Xs), pls.original_Y
-    else:
-        assert getattr(pls, "original_X", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
-        X, Y = pls.original_X, pls.original_Y
+    X, Y = _training_data(pls)
+    coupled = isinstance(X, list)
+    Xs = X if coupled else [X]
     I = Y.shape[0]
     ids, K = fold_ids(I, n_splits, folds)
     R = pls.n_components
     if not device_folds:
         why = "device folds switched off"
-    elif coupled:
-        why = _decline_blocks(pls, X, [f"block {b}" for b in range(len(X))], Y, K,
-                              ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue", "mttkrp", "xcov"))
     else:
-        why = _decline(pls, X, Y, ids, K)
+        inner = ("kfold_inner_coupled", "kfold_combine_scores") if coupled else ("kfold_inner",)
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"))
     pred = None
     if why is None:
-        pred, rep = (device_predictions_coupled if coupled else device_predictions)(pls, X, Y, ids, K, tol, max_iter)
+        pred, rep = device_predictions(pls, Xs, Y, ids, K, tol, max_iter, coupled)
         if pred is None:
             why = rep
     if pred is None:
@@ -415,3 +406,70 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
         rep = {"form": "one refit per fold on the regular engine", "folds": int(K), "x_reads": None, "n_iter": n_iter, "why": why}
     pls.q2y_report_ = rep
     return pred.reshape((R,) + tuple(Y.shape))
+
+
+# ---- passes of many models (permutation.py, repeated.py) --------------------------------------------------------------------
+def _perm_y(Y, pi: np.ndarray):
+    return Y[torch.from_numpy(pi).to(Y.device)] if isinstance(Y, torch.Tensor) else Y[pi]
+
+
+def _refit_numerators(pls, X, Y, ids, K, pi, tol, max_iter):
+    """(numerators (R,), n_iter K x R) of Y[pi] with the folds `ids` from literal refits."""
+    Yp = _perm_y(Y, pi)
+    pred, n_iter = refit_predictions(pls, X, Yp, ids, K, tol, max_iter)
+    y = _host(Yp).reshape(pred.shape[1], -1).astype(np.float64)
+    return ((pred - y) ** 2).reshape(pred.shape[0], -1).sum(axis=1), n_iter
+
+
+def _device_numerators(Tout, coef, Q, nu, Yp, rows, K: int, g: int, R: int, M: int) -> torch.Tensor:
+    """The Q2Y numerators (g x R) of a pass on the device: sum over rows of |pred_r - y_p|^2 for every component count r, pred_r
+    = nu + sum_{c < r} h_c q_c with h = scores @ coef_ (coef_ upper triangular: the r-component model's prediction)."""
+    num = torch.zeros(g, R, dtype=torch.float64, device=Tout.device)
+    coef = coef.view(K, g, R, R)
+    Q = Q.view(K, g, R, M)
+    step = max(1, (1 << 24) // (g * R * M))
+    for k in range(K):
+        for lo in range(0, rows[k].numel(), step):
+            idx = rows[k][lo:lo + step]
+            H = torch.bmm(Tout[:, idx], coef[k])                                     # g x n x R
+            C = torch.cumsum(H.unsqueeze(-1) * Q[k].unsqueeze(1), dim=2)            # g x n x R x M
+            res = C + (nu[:, k].unsqueeze(1) - Yp[:, idx]).unsqueeze(2)
+            num += (res * res).sum(dim=(1, 3))
+    return num
+
+
+def _device_passes(pls, N: int, G: int, what: str, why: Optional[str], prepare, refit):
+    """N entries (permutations, splits), G per device pass, then a literal refit of every entry the device left: (numerators N x R,
+    n_iter per entry, passes, why; with passes > 0 a why is the notes of the failed passes).  Nothing runs on the device when `why`
+    is set.  prepare() (under the device context) returns
+    run(pass, e0, g): entries e0 .. e0 + g - 1 as (numerators g x R, their n_iter, status per model), or why the device form
+    declined (then every entry refits); refit(e): (numerators (R,), n_iter)."""
+    R = pls.n_components
+    nums = np.full((N, R), np.nan)
+    n_iters = [None] * N
+    passes, notes = 0, []
+    if why is None:
+        with pls._get_engine().device_ctx():
+            run = prepare()
+            for e0 in range(0, N, G):
+                g = min(G, N - e0)
+                out = run(passes, e0, g)
+                if isinstance(out, str):
+                    why, passes, notes = out, 0, []
+                    nums[:] = np.nan
+                    n_iters = [None] * N
+                    break
+                num, n_iter, status = out
+                passes += 1
+                if status.any():
+                    notes.append(f"pass {passes - 1} ({what} {e0}..{e0 + g - 1}): non-finite loadings or coefficients in models "
+                                 f"{np.flatnonzero(status).tolist()}, refitted")
+                    continue
+                nums[e0:e0 + g] = num
+                n_iters[e0:e0 + g] = n_iter
+        if notes:
+            why = "; ".join(notes)
+    for e in range(N):                                                               # the refit path: whatever the device left
+        if n_iters[e] is None:
+            nums[e], n_iters[e] = refit(e)
+    return nums, n_iters, passes, why

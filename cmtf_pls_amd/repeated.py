@@ -11,8 +11,8 @@ K-model slice of every per-model buffer.  Per pass and block:
                         (a ctPLS: then kfold_combine_scores), kfold_epilogue_splits stage 1 (fold_of is G x I, held-out
                         scores to Tout slot g), and but for the last component the contraction and stage 2          2R - 1 reads
 The Y side, the held-out predictions and the R Q2Y numerators of every split are built on the device: per pass only status,
-n_iter and G x R numerators come back.  A pass whose status is set refits its own splits; anything outside the device form
-refits every fold of every split with kfold.refit_predictions.
+n_iter and G x R numerators come back.  The passes run through kfold._device_passes: a pass whose status is set refits its own
+splits; anything outside the device form refits every fold of every split with kfold.refit_predictions.
 """
 from __future__ import annotations
 
@@ -22,138 +22,69 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .kfold import MAX_FOLDS, _decline_blocks, _dims, _fold_means, _host, _stats_why, repeated_fold_ids
-from .permutation import _device_numerators, _groups, _refit_numerators
+from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _fold_means,
+                    _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _training_data,
+                    repeated_fold_ids)
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
 
 
-def _splits_per_pass(Xs, K: int, S: int, I: int) -> int:
-    """floor(32 / K) splits, at most floor(I / K) (n <= I models) and S, fewer while the n models' loadings exceed the LDS of the
-    score pass of any block (permutation._groups per block)."""
-    return min(_groups(None, X, K, min(S, I // K)) for X in Xs)
-
-
-def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, G: int, tol: float, max_iter: int, coupled: bool):
-    """The device form (a ctPLS: the coupled kernels, one block included): (numerators S x R with NaN rows for failed passes,
-    n_iter per split (None: failed), passes, failed pass messages, reads of each block) or (None, why) when it does not run at all.
-    A block view's own fields are S, mean, WA, WB, Wa, Wb and Rm; every other field is one buffer shared by the views."""
-    from .tpls import _as_torch_dtype, to_device_copy
-
+def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, coupled: bool):
+    """The device form's run(pass, g0, g) of kfold._device_passes (a ctPLS: the coupled kernels, one block included): splits
+    g0 .. g0 + g - 1 as g K split-major models, each split's S and mean built into its K-model slice of every block's."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
-    nb = len(Xs)
-    NS, I = ids.shape
+    I = ids.shape[1]
+    dev = be.device
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
-    dev = be.device
-    nums = np.full((NS, R), np.nan)
-    n_iters = [None] * NS
-    notes = []
-    passes, reads = 0, 0
-    with eng.device_ctx():
-        X2s, dims = [], []
-        for X in Xs:
-            Xd = to_device_copy(X, _as_torch_dtype(pls._dtype, X), dev, copy=False)  # a device tensor of the storage type: as it is
-            X2s.append(Xd.view(I, -1))
-            dims.append(_dims(X))
-        t = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-        Yd = t(Yh)
-        ydev = t(Yh - Yh.mean(axis=0))                                                # shared by every split
-        NT, stride = be.kfold_row_tiles(I)
-        kk = torch.arange(K, device=dev)
-        for g0 in range(0, NS, G):
-            g = min(G, NS - g0)
-            n = K * g
-            shared = {
-                "fold_of": t(ids[g0:g0 + g], torch.int32), "Yk": be.empty(n, I, M), "Gy": be.empty(n, NT, M, M), "Q": be.zeros(n, R, M),
-                "T": be.zeros(n, I, R), "Gt": be.zeros(n, R, R), "coef": be.zeros(n, R, R), "tm": be.empty(I, n),
-                "Tout": be.zeros(g, I, R), "vec": be.zeros(n, 3 * R + M + 2), "n_iter": torch.zeros(n, R, dtype=torch.int32, device=dev),
-                "status": torch.zeros(n, dtype=torch.int32, device=dev), "part": be.empty(n, NT, stride),
-            }
-            own = [{"S": be.empty(n, M, A * B), "mean": be.empty(n, A * B), "WA": be.empty(A, n), "WB": be.empty(B, n),
-                    "Wa": be.zeros(n, R, A), "Wb": be.zeros(n, R, B), "Rm": be.zeros(n, R, A * B)} for A, B in dims]
-            nu, rows = [], []
-            for j in range(g):                                                        # split g0 + j: models j K .. j K + K - 1
-                order, off, _, nu_j = _fold_means(Yh, ids[g0 + j], K)                 # kfold._fold_y's bits
-                order_d, off_d, nu_d = t(order, torch.int32), t(off, torch.int32), t(nu_j)
-                nudev = t(nu_j - Yh.mean(axis=0))
-                sl = slice(j * K, (j + 1) * K)
-                train = (shared["fold_of"][j].long().unsqueeze(0) != kk.unsqueeze(1)).unsqueeze(2)          # K x I x 1
-                shared["Yk"][sl] = torch.where(train, Yd.unsqueeze(0) - nu_d.unsqueeze(1), 0.0)
-                for b in range(nb):                                                   # one read of each block per split
-                    A, B = dims[b]
-                    stats = be.kfold_xcov(X2s[b], A, B, ydev, order_d, off_d, K, nudev, own[b]["S"][sl], own[b]["mean"][sl])
-                    pre = f"block {b}: " if coupled else ""
-                    if stats is None:
-                        return None, f"{pre}shape outside cmtfpls_kfold_xcov"
-                    if passes == 0 and j == 0:
-                        why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, f"block {b}" if coupled else "X")
-                        if why is not None:
-                            return None, why
-                nu.append(nu_d)
-                order_l = order_d.long()
-                rows.append([order_l[int(off[k]):int(off[k + 1])] for k in range(K)])
-            views = [_lib.KfoldState(I, A, B, M, n, R, *[(o[f] if f in o else shared[f]).data_ptr() for f, _ in _lib.KfoldState._fields_[6:]])
-                     for (A, B), o in zip(dims, own)]
-            st = (_lib.KfoldState * nb)(*views)
-            if coupled:
-                ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=dev)
-                inner = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws)
-            else:
-                ws = torch.empty(max(be.kfold_inner_workspace_bytes(*dims[0], n), 256), dtype=torch.uint8, device=dev)
-                inner = lambda a: be.kfold_inner(st[0], a, tol, max_iter, ws)
-            scs = be.empty(nb, I, n)
-            sc = scs[0] if not coupled else be.empty(I, n)
-            rs = be.empty(n * max(A * B for A, B in dims))
-            if be.kfold_epilogue_splits(st[0], g, 0, 0, None) is None:
-                return None, "shape outside cmtfpls_kfold_epilogue_splits_f64"
-            for a in range(R):
-                if inner(a) is None:
-                    return None, "shape outside cmtfpls_kfold_inner_coupled_f64" if coupled else "shape outside cmtfpls_kfold_inner_f64"
-                for b in range(nb):                                                   # X_b,0 [w_1 .. w_n]: one read each
-                    if be.mttkrp(X2s[b], *dims[b], own[b]["WA"], own[b]["WB"], scs[b]) is None:
-                        return None, "the models' loadings outside cmtfpls_mttkrp_*"
-                if coupled:
-                    be.kfold_combine_scores(scs, sc)                                  # t: the average of the blocks' scores
-                be.kfold_epilogue_splits(st[0], g, 1, a, sc)
-                if a + 1 < R:
-                    for b in range(nb):                                               # X_b,0^T [t_m * train_m]: one read each
-                        r = rs[: n * X2s[b].shape[1]].view(n, X2s[b].shape[1])
-                        be.xcov(X2s[b], shared["tm"], False, out=r)
-                        be.kfold_epilogue_splits(st[b], g, 2, a, r)
-            num = torch.cat([_device_numerators(shared["Tout"][j:j + 1], shared["coef"][j * K:(j + 1) * K], shared["Q"][j * K:(j + 1) * K],
-                                                nu[j].unsqueeze(0), Yd.unsqueeze(0), rows[j], K, 1, R, M) for j in range(g)])
-            status = shared["status"].cpu().numpy()
-            n_iter = shared["n_iter"].cpu().numpy().reshape(g, K, R)
-            num = num.cpu().numpy()
-            passes += 1
-            reads += g + 2 * R - 1
-            if status.any():
-                bad = np.flatnonzero(status)
-                notes.append(f"pass {passes - 1} (splits {g0}..{g0 + g - 1}): non-finite loadings or coefficients in models "
-                             f"{bad.tolist()}, refitted")
-                continue
-            nums[g0:g0 + g] = num
-            for j in range(g):
-                n_iters[g0 + j] = n_iter[j].tolist()
-    return nums, n_iters, passes, notes, reads
+    blocks = _device_blocks(pls, Xs, dev)
+    names = _names(Xs, coupled)
+    Yd = _to_dev(Yh, dev)
+    ydev = _to_dev(Yh - Yh.mean(axis=0), dev)                                         # shared by every split
+    kk = torch.arange(K, device=dev)
+
+    def run(passes, g0, g):
+        n = K * g
+        fold_of = _to_dev(ids[g0:g0 + g], dev, torch.int32)
+        Yk = be.empty(n, I, M)
+        built = [(A, B, be.empty(n, M, A * B), be.empty(n, A * B)) for _, A, B in blocks]
+        nu, rows = [], []
+        for j in range(g):                                                            # split g0 + j: models j K .. j K + K - 1
+            order, off, _, nu_j = _fold_means(Yh, ids[g0 + j], K)                     # kfold._fold_y's bits
+            order_d, off_d, nu_d = _to_dev(order, dev, torch.int32), _to_dev(off, dev, torch.int32), _to_dev(nu_j, dev)
+            nudev = _to_dev(nu_j - Yh.mean(axis=0), dev)
+            sl = slice(j * K, (j + 1) * K)
+            train = (fold_of[j].long().unsqueeze(0) != kk.unsqueeze(1)).unsqueeze(2)                       # K x I x 1
+            Yk[sl] = torch.where(train, Yd.unsqueeze(0) - nu_d.unsqueeze(1), 0.0)
+            for (X2, A, B), (_, _, S, mean), name in zip(blocks, built, names):      # one read of each block per split
+                stats = be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S[sl], mean[sl])
+                if stats is None:
+                    return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_xcov"
+                if passes == 0 and j == 0:
+                    why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
+                    if why is not None:
+                        return why
+            nu.append(nu_d)
+            order_l = order_d.long()
+            rows.append([order_l[int(off[k]):int(off[k + 1])] for k in range(K)])
+        st, shared, own = _state(be, fold_of, Yk, built, R, g)
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, splits=g)
+        if why is not None:
+            return why
+        num = torch.cat([_device_numerators(shared["Tout"][j:j + 1], shared["coef"][j * K:(j + 1) * K], shared["Q"][j * K:(j + 1) * K],
+                                            nu[j].unsqueeze(0), Yd.unsqueeze(0), rows[j], K, 1, R, M) for j in range(g)])
+        n_iter = shared["n_iter"].cpu().numpy().reshape(g, K, R)
+        return num.cpu().numpy(), [n_iter[j].tolist() for j in range(g)], shared["status"].cpu().numpy()
+    return run
 
 
 def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, random_state=0, per_component: bool = False,
                    device_folds: bool = True, tol: float = 1e-8, max_iter: int = 100) -> dict:
-    from .cmtf import ctPLS
-
-    coupled = isinstance(pls, ctPLS)
-    if coupled:
-        assert getattr(pls, "original_Xs", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
-        X, Y = list(pls.original_Xs), pls.original_Y
-    else:
-        assert getattr(pls, "original_X", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
-        X, Y = pls.original_X, pls.original_Y
+    X, Y = _training_data(pls)
+    coupled = isinstance(X, list)
     Xs = X if coupled else [X]
     I = Y.shape[0]
     ids, K = repeated_fold_ids(I, n_splits, n_repeats, random_state, folds)
@@ -166,39 +97,24 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
     if not device_folds:
         why = "device folds switched off"
     else:
-        G = _splits_per_pass(Xs, K, NS, I) if K <= MAX_FOLDS else 0
-        names = [f"block {b}" for b in range(len(Xs))] if coupled else ["X"]
-        why = _decline_blocks(pls, Xs, names, Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES)   # K: the n models
-    nums = np.full((NS, R), np.nan)
-    n_iters = [None] * NS
-    passes, notes, reads = 0, [], 0
-    if why is None:
-        out = _device_splits(pls, Xs, Y, ids, K, G, tol, max_iter, coupled)
-        if out[0] is None:
-            why = out[1]
-        else:
-            nums, n_iters, passes, notes, reads = out
-            if notes:
-                why = "; ".join(notes)
+        G = min(_groups(X, K, min(NS, I // K)) for X in Xs) if K <= MAX_FOLDS else 0   # n <= I models, the LDS of every block
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES)
     identity = np.arange(I)
-    for g in range(NS):                                                              # the refit path: whatever the device left
-        if n_iters[g] is None:
-            nums[g], n_iters[g] = _refit_numerators(pls, X, Y, ids[g], K, identity, tol, max_iter)
+    nums, n_iters, passes, why = _device_passes(pls, NS, G, "splits", why,
+                                                lambda: _device_splits(pls, Xs, Y, ids, K, tol, max_iter, coupled),
+                                                lambda g: _refit_numerators(pls, X, Y, ids[g], K, identity, tol, max_iter))
     q_all = 1.0 - nums / den                                                          # S x R: every component count
     q2y = q_all if per_component else q_all[:, -1]
-    if passes:
-        entries = ("cmtfpls_kfold_xcov_* per split, cmtfpls_kfold_inner_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_epilogue_splits_f64, "
-                   "cmtfpls_xcov_*") if not coupled else \
-                  ("cmtfpls_kfold_xcov_* per split, cmtfpls_kfold_inner_coupled_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64, "
-                   "cmtfpls_kfold_epilogue_splits_f64, cmtfpls_xcov_*")
-        form = f"{K * G} models per pass ({G} splits x {K} folds) from shared reads of {'every block' if coupled else 'X'} ({entries})"
-        if notes:
-            form += "; failed passes refitted per fold on the regular engine"
-    else:
-        form = "one refit per fold and split on the regular engine"
     x_reads = None
     if passes:
+        entries = _form_entries("cmtfpls_kfold_xcov_* per split", coupled, "cmtfpls_kfold_epilogue_splits_f64")
+        form = f"{K * G} models per pass ({G} splits x {K} folds) from shared reads of {'every block' if coupled else 'X'} {entries}"
+        if why is not None:
+            form += "; failed passes refitted per fold on the regular engine"
+        reads = NS + passes * (2 * R - 1)                                            # G + 2R - 1 per pass
         x_reads = [reads] * len(Xs) if coupled else reads
+    else:
+        form = "one refit per fold and split on the regular engine"
     rep = {"form": form, "splits": int(NS), "passes": int(passes), "splits_per_pass": int(G) if passes else None,
            "x_reads": x_reads, "n_iter": n_iters}
     if why is not None:

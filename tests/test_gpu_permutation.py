@@ -68,7 +68,7 @@ def test_device_null_equals_literal_refits(shape, M, R, K, folds, dtype):
 
 
 @pytest.mark.parametrize("shape,M,R,K,folds", CASES)
-def test_grouped_entries_with_identity_map_are_bitwise_kfold(shape, M, R, K, folds):
+def test_grouped_run_with_identity_map_is_bitwise_kfold(shape, M, R, K, folds):
     x, y, _ = O.import_synthetic(shape, M, R + 1, error=0.3, seed=9)
     if folds == "shuffled":
         folds = np.random.default_rng(4).permutation(np.arange(shape[0]) % K)
@@ -78,10 +78,23 @@ def test_grouped_entries_with_identity_map_are_bitwise_kfold(shape, M, R, K, fol
     want = kfold_predictions(m, n_splits=K, folds=folds)
     assert "cmtfpls_kfold_inner_f64" in m.q2y_report_["form"]
     ids, K = fold_ids(shape[0], K, folds)
-    got, rep = kfold.device_predictions(m, m.original_X, m.original_Y, ids, K, 1e-8, 100, grouped=True)
-    assert got is not None, rep
+    be = m._get_engine().be                                     # the K-fold device form with model k = fold k in one group
+    I = shape[0]
+    A, B = kfold._dims(x)
+    Yh = y.reshape(I, -1).astype(np.float64)
+    order, off, ybar, nu, Yk = kfold._fold_y(Yh, ids, K)
+    t = lambda a, dt=torch.float64: kfold._to_dev(a, be.device, dt)
+    X2 = t(x.reshape(I, A * B))
+    S, mean = be.empty(K, M, A * B), be.empty(K, A * B)
+    assert be.kfold_xcov(X2, A, B, t(Yh - ybar), t(order, torch.int32), t(off, torch.int32), K, t(nu - ybar), S, mean) is not None
+    st, shared, own = kfold._state(be, t(ids, torch.int32), t(Yk), [(A, B, S, mean)], R, 1)
+    mf = torch.arange(K, dtype=torch.int32, device=be.device)
+    assert kfold._components(be, [X2], st, shared, own, R, 1e-8, 100, False, grouped=(mf, 1)) is None
+    assert not shared["status"].any()
+    got = kfold._held_out_predictions(shared["Tout"][0].cpu().numpy(), shared["coef"].cpu().numpy(), shared["Q"].cpu().numpy(), nu,
+                                      ids, K, R, M)
     assert np.array_equal(got.reshape(want.shape), want)
-    assert rep["n_iter"] == m.q2y_report_["n_iter"]
+    assert shared["n_iter"].cpu().numpy().tolist() == m.q2y_report_["n_iter"]
 
 
 def test_identity_permutation_equals_observed():

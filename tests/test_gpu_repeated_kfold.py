@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import oracle as O
-from cmtf_pls_amd import _lib, ctPLS, kfold, tPLS
+from cmtf_pls_amd import ctPLS, kfold, tPLS
 from cmtf_pls_amd.kfold import fold_ids
 from cmtf_pls_amd.validate import get_q2y_kfold, get_q2y_repeated_kfold
 
@@ -91,9 +91,9 @@ def test_one_block_ctpls_is_bitwise_tpls():
     assert t.q2y_report_["n_iter"] == c.q2y_report_["n_iter"]
 
 
-def _kfold_buffers(m, K, epilogue):
-    """Run the tPLS K-fold device form (kfold.device_predictions' steps) with `epilogue(be, st, stage, a, src)` and return its
-    buffers after the last component."""
+def _kfold_buffers(m, K, splits):
+    """Run the tPLS K-fold device form through kfold._state and kfold._components (kfold_epilogue; with splits > 0
+    kfold_epilogue_splits with that many splits) and return its buffers after the last component."""
     be = m._get_engine().be
     X, Y = m.original_X, m.original_Y
     R = m.n_components
@@ -103,32 +103,15 @@ def _kfold_buffers(m, K, epilogue):
     ids, K = fold_ids(I, K)
     Yh = Y.reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
-    dev = be.device
     order, off, ybar, nu, Yk = kfold._fold_y(Yh, ids, K)
-    t = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+    t = lambda a, dt=torch.float64: kfold._to_dev(a, be.device, dt)
     X2 = t(X.reshape(I, P))
-    NT, stride = be.kfold_row_tiles(I)
-    buf = {
-        "fold_of": t(ids, torch.int32), "S": be.empty(K, M, P), "mean": be.empty(K, P), "Yk": t(Yk), "Gy": be.empty(K, NT, M, M),
-        "WA": be.empty(A, K), "WB": be.empty(B, K), "Q": be.zeros(K, R, M), "Wa": be.zeros(K, R, A), "Wb": be.zeros(K, R, B),
-        "T": be.zeros(K, I, R), "Gt": be.zeros(K, R, R), "coef": be.zeros(K, R, R), "Rm": be.zeros(K, R, P), "tm": be.empty(I, K),
-        "Tout": be.zeros(I, R), "vec": be.zeros(K, 3 * R + M + 2), "n_iter": torch.zeros(K, R, dtype=torch.int32, device=dev),
-        "status": torch.zeros(K, dtype=torch.int32, device=dev), "part": be.empty(K, NT, stride),
-    }
-    assert be.kfold_xcov(X2, A, B, t(Yh - ybar), t(order, torch.int32), t(off, torch.int32), K, t(nu - ybar), buf["S"], buf["mean"]) is not None
-    st = _lib.KfoldState(I, A, B, M, K, R, *[buf[f].data_ptr() for f, _ in _lib.KfoldState._fields_[6:]])
-    ws = torch.empty(max(be.kfold_inner_workspace_bytes(A, B, K), 256), dtype=torch.uint8, device=dev)
-    sc, rs = be.empty(I, K), be.empty(K, P)
-    assert epilogue(be, st, 0, 0, None)
-    for a in range(R):
-        assert be.kfold_inner(st, a, 1e-8, 100, ws)
-        be.mttkrp(X2, A, B, buf["WA"], buf["WB"], sc)
-        assert epilogue(be, st, 1, a, sc)
-        if a + 1 < R:
-            be.xcov(X2, buf["tm"], False, out=rs)
-            assert epilogue(be, st, 2, a, rs)
+    S, mean = be.empty(K, M, P), be.empty(K, P)
+    assert be.kfold_xcov(X2, A, B, t(Yh - ybar), t(order, torch.int32), t(off, torch.int32), K, t(nu - ybar), S, mean) is not None
+    st, shared, own = kfold._state(be, t(ids, torch.int32), t(Yk), [(A, B, S, mean)], R, 1)
+    assert kfold._components(be, [X2], st, shared, own, R, 1e-8, 100, False, splits=splits) is None
     torch.cuda.synchronize()
-    return buf
+    return {**shared, **own[0]}
 
 
 @pytest.mark.parametrize("shape,M,R,K", [((60, 10, 8), 4, 3, 5), ((37, 30), 2, 4, 3), ((40, 6, 5), 16, 2, 2)])
@@ -136,8 +119,8 @@ def test_splits_entry_with_one_split_is_bitwise_kfold_epilogue(shape, M, R, K):
     x, y, _ = O.import_synthetic(shape, M, R + 1, error=0.3, seed=4)
     m = tPLS(R, dtype="float64")
     m.fit(x, y)
-    want = _kfold_buffers(m, K, lambda be, st, stage, a, src: be.kfold_epilogue(st, stage, a, src))
-    got = _kfold_buffers(m, K, lambda be, st, stage, a, src: be.kfold_epilogue_splits(st, 1, stage, a, src))
+    want = _kfold_buffers(m, K, 0)
+    got = _kfold_buffers(m, K, 1)
     for f in ("Tout", "coef", "Q", "S", "Yk", "T", "n_iter", "status"):
         assert torch.equal(got[f], want[f]), f
 
