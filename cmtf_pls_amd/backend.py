@@ -747,6 +747,35 @@ class HipBackend:
         _lib.check(rc, "kfold_epilogue_splits")
         return True
 
+    # -- bootstrap of the factors (validate.bootstrap_factors, bootstrap.py): n weighted resamples per pass ------------------
+    def kfold_weighted_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, n: int, M: int, S: torch.Tensor,
+                            mean: torch.Tensor) -> Optional[torch.Tensor]:
+        """Every resample's cross-covariance S (n x M x P) and means (n x P) from ONE read of the uncentred X2 on the f64 matrix
+        cores (cmtfpls_kfold_weighted_xcov_*); Y = [c_1 * (Y - nu_1) .. c_n * (Y - nu_n) | c_1 .. c_n] (I x n (M + 1)).  Returns
+        the column sums / sums of squares of all rows (2 P), or None when the shape is outside the device form.  The partial-sum
+        workspace is local to the call."""
+        I, P = X2.shape
+        assert Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape == (I, n * (M + 1)) and P == A * B
+        assert S.is_contiguous() and S.numel() == n * M * P and mean.is_contiguous() and mean.numel() == n * P
+        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M)), 256), dtype=torch.uint8,
+                         device=self.device)
+        stats = self.empty(2 * P)
+        rc = self._fn("kfold_weighted_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), n, M, _ptr(S), _ptr(mean), _ptr(stats), _ptr(ws),
+                                                 ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_weighted_xcov")
+        return stats
+
+    def kfold_epilogue_weighted(self, state, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
+        """kfold_epilogue for state.K weighted models (cmtfpls_kfold_epilogue_weighted_f64): fold_of is the n x I row counts,
+        every training-row sum is weighted by them; the rows with count 0 keep their projection in T."""
+        rc = self.lib.cmtfpls_kfold_epilogue_weighted_f64(ctypes.byref(state), int(stage), int(a), _ptr(src), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_epilogue_weighted")
+        return True
+
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
         returns a dict of device tensors (T, U, WA, WB, Q, x_mean, y_mean) and host arrays (coef, ssq, n_iter), or None

@@ -22,8 +22,9 @@ namespace cmtfpls {
 constexpr int kKfMaxK = 32, kKfMaxM = 64, kKfMaxR = 64, kKfMaxN = 256;
 constexpr int kKfCols = 256;          // columns per workgroup of the column-owner kernels (one per thread)
 // which fold a model holds out and where its held-out scores go (kfold_rows_kernel, kfold_ydefl_kernel): model k = fold k
-// (kKfPlain), the grouped models of the permutation test (kKfGrouped) or the split-major models of repeated K-fold (kKfSplits)
-enum KfMode : int { kKfPlain = 0, kKfGrouped = 1, kKfSplits = 2 };
+// (kKfPlain), the grouped models of the permutation test (kKfGrouped), the split-major models of repeated K-fold (kKfSplits) or
+// the bootstrap models, each row weighted by its count in the model's resample (kKfWeighted)
+enum KfMode : int { kKfPlain = 0, kKfGrouped = 1, kKfSplits = 2, kKfWeighted = 3 };
 
 // ---- kfold_xcov ------------------------------------------------------------------------------------------------------------
 // Row chunks per fold so that the partial-sum grid has >= ~2048 workgroups (a thread per column, rows sequential: the rows of a
@@ -215,7 +216,8 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
 // T_train^T t (the Gram row a), T_train^T u, 1^T t_train and Y_k^T t.  kKfGrouped: model k holds out fold model_fold[k] and writes
 // its held-out scores to group k % groups of Tout (groups x I x R).  kKfSplits: `groups` is the folds per split; model k holds out
 // fold k % groups of split k / groups, whose fold map is row k / groups of fold_of, and writes its held-out scores to that split's
-// slot of Tout (splits x I x R)
+// slot of Tout (splits x I x R).  kKfWeighted: fold_of is n x I counts, model k trains on the rows with c = fold_of[k I + i] > 0
+// and every training-row sum is weighted by c (tm = c t); Tout is not written (the rows with c = 0 keep their projection in T)
 template <int MODE>
 __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold_state st, int a, const double* __restrict__ sc,
                                                                    const int* __restrict__ model_fold, int groups) {
@@ -227,7 +229,8 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
   const double mw = vec[3 * R + M + 1];
   const int own = MODE == kKfGrouped ? model_fold[k] : MODE == kKfSplits ? k % groups : k;
-  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / groups) * I : st.fold_of;
+  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / groups) * I
+                       : MODE == kKfWeighted ? st.fold_of + (int64_t)k * I : st.fold_of;
   double* Tout = MODE == kKfGrouped ? st.Tout + (int64_t)(k % groups) * I * R
                  : MODE == kKfSplits ? st.Tout + (int64_t)(k / groups) * I * R : st.Tout;
   for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
@@ -242,18 +245,25 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
     const int i = i0 + tid;
     const bool ok = i < hi;
     bool train = false;
-    double t = 0.0, u = 0.0;
+    double t = 0.0, u = 0.0, wt = 0.0;
     if (ok) {
       t = sc[(int64_t)i * K + k] - mw;
       for (int j = 0; j < a; ++j) t = fma(-T[(int64_t)i * R + j], g[j], t);
       T[(int64_t)i * R + a] = t;
-      train = fold_of[i] != own;
-      if (!train) Tout[(int64_t)i * R + a] = t;
-      st.tm[(int64_t)i * K + k] = train ? t : 0.0;
+      if (MODE == kKfWeighted) {
+        const int c = fold_of[i];
+        train = c > 0;
+        wt = (double)c;
+      } else {
+        train = fold_of[i] != own;
+        if (!train) Tout[(int64_t)i * R + a] = t;
+      }
+      st.tm[(int64_t)i * K + k] = train ? (MODE == kKfWeighted ? wt * t : t) : 0.0;
       if (train)
         for (int m = 0; m < M; ++m) u = fma(Yk[(int64_t)i * M + m], q[m], u);
+      if (MODE == kKfWeighted) u *= wt;
     }
-    const double tt = train ? t : 0.0;
+    const double tt = train ? (MODE == kKfWeighted ? wt * t : t) : 0.0;
     for (int p = 0; p < kk; ++p) {
       const double tp = train ? (p == a ? t : T[(int64_t)i * R + p]) : 0.0;
       const double s1 = wave_sum(tp * tt), s2 = wave_sum(tp * u);
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_rows_kernel(cmtfpls_kfold
     const double s3 = wave_sum(tt);
     if (lane == 0) acc[wv][2 * kk] += s3;
     for (int m = 0; m < M; ++m) {                                  // (held-out rows of Y_k are 0)
-      const double s4 = wave_sum(ok ? Yk[(int64_t)i * M + m] * t : 0.0);
+      const double s4 = wave_sum(ok ? Yk[(int64_t)i * M + m] * (MODE == kKfWeighted ? tt : t) : 0.0);
       if (lane == 0) acc[wv][2 * kk + 1 + m] += s4;
     }
   }
@@ -334,18 +344,21 @@ __global__ __launch_bounds__(64) void kfold_solve_kernel(cmtfpls_kfold_state st,
 
 // stage 0 / 1c, grid (row tiles, folds): (deflate: Y_k -= (T b) q^T on the training rows, tpls.py:113) and the tile's partial
 // Y_k^T Y_k for the next component's convergence test, rows staged through LDS a chunk at a time.  MODE: the training rows as in
-// kfold_rows_kernel (`folds`: the folds per split of kKfSplits)
+// kfold_rows_kernel (`folds`: the folds per split of kKfSplits; kKfWeighted: the rows with a count > 0 deflated, the Gram
+// sum_i c_i y_i y_i^T)
 template <int MODE>
 __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfold_state st, int a, int deflate,
                                                                     const int* __restrict__ model_fold, int folds) {
   constexpr int EPT = kKfMaxM * kKfMaxM / kKfRowThreads;          // Gram entries per thread
   __shared__ double Ys[kKfChunk][kKfMaxM + 1];
   __shared__ double q[kKfMaxM], b[kKfMaxR];
+  __shared__ double wr[MODE == kKfWeighted ? kKfChunk : 1];       // the staged rows' counts
   const int tid = threadIdx.x, tile = blockIdx.x, k = blockIdx.y;
   const int I = st.I, M = st.M, R = st.R, kk = a + 1, NT = kf_tiles(I);
   const double* vec = st.vec + (int64_t)k * kf_vec_len(R, M);
   const int own = MODE == kKfGrouped ? model_fold[k] : MODE == kKfSplits ? k % folds : k;
-  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / folds) * I : st.fold_of;
+  const int* fold_of = MODE == kKfSplits ? st.fold_of + (int64_t)(k / folds) * I
+                       : MODE == kKfWeighted ? st.fold_of + (int64_t)k * I : st.fold_of;
   if (deflate) {
     for (int m = tid; m < M; m += kKfRowThreads) q[m] = st.Q[((int64_t)k * R + a) * M + m];
     for (int j = tid; j < kk; j += kKfRowThreads) b[j] = vec[j];
@@ -364,7 +377,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
       double y = 0.0;
       if (i < hi) {
         y = Yk[(int64_t)i * M + m];
-        if (deflate && fold_of[i] != own) {
+        if (deflate && (MODE == kKfWeighted ? fold_of[i] > 0 : fold_of[i] != own)) {
           double yh = 0.0;
           for (int j = 0; j < kk; ++j) yh = fma(T[(int64_t)i * R + j], b[j], yh);
           y = fma(-yh, q[m], y);
@@ -372,6 +385,7 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
         }
       }
       Ys[r][m] = y;
+      if (MODE == kKfWeighted && m == 0) wr[r] = i < hi ? (double)fold_of[i] : 0.0;
     }
     __syncthreads();
 #pragma unroll
@@ -380,7 +394,10 @@ __global__ __launch_bounds__(kKfRowThreads) void kfold_ydefl_kernel(cmtfpls_kfol
       if (o < M * M) {
         const int m1 = o / M, m2 = o % M;
         double s = accg[e];
-        for (int r = 0; r < kKfChunk; ++r) s = fma(Ys[r][m1], Ys[r][m2], s);
+        if (MODE == kKfWeighted)
+          for (int r = 0; r < kKfChunk; ++r) s = fma(Ys[r][m1] * wr[r], Ys[r][m2], s);
+        else
+          for (int r = 0; r < kKfChunk; ++r) s = fma(Ys[r][m1], Ys[r][m2], s);
         accg[e] = s;
       }
     }
@@ -889,6 +906,83 @@ static int kf_epilogue_launch(const cmtfpls_kfold_state* st, const int* model_fo
 // splits x I, model m reads row m / K of it, and its held-out scores go to slot m / K of Tout (splits x I x R).  The splits are
 // partitions of the rows, so every row of every slot is written exactly once.
 
+// ---- weighted models (bootstrap, bootstrap.py) -----------------------------------------------------------------------------
+// A bootstrap resample differs from the fitted data only in each row's multiplicity c_i (0, 1, 2, ..): the refit on the resampled
+// rows is the fit in which every sum over rows is weighted by c.  A pass carries n <= 32 resamples as models of one state; its
+// fold_of is n x I counts.  Per pass:
+//   kfold_weighted  every model's S_b = X_0^T (c_b * (Y - nu_b)) and mu_b = X_0^T c_b / I from ONE pass over X: kfold_wide_kernel
+//                   over Y'' = [c_1 * (Y - nu_1) .. c_n * (Y - nu_n) | c_1 .. c_n] (W = n (M + 1) <= 1024 columns) with all rows
+//                   as one fold, then the chunks' partials added in chunk order.  (sum_i c_i (Y_i - nu_b) = 0, so S_b is the
+//                   centred cross-covariance of the resample.)  Also the column sums / sums of squares of all rows, unweighted
+//   the inner loop, the score pass, the contraction and stage 2 are those of the folds above with n columns; stages 0 and 1 are
+//   the kKfWeighted instantiations of kfold_ydefl_kernel / kfold_rows_kernel
+// identity row order and one fold of all rows for kfold_wide_kernel
+__global__ __launch_bounds__(256) void kfold_iota_kernel(int* __restrict__ order, int I, int* __restrict__ off) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < I; i += gridDim.x * 256) order[i] = i;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { off[0] = 0; off[1] = I; }
+}
+
+// a thread per column: S (n x M x P) = the first n M columns of Y'', mean (n x P) = the count columns / I, stats (2 P)
+__global__ __launch_bounds__(kKfCols) void kfold_weighted_finish_kernel(int64_t P, int n, int M, int nch, int I,
+                                                                        const double* __restrict__ part, double* __restrict__ S,
+                                                                        double* __restrict__ mean, double* __restrict__ stats) {
+  const int64_t c = (int64_t)blockIdx.x * kKfCols + threadIdx.x;
+  if (c >= P) return;
+  const int W = n * (M + 1);
+  auto sum = [&](int j) {
+    double s = 0.0;
+    for (int ch = 0; ch < nch; ++ch) s += part[((int64_t)ch * (W + 2) + j) * P + c];
+    return s;
+  };
+  stats[c] = sum(W);
+  stats[P + c] = sum(W + 1);
+  for (int b = 0; b < n; ++b) mean[(int64_t)b * P + c] = sum(n * M + b) / (double)I;
+  for (int j = 0; j < n * M; ++j) S[(int64_t)j * P + c] = sum(j);
+}
+
+static size_t kf_weighted_part_bytes(int64_t I, int64_t P, int W) {
+  return (size_t)kf_wide_plan(I, P, W, 1).nch * (size_t)(W + 2) * (size_t)P * sizeof(double);
+}
+
+template <typename T>
+static int run_kfold_weighted(const T* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                              double* stats, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!X || !Y || !S || !mean || !stats || I <= 0 || A <= 0 || B <= 0 || n <= 0 || M <= 0) {
+    set_error("kfold_weighted_xcov: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  const int64_t P = (int64_t)A * B;
+  const int W = n * (M + 1);
+  if (n > kKfMaxK || M > kKfMaxM || W > kKfWideMaxW || I > (int64_t)1 << 30 || P > (int64_t)1 << 24) {
+    set_error("kfold_weighted_xcov: shape outside the device form (n <= 32, M <= 64, n (M + 1) <= 1024, A * B <= 2^24)");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t need = cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M);
+  if (!ws || ws_bytes < need) { set_error("kfold_weighted_xcov: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const KfWidePlan pl = kf_wide_plan(I, P, W, 1);
+  double* part = static_cast<double*>(ws);
+  int* order = reinterpret_cast<int*>(static_cast<char*>(ws) + kf_weighted_part_bytes(I, P, W));
+  int* off = order + I;
+  int64_t gi = (I + 255) / 256;
+  if (gi > 4096) gi = 4096;
+  hipLaunchKernelGGL(kfold_iota_kernel, dim3((unsigned)gi), dim3(256), 0, st, order, (int)I, off);
+  int rc = check_launch("kfold_weighted_xcov");
+  if (rc) return rc;
+  const int64_t ct = (P + kKfWideCols - 1) / kKfWideCols;
+  const dim3 g((unsigned)(ct * pl.nyb), (unsigned)pl.nch);
+  switch (pl.mt) {
+    case 1: kf_wide_launch<T, 1>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    case 2: kf_wide_launch<T, 2>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    case 3: kf_wide_launch<T, 3>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    default: kf_wide_launch<T, 4>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+  }
+  rc = check_launch("kfold_weighted_xcov");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kfold_weighted_finish_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols)), dim3(kKfCols), 0, st, P, n, M,
+                     pl.nch, (int)I, part, S, mean, stats);
+  return check_launch("kfold_weighted_xcov");
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -1021,6 +1115,33 @@ int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits,
     return CMTFPLS_EUNSUPPORTED;
   }
   return kf_epilogue_launch<kKfSplits>(st, nullptr, folds, stage, a, in, (hipStream_t)stream, "kfold_epilogue_splits");
+}
+
+size_t cmtfpls_kfold_weighted_xcov_workspace_bytes(int64_t I, int64_t P, int n, int M) {
+  if (I <= 0 || P <= 0 || n <= 0 || M <= 0) return 0;
+  return kf_weighted_part_bytes(I, P, n * (M + 1)) + (size_t)(I + 2) * sizeof(int);
+}
+
+int cmtfpls_kfold_weighted_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_weighted<float>(X, I, A, B, Y, n, M, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_weighted<double>(X, I, A, B, Y, n, M, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_epilogue_weighted_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {
+  if (!kf_state_ok(st) || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+    set_error("kfold_epilogue_weighted: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if (!kf_shape_ok(st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold_epilogue_weighted: shape outside the device form (2 <= n <= 32 models <= I, M <= 64, R <= 64); refit");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  return kf_epilogue_launch<kKfWeighted>(st, nullptr, 1, stage, a, in, (hipStream_t)stream, "kfold_epilogue_weighted");
 }
 
 }  // extern "C"

@@ -17,9 +17,9 @@ the shared t, one contraction and stage 2 per block: 2R reads of each block.
 
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
 
-The permutation test (permutation.py) and repeated K-fold (repeated.py) run the same state with more models per pass: _state
-allocates it (a view per block), _components makes every launch of a pass with the inner and epilogue entries of the form, and
-_device_passes runs the passes and refits whatever they leave.
+The permutation test (permutation.py), repeated K-fold (repeated.py) and the bootstrap (bootstrap.py) run the same state with
+more models per pass: _state allocates it (a view per block), _components makes every launch of a pass with the inner and
+epilogue entries of the form, and _device_passes runs the passes and refits whatever they leave.
 """
 from __future__ import annotations
 
@@ -279,11 +279,13 @@ def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: i
     return (_lib.KfoldState * len(views))(*views), shared, own
 
 
-def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0):
+def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0,
+                weighted: bool = False):
     """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
     ctPLS, one block included: then the blocks' scores averaged), stage 1 and, but for the last, one contraction and stage 2 per
     block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled) or kfold_inner_grouped; the epilogue: kfold_epilogue,
-    kfold_epilogue_grouped (grouped = (model_fold, groups)) or kfold_epilogue_splits (splits > 0).  None, or why a kernel declined."""
+    kfold_epilogue_grouped (grouped = (model_fold, groups)), kfold_epilogue_splits (splits > 0) or kfold_epilogue_weighted
+    (weighted: fold_of holds the models' row counts).  None, or why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled:
         ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
@@ -298,6 +300,8 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
         epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_grouped(st[b], *grouped, *args), "kfold_epilogue_grouped_f64"
     elif splits:
         epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_splits(st[b], splits, *args), "kfold_epilogue_splits_f64"
+    elif weighted:
+        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_weighted(st[b], *args), "kfold_epilogue_weighted_f64"
     else:
         epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue(st[b], *args), "kfold_epilogue_f64"
     scs = be.empty(nb, I, n)

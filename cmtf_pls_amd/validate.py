@@ -120,3 +120,23 @@ def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, f
     from .repeated import repeated_kfold
 
     return repeated_kfold(pls_tensor, n_splits, n_repeats, folds, random_state, per_component, device_folds)
+
+
+def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random_state=0, level: float = 0.95,
+                      device_folds: bool = True) -> dict:
+    """Bootstrap of a fitted tPLS or ctPLS: resample b refits the model, with its dtype, device, backend, algorithm and options,
+    on X[idx_b], Y[idx_b] (a ctPLS: every block with the same rows), and is aligned to the fitted model (bootstrap.align_factors:
+    every X-mode loading column flipped to a nonnegative inner product with the fitted one, a zero counting as +1; d_a the product
+    of the first block's flips of component a; q_a -> d_a q_a and coef_ -> D coef_ D, D = diag(d)).  Resamples: B = n_resamples
+    rows of np.random.default_rng(random_state).integers(0, I, size=(B, I)), or `resamples`, a (B, I) integer array of row indices
+    in [0, I) (ValueError otherwise, when B < 2 or when level is not in (0, 1)).
+    Returns {"resamples": (B, I), "X_factors": per mode 1.. a (B, dim, R) stack laid out like X_factors[1:] (a ctPLS: one such
+    list per block), "Y_loadings": (B, M, R), "coef": (B, R, R), "se": those three with the std over the resamples (ddof 1),
+    "ci": with np.percentile at 100 (1 -/+ level) / 2 on a leading axis of 2, "oob_q2y": (R,) the Q2Y (validate.py:35-37) of the
+    out-of-bag predictions with r = 1..R components (row i's: the mean over the resamples that left it out of their models'
+    predictions) over "oob_rows" rows, those left out at least once}.  On the GPU up to 32 resamples per pass share every read of X
+    (2R reads per pass and block, bootstrap.py); anything else refits every resample.  Which form ran is recorded on the model
+    (``bootstrap_report_``)."""
+    from .bootstrap import bootstrap
+
+    return bootstrap(pls_tensor, n_resamples, resamples, random_state, level, device_folds)

@@ -574,6 +574,29 @@ int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int*
  * held-out scores to Tout slot m / folds.  Stages 0 and 2 are those of cmtfpls_kfold_epilogue_f64; with splits = 1 the entry is
  * bitwise cmtfpls_kfold_epilogue_f64. */
 int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits, int stage, int a, const double* in, void* stream);
+
+/* ---- Bootstrap of the factors (validate.bootstrap_factors) --------------------------------------------------------------------
+ * A resample differs from the fitted data only in each row's multiplicity c (0, 1, 2, ..).  A pass carries n <= 32 resamples
+ * (n <= I) as the models of one cmtfpls_kfold_state (its K = n), whose fold_of is n x I counts: model b trains on the rows with
+ * c_b,i > 0, every training-row sum weighted by c_b,i.  Per pass: kfold_weighted_xcov (every model's S and mean from ONE pass
+ * over X), kfold_epilogue_weighted stage 0, then per component cmtfpls_kfold_inner_f64 (a ctPLS: cmtfpls_kfold_inner_coupled_f64),
+ * the MTTKRP with n columns, kfold_epilogue_weighted stage 1, and (all but the last) the contraction X_0^T tm and stage 2.  2R
+ * reads of X per pass. */
+/* kfold_weighted_xcov: S (n x M x A*B) = X_0^T (c_b * (Y - nu_b)) and mean (n x A*B) = X_0^T c_b / I for every model b from ONE
+ * pass over X on the f64 matrix cores; Y (I x n (M + 1), n (M + 1) <= 1024) holds the columns c_b * (Y - nu_b) model by model,
+ * then the n count columns c_b as doubles (sum_i c_b,i = I).  stats (2 A*B): column sums and sums of squares of all rows,
+ * unweighted.  Sums run in a fixed order.  ws >= cmtfpls_kfold_weighted_xcov_workspace_bytes(I, A * B, n, M). */
+size_t cmtfpls_kfold_weighted_xcov_workspace_bytes(int64_t I, int64_t P, int n, int M);
+int cmtfpls_kfold_weighted_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream);
+/* kfold_epilogue_weighted: cmtfpls_kfold_epilogue_f64 for st->K = n weighted models (2 <= n <= I): stage 0 builds the Gram
+ * sum_i c_i y_i y_i^T of each model's Yk (rows with c = 0 must be 0); stage 1 weights every training-row sum by c, writes
+ * tm = c t and deflates the rows with c > 0; T keeps every row's score, the rows with c = 0 their projection (Tout is not
+ * written); stage 2 is that of cmtfpls_kfold_epilogue_f64.  With 0/1 counts the entry is bitwise cmtfpls_kfold_epilogue_f64 on
+ * the folds whose training rows they mark. */
+int cmtfpls_kfold_epilogue_weighted_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
