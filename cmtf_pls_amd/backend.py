@@ -586,6 +586,25 @@ class HipBackend:
         _lib.check(rc, "recon_r2")
         return out
 
+    def resid_rows(self, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+                   want_cols: bool) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+        """recon_r2's residual kept per row and per column, in one read of X2 (uncentred, storage type): rows (I, 3) =
+        [sum e^2, sum x^2, observed entries] per sample and, with want_cols, cols (P, 2) = [sum e^2, sum x^2] per variable,
+        x = X2 - mean over its finite entries, e = x - T (WA (.) WB)^T; None when the shape has no device form (R > 16)."""
+        I, P = X2.shape
+        R = T.shape[1]
+        A, B = WA.shape[0], WB.shape[0]
+        assert X2.is_contiguous() and T.stride(1) == 1 and WA.is_contiguous() and WB.is_contiguous() and P == A * B
+        ws = self._workspace("resid_rows", self.lib.cmtfpls_resid_rows_workspace_bytes(I, P))
+        rows = self.empty(I, 3)
+        cols = self.empty(P, 2) if want_cols else None
+        rc = self._fn("resid_rows", X2)(_ptr(X2), _ptr(T), I, T.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean), _ptr(rows),
+                                       _ptr(cols), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "resid_rows")
+        return rows, cols
+
     def loo_tpls(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int,
                  max_ws_bytes: Optional[int] = None, forms=("lds", "xcov")) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
         """Leave-one-out predictions of a tPLS model (validate.py:24-33), every fold a workgroup: returns

@@ -8,7 +8,7 @@ Forms, in the order they are tried (`NipalsEngine.last_projection` records which
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -198,6 +198,62 @@ class ProjectionMixin:
                 return None
             res, ssq = self.comm.allreduce(out).cpu().tolist()
             return 1.0 - res / ssq
+
+    def residual_rows(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, want_cols: bool = True,
+                      device: bool = True) -> List[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+        """Per block, for the rows Xs[b] (device, storage type, UNCENTRED, read only) with scores T (I x R):
+        (rows (I, 3) = [sum e^2, sum x^2, observed entries] per sample, cols (P, 2) = [sum e^2, sum x^2] per variable or
+        None), x = X - mean over the finite entries (the calcR2X mask, util.py:7-15), e = x - T W_b^T.  One read of every
+        block through cmtfpls_resid_rows_*; where the backend declines (R > 16, no such kernel, device=False) the same sums
+        from torch ops on row blocks of <= 256 MB.  `last_residual` records, per block, the form that ran and why."""
+        be = self.be
+        R = state.n_components
+        out, forms = [], []
+        with self.device_ctx():
+            for blk, X in zip(state.blocks, Xs):
+                I = X.shape[0]
+                X2 = X.reshape(I, -1)
+                WA, WB = self._kr_operands(blk, R)
+                res, why = None, None
+                if not device:
+                    why = "device pass switched off"
+                elif not hasattr(be, "resid_rows"):
+                    why = "backend has no resid_rows kernel"
+                elif I > 0:
+                    res = be.resid_rows(X2, T, WA, WB, blk.mean, want_cols)
+                    if res is None:
+                        why = f"R = {R} > 16: outside cmtfpls_resid_rows"
+                if res is None:
+                    res = self._residual_rows_torch(X2, T, WA, WB, blk.mean, want_cols)
+                out.append(res)
+                forms.append({"form": "torch fallback" if why else "residual pass (cmtfpls_resid_rows)", "why": why})
+        self.last_residual = forms
+        return out
+
+    @staticmethod
+    def _residual_rows_torch(X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+                             want_cols: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        I, P = X2.shape
+        dev = T.device
+        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        rows = torch.empty(I, 3, dtype=torch.float64, device=dev)
+        cols = torch.zeros(P, 2, dtype=torch.float64, device=dev) if want_cols else None
+        step = max(1, (256 << 20) // max(P * 8, 1))
+        for r0 in range(0, I, step):
+            x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
+            if mean is not None:
+                x = x - mean
+            fin = torch.isfinite(x)
+            e = torch.where(fin, x - T[r0:r0 + step] @ W.T, 0.0)
+            x = torch.where(fin, x, 0.0)
+            e2, x2 = e * e, x * x
+            rows[r0:r0 + step, 0] = e2.sum(dim=1)
+            rows[r0:r0 + step, 1] = x2.sum(dim=1)
+            rows[r0:r0 + step, 2] = fin.sum(dim=1).to(torch.float64)
+            if want_cols:
+                cols[:, 0] += e2.sum(dim=0)
+                cols[:, 1] += x2.sum(dim=0)
+        return rows, cols
 
     def _project_one_pass(self, state: FitState, Xs: List[torch.Tensor], mixed: bool = False, centred: bool = True,
                           nan_flag: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:

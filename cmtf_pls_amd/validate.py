@@ -140,3 +140,20 @@ def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random
     from .bootstrap import bootstrap
 
     return bootstrap(pls_tensor, n_resamples, resamples, random_state, level, device_folds)
+
+
+def sample_diagnostics(pls_tensor, X=None, Y=None, level: float = 0.95, device: bool = True) -> dict:
+    """Which samples and variables a fitted tPLS or ctPLS fails to describe.  X=None: the training rows (their fitted scores and
+    ``original_X``; ValueError after a copy_X=False fit); otherwise new rows (a ctPLS: a list of blocks, as for transform), scored
+    as transform scores them.  Y (training rows: ``original_Y`` by default) adds the prediction residual.
+    Returns {"scores": (I', R), "t2": (I',) Hotelling's T^2 against the training scores' mean and covariance (ddof 1, pseudo-
+    inverse), "t2_limit", "spe" (I',) the Q residual sum_c e^2 of x = X - X_mean over its finite entries, "ssq" (I',) sum_c x^2,
+    "n_observed" (I',), "spe_limit" (Box's chi^2 approximation from the training SPE), "r2x_per_variable" (X.shape[1:]: 1 -
+    sum_i e^2 / sum_i x^2 over the diagnosed rows, NaN without an observed entry or variance), "y_residual" (I',) sum_m (y -
+    y_hat)^2 or None, "level"}; a ctPLS gives spe, ssq, n_observed, spe_limit and r2x_per_variable as lists over its blocks.
+    Limits at `level` (in (0, 1), ValueError otherwise), NaN with a why in the report when I <= R + 1 or the SPE has no spread.
+    On the GPU every block is read once per residual pass (cmtfpls_resid_rows_*); device=False, or R > 16, takes torch ops
+    instead.  The training statistics are cached on the model.  Which form ran: ``diagnostics_report_`` (diagnostics.py)."""
+    from .diagnostics import sample_diagnostics as _run
+
+    return _run(pls_tensor, X, Y, level, device)

@@ -444,6 +444,20 @@ int cmtfpls_recon_r2_f32(const float* X, const double* T, int64_t I, int ldt, in
 int cmtfpls_recon_r2_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
                          int A, int B, const double* mean, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* resid_rows: the residual of recon_r2 kept per sample and per variable (validate.sample_diagnostics), in ONE read of the
+ * uncentred X (I x A*B, storage type, any alignment), the reconstruction never materialised.  With x = X[i,c] - mean[c]
+ * (mean nullable) and e = x - sum_r T[i*ldt + r] WA[(c / B)*R + r] WB[(c % B)*R + r], over the entries with x finite (the
+ * calcR2X mask, util.py:7-15):
+ *   rows[3*i + 0] = sum_c e^2 (the Q residual / SPE),  rows[3*i + 1] = sum_c x^2,  rows[3*i + 2] = number of such entries;
+ *   cols[2*c + 0] = sum_i e^2,  cols[2*c + 1] = sum_i x^2  (cols nullable: the column sums are skipped).
+ * A NaN score row gives a NaN rows[3*i + 0].  Deterministic: partials per (column tile, row) and per (row block, column),
+ * closed by fixed-order reduces; no atomics.  R <= 16 (CMTFPLS_EUNSUPPORTED beyond); ws: cmtfpls_resid_rows_workspace_bytes. */
+size_t cmtfpls_resid_rows_workspace_bytes(int64_t I, int64_t P);
+int cmtfpls_resid_rows_f32(const float* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                           int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_resid_rows_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                           int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- leave-one-out refits, all folds in one launch: validate.get_q2y  (cmtf_pls/validate.py:7-37) ------------
  * For every fold i in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113; R components, tol, max_iter, the
  * reference's loop and convergence test) on the I - 1 samples other than i, then predict (tpls.py:122-143) of sample
