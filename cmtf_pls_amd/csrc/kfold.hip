@@ -807,7 +807,9 @@ __global__ __launch_bounds__(kKfWideCols) void kfold_wide_kernel(const T* __rest
 template <typename T, int MT>
 static void kf_wide_launch(dim3 g, hipStream_t st, const T* X, int64_t P, const double* Y, int W, const int* order, const int* off,
                            int nyb, int nch, double* part) {
-  if (P % 4 == 0)
+  // VEC reads X + i P + c as a Pack<T, 4>: every row start is aligned only when P % 4 == 0 and X itself is (a view into a larger
+  // buffer need not be)
+  if (P % 4 == 0 && reinterpret_cast<uintptr_t>(X) % sizeof(Pack<T, 4>) == 0)
     hipLaunchKernelGGL((kfold_wide_kernel<T, MT, true>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);
   else
     hipLaunchKernelGGL((kfold_wide_kernel<T, MT, false>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);

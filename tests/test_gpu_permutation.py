@@ -172,11 +172,28 @@ def test_coupled_model_refits_with_why():
 @pytest.mark.parametrize("I,A,B,W,K", [(300, 7, 9, 5, 2), (300, 16, 32, 96, 2), (517, 1, 130, 37, 32), (400, 12, 20, 1024, 2),
                                        (2000, 8, 8, 200, 32), (5000, 33, 40, 64, 5)])
 def test_wide_build_against_float64_torch(I, A, B, W, K, xdtype):
+    _check_wide_build(I, A, B, W, K, xdtype)
+
+
+@pytest.mark.parametrize("xdtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("I,A,B,W,K", [(300, 16, 32, 96, 2), (2000, 8, 8, 200, 32)])
+def test_wide_build_of_a_misaligned_view_against_float64_torch(I, A, B, W, K, xdtype):
+    """X a view one element into its storage: P % 4 == 0, but the rows are not aligned to the vector loads of the VEC instance."""
+    _check_wide_build(I, A, B, W, K, xdtype, base=1)
+
+
+def _check_wide_build(I, A, B, W, K, xdtype, base=0):
     from cmtf_pls_amd.backend import HipBackend
     be = HipBackend(torch.device("cuda:0"))
     g = torch.Generator(device="cuda:0").manual_seed(I + W)
     P = A * B
     X = (torch.randn(I, P, device="cuda:0", dtype=torch.float64, generator=g) + 0.3).to(xdtype)
+    if base:
+        buf = torch.zeros(base + I * P, device="cuda:0", dtype=xdtype)
+        buf[base:].view(I, P).copy_(X)
+        X = buf[base:].view(I, P)
+        assert X.is_contiguous() and X.data_ptr() % 16 != 0
+    before = X.clone()
     Yw = torch.randn(I, W, device="cuda:0", dtype=torch.float64, generator=g)
     ids = np.random.default_rng(W).permutation(np.arange(I) % K)
     counts = np.bincount(ids, minlength=K)
@@ -189,6 +206,7 @@ def test_wide_build_against_float64_torch(I, A, B, W, K, xdtype):
     S2, mean2 = torch.empty_like(S), torch.empty_like(mean)
     stats2 = be.kfold_wide_xcov(X, A, B, Yw, order, off, K, ydev, S2, mean2)
     assert torch.equal(S, S2) and torch.equal(mean, mean2) and torch.equal(stats, stats2)    # the same bits on every run
+    assert torch.equal(X, before)
     X64 = X.to(torch.float64)
     idt = torch.from_numpy(ids).cuda()
     Sf = torch.stack([X64[idt == f].T @ Yw[idt == f] for f in range(K)])                     # P x W per fold group
