@@ -239,6 +239,15 @@ class NipalsEngine(ProjectionMixin):
             return None
         R = n_components
         ssq = out["ssq"]
+        if X.dim() == 3 and A == 1:
+            # the kernel's A == 1 branch is the vector rule (tpls.py:84: Z / |Z|, unsigned); an order-3 block (I, 1, B) gets
+            # parafac's rule instead, as the regular engine and the oracle give it: wB's largest-|.| entry positive (first index
+            # on ties), wA = -1 where that flips wB.  wA (x) wB, hence T, U, Q, coef_ and R2, does not change.
+            WB = out["WB"]
+            top = WB.gather(0, WB.abs().argmax(dim=0, keepdim=True))
+            sgn = 1.0 - 2.0 * (top < 0).to(WB.dtype)
+            out["WA"].mul_(sgn)
+            WB.mul_(sgn)
         loadings = [out["WB"]] if X.dim() == 2 else [out["WA"], out["WB"]]
         blk = BlockState(shape=tuple(X.shape), A=A, B=B, mean=out["x_mean"], has_miss=False, colcnt=None, rowcnt=None,
                          ssq0=float(ssq[0, 0]), dtype=X.dtype, loadings=loadings, r2x=1.0 - ssq[1:, 0] / ssq[0, 0])

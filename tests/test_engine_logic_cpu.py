@@ -660,3 +660,36 @@ def test_fit_with_more_than_64_components_numpy_backend():
         np.testing.assert_allclose(m.R2X, fit.r2x[0], rtol=1e-6, atol=1e-9)
         np.testing.assert_allclose(m.R2Y, fit.r2y, rtol=1e-6, atol=1e-9)
         np.testing.assert_allclose(m.transform(x), m.X_factors[0], rtol=1e-6, atol=1e-9)
+
+
+@pytest.mark.parametrize("order", [2, 3])
+def test_small_fit_of_a_singleton_first_trailing_mode_takes_parafacs_sign(order):
+    """cmtfpls_fit_small_f64 treats A == 1 as a vector (wA = 1, wB = Z / |Z|, unsigned: tpls.py:84).  For an order-3 block
+    (I, 1, B) the engine turns that into parafac's sign, as the regular engine and the oracle give it: wB's largest-|.| entry
+    positive, wA = -1 where that flips wB.  An order-2 block keeps the unsigned vector."""
+    from cmtf_pls_amd import engine
+
+    I, B, R = 5, 4, 3
+    WB = torch.tensor([[0.5, -0.1, 0.6], [-0.7, 0.2, -0.6], [0.1, -0.9, 0.0], [0.3, 0.1, 0.4]], dtype=torch.float64)
+
+    class KernelOutput:                   # what the kernel's A == 1 branch hands back
+        name = "stub"
+        device = None
+
+        def fit_small(self, X2, Y, A, B_, R_, tol, max_iter):
+            assert A == 1 and B_ == B and R_ == R
+            z = lambda *s: torch.zeros(*s, dtype=torch.float64)
+            return {"T": z(I, R), "U": z(I, R), "WA": torch.ones(1, R, dtype=torch.float64), "WB": WB.clone(), "Q": z(2, R),
+                    "x_mean": z(B), "y_mean": z(2), "coef": np.eye(R), "ssq": np.ones((R + 1, 2)), "n_iter": [2] * R}
+
+    eng = engine.NipalsEngine(KernelOutput(), options=engine.EngineOptions(small_fit=True))
+    X = torch.zeros((I, 1, B) if order == 3 else (I, B), dtype=torch.float64)
+    st = eng._fit_small([X], torch.zeros(I, 2, dtype=torch.float64), R, 1e-8, 100, False, 0, None)
+    loads = [L.numpy() for L in st.blocks[0].loadings]
+    if order == 2:
+        assert len(loads) == 1 and np.array_equal(loads[0], WB.numpy())
+        return
+    # largest |.| per column: -0.7 (row 1, flipped), -0.9 (row 2, flipped), 0.6 / -0.6 tie (row 0 first, kept)
+    sgn = np.array([-1.0, -1.0, 1.0])
+    assert np.array_equal(loads[0], sgn[None, :]) and np.array_equal(loads[1], WB.numpy() * sgn)
+    assert np.array_equal(loads[0] * loads[1], WB.numpy())          # wA (x) wB, hence every score, is unchanged
