@@ -650,6 +650,40 @@ class HipBackend:
                 return Ypred, n_iter, form
         return None
 
+    def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
+                  max_iter: int, max_ws_bytes: Optional[int] = None
+                  ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """Cross-validation refits of a tPLS on X2 with missing values (NaN), a workgroup per fold (cmtfpls_cv_masked_f64): returns
+        (Ypred (R, I, M): [r - 1, i] = row i predicted by its fold's model with r components, n_iter (K, R), status (K), info (K, 2):
+        whether the fold's training rows / held-out batch took the masked arithmetic), or None when the shape is outside the form.
+        fold_of: (I,) int32 fold ids 0..K-1 (leave-one-out: arange(I), K = I).  Folds run in chunks whose workspace fits
+        `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
+        I, P = X2.shape
+        M = Y.shape[1]
+        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
+        assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
+        colsum_x, colcnt_x = self.colstats(X2)
+        colsum_y, _ = self.colstats(Y)
+        Ypred = self.zeros(R, I, M)
+        n_iter = torch.zeros(K, R, dtype=torch.int32, device=self.device)
+        status = torch.zeros(K, dtype=torch.int32, device=self.device)
+        info = torch.zeros(K, 2, dtype=torch.int32, device=self.device)
+        fn = self.lib.cmtfpls_cv_masked_f64
+        args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
+                int(max_iter))
+        outs = (_ptr(Ypred), _ptr(n_iter), _ptr(status), _ptr(info))
+        # probe without a workspace: the shape check comes first (4 = declined, 2 = only the workspace is missing)
+        if fn(*args, 0, 1, *outs, None, 0, self._stream()) == 4:
+            return None
+        per = int(self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R))
+        budget = (4 << 30) if max_ws_bytes is None else int(max_ws_bytes)
+        chunk = max(1, min(K, budget // max(per, 1)))
+        ws = torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
+        for f0 in range(0, K, chunk):
+            nf = min(chunk, K - f0)
+            _lib.check(fn(*args, f0, nf, *outs, _ptr(ws), ws.numel(), self._stream()), "cv_masked")
+        return Ypred, n_iter, status, info
+
     # -- K-fold cross-validation (validate.kfold_predictions, kfold.py): every fold from the same reads of X ----------------
     def kfold_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,
                    ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:

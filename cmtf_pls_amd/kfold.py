@@ -386,6 +386,59 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
     return pred, report
 
 
+MASKED_FORM = "cmtfpls_cv_masked_f64"
+
+
+def has_missing(X) -> bool:
+    """Whether X (a host array or a device tensor) holds a NaN."""
+    if isinstance(X, torch.Tensor):
+        return bool(torch.isnan(X).any().item())
+    return bool(np.isnan(np.asarray(X)).any())
+
+
+def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
+    """Refits of a tPLS on X with missing values, a workgroup per fold in one launch (cmtfpls_cv_masked_f64), in float64
+    on the original data whatever the model's storage type: (pred (R, I, M), report) or (None, why).  Leave-one-out: ids =
+    arange(I), K = I."""
+    eng = pls._get_engine()
+    be = eng.be
+    R = pls.n_components
+    I = ids.shape[0]
+    if not hasattr(be, "cv_masked"):
+        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked fold kernel"
+    if pls._comm is not None:
+        return None, "sharded model (comm)"
+    if X.ndim not in (2, 3):
+        return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
+    if has_missing(Y):
+        return None, "missing values in Y"
+    train = I - np.bincount(ids, minlength=K)
+    if train.min() < 2:
+        return None, f"fold {int(np.argmin(train))} leaves {int(train.min())} training rows (the masked form needs 2)"
+    A, B = _dims(X)
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    dev = be.device
+
+    def f64(a):                                                                 # the original data in float64, on the device
+        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
+
+    with eng.device_ctx():
+        out = be.cv_masked(f64(X).contiguous().view(I, -1), f64(Y).contiguous().view(I, M), _to_dev(ids, dev, torch.int32), K, A, B, R,
+                           tol, max_iter)
+        if out is None:
+            return None, (f"shape outside {MASKED_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
+                          f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+        pred, n_iter, status, info = (t.cpu().numpy() for t in out)
+    if status.any():
+        empty, small = np.flatnonzero(status == 1).tolist(), np.flatnonzero(status == 2).tolist()
+        return None, "; ".join(w for w in (f"training rows without an observed entry of X in folds {empty}" if empty else "",
+                                            f"fewer than 2 training rows in folds {small}" if small else "") if w)
+    report = {"form": f"a workgroup per fold on X with missing values, all folds in one launch ({MASKED_FORM})", "folds": int(K),
+              "x_reads": None, "n_iter": n_iter.tolist(), "masked_folds": int(info[:, 0].sum()),
+              "masked_batches": int(info[:, 1].sum())}
+    return pred, report
+
+
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
     """pred (R, *Y.shape): pred[r - 1, i] = prediction for sample i by the model fitted without sample i's fold, with its first
     r components.  `pls` a fitted tPLS or ctPLS.  Sets pls.q2y_report_."""
@@ -395,13 +448,16 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
     I = Y.shape[0]
     ids, K = fold_ids(I, n_splits, folds)
     R = pls.n_components
+    pred = None
     if not device_folds:
         why = "device folds switched off"
+    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):
+        pred, rep = masked_predictions(pls, X, Y, ids, K, tol, max_iter)
+        why = None if pred is not None else f"the masked form ({MASKED_FORM}) declined: {rep}"
     else:
         inner = ("kfold_inner_coupled", "kfold_combine_scores") if coupled else ("kfold_inner",)
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"))
-    pred = None
-    if why is None:
+    if why is None and pred is None:
         pred, rep = device_predictions(pls, Xs, Y, ids, K, tol, max_iter, coupled)
         if pred is None:
             why = rep

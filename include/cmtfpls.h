@@ -481,6 +481,27 @@ size_t cmtfpls_loo_xcov_fold_workspace_bytes(int I, int A, int B, int M, int R);
 int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
                          int B, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
                          int* n_iter, void* ws, size_t ws_bytes, void* stream);
+/* ---- cross-validation refits of a tPLS whose X has missing values, all folds in one launch: validate.get_q2y / kfold_predictions
+ * with EngineOptions.masked_folds (cmtf_pls/validate.py:7-37; tpls.py:61-63 X_hasMiss; missingvals.py:7-38) -------------------
+ * For every fold f in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113) on the rows r with fold_of[r] != f, with the
+ * reference's missing-value arithmetic when one of those rows has a missing entry (miss_tensordot: the column sum / c_p * n_f, 0
+ * where c_p = 0; miss_mmodedot: the row sum / o_r * P; deflation of observed entries only), then predict (tpls.py:122-143) of
+ * the held-out rows, centred by the fold's means and THEN masked (a column without a training observation has a NaN mean, so its
+ * held-out entries count as missing), with the masked score for the whole batch when any held-out entry is missing.
+ * Ypred[((r - 1) * I + i) * M + m] (R x I x M) = the prediction of held-out row i with the first r components (coef_ is upper
+ * triangular).  One workgroup per fold.  X (I x A*B, NaN = missing) and Y (I x M, complete) are the ORIGINAL float64 data;
+ * colsum_x / colcnt_x = cmtfpls_colstats_f64 of X (the fold's counts and means are down-dated from them), colsum_y the column sums
+ * of Y; leave-one-out is fold_of = 0..I-1, K = I.  n_iter (nullable, K x R): inner iterations; status (K): 0 ok, 1 a training
+ * row without an observed entry (the reference is NaN everywhere: refit or decline), 2 fewer than 2 training rows; info
+ * (nullable, K x 2): [f, 0] = 1 when the training rows took the masked arithmetic, [f, 1] = 1 when the held-out batch did.
+ * ws >= nfolds * cmtfpls_cv_masked_fold_workspace_bytes(...) (Xf | Yf | T per resident fold, deflated in place, and the fold's
+ * column counts and means).  CMTFPLS_EUNSUPPORTED (checked before the workspace) when K > I, min(A, B) > 64, M > 64, R > 16 or
+ * the per-fold vectors and per-row counts exceed 150 KB of LDS. */
+size_t cmtfpls_cv_masked_fold_workspace_bytes(int I, int A, int B, int M, int R);
+int cmtfpls_cv_masked_f64(const double* X, const double* Y, const int* fold_of, int K, const double* colsum_x,
+                          const double* colcnt_x, const double* colsum_y, int I, int A, int B, int M, int R, double tol,
+                          int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status, int* info, void* ws,
+                          size_t ws_bytes, void* stream);
 /* ---- K-fold cross-validation with every fold served by the same reads of X (validate.kfold_predictions) ------------------------
  * The folds of a K-fold split share X_0 (the caller's uncentred tensor, never written); a fold differs only in its training rows,
  * their means and its loadings.  Per component: kfold_inner (the inner loop of every fold on its training cross-covariance, a
