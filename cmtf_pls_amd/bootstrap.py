@@ -15,6 +15,9 @@ That is 2R reads of each block per pass.  The OOB prediction sums are built on t
 per pass only the models' loadings, coef_, status and n_iter come back.  A one-model pass runs its resample twice (the
 K-fold kernels take at least two models).  The passes run through kfold._device_passes: a pass whose status is set refits
 its own resamples; anything outside the device form refits every resample on the regular engine.
+
+With EngineOptions.masked_folds, a tPLS whose X has missing values runs every resample as a count-weighted workgroup of
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model.
 """
 from __future__ import annotations
 
@@ -23,8 +26,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups, _host,
-                    _names, _state, _stats_why, _to_dev, _training_data)
+from .kfold import (MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
+                    _host, _names, _state, _stats_why, _to_dev, _training_data, has_missing, masked_models, masked_models_report)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -200,13 +203,18 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
 
     why: Optional[str] = None
     G = 0
+    masked = None
     if not device_folds:
         why = "device folds switched off"
+    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):        # EngineOptions.masked_folds
+        masked, mwhy = masked_models(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
+        if masked is None:
+            why = f"the masked form ({MODELS_FORM}) declined: {mwhy}"
     else:
         G = min(_groups(X, 1, min(NB, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for X in Xs)   # the LDS of every block's score pass
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES)
     res = [None] * NB
-    dev = pls._get_engine().be.device if why is None else torch.device("cpu")
+    dev = pls._get_engine().be.device if why is None and masked is None else torch.device("cpu")
     oob_sum = [torch.zeros(R, I, M, dtype=torch.float64, device=dev), torch.zeros(I, dtype=torch.float64, device=dev)]
 
     def refit_one(e):
@@ -218,9 +226,21 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
             oob_sum[1][torch.from_numpy(oob).to(dev)] += 1.0
         return np.zeros(R), n_iter
 
-    _, n_iters, passes, why = _device_passes(pls, NB, G, "resamples", why,
-                                             lambda: _device_resamples(pls, Xs, Y, counts, tol, max_iter, coupled, res, oob_sum),
-                                             refit_one)
+    if masked is not None:                                                            # resample b is model b; Ypred is 0 in its bag
+        n_iters, refitted = masked["n_iter"].tolist(), []
+        for e in range(NB):
+            if masked["status"][e]:
+                _, n_iters[e] = refit_one(e)
+                refitted.append(e)
+                continue
+            modes = [masked["Wb"][e].T] if X.ndim == 2 else [masked["Wa"][e].T, masked["Wb"][e].T]
+            res[e] = ([modes], masked["Q"][e].T, masked["coef"][e])
+            oob_sum[0] += torch.from_numpy(masked["Ypred"][e])
+            oob_sum[1] += torch.from_numpy((counts[e] == 0).astype(np.float64))
+    else:
+        _, n_iters, passes, why = _device_passes(pls, NB, G, "resamples", why,
+                                                 lambda: _device_resamples(pls, Xs, Y, counts, tol, max_iter, coupled, res, oob_sum),
+                                                 refit_one)
     aligned = [align_factors(ref, *r) for r in res]
     nmodes = [len(b) for b in ref]
     Xf = [[np.stack([a[0][b][j] for a in aligned]) for j in range(nmodes[b])] for b in range(len(ref))]
@@ -236,7 +256,11 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
         y = Yh[rows]
         oob_q2y = 1.0 - ((pred - y) ** 2).reshape(R, -1).sum(axis=1) / (y ** 2).sum()   # validate.py:35-37 on the OOB rows
 
-    if passes:
+    if masked is not None:
+        rep = masked_models_report(masked, refitted, "resamples")
+        pls.bootstrap_report_ = dict(rep, resamples=int(NB), passes=rep["launches"], models_per_pass=-(-NB // rep["launches"]),
+                                     n_iter=n_iters)
+    elif passes:
         from .kfold import _form_entries
 
         entries = _form_entries("cmtfpls_kfold_weighted_xcov_*", coupled, "cmtfpls_kfold_epilogue_weighted_f64")
@@ -246,10 +270,11 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
         x_reads = [2 * R * passes] * len(Xs) if coupled else 2 * R * passes
     else:
         form, x_reads = "one refit per resample on the regular engine", None
-    rep = {"form": form, "resamples": int(NB), "passes": int(passes), "models_per_pass": int(G) if passes else None,
-           "x_reads": x_reads, "n_iter": n_iters}
-    if why is not None:
-        rep["why"] = why
-    pls.bootstrap_report_ = rep
+    if masked is None:
+        rep = {"form": form, "resamples": int(NB), "passes": int(passes), "models_per_pass": int(G) if passes else None,
+               "x_reads": x_reads, "n_iter": n_iters}
+        if why is not None:
+            rep["why"] = why
+        pls.bootstrap_report_ = rep
     return {"resamples": idx, **stacks, "se": {k: v[0] for k, v in spread.items()}, "ci": {k: v[1] for k, v in spread.items()},
             "oob_q2y": oob_q2y, "oob_rows": int(rows.sum())}

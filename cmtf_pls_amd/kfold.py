@@ -113,10 +113,6 @@ def _rows(X, sel: np.ndarray):
 def refit_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
     """One literal refit per fold on the regular engine with the model's storage type, algorithm, backend and options:
     returns (pred (R, I, M), n_iter K x R).  X a list of blocks: ctPLS refits (each block's rows taken alike)."""
-    from .cmtf import ctPLS
-    from .tpls import tPLS
-
-    coupled = isinstance(X, list)
     R = pls.n_components
     I = ids.shape[0]
     Y2 = Y.reshape(I, -1)
@@ -124,19 +120,30 @@ def refit_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: 
     n_iter = []
     for k in range(K):
         test = ids == k
-        if coupled:
-            Xtr, Xte = [_rows(b, ~test) for b in X], [_rows(b, test) for b in X]
-        else:
-            Xtr, Xte = _rows(X, ~test), _rows(X, test)
-        Ytr = Y[torch.from_numpy(~test).to(Y.device)] if isinstance(Y, torch.Tensor) else Y[~test]
-        m = (ctPLS if coupled else tPLS)(R, dtype=pls._dtype, device=pls._device, backend=pls._backend, algorithm=pls._algorithm,
-                                         graphs=pls._graphs, matrix_precision="f32" if pls._mixed else "f64", options=pls._options)
-        m.fit(Xtr, Ytr, tol=tol, max_iter=max_iter)
-        scores = m.transform(Xte)
-        for r in range(1, R + 1):
-            pred[r - 1, test] = _from_scores(scores, m.coef_, m.Y_factors[1].T, m.Y_mean, r)
-        n_iter.append([int(v) for v in m.n_iter_])
+        pred[:, test], it = refit_fold(pls, X, Y, test, tol, max_iter)
+        n_iter.append(it)
     return pred, n_iter
+
+
+def refit_fold(pls, X, Y, test: np.ndarray, tol: float, max_iter: int):
+    """One literal refit on the rows outside the boolean mask `test` (refit_predictions' per-fold step): (the predictions
+    (R, n_test, M) of the rows in `test` with the first r = 1..R components, n_iter)."""
+    from .cmtf import ctPLS
+    from .tpls import tPLS
+
+    coupled = isinstance(X, list)
+    R = pls.n_components
+    if coupled:
+        Xtr, Xte = [_rows(b, ~test) for b in X], [_rows(b, test) for b in X]
+    else:
+        Xtr, Xte = _rows(X, ~test), _rows(X, test)
+    Ytr = Y[torch.from_numpy(~test).to(Y.device)] if isinstance(Y, torch.Tensor) else Y[~test]
+    m = (ctPLS if coupled else tPLS)(R, dtype=pls._dtype, device=pls._device, backend=pls._backend, algorithm=pls._algorithm,
+                                     graphs=pls._graphs, matrix_precision="f32" if pls._mixed else "f64", options=pls._options)
+    m.fit(Xtr, Ytr, tol=tol, max_iter=max_iter)
+    scores = m.transform(Xte)
+    pred = np.stack([_from_scores(scores, m.coef_, m.Y_factors[1].T, m.Y_mean, r) for r in range(1, R + 1)])
+    return pred, [int(v) for v in m.n_iter_]
 
 
 def _dims(X) -> Tuple[int, int]:
@@ -437,6 +444,92 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
               "x_reads": None, "n_iter": n_iter.tolist(), "masked_folds": int(info[:, 0].sum()),
               "masked_batches": int(info[:, 1].sum())}
     return pred, report
+
+
+MODELS_FORM = "cmtfpls_cv_masked_models_f64"
+
+
+def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol: float, max_iter: int, factors: bool = False,
+                  max_ws_bytes: Optional[int] = None):
+    """Refits of a tPLS on X with missing values on count-weighted rows, a workgroup per model in one launch per chunk
+    (cmtfpls_cv_masked_models_f64), in float64 on the original data whatever the model's storage type.  Model m trains on
+    counts[m, r] copies of X row r paired with Y row yrow[m, r] (yrow None: identity) and predicts its rows with count 0.  Returns
+    (out, None) -- out the backend's dict on the host (Ypred (n, R, I, M), n_iter, status, info, launches, with `factors` Wa, Wb,
+    coef, Q) -- or (None, why) with masked_predictions' declines.  Models with a status are the caller's to refit."""
+    eng = pls._get_engine()
+    be = eng.be
+    R = pls.n_components
+    I = counts.shape[1]
+    if not hasattr(be, "cv_masked_models"):
+        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked model kernel"
+    if pls._comm is not None:
+        return None, "sharded model (comm)"
+    if X.ndim not in (2, 3):
+        return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
+    if has_missing(Y):
+        return None, "missing values in Y"
+    A, B = _dims(X)
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    dev = be.device
+
+    def f64(a):                                                                 # the original data in float64, on the device
+        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
+
+    with eng.device_ctx():
+        out = be.cv_masked_models(f64(X).contiguous().view(I, -1), f64(Y).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+                                  None if yrow is None else _to_dev(yrow, dev, torch.int32), A, B, R, tol, max_iter, factors,
+                                  max_ws_bytes)
+        if out is None:
+            return None, (f"shape outside {MODELS_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
+                          f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+        return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}, None
+
+
+def masked_models_report(out: dict, refitted, what: str) -> dict:
+    """The report entries of a masked-models run (form, models, launches, masked_models, masked_batches, x_reads); `refitted`
+    the models whose status made them refit alone on the regular engine."""
+    status = out["status"]
+    ok = status == 0
+    form = f"a workgroup per model on X with missing values, {len(status)} models in {out['launches']} launch(es) ({MODELS_FORM})"
+    rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
+           "models": int(len(status)), "launches": int(out["launches"]), "masked_models": int(out["info"][ok, 0].sum()),
+           "masked_batches": int(out["info"][ok, 1].sum()), "x_reads": None}
+    if len(refitted):
+        names = {1: "a training row without an observed entry of X", 2: "fewer than 2 training rows", 3: "bad counts or Y rows"}
+        rep["refitted"] = [int(m) for m in refitted]
+        rep["why"] = "; ".join(f"{names[s]} in {what} {np.flatnonzero(status == s).tolist()}"
+                                     for s in (1, 2, 3) if (status == s).any())
+    return rep
+
+
+def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[np.ndarray], tol: float, max_iter: int):
+    """The Q2Y numerators of N K-fold entries (permutations, splits) from masked_models: entry e has the fold ids ids[e] (N x I)
+    and pairs X row r with Y row yrows[e, r] (None: identity); model e K + k holds out its fold k.  Returns (numerators N x R,
+    n_iter per entry (K x R lists), report) or (None, why, None).  A model with a status refits alone (refit_fold)."""
+    N, I = ids.shape
+    R = pls.n_components
+    counts = (ids[:, None, :] != np.arange(K)[None, :, None]).reshape(N * K, I).astype(np.int32)
+    out, why = masked_models(pls, X, Y, counts, None if yrows is None else np.repeat(yrows, K, axis=0), tol, max_iter)
+    if out is None:
+        return None, why, None
+    Yh = _host(Y).reshape(I, -1).astype(np.float64)
+    pred = out["Ypred"].reshape(N, K, R, I, Yh.shape[1])
+    status = out["status"].reshape(N, K)
+    n_iter = out["n_iter"].reshape(N, K, R).tolist()
+    nums = np.zeros((N, R))
+    refitted = []
+    for e in range(N):
+        y = Yh if yrows is None else Yh[yrows[e]]
+        pe = np.zeros((R,) + Yh.shape)
+        for k in range(K):
+            test = ids[e] == k
+            if status[e, k]:
+                pe[:, test], n_iter[e][k] = refit_fold(pls, X, Y if yrows is None else _perm_y(Y, yrows[e]), test, tol, max_iter)
+                refitted.append(e * K + k)
+            else:
+                pe[:, test] = pred[e, k][:, test]
+        nums[e] = ((pe - y) ** 2).reshape(R, -1).sum(axis=1)                   # _refit_numerators' sum
+    return nums, n_iter, masked_models_report(out, refitted, "models")
 
 
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:

@@ -49,9 +49,11 @@ class EngineOptions:
     # transform / predict of samples with missing values: rows WITHOUT a missing value keep the one-pass MTTKRP result and
     # only the affected rows take the masked sequential form; False runs the sequential form on every row of such a batch
     project_split_rows: bool = True
-    # leave-one-out and K-fold Q2Y of a tPLS whose X has missing values: every fold refitted by one workgroup in ONE launch with
-    # the reference's masked arithmetic (cmtfpls_cv_masked_f64, kfold.masked_predictions) instead of one regular-engine refit per
-    # fold; opt-in until the form has been measured (report: q2y_report_, a decline names its reason)
+    # cross-validation of a tPLS whose X has missing values with the reference's masked arithmetic, a workgroup per model instead
+    # of one regular-engine refit per model: leave-one-out and K-fold Q2Y (every fold in ONE launch, cmtfpls_cv_masked_f64,
+    # kfold.masked_predictions), and the permutation test, repeated K-fold and the bootstrap (every permutation x fold, split x
+    # fold or resample as a count-weighted model, cmtfpls_cv_masked_models_f64, kfold.masked_models); opt-in (reports:
+    # q2y_report_ / bootstrap_report_, a decline names its reason)
     masked_folds: bool = False
 
     def but(self, **changes) -> "EngineOptions":

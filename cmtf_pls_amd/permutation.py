@@ -13,6 +13,9 @@ The pass's Y side (each model's centred, held-out-zeroed Y) is built on the devi
 so are the held-out predictions and the Q2Y numerators: per pass only status, n_iter and G x R numerators come back.  2R reads of
 X per pass, ceil(P / G) passes, run by kfold._device_passes.  A pass whose status is set refits its permutations; anything
 outside the device form (a ctPLS among it) refits every permutation with kfold.refit_predictions.
+
+With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators).
 """
 from __future__ import annotations
 
@@ -21,8 +24,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups, _host,
-                    _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids)
+from .kfold import (MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
+                    _host, _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids, has_missing,
+                    masked_fold_numerators)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
 
@@ -113,19 +117,32 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
 
     why: Optional[str] = None
     G = 0
+    masked = None
     if not device_folds:
         why = "device folds switched off"
     elif isinstance(X, list):
         why = "coupled model: permutation device form not built"
+    elif pls._get_engine().opt.masked_folds and has_missing(X):                       # EngineOptions.masked_folds
+        got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter)
+        if got[0] is None:
+            why = f"the masked form ({MODELS_FORM}) declined: {got[1]}"
+        else:
+            nums, n_iters, masked = got
     else:
         G = _groups(X, K, NP) if K <= MAX_FOLDS else 0
         why = _decline_blocks(pls, [X], ["X"], Y, K * G if G else K, _ENTRIES)     # the checks with K made with the n models
-    nums, n_iters, passes, why = _device_passes(pls, NP, G, "permutations", why,
-                                                lambda: _device_null(pls, X, Y, ids, K, perms, tol, max_iter),
-                                                lambda p: _refit_numerators(pls, X, Y, ids, K, perms[p], tol, max_iter))
+    if masked is None:
+        nums, n_iters, passes, why = _device_passes(pls, NP, G, "permutations", why,
+                                                    lambda: _device_null(pls, X, Y, ids, K, perms, tol, max_iter),
+                                                    lambda p: _refit_numerators(pls, X, Y, ids, K, perms[p], tol, max_iter))
     null_all = 1.0 - nums / den                                                       # P x R: every component count
     null = null_all if per_component else null_all[:, -1]
     p_value = (1.0 + (null >= q2y).sum(axis=0)) / (NP + 1.0)
+    if masked is not None:
+        rep = dict(masked, permutations=int(NP), passes=masked["launches"], models_per_pass=-(-masked["models"] // masked["launches"]),
+                   n_iter=n_iters, observed=observed)
+        pls.q2y_report_ = rep
+        return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}
     if passes:
         form = (f"{K * G} models per pass ({G} permutations x {K} folds) from shared reads of X (cmtfpls_kfold_wide_xcov_*, "
                 "cmtfpls_kfold_inner_grouped_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_epilogue_grouped_f64, cmtfpls_xcov_*)")

@@ -13,6 +13,9 @@ K-model slice of every per-model buffer.  Per pass and block:
 The Y side, the held-out predictions and the R Q2Y numerators of every split are built on the device: per pass only status,
 n_iter and G x R numerators come back.  The passes run through kfold._device_passes: a pass whose status is set refits its own
 splits; anything outside the device form refits every fold of every split with kfold.refit_predictions.
+
+With EngineOptions.masked_folds, a tPLS whose X has missing values runs every split x fold as a workgroup of
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators).
 """
 from __future__ import annotations
 
@@ -22,9 +25,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _fold_means,
-                    _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _training_data,
-                    repeated_fold_ids)
+from .kfold import (MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes,
+                    _fold_means, _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev,
+                    _training_data, has_missing, masked_fold_numerators, repeated_fold_ids)
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
@@ -94,17 +97,29 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
 
     why: Optional[str] = None
     G = 0
+    masked = None
     if not device_folds:
         why = "device folds switched off"
+    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):        # EngineOptions.masked_folds
+        got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter)
+        if got[0] is None:
+            why = f"the masked form ({MODELS_FORM}) declined: {got[1]}"
+        else:
+            nums, n_iters, masked = got
     else:
         G = min(_groups(X, K, min(NS, I // K)) for X in Xs) if K <= MAX_FOLDS else 0   # n <= I models, the LDS of every block
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES)
     identity = np.arange(I)
-    nums, n_iters, passes, why = _device_passes(pls, NS, G, "splits", why,
-                                                lambda: _device_splits(pls, Xs, Y, ids, K, tol, max_iter, coupled),
-                                                lambda g: _refit_numerators(pls, X, Y, ids[g], K, identity, tol, max_iter))
+    if masked is None:
+        nums, n_iters, passes, why = _device_passes(pls, NS, G, "splits", why,
+                                                    lambda: _device_splits(pls, Xs, Y, ids, K, tol, max_iter, coupled),
+                                                    lambda g: _refit_numerators(pls, X, Y, ids[g], K, identity, tol, max_iter))
     q_all = 1.0 - nums / den                                                          # S x R: every component count
     q2y = q_all if per_component else q_all[:, -1]
+    if masked is not None:
+        pls.q2y_report_ = dict(masked, splits=int(NS), passes=masked["launches"],
+                               splits_per_pass=-(-NS // masked["launches"]), n_iter=n_iters)
+        return dict(summary(q2y), folds=ids)
     x_reads = None
     if passes:
         entries = _form_entries("cmtfpls_kfold_xcov_* per split", coupled, "cmtfpls_kfold_epilogue_splits_f64")

@@ -116,8 +116,9 @@ def permutation_test_q2y(pls_tensor, n_permutations: int = 99, n_splits: int = 5
     0..I-1 (ValueError otherwise, or when n_permutations < 1).  Returns {"q2y": get_q2y_kfold(pls_tensor, n_splits, folds,
     per_component), "null": (P,) or (P, R), "p_value": (1 + #{null >= q2y}) / (P + 1) (per component with per_component),
     "permutations": (P, I)}.  On the GPU a tPLS runs floor(32 / K) permutations x K folds per pass from shared reads of X (2R reads
-    per pass, permutation.py); anything else refits every fold of every permutation.  Which form ran is recorded on the model
-    (``q2y_report_``)."""
+    per pass, permutation.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes cmtfpls_cv_masked_models_f64 when
+    EngineOptions.masked_folds is on: every permutation x fold is a workgroup with the reference's masked arithmetic.
+    Anything else refits every fold of every permutation.  Which form ran is recorded on the model (``q2y_report_``)."""
     from .permutation import permutation_test
 
     return permutation_test(pls_tensor, n_permutations, n_splits, folds, permutations, random_state, per_component, device_folds)
@@ -132,7 +133,9 @@ def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, f
     then ignored).  Returns {"q2y": (S,) or (S, R), "mean" and "std" (ddof=0) over the splits, "folds": (S, I)}, and with
     per_component "one_se": the smallest component count r (from 1) whose mean is at least max(mean) - std[argmax] / sqrt(S).
     On the GPU floor(32 / K) splits x K folds of a tPLS or ctPLS share every MTTKRP and contraction of X (G + 2R - 1 reads
-    per pass and block, repeated.py); anything else refits every fold of every split.  Which form ran is recorded on the model
+    per pass and block, repeated.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
+    cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every split x fold is a workgroup with the reference's
+    masked arithmetic.  Anything else refits every fold of every split.  Which form ran is recorded on the model
     (``q2y_report_``)."""
     from .repeated import repeated_kfold
 
@@ -152,7 +155,9 @@ def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random
     "ci": with np.percentile at 100 (1 -/+ level) / 2 on a leading axis of 2, "oob_q2y": (R,) the Q2Y (validate.py:35-37) of the
     out-of-bag predictions with r = 1..R components (row i's: the mean over the resamples that left it out of their models'
     predictions) over "oob_rows" rows, those left out at least once}.  On the GPU up to 32 resamples per pass share every read of X
-    (2R reads per pass and block, bootstrap.py); anything else refits every resample.  Which form ran is recorded on the model
+    (2R reads per pass and block, bootstrap.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
+    cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every resample is a count-weighted workgroup with the
+    reference's masked arithmetic.  Anything else refits every resample.  Which form ran is recorded on the model
     (``bootstrap_report_``)."""
     from .bootstrap import bootstrap
 

@@ -502,6 +502,26 @@ int cmtfpls_cv_masked_f64(const double* X, const double* Y, const int* fold_of, 
                           const double* colcnt_x, const double* colsum_y, int I, int A, int B, int M, int R, double tol,
                           int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status, int* info, void* ws,
                           size_t ws_bytes, void* stream);
+/* ---- refits of a tPLS whose X has missing values on count-weighted rows, all models of a chunk in one launch: the permutation
+ * test, repeated K-fold and the bootstrap (validate.py) with EngineOptions.masked_folds ------------------------------------------
+ * Model m in [model0, model0 + nmodels) of nm: counts[m * I + r] >= 0 copies of X row r paired with Y row yrow[m * I + r]
+ * (yrow nullable: identity) are its training data; counts 0 are held out.  A complete tPLS fit (tpls.py:73-113) on that literal
+ * data, with the reference's missing-value arithmetic when some column has fewer weighted observations than n = sum_r counts
+ * (every sum over rows weighted by the counts: means, miss_tensordot's c_p and n, q, the convergence norm, the normal equations of
+ * the inner regression), then predict (tpls.py:122-143) of the held-out rows as one batch, as cmtfpls_cv_masked_f64 does.
+ * Ypred[(((m * R) + r - 1) * I + i) * M + j] (nm x R x I x M, written at held-out rows only) = the prediction of held-out row i
+ * with the first r components.  Factors (nullable, written by every model without a status): Wa (nm x R x A), Wb (nm x R x B),
+ * coef (nm x R x R, coef_[row, component]), Q (nm x R x M).  n_iter (nullable, nm x R); status (nm): 0 ok, 1 a training row
+ * without an observed entry, 2 n < 2, 3 a negative count or a yrow outside 0..I-1; info (nullable, nm x 2): whether the training
+ * rows / the held-out batch took the masked arithmetic.  X (I x A*B, NaN = missing) and Y (I x M, complete) are the ORIGINAL
+ * float64 data.  One workgroup per model.  ws >= nmodels * cmtfpls_cv_masked_model_workspace_bytes(...) (Xf | Yf | T per resident
+ * model, deflated in place, and the model's column counts and means).  CMTFPLS_EUNSUPPORTED (checked before the workspace) when
+ * min(A, B) > 64, M > 64, R > 16 or the per-model vectors and per-row counts exceed 150 KB of LDS. */
+size_t cmtfpls_cv_masked_model_workspace_bytes(int I, int A, int B, int M, int R);
+int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* counts, const int* yrow, int nm, int I, int A,
+                                 int B, int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred,
+                                 double* Wa, double* Wb, double* coef, double* Q, int* n_iter, int* status, int* info,
+                                 void* ws, size_t ws_bytes, void* stream);
 /* ---- K-fold cross-validation with every fold served by the same reads of X (validate.kfold_predictions) ------------------------
  * The folds of a K-fold split share X_0 (the caller's uncentred tensor, never written); a fold differs only in its training rows,
  * their means and its loadings.  Per component: kfold_inner (the inner loop of every fold on its training cross-covariance, a
