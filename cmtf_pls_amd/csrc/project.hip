@@ -13,9 +13,9 @@
 // 256 * 16 vectors (128 x 128 f32, 64 x 128 f64), four samples in flight per CU; 1024-thread workgroups (one sample per
 // CU, 128 registers per lane) take rows of up to 1024 * 16 vectors (256 x 256 f32 = BASELINE configs[4], 256 x 128 f64).
 // Two coupled blocks share a 256-thread workgroup when the second (shorter) one needs at most 4 vectors per lane (the
-// I x 512 matrix block of BASELINE configs[2]: one).  In every case the trailing extent B of a block must divide the
-// workgroup stride (NT * V elements: "k constant per lane", every power-of-two B); other shapes, three or more coupled
-// blocks, and blocks of different storage types keep the passes.
+// I x 512 matrix block of BASELINE configs[2]: one), and only one beside a longer block of more than 8.  In every case
+// the trailing extent B of a block must divide the workgroup stride (NT * V elements: "k constant per lane", every
+// power-of-two B); other shapes, three or more coupled blocks, and blocks of different storage types keep the passes.
 #include "common.hpp"
 
 namespace cmtfpls {
@@ -244,7 +244,8 @@ static int run_project_rows(ProjBlock<T> b0, ProjBlock<T> b1, int nblocks, int64
   }
   // two coupled blocks: the longer one first (the score is their mean: the order does not matter)
   if ((int64_t)b1.A * b1.B > (int64_t)b0.A * b0.B) { const ProjBlock<T> t = b0; b0 = b1; b1 = t; }
-  if (!block_fits(b0, 256, 16, &nv0) || !block_fits(b1, 256, 4, &nv1) || nv0 + nv1 > 17) { set_error(outside); return CMTFPLS_EUNSUPPORTED; }
+  // instances (2|4|8, 1|4) and (16, 1): a 16-vector block leaves room for one vector of the other
+  if (!block_fits(b0, 256, 16, &nv0) || !block_fits(b1, 256, 4, &nv1)) { set_error(outside); return CMTFPLS_EUNSUPPORTED; }
   const int s0 = nv0 <= 2 ? 2 : nv0 <= 4 ? 4 : nv0 <= 8 ? 8 : 16, s1 = nv1 <= 1 ? 1 : 4;
   if (s0 == 16 && s1 == 4) { set_error(outside); return CMTFPLS_EUNSUPPORTED; }
   switch (s0 * 8 + s1) {
@@ -277,31 +278,31 @@ int cmtfpls_project_rows_f64(const double* X, int64_t I, int A, int B, int R, co
 }
 int cmtfpls_project_rows_idx_f32(const float* X, const int64_t* rows, int64_t n_rows, int A, int B, int R, const double* WA, const double* WB,
                                  const double* mean, double* scores, int ld, void* stream) {
-  if (!rows) { set_error("project_rows_idx: bad argument"); return CMTFPLS_EINVAL; }
-  if (n_rows == 0) return CMTFPLS_OK;
+  if (n_rows == 0) return CMTFPLS_OK;                       // (an empty list may come without storage)
+  if (!rows || n_rows < 0) { set_error("project_rows_idx: bad argument"); return CMTFPLS_EINVAL; }
   return run_project_rows<float>(ProjBlock<float>{X, WA, WB, mean, A, B}, ProjBlock<float>{nullptr, nullptr, nullptr, nullptr, 0, 0}, 1, n_rows, R,
                                  scores, ld, (hipStream_t)stream, rows);
 }
 int cmtfpls_project_rows_idx_f64(const double* X, const int64_t* rows, int64_t n_rows, int A, int B, int R, const double* WA, const double* WB,
                                  const double* mean, double* scores, int ld, void* stream) {
-  if (!rows) { set_error("project_rows_idx: bad argument"); return CMTFPLS_EINVAL; }
-  if (n_rows == 0) return CMTFPLS_OK;
+  if (n_rows == 0) return CMTFPLS_OK;                       // (an empty list may come without storage)
+  if (!rows || n_rows < 0) { set_error("project_rows_idx: bad argument"); return CMTFPLS_EINVAL; }
   return run_project_rows<double>(ProjBlock<double>{X, WA, WB, mean, A, B}, ProjBlock<double>{nullptr, nullptr, nullptr, nullptr, 0, 0}, 1, n_rows, R,
                                   scores, ld, (hipStream_t)stream, rows);
 }
 int cmtfpls_project_rows2_idx_f32(const float* X0, int A0, int B0, const double* WA0, const double* WB0, const double* mean0,
                                   const float* X1, int A1, int B1, const double* WA1, const double* WB1, const double* mean1,
                                   const int64_t* rows, int64_t n_rows, int R, double* scores, int ld, void* stream) {
-  if (!rows) { set_error("project_rows2_idx: bad argument"); return CMTFPLS_EINVAL; }
-  if (n_rows == 0) return CMTFPLS_OK;
+  if (n_rows == 0) return CMTFPLS_OK;                       // (an empty list may come without storage)
+  if (!rows || n_rows < 0) { set_error("project_rows2_idx: bad argument"); return CMTFPLS_EINVAL; }
   return run_project_rows<float>(ProjBlock<float>{X0, WA0, WB0, mean0, A0, B0}, ProjBlock<float>{X1, WA1, WB1, mean1, A1, B1}, 2, n_rows, R,
                                  scores, ld, (hipStream_t)stream, rows);
 }
 int cmtfpls_project_rows2_idx_f64(const double* X0, int A0, int B0, const double* WA0, const double* WB0, const double* mean0,
                                   const double* X1, int A1, int B1, const double* WA1, const double* WB1, const double* mean1,
                                   const int64_t* rows, int64_t n_rows, int R, double* scores, int ld, void* stream) {
-  if (!rows) { set_error("project_rows2_idx: bad argument"); return CMTFPLS_EINVAL; }
-  if (n_rows == 0) return CMTFPLS_OK;
+  if (n_rows == 0) return CMTFPLS_OK;                       // (an empty list may come without storage)
+  if (!rows || n_rows < 0) { set_error("project_rows2_idx: bad argument"); return CMTFPLS_EINVAL; }
   return run_project_rows<double>(ProjBlock<double>{X0, WA0, WB0, mean0, A0, B0}, ProjBlock<double>{X1, WA1, WB1, mean1, A1, B1}, 2, n_rows, R,
                                   scores, ld, (hipStream_t)stream, rows);
 }

@@ -24,6 +24,10 @@ class EngineOptions:
     # the uncentred form works by cancellation: its error grows with max|column mean| / rms spread of the centred data.
     # Beyond this ratio the fit falls back to the centred private copy (report: raw = False, raw_declined = ratio)
     xcov_raw_max_offset: float = 1e4
+    # the same cancellation in transform / predict: the one-pass MTTKRP on the caller's UNCENTRED rows subtracts mean^T W
+    # from X W.  Beyond this ratio (estimated from <= 256 rows of the batch) the rows are centred first: in registers where
+    # the shape allows it, else on private copies (projection_report_: offset_ratio and why)
+    project_raw_max_offset: float = 1e4
     # the largest block: score and the contraction with the (block-averaged) score from ONE read of it, the second read per
     # component replaced by a P x a matrix-vector product; False keeps the two reads
     xcov_one_read: bool = True

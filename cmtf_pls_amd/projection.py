@@ -8,6 +8,7 @@ Forms, in the order they are tried (`NipalsEngine.last_projection` records which
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
 import torch
@@ -34,7 +35,8 @@ class ProjectionMixin:
         more read of just those rows (one block, or two coupled blocks in one workgroup), else on compact private copies of
         those rows through the sequential passes (any number of blocks, any storage types).  A strided sample of the batch
         is probed first: when most samples are incomplete the MTTKRP attempt would be a wasted read and every row goes
-        through the masked sequence directly.
+        through the masked sequence directly; when max|column mean| / spread exceeds `EngineOptions.project_raw_max_offset`
+        the one-pass form would lose digits to cancellation, and the rows are centred first (in registers, else None).
 
         None when no read-only form applies (a training column without observations, a shape neither the MTTKRP nor the
         rows-in-registers kernel takes): the caller then runs `project` on private copies.  `last_projection` records the
@@ -60,20 +62,26 @@ class ProjectionMixin:
                                         [o[0].contiguous() for o in ops], [o[1].contiguous() for o in ops],
                                         [b.mean for b in state.blocks], out, rows=rows)
 
-            # probe <= 256 samples strided over the batch: mostly incomplete -> skip the MTTKRP attempt (it would be one wasted read)
-            if can_rows and I > 0:
-                step = max(1, I // 256)
-                bad = None
-                for X in Xs:
-                    r = torch.isnan(X.view(I, -1)[::step][:256]).any(dim=1)
-                    bad = r if bad is None else (bad | r)
-                frac = float(bad.double().mean().item())
+            # probe <= 256 samples strided over the batch: mostly incomplete -> skip the MTTKRP attempt (it would be one wasted
+            # read); badly offset data -> centre first (the one-pass form below works on the uncentred rows by cancellation)
+            frac, ratio = self._projection_probe(state, Xs) if I > 0 else (0.0, 0.0)
+            rep["offset_ratio"] = ratio
+            if can_rows:
                 rep["probe_incomplete_fraction"] = frac
-                if frac > 0.5:
+            if not ratio <= self.opt.project_raw_max_offset:
+                rep["why"] = (f"max|column mean| / spread = {ratio:.3g} > {self.opt.project_raw_max_offset:g}: the one-pass form on "
+                              "uncentred rows would lose digits; rows centred first")
+                if can_rows:
                     out = be.empty(I, R)
                     if in_registers(out, None) is not None:
-                        rep.update(form="masked sequence, every row in registers (one read)", why="most samples have a missing value")
+                        rep["form"] = "masked sequence, every row in registers (one read)"
                         return out
+                return None
+            if can_rows and frac > 0.5:
+                out = be.empty(I, R)
+                if in_registers(out, None) is not None:
+                    rep.update(form="masked sequence, every row in registers (one read)", why="most samples have a missing value")
+                    return out
             flag = torch.zeros(1, dtype=torch.int32, device=be.device)
             scores = self._project_one_pass(state, Xs, False, centred=False, nan_flag=flag)
             if scores is not None and int(flag.item()) == 0:
@@ -88,9 +96,12 @@ class ProjectionMixin:
             if can_rows:
                 out = scores if rows is not None else be.empty(I, R)
                 if in_registers(out, rows) is not None:
+                    # scores None: the MTTKRP declined the shape, whether or not the batch has a missing value
+                    why = "missing values in the batch" if scores is not None else (
+                        f"one-pass MTTKRP declined: R = {R} > 32" if R > 32 else "one-pass MTTKRP declined: loadings beyond its LDS")
                     rep.update(form=("one-pass MTTKRP for the complete samples + masked sequence in registers for the incomplete ones"
                                      if rows is not None else "masked sequence, every row in registers (one read)"),
-                               why="missing values in the batch")
+                               why=why)
                     return out
             if rows is not None:
                 # any number of blocks / storage types / trailing extents: compact private copies of the incomplete samples only
@@ -102,6 +113,33 @@ class ProjectionMixin:
             rep["why"] = ("shape outside the MTTKRP and the rows-in-registers kernel" if scores is None
                           else "every sample has a missing value; shape outside the rows-in-registers kernel")
             return None
+
+    @staticmethod
+    def _projection_probe(state: FitState, Xs: List[torch.Tensor]) -> Tuple[float, float]:
+        """(fraction of <= 256 samples strided over the batch with a missing value in some block, max over blocks of
+        max|column mean| / rms spread of the observed centred entries of <= 256 strided samples, at most 65536 entries per
+        block so that the float64 temporaries stay small next to X).  The one-pass form computes X W - 1 (mean^T W)^T with
+        error ~ 1e-16 * that ratio relative to the scores (DESIGN "Conditioning guard").  Local to this rank: rows are
+        independent, a transform communicates nothing.  One host transfer."""
+        I = Xs[0].shape[0]
+        bad, stats = None, []
+        for blk, X in zip(state.blocks, Xs):
+            X2 = X.view(I, -1)
+            r = torch.isnan(X2[:: max(1, I // 256)][:256]).any(dim=1)
+            bad = r if bad is None else (bad | r)
+            k = max(1, min(256, (1 << 16) // max(X2.shape[1], 1)))
+            d = X2[:: max(1, I // k)][:k].to(torch.float64) - blk.mean
+            miss = torch.isnan(d)
+            d = d.masked_fill_(miss, 0.0)
+            stats += [(d * d).sum(), (~miss).sum().to(torch.float64), blk.mean.abs().max()]
+        vals = torch.stack(stats + [bad.to(torch.float64).mean()]).cpu().tolist()
+        worst = 0.0
+        for ssq, cnt, top in zip(vals[0:-1:3], vals[1:-1:3], vals[2:-1:3]):
+            if top == 0.0 or cnt == 0.0:                 # nothing to cancel / no observed entry to measure the spread on
+                continue
+            ratio = top / math.sqrt(ssq / cnt) if ssq > 0.0 else float("inf")
+            worst = ratio if not ratio <= worst else worst
+        return vals[-1], worst
 
     def _project(self, state: FitState, Xs: List[torch.Tensor], one_pass: bool, mixed: bool) -> torch.Tensor:
         be = self.be

@@ -355,8 +355,9 @@ int cmtfpls_sum_f64(const double* in, int64_t n, double* out, void* stream);
  * 16 / sizeof(T) elements), or loadings beyond 144 KB of LDS: the caller keeps the passes.
  * project_rows2: the same for TWO COUPLED blocks sharing the sample mode (ctPLS.transform / predict with missing values,
  * cmtf.py:143-177,180-210): one workgroup holds the sample's row of both blocks, the score of a step is the mean of the two
- * masked block scores (np.average, cmtf.py:155,206) and deflates both.  The shorter block may take at most 4 vectors per lane
- * (an I x 512 matrix block: one), both blocks together at most 17; otherwise CMTFPLS_EUNSUPPORTED. */
+ * masked block scores (np.average, cmtf.py:155,206) and deflates both.  Always 256-thread workgroups: the longer block may take
+ * at most 16 vectors per lane and the shorter at most 4 (an I x 512 matrix block: one); beside a longer block of more than 8
+ * vectors the shorter may take only one (instances (2|4|8, 1|4) and (16, 1)); otherwise CMTFPLS_EUNSUPPORTED. */
 int cmtfpls_project_rows_f32(const float* X, int64_t I, int A, int B, int R, const double* WA, const double* WB,
                              const double* mean, double* scores, int ld, void* stream);
 int cmtfpls_project_rows_f64(const double* X, int64_t I, int A, int B, int R, const double* WA, const double* WB,

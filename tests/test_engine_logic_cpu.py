@@ -693,3 +693,64 @@ def test_small_fit_of_a_singleton_first_trailing_mode_takes_parafacs_sign(order)
     sgn = np.array([-1.0, -1.0, 1.0])
     assert np.array_equal(loads[0], sgn[None, :]) and np.array_equal(loads[1], WB.numpy() * sgn)
     assert np.array_equal(loads[0] * loads[1], WB.numpy())          # wA (x) wB, hence every score, is unchanged
+
+
+def _oracle_of(m):
+    """OracleFit carrying the model's OWN factors and means: O.transform then centres first and runs the reference's
+    sequence in float64 NumPy (tpls.py:151-165)."""
+    R = m.n_components
+    return O.OracleFit(coupled=False, n_components=R, block_shapes=[m.X_shape], y_shape=m.Y_shape, T=m.X_factors[0],
+                       loadings=[list(m.X_factors[1:])], U=m.Y_factors[0], Q=m.Y_factors[1], coef=m.coef_,
+                       r2x=[np.zeros(R)], r2y=m.R2Y, x_means=[m.X_mean], y_mean=m.Y_mean, has_miss=[False])
+
+
+@pytest.mark.parametrize("offset,centred", [(20.0, False), (1e6, True), (1e10, True)])
+def test_transform_of_badly_offset_rows_centres_them_first(offset, centred):
+    """The one-pass transform computes X W - 1 (mean^T W)^T on the caller's uncentred rows: error ~ 1e-16 * max|mean| / spread.
+    Beyond `project_raw_max_offset` (1e4, estimated from <= 256 rows, NaN-aware) the rows are centred first, and transform
+    matches the reference's centre-then-project to 1e-9 -- on new rows and on the training rows (the fitted scores)."""
+    rng = np.random.default_rng(17)
+    x = rng.normal(size=(80, 6, 5)) + offset
+    y = rng.normal(size=(80, 3))
+    m = tPLS(3, backend=NumpyBackend())
+    m.fit(x, y)
+    new = rng.normal(size=(9, 6, 5)) + offset
+    new[2, 1, 3] = np.nan                                          # NaN-aware probe; the row takes the masked sequence
+    fit = _oracle_of(m)
+    got = m.transform(new)
+    rep = m.projection_report_
+    assert (rep["offset_ratio"] > 1e4) == centred, rep
+    assert rep["form"].startswith("one-pass MTTKRP") != centred, rep
+    if centred:
+        assert rep["why"].startswith("max|column mean| / spread"), rep
+    tol = 1e-9 * np.abs(fit.T).max()
+    np.testing.assert_allclose(got, O.transform(fit, new), rtol=0, atol=tol)
+    np.testing.assert_allclose(m.transform(x), m.X_factors[0], rtol=0, atol=tol)
+    np.testing.assert_allclose(m.predict(x[:5]), O.predict(fit, x[:5]), rtol=0, atol=1e-9 * np.abs(y).max())
+    if centred:                                                    # the guard is what kept the digits
+        forced = tPLS(3, backend=NumpyBackend(), options=default_options().but(project_raw_max_offset=float("inf")))
+        forced.fit(x, y)
+        raw = forced.transform(x[:40])
+        assert forced.projection_report_["form"].startswith("one-pass MTTKRP (one read"), forced.projection_report_
+        err = np.abs(raw - forced.X_factors[0][:40]).max() / np.abs(forced.X_factors[0]).max()
+        print(f"offset {offset:g}: uncentred one-pass transform {err:.2e} normwise off the fitted scores")
+        if offset >= 1e10:
+            assert err > 1e-9
+
+
+def test_projection_report_names_the_mttkrp_decline_without_missing_values():
+    """A complete batch the MTTKRP declines (R > 32) must not be reported as having missing values."""
+    from cmtf_pls_amd.tpls import to_device_copy
+    rng = np.random.default_rng(3)
+    m = tPLS(4, backend=NumpyBackend())
+    m.fit(rng.normal(size=(30, 5, 4)), rng.normal(size=(30, 2)))
+    eng = m._get_engine()
+    eng.be.project_rows = lambda X2, A, B, WA, WB, mean, out, rows=None: None if rows is not None else out.zero_()
+    try:
+        eng.be.mttkrp = lambda *a, **k: None                      # the MTTKRP declines the shape
+        got = eng.project_readonly(m._state, [to_device_copy(rng.normal(size=(6, 5, 4)), torch.float64, "cpu")])
+    finally:
+        del eng.be.project_rows, eng.be.mttkrp
+    rep = eng.last_projection
+    assert got is not None and rep["form"] == "masked sequence, every row in registers (one read)", rep
+    assert rep["why"] == "one-pass MTTKRP declined: loadings beyond its LDS", rep
