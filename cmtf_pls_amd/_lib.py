@@ -28,6 +28,11 @@ class KfoldState(ctypes.Structure):
                                 "Tout", "vec", "n_iter", "status", "part")]
 
 
+class CvCoupledBlock(ctypes.Structure):
+    """cmtfpls_cv_coupled_block (include/cmtfpls.h): one block of cmtfpls_cv_masked_coupled_f64."""
+    _fields_ = [("X", _P), ("order", c_int), ("A", c_int), ("B", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/cmtfpls.h one to one
 SIGNATURES = {
     "cmtfpls_xcov_iterate_blocks_f64": (c_int, [ctypes.POINTER(XcovBlock), c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
@@ -156,6 +161,10 @@ SIGNATURES = {
     "cmtfpls_cv_masked_model_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_models_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int]
                                      + [_P] * 8 + [_P, c_size_t, _P]),
+    "cmtfpls_cv_masked_coupled_workspace_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, c_int, c_int, c_int]),
+    "cmtfpls_cv_masked_coupled_lds_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, c_int, c_int, c_int]),
+    "cmtfpls_cv_masked_coupled_f64": (c_int, [ctypes.POINTER(CvCoupledBlock), c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_double,
+                                              c_int, c_int, c_int] + [_P] * 8 + [_P, c_size_t, _P]),
     "cmtfpls_fit_small_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cmtfpls_fit_small_f64": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int] + [_P] * 11 + [_P, c_size_t, _P]),
     "cmtfpls_add_noise_f32": (c_int, [_P, c_int64, c_double, c_uint64, c_uint64, c_double, _P]),

@@ -723,6 +723,57 @@ class HipBackend:
         out["launches"] = launches
         return out
 
+    def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
+                          max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
+        """Refits of a ctPLS whose blocks X2s (each I x P_b, NaN = missing) have missing values on count-weighted rows, a workgroup
+        per model (cmtfpls_cv_masked_coupled_f64): model m trains on counts[m, r] copies of row r of every block paired with Y row
+        yrow[m, r] and predicts its rows with count 0.  dims: (order, A, B) per block; counts: (n, I) int32; yrow: (n, I) int32 or
+        None (identity).  Returns a dict of device tensors -- Ypred (n, R, I, M) (zero where the model trained), n_iter (n, R),
+        status (n), info (n, 2) (bit masks over the blocks) and with `factors` Wa, Wb (lists: per block (n, R, A_b) / (n, R, B_b)),
+        coef (n, R, R), Q (n, R, M) -- or None when the shape is outside the form.  Models run in chunks whose workspace and Ypred
+        rows fit `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
+        nb = len(X2s)
+        I = X2s[0].shape[0]
+        M = Y.shape[1]
+        nm = counts.shape[0]
+        assert nb >= 1 and len(dims) == nb and Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape[0] == I
+        for X2, (_, A, B) in zip(X2s, dims):
+            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
+        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
+        blocks = (_lib.CvCoupledBlock * nb)(*[_lib.CvCoupledBlock(_ptr(X2), int(o), int(A), int(B)) for X2, (o, A, B) in zip(X2s, dims)])
+        sumA, sumB = sum(A for _, A, _ in dims), sum(B for _, _, B in dims)
+        out = {"Ypred": self.zeros(nm, R, I, M), "n_iter": torch.zeros(nm, R, dtype=torch.int32, device=self.device),
+               "status": torch.zeros(nm, dtype=torch.int32, device=self.device),
+               "info": torch.zeros(nm, 2, dtype=torch.int32, device=self.device)}
+        if factors:
+            out.update(Wa=self.zeros(nm, R * sumA), Wb=self.zeros(nm, R * sumB), coef=self.zeros(nm, R, R), Q=self.zeros(nm, R, M))
+        fn = self.lib.cmtfpls_cv_masked_coupled_f64
+        args = (blocks, nb, _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, M, R, float(tol), int(max_iter))
+        outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wb", "coef", "Q")) if factors else (None,) * 4),
+                _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
+        # probe without a workspace: the shape check comes first (4 = declined, 2 = only the workspace is missing)
+        if fn(*args, 0, 1, *outs, None, 0, self._stream()) == 4:
+            return None
+        per = int(self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R))
+        budget = (4 << 30) if max_ws_bytes is None else int(max_ws_bytes)
+        chunk = max(1, min(nm, budget // max(per + R * I * M * 8, 1)))
+        ws = torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
+        launches = 0
+        for m0 in range(0, nm, chunk):
+            _lib.check(fn(*args, m0, min(chunk, nm - m0), *outs, _ptr(ws), ws.numel(), self._stream()), "cv_masked_coupled")
+            launches += 1
+        out["launches"] = launches
+        if factors:                                                                  # block b's R x A_b at R * (A_0 + .. + A_(b-1))
+            oa = ob = 0
+            Wa, Wb = [], []
+            for _, A, B in dims:
+                Wa.append(out["Wa"][:, R * oa:R * (oa + A)].reshape(nm, R, A))
+                Wb.append(out["Wb"][:, R * ob:R * (ob + B)].reshape(nm, R, B))
+                oa, ob = oa + A, ob + B
+            out["Wa"], out["Wb"] = Wa, Wb
+        return out
+
     # -- K-fold cross-validation (validate.kfold_predictions, kfold.py): every fold from the same reads of X ----------------
     def kfold_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,
                    ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:

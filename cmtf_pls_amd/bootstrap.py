@@ -17,7 +17,9 @@ K-fold kernels take at least two models).  The passes run through kfold._device_
 its own resamples; anything outside the device form refits every resample on the regular engine.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every resample as a count-weighted workgroup of
-cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model.
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model.  With
+EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
+(kfold.masked_models_coupled), every block's factors aligned by align_factors.
 """
 from __future__ import annotations
 
@@ -26,8 +28,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
-                    _host, _names, _state, _stats_why, _to_dev, _training_data, has_missing, masked_models, masked_models_report)
+from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
+                    _host, _names, _state, _stats_why, _to_dev, _training_data, has_missing, masked_coupled_report, masked_models,
+                    masked_models_coupled, masked_models_report, wants_masked_coupled)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -210,6 +213,10 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
         masked, mwhy = masked_models(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
         if masked is None:
             why = f"the masked form ({MODELS_FORM}) declined: {mwhy}"
+    elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
+        masked, mwhy = masked_models_coupled(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
+        if masked is None:
+            why = f"the masked form ({COUPLED_FORM}) declined: {mwhy}"
     else:
         G = min(_groups(X, 1, min(NB, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for X in Xs)   # the LDS of every block's score pass
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES)
@@ -233,8 +240,11 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
                 _, n_iters[e] = refit_one(e)
                 refitted.append(e)
                 continue
-            modes = [masked["Wb"][e].T] if X.ndim == 2 else [masked["Wa"][e].T, masked["Wb"][e].T]
-            res[e] = ([modes], masked["Q"][e].T, masked["coef"][e])
+            if coupled:
+                modes = [[wb[e].T] if Xb.ndim == 2 else [wa[e].T, wb[e].T] for Xb, wa, wb in zip(Xs, masked["Wa"], masked["Wb"])]
+            else:
+                modes = [[masked["Wb"][e].T] if X.ndim == 2 else [masked["Wa"][e].T, masked["Wb"][e].T]]
+            res[e] = (modes, masked["Q"][e].T, masked["coef"][e])
             oob_sum[0] += torch.from_numpy(masked["Ypred"][e])
             oob_sum[1] += torch.from_numpy((counts[e] == 0).astype(np.float64))
     else:
@@ -257,7 +267,7 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
         oob_q2y = 1.0 - ((pred - y) ** 2).reshape(R, -1).sum(axis=1) / (y ** 2).sum()   # validate.py:35-37 on the OOB rows
 
     if masked is not None:
-        rep = masked_models_report(masked, refitted, "resamples")
+        rep = (masked_coupled_report if coupled else masked_models_report)(masked, refitted, "resamples")
         pls.bootstrap_report_ = dict(rep, resamples=int(NB), passes=rep["launches"], models_per_pass=-(-NB // rep["launches"]),
                                      n_iter=n_iters)
     elif passes:

@@ -20,6 +20,11 @@ Anything outside the device form refits once per fold on the regular engine (X[t
 The permutation test (permutation.py), repeated K-fold (repeated.py) and the bootstrap (bootstrap.py) run the same state with
 more models per pass: _state allocates it (a view per block), _components makes every launch of a pass with the inner and
 epilogue entries of the form, and _device_passes runs the passes and refits whatever they leave.
+
+Missing values in X (opt-in): a tPLS with EngineOptions.masked_folds refits every fold in a workgroup of cmtfpls_cv_masked_f64
+(masked_predictions) or, count-weighted, of cmtfpls_cv_masked_models_f64 (masked_models); a ctPLS with
+EngineOptions.masked_folds_coupled and a NaN in at least one block refits every model in a workgroup of
+cmtfpls_cv_masked_coupled_f64 (masked_models_coupled, masked_predictions_coupled).
 """
 from __future__ import annotations
 
@@ -502,14 +507,17 @@ def masked_models_report(out: dict, refitted, what: str) -> dict:
     return rep
 
 
-def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[np.ndarray], tol: float, max_iter: int):
-    """The Q2Y numerators of N K-fold entries (permutations, splits) from masked_models: entry e has the fold ids ids[e] (N x I)
-    and pairs X row r with Y row yrows[e, r] (None: identity); model e K + k holds out its fold k.  Returns (numerators N x R,
-    n_iter per entry (K x R lists), report) or (None, why, None).  A model with a status refits alone (refit_fold)."""
+def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[np.ndarray], tol: float, max_iter: int,
+                           coupled: bool = False):
+    """The Q2Y numerators of N K-fold entries (permutations, splits) from masked_models (coupled: X a list of blocks, from
+    masked_models_coupled): entry e has the fold ids ids[e] (N x I) and pairs X row r with Y row yrows[e, r] (None: identity);
+    model e K + k holds out its fold k.  Returns (numerators N x R, n_iter per entry (K x R lists), report) or (None, why, None).
+    A model with a status refits alone (refit_fold)."""
     N, I = ids.shape
     R = pls.n_components
     counts = (ids[:, None, :] != np.arange(K)[None, :, None]).reshape(N * K, I).astype(np.int32)
-    out, why = masked_models(pls, X, Y, counts, None if yrows is None else np.repeat(yrows, K, axis=0), tol, max_iter)
+    models, report = (masked_models_coupled, masked_coupled_report) if coupled else (masked_models, masked_models_report)
+    out, why = models(pls, X, Y, counts, None if yrows is None else np.repeat(yrows, K, axis=0), tol, max_iter)
     if out is None:
         return None, why, None
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
@@ -529,7 +537,119 @@ def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[n
             else:
                 pe[:, test] = pred[e, k][:, test]
         nums[e] = ((pe - y) ** 2).reshape(R, -1).sum(axis=1)                   # _refit_numerators' sum
-    return nums, n_iter, masked_models_report(out, refitted, "models")
+    return nums, n_iter, report(out, refitted, "models")
+
+
+# ---- a ctPLS with missing values in its blocks (EngineOptions.masked_folds_coupled) ---------------------------------
+COUPLED_FORM = "cmtfpls_cv_masked_coupled_f64"
+COUPLED_LDS_CAP = 150 * 1024
+
+
+def coupled_lds_bytes(dims, I: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_f64 for blocks of trailing shape dims = [(A, B), ..] (the library's
+    cmtfpls_cv_masked_coupled_lds_bytes): the per-block scratch is shared, sized for the largest block."""
+    Pmax = max(A * B for A, B in dims)
+    nmax = max(min(A, B) for A, B in dims)
+    kmax = max(max(A, B) for A, B in dims)
+    own = sum((R + 1) * (A + B) + I for A, B in dims)
+    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 256 + Pmax + 2 * nmax * nmax + nmax + kmax + own)
+
+
+def wants_masked_coupled(pls, X) -> bool:
+    """Whether the coupled masked form is asked for: a ctPLS (X a list of blocks) with EngineOptions.masked_folds_coupled and a
+    missing value in at least one block."""
+    return isinstance(X, list) and pls._get_engine().opt.masked_folds_coupled and any(has_missing(b) for b in X)
+
+
+def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol: float, max_iter: int,
+                          factors: bool = False, max_ws_bytes: Optional[int] = None):
+    """Refits of a ctPLS whose blocks Xs have missing values on count-weighted rows, a workgroup per model in one launch per chunk
+    (cmtfpls_cv_masked_coupled_f64), in float64 on the original data whatever the model's storage type.  Model m trains
+    on counts[m, r] copies of row r of every block paired with Y row yrow[m, r] (yrow None: identity) and predicts its rows with
+    count 0.  Returns (out, None) -- out the backend's dict on the host (Ypred (n, R, I, M), n_iter, status, info, launches, with
+    `factors` Wa, Wb (per block), coef, Q) -- or (None, why) with masked_models' declines.  Models with a status are the caller's to
+    refit."""
+    eng = pls._get_engine()
+    be = eng.be
+    R = pls.n_components
+    I = counts.shape[1]
+    if not hasattr(be, "cv_masked_coupled"):
+        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no coupled masked model kernel"
+    if pls._comm is not None:
+        return None, "sharded model (comm)"
+    for X, name in zip(Xs, _names(Xs, True)):
+        if X.ndim not in (2, 3):
+            return None, f"{name} of order {X.ndim} (the masked form takes order 2 and 3)"
+    if has_missing(Y):
+        return None, "missing values in Y"
+    dims = [_dims(X) for X in Xs]
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    dev = be.device
+
+    def f64(a):                                                                 # the original data in float64, on the device
+        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
+
+    with eng.device_ctx():
+        out = None
+        if len(Xs) <= MAX_BLOCKS:                                                # (the entry declines more blocks itself)
+            out = be.cv_masked_coupled([f64(X).contiguous().view(I, -1) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
+                                       f64(Y).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+                                       None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol, max_iter, factors, max_ws_bytes)
+        if out is None:
+            return None, (f"shape outside {COUPLED_FORM} (it takes at most {MAX_BLOCKS} blocks, min(J, K) <= 64 in every block, "
+                          f"M <= 64, R <= 16 and its vectors within {COUPLED_LDS_CAP} bytes of LDS): {len(Xs)} blocks, min(J, K) = "
+                          f"{[min(A, B) for A, B in dims]}, M = {M}, R = {R}, LDS = {coupled_lds_bytes(dims, I, M, R)} bytes")
+        host = {k: ([t.cpu().numpy() for t in v] if isinstance(v, list) else v.cpu().numpy() if isinstance(v, torch.Tensor) else v)
+                for k, v in out.items()}
+        return dict(host, blocks=len(Xs)), None
+
+
+def _block_bits(mask: np.ndarray, nb: int):
+    """Per block, how many entries of the bit masks `mask` have the block's bit set."""
+    return [int(((mask >> b) & 1).sum()) for b in range(nb)]
+
+
+def masked_coupled_report(out: dict, refitted, what: str) -> dict:
+    """The report entries of a coupled masked-models run: form, models, launches, masked_blocks / masked_batches (per block: the
+    models whose training rows / held-out batch took the masked arithmetic in that block), x_reads; `refitted` (always present)
+    the models whose status made them refit alone on the regular engine, with the reason in `why`."""
+    status = out["status"]
+    ok = status == 0
+    nb = int(out["blocks"])
+    form = (f"a workgroup per model on {nb} coupled blocks with missing values, {len(status)} models in {out['launches']} "
+            f"launch(es) ({COUPLED_FORM})")
+    rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
+           "models": int(len(status)), "launches": int(out["launches"]), "masked_blocks": _block_bits(out["info"][ok, 0], nb),
+           "masked_batches": _block_bits(out["info"][ok, 1], nb), "x_reads": None, "refitted": [int(m) for m in refitted]}
+    if len(refitted):
+        names = {1: "a training row without an observed entry in some block", 2: "fewer than 2 training rows",
+                 3: "bad counts or Y rows"}
+        rep["why"] = "; ".join(f"{names[s]} in {what} {np.flatnonzero(status == s).tolist()}"
+                                     for s in (1, 2, 3) if (status == s).any())
+    return rep
+
+
+def masked_predictions_coupled(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
+    """K-fold (leave-one-out: ids = arange(I), K = I) predictions of a ctPLS whose blocks have missing values from
+    masked_models_coupled, fold k as the model with count 0 on its rows: (pred (R, I, M), report) or (None, why).  A fold with a
+    status refits alone (refit_fold) and is listed in the report's `refitted`."""
+    I = ids.shape[0]
+    R = pls.n_components
+    counts = (ids[None, :] != np.arange(K)[:, None]).astype(np.int32)
+    out, why = masked_models_coupled(pls, Xs, Y, counts, None, tol, max_iter)
+    if out is None:
+        return None, why
+    n_iter = out["n_iter"].tolist()
+    pred = np.zeros((R, I, out["Ypred"].shape[3]))
+    refitted = []
+    for k in range(K):
+        test = ids == k
+        if out["status"][k]:
+            pred[:, test], n_iter[k] = refit_fold(pls, Xs, Y, test, tol, max_iter)
+            refitted.append(k)
+        else:
+            pred[:, test] = out["Ypred"][k][:, test]
+    return pred, dict(masked_coupled_report(out, refitted, "folds"), folds=int(K), n_iter=n_iter)
 
 
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
@@ -547,6 +667,9 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
     elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):
         pred, rep = masked_predictions(pls, X, Y, ids, K, tol, max_iter)
         why = None if pred is not None else f"the masked form ({MASKED_FORM}) declined: {rep}"
+    elif wants_masked_coupled(pls, X):                                              # EngineOptions.masked_folds_coupled
+        pred, rep = masked_predictions_coupled(pls, X, Y, ids, K, tol, max_iter)
+        why = None if pred is not None else f"the masked form ({COUPLED_FORM}) declined: {rep}"
     else:
         inner = ("kfold_inner_coupled", "kfold_combine_scores") if coupled else ("kfold_inner",)
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"))

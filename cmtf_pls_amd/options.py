@@ -59,6 +59,11 @@ class EngineOptions:
     # fold or resample as a count-weighted model, cmtfpls_cv_masked_models_f64, kfold.masked_models); opt-in (reports:
     # q2y_report_ / bootstrap_report_, a decline names its reason)
     masked_folds: bool = False
+    # the same for a ctPLS with a missing value in at least one block: every fold, permutation x fold, split x fold or resample as
+    # a count-weighted model of all blocks with the reference's per-block masked arithmetic, a workgroup per model
+    # (cmtfpls_cv_masked_coupled_f64, kfold.masked_models_coupled): K-fold / leave-one-out Q2Y, the permutation test, repeated
+    # K-fold and the bootstrap; opt-in, and separate from masked_folds, under which a ctPLS keeps its refit routing
+    masked_folds_coupled: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -15,7 +15,8 @@ X per pass, ceil(P / G) passes, run by kfold._device_passes.  A pass whose statu
 outside the device form (a ctPLS among it) refits every permutation with kfold.refit_predictions.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
-cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators).
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators); with EngineOptions.masked_folds_coupled, a ctPLS
+with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
 """
 from __future__ import annotations
 
@@ -24,9 +25,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
+from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
                     _host, _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids, has_missing,
-                    masked_fold_numerators)
+                    masked_fold_numerators, wants_masked_coupled)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
 
@@ -120,6 +121,12 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
     masked = None
     if not device_folds:
         why = "device folds switched off"
+    elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
+        got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter, coupled=True)
+        if got[0] is None:
+            why = f"the masked form ({COUPLED_FORM}) declined: {got[1]}"
+        else:
+            nums, n_iters, masked = got
     elif isinstance(X, list):
         why = "coupled model: permutation device form not built"
     elif pls._get_engine().opt.masked_folds and has_missing(X):                       # EngineOptions.masked_folds

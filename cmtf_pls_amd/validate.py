@@ -91,6 +91,9 @@ def kfold_predictions(pls_tensor, n_splits: int = 5, folds=None, tol: float = 1e
     KFold(n_splits, shuffle=False); otherwise an int array of fold ids 0..K-1, one per sample.  On the GPU every fold is served
     by the same reads of X (2R in all, X never copied or written: kfold.py); anything outside that form refits once per fold.
     `pls_tensor` is a fitted tPLS or ctPLS (a coupled model: 2R reads of each block, ``x_reads`` one entry per block).
+    With missing values in X a tPLS takes cmtfpls_cv_masked_f64 under EngineOptions.masked_folds, and a ctPLS with a NaN in some
+    block takes cmtfpls_cv_masked_coupled_f64 under EngineOptions.masked_folds_coupled (every fold a workgroup, leave-one-out is
+    n_splits = I); the permutation test, repeated K-fold and the bootstrap below route the same way.
     Which form ran is recorded on the model (``q2y_report_``)."""
     from .kfold import kfold_run
 

@@ -523,6 +523,45 @@ int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* co
                                  int B, int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred,
                                  double* Wa, double* Wb, double* coef, double* Q, int* n_iter, int* status, int* info,
                                  void* ws, size_t ws_bytes, void* stream);
+/* ---- refits of a coupled model (ctPLS) whose blocks have missing values on count-weighted rows, all models of a chunk in one
+ * launch: K-fold / leave-one-out Q2Y, the permutation test, repeated K-fold and the bootstrap (validate.py) with
+ * EngineOptions.masked_folds_coupled (cmtf.py:69-139 fit with the per-block Xs_hasMiss / Xs_miss, cmtf.py:141-175 predict;
+ * missingvals.py:7-38) ------------------------------------------------------------------------------------------------------------
+ * The count-weighted model of cmtfpls_cv_masked_models_f64 for nb blocks that share one score.  Model m in [model0, model0 +
+ * nmodels) of nm: counts[m * I + r] >= 0 copies of row r of EVERY block paired with Y row yrow[m * I + r] (yrow nullable:
+ * identity); counts 0 are held out.  A complete ctPLS fit on that literal data, every sum over rows weighted by the counts, the
+ * missing-value arithmetic per block: block b is masked when one of its columns has fewer weighted observations than n = sum_r
+ * counts (Xs_hasMiss[b], cmtf.py:77); then miss_tensordot (cmtf.py:95) and miss_mmodedot (cmtf.py:111-117) for that block, the
+ * plain sums (cmtf.py:93, 106-110) for a complete one; the blocks' scores averaged in block order (cmtf.py:119); every block
+ * deflated by the shared score on its observed entries (cmtf.py:130-131); the inner regression on the weighted rows
+ * (cmtf.py:136-138).  Then predict (cmtf.py:141-175) of the held-out rows as one batch: each block centred by the model's means and
+ * THEN masked, block b of the batch masked when any of its entries is missing, the blocks' scores averaged, every block deflated by
+ * the average; a held-out row with nothing observed in some block predicts NaN.
+ * Ypred[(((m * R) + r - 1) * I + i) * M + j] (nm x R x I x M, written at held-out rows only) = the prediction of held-out row i
+ * with the first r components.  Factors (nullable, written by every model without a status): Wa (nm x R sumA; model m's block b is
+ * the R x A_b matrix at m * R * sumA + R * (A_0 + .. + A_(b-1))), Wb (nm x R sumB, likewise), coef (nm x R x R, coef_[row,
+ * component]), Q (nm x R x M).  n_iter (nullable, nm x R); status (nm): 0 ok, 1 a training row without an observed entry in some
+ * block, 2 n < 2, 3 a negative count or a yrow outside 0..I-1 (a model with a status writes nothing else); info (nullable, nm x 2):
+ * bit b of [m, 0] = block b's training rows took the masked arithmetic, bit b of [m, 1] = block b's held-out batch did.
+ * Every block's X (I x A*B, NaN = missing) and Y (I x M, complete) are the ORIGINAL float64 data.  One 256-thread workgroup per
+ * model.  ws >= nmodels * cmtfpls_cv_masked_coupled_workspace_bytes(...): per resident model sum_b (I P_b + 2 P_b) + I M + I R
+ * doubles (per block the working copy, deflated in place, and the model's column counts and means; then Yf | T).
+ * cmtfpls_cv_masked_coupled_lds_bytes: the LDS of a workgroup, in doubles 3 I + 3 M + 2 R^2 + R M + 3 R + 256 + Pmax + 2 nmax^2 +
+ * nmax + kmax + sum_b [(R + 1)(A_b + B_b) + I] with Pmax = max A_b B_b, nmax = max min(A_b, B_b), kmax = max max(A_b, B_b) (the
+ * per-block scratch is shared by the blocks); 0 for a bad argument.
+ * CMTFPLS_EUNSUPPORTED (checked before the workspace and before any pointer is read) when nb > 8, a block's order is not 2 or 3,
+ * a block's min(A, B) > 64, M > 64, R > 16 or the LDS exceeds 150 KB. */
+typedef struct {
+  const double* X;        /* I x A*B row-major, the original block, NaN = missing */
+  int order;              /* 2 (a matrix: A = 1) or 3 */
+  int A, B;
+} cmtfpls_cv_coupled_block;
+size_t cmtfpls_cv_masked_coupled_workspace_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, int I, int M, int R);
+size_t cmtfpls_cv_masked_coupled_lds_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, int I, int M, int R);
+int cmtfpls_cv_masked_coupled_f64(const cmtfpls_cv_coupled_block* blocks, int nb, const double* Y, const int* counts,
+                                  const int* yrow, int nm, int I, int M, int R, double tol, int max_iter, int model0, int nmodels,
+                                  double* Ypred, double* Wa, double* Wb, double* coef, double* Q, int* n_iter, int* status,
+                                  int* info, void* ws, size_t ws_bytes, void* stream);
 /* ---- K-fold cross-validation with every fold served by the same reads of X (validate.kfold_predictions) ------------------------
  * The folds of a K-fold split share X_0 (the caller's uncentred tensor, never written); a fold differs only in its training rows,
  * their means and its loadings.  Per component: kfold_inner (the inner loop of every fold on its training cross-covariance, a
