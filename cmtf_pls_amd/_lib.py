@@ -148,6 +148,8 @@ SIGNATURES = {
     "cmtfpls_kfold_wide_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_wide_xcov_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_inner_grouped_f64": (c_int, [ctypes.POINTER(KfoldState), _P, c_int, c_int, c_double, c_int, _P, c_size_t, _P]),
+    "cmtfpls_kfold_inner_coupled_grouped_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, _P, c_int, c_int, c_double, c_int, _P, c_size_t,
+                                                        _P]),
     "cmtfpls_kfold_epilogue_grouped_f64": (c_int, [ctypes.POINTER(KfoldState), _P, c_int, c_int, c_int, _P, _P]),
     "cmtfpls_kfold_epilogue_splits_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, c_int, _P, _P]),
     "cmtfpls_kfold_weighted_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),

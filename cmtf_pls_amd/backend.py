@@ -880,6 +880,18 @@ class HipBackend:
         _lib.check(rc, "kfold_epilogue_grouped")
         return True
 
+    def kfold_inner_coupled_grouped(self, views, model_fold: torch.Tensor, groups: int, a: int, tol: float, max_iter: int,
+                                    ws: torch.Tensor) -> Optional[bool]:
+        """kfold_inner_coupled for views[0].K models in `groups` groups, model m holding out fold model_fold[m]: every view's mean is
+        per fold (cmtfpls_kfold_inner_coupled_grouped_f64).  None when a block or the LDS is outside the device form."""
+        assert model_fold.dtype == torch.int32 and model_fold.numel() == views[0].K
+        rc = self.lib.cmtfpls_kfold_inner_coupled_grouped_f64(views, len(views), _ptr(model_fold), int(groups), int(a), float(tol),
+                                                              int(max_iter), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner_coupled_grouped")
+        return True
+
     # -- repeated K-fold Q2Y (validate.get_q2y_repeated_kfold, repeated.py): G shuffled splits x K folds per pass ----------------
     def kfold_epilogue_splits(self, state, splits: int, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
         """kfold_epilogue for state.K models in `splits` split-major splits (cmtfpls_kfold_epilogue_splits_f64): fold_of is

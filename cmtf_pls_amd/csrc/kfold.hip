@@ -523,9 +523,13 @@ static size_t kf_coupled_lds_bytes(const KfCoupledDims& d, int M) {
 static int64_t kf_coupled_ws_per_fold(const KfCoupledDims& d) { return 2 * d.pmax + 2 * (int64_t)d.nmax * d.nmax + d.psum; }
 
 // a workgroup per fold.  With one block every step is the one of kfold_inner_kernel (lx_inner_loop) in the same order, so the
-// result is bitwise that of the tPLS kernel.
+// result is bitwise that of the tPLS kernel.  GROUPED (permutation test, see "grouped models" below): every view's mean is per
+// fold (folds x P_b) and model m reads row model_fold[m] of it; S, the loadings, Q, vec, n_iter, status and Gy are per model in
+// every layout.  Without it model k is fold k and the code is the one it always was.
+template <bool GROUPED>
 __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl, int a, double tol, int max_iter, double* ws,
-                                                                    int64_t ws_per_fold, int64_t pmax, int nmax, int amax, int bmax) {
+                                                                    int64_t ws_per_fold, int64_t pmax, int nmax, int amax, int bmax,
+                                                                    const int* __restrict__ model_fold) {
   extern __shared__ double sm[];
   __shared__ double red[kLxWaves];
   __shared__ double bestv[kLxWaves];
@@ -622,7 +626,7 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl,
     const double* wb = v.Wb + ((int64_t)fold * R + a) * v.B;
     for (int j = tid; j < v.A; j += kLxNT) { v.WA[(int64_t)j * K + fold] = wa[j]; bad |= !isfinite(wa[j]); }
     for (int j = tid; j < v.B; j += kLxNT) { v.WB[(int64_t)j * K + fold] = wb[j]; bad |= !isfinite(wb[j]); }
-    const double* mean = v.mean + (int64_t)fold * P;
+    const double* mean = v.mean + (int64_t)(GROUPED ? model_fold[fold] : fold) * P;
     double s = 0.0;
     for (int64_t c = tid; c < P; c += kLxNT) s = fma(mean[c], wk[c], s);
     mw += lx_sum(s, red);
@@ -657,8 +661,9 @@ __global__ __launch_bounds__(256) void kfold_combine_kernel(const double* __rest
   }
 }
 
-// every view valid, inside the device form, and sharing every field that is not the block's own
-static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* what) {
+// every view valid, inside the device form, and sharing every field that is not the block's own.  folds > 0 (the grouped entry):
+// the K models hold out `folds` folds, so I >= folds is enough (every model of a fold shares its rows), as in kf_grouped_check
+static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* what, int folds = 0) {
   if (!v || nb < 1 || nb > kKfMaxBlocks) { set_error("kfold coupled: 1 <= nb <= 8 block views"); return CMTFPLS_EINVAL; }
   const cmtfpls_kfold_state& s = v[0];
   for (int b = 0; b < nb; ++b) {
@@ -669,7 +674,7 @@ static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* wha
       set_error(what);
       return CMTFPLS_EINVAL;
     }
-    if (!kf_shape_ok(o.I, o.A, o.B, o.M, o.K, o.R)) {
+    if ((folds && (folds < 2 || o.I < folds)) || !kf_shape_ok(folds && o.I < o.K ? o.K : o.I, o.A, o.B, o.M, o.K, o.R)) {
       set_error("kfold coupled: a block outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256); refit per fold");
       return CMTFPLS_EUNSUPPORTED;
     }
@@ -687,6 +692,9 @@ static int kf_blocks_check(const cmtfpls_kfold_state* v, int nb, const char* wha
 //   the inner loop, the score pass, the epilogue and the contraction are those of the folds above with n columns; the grouped
 //   instantiations (GROUPED = true) read which fold a model holds out from model_fold[m] and write its held-out scores to group
 //   m % groups of Tout (groups x I x R)
+// A coupled model (ctPLS, EngineOptions.coupled_permutations) runs the same pass on a state view per block: kfold_wide per block
+// into that view's S and per-fold mean, kfold_inner_coupled_kernel<true> (model m reads row model_fold[m] of every view's mean),
+// the score pass per block and kfold_combine, stage 1 on the first view, the contraction and the grouped stage 2 per view.
 constexpr int kKfWideMaxW = 1024, kKfWideCols = 256, kKfWideUn = 4;
 
 
@@ -878,6 +886,33 @@ static int kf_inner_launch(const cmtfpls_kfold_state* st, const int* model_fold,
   return check_launch(GROUPED ? "kfold_inner_grouped" : "kfold_inner");
 }
 
+// the launch of the plain and grouped coupled inner entries, after their argument checks
+template <bool GROUPED>
+static int kf_inner_coupled_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int a, double tol, int max_iter,
+                                   void* ws, size_t ws_bytes, hipStream_t s) {
+  const KfCoupledDims d = kf_coupled_dims(blocks, nb);
+  const size_t lds = kf_coupled_lds_bytes(d, blocks[0].M);
+  if (lds > 150 * 1024) {
+    set_error(GROUPED ? "kfold_inner_coupled_grouped: the blocks' vectors exceed the LDS of one workgroup; refit per fold"
+                      : "kfold_inner_coupled: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t need = cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb);
+  if (!ws || ws_bytes < need) {
+    set_error(GROUPED ? "kfold_inner_coupled_grouped: workspace too small" : "kfold_inner_coupled: workspace too small");
+    return CMTFPLS_EWORKSPACE;
+  }
+  KfBlocks bl;
+  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
+  bl.nb = nb;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel<GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+  hipLaunchKernelGGL(kfold_inner_coupled_kernel<GROUPED>, dim3(blocks[0].K), dim3(kLxNT), lds, s, bl, a, tol, max_iter,
+                     static_cast<double*>(ws), kf_coupled_ws_per_fold(d), d.pmax, d.nmax, d.amax, d.bmax, model_fold);
+  return check_launch(GROUPED ? "kfold_inner_coupled_grouped" : "kfold_inner_coupled");
+}
+
 // the stage switch of the three epilogue entries, after their argument checks: stage 0 the Y-side Gram, stage 1 the row work, the
 // solve and (but for the last component) the Y deflation, stage 2 the down-date of S.  kKfGrouped: model_fold and its `groups`;
 // kKfSplits: `groups` is the folds per split; kKfPlain: model_fold null, groups 1
@@ -1049,22 +1084,7 @@ int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, i
   int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled: bad block views (the shared fields must be the same in every view)");
   if (rc) return rc;
   if (a < 0 || a >= blocks[0].R || max_iter <= 0) { set_error("kfold_inner_coupled: bad argument"); return CMTFPLS_EINVAL; }
-  const KfCoupledDims d = kf_coupled_dims(blocks, nb);
-  const size_t lds = kf_coupled_lds_bytes(d, blocks[0].M);
-  if (lds > 150 * 1024) {
-    set_error("kfold_inner_coupled: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t need = cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb);
-  if (!ws || ws_bytes < need) { set_error("kfold_inner_coupled: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  KfBlocks bl;
-  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
-  bl.nb = nb;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfold_inner_coupled_kernel, dim3(blocks[0].K), dim3(kLxNT), lds, (hipStream_t)stream, bl, a, tol, max_iter,
-                     static_cast<double*>(ws), kf_coupled_ws_per_fold(d), d.pmax, d.nmax, d.amax, d.bmax);
-  return check_launch("kfold_inner_coupled");
+  return kf_inner_coupled_launch<false>(blocks, nb, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream) {
@@ -1096,6 +1116,22 @@ int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* mo
   if (rc) return rc;
   if (max_iter <= 0) { set_error("kfold_inner_grouped: bad argument"); return CMTFPLS_EINVAL; }
   return kf_inner_launch<true>(st, model_fold, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_inner_coupled_grouped_f64(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int groups, int a, double tol,
+                                            int max_iter, void* ws, size_t ws_bytes, void* stream) {
+  if (!blocks || nb < 1 || nb > kKfMaxBlocks || !model_fold || groups < 1) {             // before any pointer is looked at
+    set_error("kfold_inner_coupled_grouped: bad argument (1 <= nb <= 8 block views, model_fold, groups >= 1)");
+    return CMTFPLS_EINVAL;
+  }
+  if (blocks[0].K % groups != 0 || a < 0 || a >= blocks[0].R || max_iter <= 0) {
+    set_error("kfold_inner_coupled_grouped: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled_grouped: bad block views (the shared fields must be the same in every view)",
+                           blocks[0].K / groups);
+  if (rc) return rc;
+  return kf_inner_coupled_launch<true>(blocks, nb, model_fold, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,

@@ -190,7 +190,7 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
     eng = pls._get_engine()
     be = eng.be
     if not all(hasattr(be, f) for f in entries):
-        kind = "coupled " if "kfold_inner_coupled" in entries else ""
+        kind = "coupled " if any(e.startswith("kfold_inner_coupled") for e in entries) else ""
         return f"the {getattr(be, 'name', type(be).__name__)} backend has no {kind}K-fold kernels"
     if pls._comm is not None:
         return "sharded model (comm)"
@@ -295,13 +295,17 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
                 weighted: bool = False):
     """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
     ctPLS, one block included: then the blocks' scores averaged), stage 1 and, but for the last, one contraction and stage 2 per
-    block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled) or kfold_inner_grouped; the epilogue: kfold_epilogue,
+    block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled), kfold_inner_grouped or kfold_inner_coupled_grouped (coupled
+    and grouped: every view's mean is per fold); the epilogue: kfold_epilogue,
     kfold_epilogue_grouped (grouped = (model_fold, groups)), kfold_epilogue_splits (splits > 0) or kfold_epilogue_weighted
     (weighted: fold_of holds the models' row counts).  None, or why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled:
         ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
-        inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
+        if grouped:
+            inner, inner_name = lambda a: be.kfold_inner_coupled_grouped(st, *grouped, a, tol, max_iter, ws), "kfold_inner_coupled_grouped_f64"
+        else:
+            inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
     else:
         ws = torch.empty(max(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), 256), dtype=torch.uint8, device=be.device)
         if grouped:

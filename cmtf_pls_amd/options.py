@@ -64,6 +64,10 @@ class EngineOptions:
     # (cmtfpls_cv_masked_coupled_f64, kfold.masked_models_coupled): K-fold / leave-one-out Q2Y, the permutation test, repeated
     # K-fold and the bootstrap; opt-in, and separate from masked_folds, under which a ctPLS keeps its refit routing
     masked_folds_coupled: bool = False
+    # the permutation test of a ctPLS on complete data on the device: G permutations x K folds per pass share each read of every
+    # block (cmtfpls_kfold_wide_xcov_* per block, cmtfpls_kfold_inner_coupled_grouped_f64, permutation._device_null)
+    # instead of one regular-engine refit per fold and permutation; opt-in (report: q2y_report_, a decline names its reason)
+    coupled_permutations: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -12,7 +12,14 @@ K folds = n models share each read of X, model m = k G + p holding out fold k wi
 The pass's Y side (each model's centred, held-out-zeroed Y) is built on the device from one upload of the permutation index, and
 so are the held-out predictions and the Q2Y numerators: per pass only status, n_iter and G x R numerators come back.  2R reads of
 X per pass, ceil(P / G) passes, run by kfold._device_passes.  A pass whose status is set refits its permutations; anything
-outside the device form (a ctPLS among it) refits every permutation with kfold.refit_predictions.
+outside the device form (a ctPLS without EngineOptions.coupled_permutations among it) refits every permutation with
+kfold.refit_predictions.
+
+A ctPLS on complete data with EngineOptions.coupled_permutations ("coupled") runs the same pass on a state view per
+block: the Y side of the pass is built once, kfold_wide_xcov once per block into that block's S (n x M x P_b) and per-fold mean
+(K x P_b), then per component kfold_inner_coupled_grouped (model m reads row model_fold[m] of every block's mean), one MTTKRP per
+block, kfold_combine_scores, kfold_epilogue_grouped stage 1 on the shared score, one contraction and stage 2 per block: 2R reads of
+each block per pass, G the smallest of the blocks' G.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators); with EngineOptions.masked_folds_coupled, a ctPLS
@@ -26,10 +33,11 @@ import numpy as np
 import torch
 
 from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
-                    _host, _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids, has_missing,
+                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids, has_missing,
                     masked_fold_numerators, wants_masked_coupled)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
+_ENTRIES_COUPLED = ("kfold_wide_xcov", "kfold_inner_coupled_grouped", "kfold_combine_scores", "kfold_epilogue_grouped", "mttkrp", "xcov")
 
 
 def permutations_for(I: int, n_permutations: int, permutations, random_state) -> np.ndarray:
@@ -52,14 +60,16 @@ def permutations_for(I: int, n_permutations: int, permutations, random_state) ->
     return pm
 
 
-def _device_null(pls, X, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: float, max_iter: int):
+def _device_null(pls, Xs, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: float, max_iter: int, coupled: bool = False):
     """The device form's run(pass, p0, g) of kfold._device_passes: permutations p0 .. p0 + g - 1 as K g models, model k g + p
-    holding out fold k with Y[pi_p0+p]."""
+    holding out fold k with Y[pi_p0+p].  Xs: [X] of a tPLS, or the blocks of a ctPLS (coupled: a state view per block, the Y side
+    shared)."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
-    ((X2, A, B),) = _device_blocks(pls, [X], be.device)
-    I, P = X2.shape
+    blocks = _device_blocks(pls, Xs, be.device)
+    names = _names(Xs, coupled)
+    I = blocks[0][0].shape[0]
     dev = be.device
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
@@ -75,7 +85,7 @@ def _device_null(pls, X, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: flo
     ntr = _to_dev(I - counts, dev).view(1, K, 1)
     rows = [torch.from_numpy(np.flatnonzero(ids == k)).to(dev) for k in range(K)]
     perms_d = torch.from_numpy(perms).to(dev)                                         # one upload of the index
-    mean = be.empty(K, P)
+    means = [be.empty(K, A * B) for _, A, B in blocks]                                # per fold: shared by the G models of a fold
 
     def run(passes, p0, g):
         n = K * g
@@ -83,18 +93,21 @@ def _device_null(pls, X, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: flo
         nu = (colsum - torch.matmul(onehot, Yp)) / ntr                                # g x K x M: training means
         Yw = (Yp - ybar).permute(1, 0, 2).reshape(I, g * M).contiguous()            # Y': column p M + j
         ydev = (nu - ybar).permute(1, 0, 2).reshape(K, g * M).contiguous()
-        S = be.empty(n, M, P)                                                          # = K x (g M) x P: model k g + p
-        stats = be.kfold_wide_xcov(X2, A, B, Yw, order_d, off_d, K, ydev, S, mean)
-        if stats is None:
-            return "shape outside cmtfpls_kfold_wide_xcov"
-        if passes == 0:
-            why = _stats_why(stats, P, I, eng.opt.xcov_raw_max_offset, "X")
-            if why is not None:
-                return why
+        built = []
+        for (X2, A, B), mean, name in zip(blocks, means, names):                       # one read of each block
+            S = be.empty(n, M, A * B)                                                  # = K x (g M) x P: model k g + p
+            stats = be.kfold_wide_xcov(X2, A, B, Yw, order_d, off_d, K, ydev, S, mean)
+            if stats is None:
+                return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_wide_xcov"
+            if passes == 0:
+                why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
+                if why is not None:
+                    return why
+            built.append((A, B, S, mean))
         Yk = torch.where(train, Yp.unsqueeze(0) - nu.permute(1, 0, 2).unsqueeze(2), 0.0).reshape(n, I, M)
         mf = torch.arange(n, dtype=torch.int32, device=dev) // g
-        st, shared, own = _state(be, fold_of, Yk, [(A, B, S, mean)], R, g)
-        why = _components(be, [X2], st, shared, own, R, tol, max_iter, False, grouped=(mf, g))
+        st, shared, own = _state(be, fold_of, Yk, built, R, g)
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, grouped=(mf, g))
         if why is not None:
             return why
         num = _device_numerators(shared["Tout"], shared["coef"], shared["Q"], nu, Yp, rows, K, g, R, M)
@@ -127,6 +140,9 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
             why = f"the masked form ({COUPLED_FORM}) declined: {got[1]}"
         else:
             nums, n_iters, masked = got
+    elif isinstance(X, list) and pls._get_engine().opt.coupled_permutations:          # EngineOptions.coupled_permutations
+        G = min(_groups(b, K, NP) for b in X) if K <= MAX_FOLDS else 0                # the LDS of every block's score pass
+        why = _decline_blocks(pls, X, _names(X, True), Y, K * G if G else K, _ENTRIES_COUPLED)
     elif isinstance(X, list):
         why = "coupled model: permutation device form not built"
     elif pls._get_engine().opt.masked_folds and has_missing(X):                       # EngineOptions.masked_folds
@@ -138,9 +154,11 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
     else:
         G = _groups(X, K, NP) if K <= MAX_FOLDS else 0
         why = _decline_blocks(pls, [X], ["X"], Y, K * G if G else K, _ENTRIES)     # the checks with K made with the n models
+    coupled = isinstance(X, list)
     if masked is None:
         nums, n_iters, passes, why = _device_passes(pls, NP, G, "permutations", why,
-                                                    lambda: _device_null(pls, X, Y, ids, K, perms, tol, max_iter),
+                                                    lambda: _device_null(pls, X if coupled else [X], Y, ids, K, perms, tol, max_iter,
+                                                                         coupled),
                                                     lambda p: _refit_numerators(pls, X, Y, ids, K, perms[p], tol, max_iter))
     null_all = 1.0 - nums / den                                                       # P x R: every component count
     null = null_all if per_component else null_all[:, -1]
@@ -150,7 +168,11 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
                    n_iter=n_iters, observed=observed)
         pls.q2y_report_ = rep
         return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}
-    if passes:
+    if passes and coupled:
+        form = (f"{K * G} models per pass ({G} permutations x {K} folds) from shared reads of every block (cmtfpls_kfold_wide_xcov_*, "
+                "cmtfpls_kfold_inner_coupled_grouped_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64, "
+                "cmtfpls_kfold_epilogue_grouped_f64, cmtfpls_xcov_*)")
+    elif passes:
         form = (f"{K * G} models per pass ({G} permutations x {K} folds) from shared reads of X (cmtfpls_kfold_wide_xcov_*, "
                 "cmtfpls_kfold_inner_grouped_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_epilogue_grouped_f64, cmtfpls_xcov_*)")
         if why is not None:
@@ -158,8 +180,9 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
     else:
         form = "one refit per fold and permutation on the regular engine"
     R = pls.n_components
+    x_reads = ([2 * R * passes] * len(X) if coupled else 2 * R * passes) if passes else None
     rep = {"form": form, "permutations": int(NP), "passes": int(passes), "models_per_pass": int(K * G) if passes else None,
-           "x_reads": 2 * R * passes if passes else None, "n_iter": n_iters, "observed": observed}
+           "x_reads": x_reads, "n_iter": n_iters, "observed": observed}
     if why is not None:
         rep["why"] = why
     pls.q2y_report_ = rep

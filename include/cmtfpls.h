@@ -655,6 +655,18 @@ int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* mo
                                     void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
                                        void* stream);
+/* kfold_inner_coupled_grouped: cmtfpls_kfold_inner_coupled_f64 for the permutation test of a coupled model: `blocks` holds nb <= 8
+ * views of n = K models in `groups` groups (n % groups == 0, n / groups >= 2 folds, I >= the number of folds), model m holding out
+ * fold model_fold[m] (device, n entries, < n / groups).  Every view's mean is folds x A_b*B_b (what kfold_wide_xcov writes for that
+ * block) and model m reads row model_fold[m] of it; S, the loadings, Q, vec, n_iter, status and Gy are per model.  Per pass:
+ * kfold_wide_xcov per block (Y', ydev shared), kfold_epilogue_grouped stage 0 on blocks[0], then per component this entry, the MTTKRP
+ * per block with n columns, kfold_combine_scores, kfold_epilogue_grouped stage 1 on blocks[0] and (all but the last) per block the
+ * contraction and kfold_epilogue_grouped stage 2 on blocks[b]: 2R reads of each block per pass.  Same workspace
+ * (cmtfpls_kfold_inner_coupled_workspace_bytes), view checks and limits as cmtfpls_kfold_inner_coupled_f64; nb, model_fold and
+ * groups are checked first (CMTFPLS_EINVAL), everything on the host before anything is launched.  With model_fold[m] = m and
+ * groups = 1 it is bitwise cmtfpls_kfold_inner_coupled_f64. */
+int cmtfpls_kfold_inner_coupled_grouped_f64(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int groups, int a, double tol,
+                                            int max_iter, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Repeated K-fold Q2Y (validate.get_q2y_repeated_kfold) -------------------------------------------------------------------
  * A pass carries G shuffled splits x K folds = n <= 32 models (n <= I) in one cmtfpls_kfold_state (its K = n), split-major: model
