@@ -931,6 +931,28 @@ class HipBackend:
         _lib.check(rc, "kfold_epilogue_weighted")
         return True
 
+    def press_rows(self, T: torch.Tensor, coef: torch.Tensor, Q: torch.Tensor, nu: torch.Tensor, Y: torch.Tensor, ev: torch.Tensor,
+                   pred: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """press (n, R): model j's squared prediction errors with r = 1..R components, summed over the rows with ev[j, i] > 0
+        (cmtfpls_press_rows_f64): pred_r = nu[j] + sum_{c < r} (T[j, i] @ coef[j])_c Q[j, c] against Y[i].  T (n, I, R), coef
+        (n, R, R) upper triangular, Q (n, R, M), nu (n, M), Y (I, M), ev (n, I) int32; where ev == 2 the r-component prediction
+        goes to pred[r - 1, i] (pred (R, I, M), optional).  None when R or M is outside the kernel (64 each)."""
+        n, I, R = T.shape
+        M = Y.shape[1]
+        for t, shape in ((T, (n, I, R)), (coef, (n, R, R)), (Q, (n, R, M)), (nu, (n, M)), (Y, (I, M))):
+            assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device
+        assert ev.dtype == torch.int32 and ev.is_contiguous() and tuple(ev.shape) == (n, I) and ev.device == self.device
+        assert pred is None or (pred.dtype == torch.float64 and pred.is_contiguous() and tuple(pred.shape) == (R, I, M)
+                                and pred.device == self.device)
+        ws = self._workspace("press_rows", self.lib.cmtfpls_press_rows_workspace_bytes(n, I, R, M))
+        press = self.empty(n, R)
+        rc = self.lib.cmtfpls_press_rows_f64(_ptr(T), _ptr(coef), _ptr(Q), _ptr(nu), _ptr(Y), _ptr(ev), n, I, R, M, _ptr(press),
+                                             _ptr(pred), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "press_rows")
+        return press
+
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
         returns a dict of device tensors (T, U, WA, WB, Q, x_mean, y_mean) and host arrays (coef, ssq, n_iter), or None

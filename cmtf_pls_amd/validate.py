@@ -145,6 +145,31 @@ def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, f
     return repeated_kfold(pls_tensor, n_splits, n_repeats, folds, random_state, per_component, device_folds)
 
 
+def get_q2y_nested_kfold(pls_tensor, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inner_folds=None, random_state=0,
+                         device_folds: bool = True) -> dict:
+    """Nested ("double") K-fold Q2Y of a fitted tPLS or ctPLS: the Q2Y of a model whose component count is chosen by
+    cross-validation, on rows that had no part in the choice.  Every outer fold o chooses its own r by an inner K-fold over its
+    training rows, and its held-out rows are predicted by the model fitted on those training rows with that r.
+    Splits: outer_folds=None draws one shuffled split, the test folds of sklearn's KFold(n_outer, shuffle=True, random_state);
+    otherwise an (I,) integer array of ids 0..K_o-1 with no empty fold.  inner_folds=None splits the training rows of outer fold o
+    (ascending row order) the same way with random_state + 1 + o; otherwise a (K_o, I) integer array whose row o holds -1 exactly
+    on the rows of outer fold o and ids 0..K_i-1 elsewhere, no fold empty, the same K_i in every row.  random_state must be an int
+    when a split is drawn; ValueError for anything malformed.
+    Returns {"q2y": the nested estimate, the Q2Y (validate.py:35-37: 1 - sum (pred - y)^2 / sum y^2) of "predictions";
+    "predictions": Y's shape, row i by outer model outer[i] with selected[outer[i]] components; "selected": (K_o,) ints in 1..R,
+    the argmax of inner_q2y[o] (the smallest r on an exact tie); "inner_q2y": (K_o, R), for outer fold o the Q2Y of the inner
+    folds' predictions over o's training rows with r = 1..R components (get_q2y_kfold of a model fitted on X[train_o] with
+    folds=inner[o][train_o], per_component=True); "outer_q2y": (R,) the Q2Y of the outer models' predictions with a fixed r
+    (get_q2y_kfold(pls_tensor, folds=outer, per_component=True)): max(outer_q2y) - q2y is the optimism of choosing R on the
+    scored rows; "outer_folds": (I,), "inner_folds": (K_o, I)}.
+    On the GPU the K_o (K_i + 1) models are 0/1-weighted models of the bootstrap's pass, up to 32 per pass from shared reads of X
+    (2R reads per pass and block), scored where their state lies by cmtfpls_press_rows_f64 (nested.py).  Anything
+    else -- missing values in X included -- refits every model.  Which form ran is recorded on the model (``q2y_report_``)."""
+    from .nested import nested_kfold
+
+    return nested_kfold(pls_tensor, n_outer, n_inner, outer_folds, inner_folds, random_state, device_folds)
+
+
 def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random_state=0, level: float = 0.95,
                       device_folds: bool = True) -> dict:
     """Bootstrap of a fitted tPLS or ctPLS: resample b refits the model, with its dtype, device, backend, algorithm and options,

@@ -704,6 +704,20 @@ int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, co
  * written); stage 2 is that of cmtfpls_kfold_epilogue_f64.  With 0/1 counts the entry is bitwise cmtfpls_kfold_epilogue_f64 on
  * the folds whose training rows they mark. */
 int cmtfpls_kfold_epilogue_weighted_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream);
+/* ---- Nested K-fold Q2Y (validate.get_q2y_nested_kfold) ------------------------------------------------------------------------
+ * The K_o (K_i + 1) models of a nested cross-validation are 0/1-weighted models of the bootstrap's pass (kfold_weighted_xcov ..
+ * kfold_epilogue_weighted above), which leaves T (n x I x R: every row's score, the rows with weight 0 their projection), coef
+ * (n x R x R, upper triangular) and Q (n x R x M) on the device.  press_rows scores them there:
+ *   h = T[j, i, :] coef[j],   pred_r[j, i, :] = nu[j] + sum_{c < r} h_c Q[j, c, :]         (nu: n x M, the models' means of Y)
+ *   press[j, r - 1] = sum over the rows i with eval[j, i] > 0 and over m of (pred_r[j, i, m] - Y[i, m])^2        (press: n x R)
+ * and, where eval[j, i] == 2 and pred is not NULL, pred[r - 1, i, :] = pred_r[j, i, :] (pred: R x I x M; a row may have
+ * eval == 2 in at most one model; other rows of pred are left as they are).  eval is n x I ints: 0 = the row is skipped and
+ * nothing of it is read but that word.  The strictly lower triangle of coef is not read.  Sums run in a fixed order (the same
+ * bits on every call).  Limits: R <= 64, M <= 64, n <= 65535 (CMTFPLS_EUNSUPPORTED otherwise, before anything is launched).
+ * ws >= cmtfpls_press_rows_workspace_bytes(n, I, R, M). */
+size_t cmtfpls_press_rows_workspace_bytes(int n, int64_t I, int R, int M);
+int cmtfpls_press_rows_f64(const double* T, const double* coef, const double* Q, const double* nu, const double* Y, const int* eval,
+                           int n, int64_t I, int R, int M, double* press, double* pred, void* ws, size_t ws_bytes, void* stream);
 /* fit_small: the COMPLETE tPLS.fit (tpls.py:73-120: preprocess, every component's NIPALS loop with its convergence test,
  * rank-1 extraction, deflation, inner regression, Y deflation) of a small problem in ONE launch of one workgroup -- a fit of
  * BASELINE configs[0] (200 x 10 x 8, R = 3) is otherwise a few hundred launches of pure latency.  float64, X of order 2 or 3
