@@ -130,6 +130,8 @@ SIGNATURES = {
     "cmtfpls_resid_rows_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "cmtfpls_resid_rows_f32": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_resid_rows_f64": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_contrib_rows_f32": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "cmtfpls_contrib_rows_f64": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "cmtfpls_loo_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_tpls_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -605,6 +605,27 @@ class HipBackend:
         _lib.check(rc, "resid_rows")
         return rows, cols
 
+    def contrib_rows(self, X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+                     mean: Optional[torch.Tensor], rows: Optional[torch.Tensor] = None):
+        """Per-mode SPE and T^2 contributions of n samples in one read of their rows of X2 (uncentred, storage type): (speA (n, A),
+        speB (n, B), t2A (n, A), t2B (n, B)) with e = x - T (WA (.) WB)^T and d = x * (H (WA (.) WB)^T) over the finite entries of
+        x = X2 - mean, e^2 and d summed over the other mode (cmtfpls_contrib_rows_*).  Output row i reads row rows[i] of X2 (int64 on
+        the device; None: row i) and rows i of T and H.  A matrix block (A = 1) gets speA = t2A = None.  None when the shape has no
+        device form: R > 16, or 2 A (R + 1) doubles beyond the LDS.  No workspace: a workgroup closes both sums of its rows."""
+        I, P = X2.shape
+        n, R = T.shape
+        A, B = WA.shape[0], WB.shape[0]
+        assert X2.is_contiguous() and T.stride(1) == 1 and H.stride(1) == 1 and WA.is_contiguous() and WB.is_contiguous() and P == A * B
+        assert H.shape == T.shape and (rows is None or (rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == n))
+        speB, t2B = self.empty(n, B), self.empty(n, B)
+        speA, t2A = (self.empty(n, A), self.empty(n, A)) if A > 1 else (None, None)
+        rc = self._fn("contrib_rows", X2)(_ptr(X2), I, _ptr(T), T.stride(0), _ptr(H), H.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean),
+                                         _ptr(rows), n, _ptr(speA), _ptr(speB), _ptr(t2A), _ptr(t2B), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "contrib_rows")
+        return speA, speB, t2A, t2B
+
     def loo_tpls(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int,
                  max_ws_bytes: Optional[int] = None, forms=("lds", "xcov")) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
         """Leave-one-out predictions of a tPLS model (validate.py:24-33), every fold a workgroup: returns

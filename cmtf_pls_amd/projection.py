@@ -293,6 +293,87 @@ class ProjectionMixin:
                 cols[:, 1] += x2.sum(dim=0)
         return rows, cols
 
+    def contribution_rows(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, H: torch.Tensor,
+                          rows: Optional[torch.Tensor] = None, device: bool = True) -> List[tuple]:
+        """Per block, for n samples with scores T and T^2 directions H (both n x R; H already divided by the number of blocks):
+        (speA (n, A) or None for a matrix block, speB (n, B), t2A, t2B), the sums over the other mode of e^2 and d, where
+        e = x - T W_b^T and d = x * (H W_b^T) over the finite entries of x = X - mean.  Sample i is row rows[i] of Xs[b] (int64;
+        None: row i); only those rows of Xs[b] (device, storage type, UNCENTRED, read only) are read, once, through
+        cmtfpls_contrib_rows_*.  Where the backend declines (R > 16, loadings beyond the LDS, no such kernel, device=False) the same
+        sums from torch ops on row blocks of <= 256 MB.  `last_contribution` records, per block, the form that ran and why."""
+        be = self.be
+        R = state.n_components
+        out, forms = [], []
+        with self.device_ctx():
+            for blk, X in zip(state.blocks, Xs):
+                X2 = X.reshape(X.shape[0], -1)
+                WA, WB = self._kr_operands(blk, R)
+                res, why = None, None
+                if not device:
+                    why = "device pass switched off"
+                elif not hasattr(be, "contrib_rows"):
+                    why = "backend has no contrib_rows kernel"
+                elif T.shape[0] > 0:
+                    res = be.contrib_rows(X2, T, H, WA.contiguous(), WB.contiguous(), blk.mean, rows)
+                    if res is None:
+                        why = (f"R = {R} > 16: outside cmtfpls_contrib_rows" if R > 16 else
+                               f"first mode of {blk.A} slices x R = {R}: 2 A (R + 1) doubles beyond the LDS of cmtfpls_contrib_rows")
+                if res is None:
+                    res = self._contribution_rows_torch(X2, T, H, WA, WB, blk.mean, rows)
+                out.append(res)
+                forms.append({"form": "torch fallback" if why else "contribution pass (cmtfpls_contrib_rows)", "why": why})
+        self.last_contribution = forms
+        return out
+
+    @staticmethod
+    def contribution_cells(X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+                           mean: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(e, d), both (n, P) float64: the signed residual and the T^2 contribution of every cell of the rows X2 (0 where
+        x = X2 - mean is not finite), W materialised.  For a handful of rows; the callers bound n * P."""
+        P = X2.shape[1]
+        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        x = X2.to(device=T.device, dtype=torch.float64)
+        if mean is not None:
+            x = x - mean
+        fin = torch.isfinite(x)
+        e = torch.where(fin, x - T @ W.T, 0.0)
+        d = torch.where(fin, x * (H @ W.T), 0.0)
+        return e, d
+
+    @classmethod
+    def _contribution_rows_torch(cls, X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+                                 mean: Optional[torch.Tensor], rows: Optional[torch.Tensor]):
+        n, P = T.shape[0], X2.shape[1]
+        A, B = WA.shape[0], WB.shape[0]
+        dev = T.device
+        speB, t2B = (torch.empty(n, B, dtype=torch.float64, device=dev) for _ in range(2))
+        speA, t2A = (torch.empty(n, A, dtype=torch.float64, device=dev) for _ in range(2)) if A > 1 else (None, None)
+        step = max(1, (256 << 20) // max(P * 8, 1))
+        for r0 in range(0, n, step):
+            sl = slice(r0, r0 + step)
+            e, d = cls.contribution_cells(X2[sl] if rows is None else X2.index_select(0, rows[sl].to(X2.device)), T[sl], H[sl], WA, WB, mean)
+            e2 = (e * e).view(-1, A, B)
+            d = d.view(-1, A, B)
+            speB[sl], t2B[sl] = e2.sum(dim=1), d.sum(dim=1)
+            if A > 1:
+                speA[sl], t2A[sl] = e2.sum(dim=2), d.sum(dim=2)
+        return speA, speB, t2A, t2B
+
+    def t2_direction_solve(self, state: FitState, Gd: torch.Tensor) -> torch.Tensor:
+        """Rows h_i = U^-1 g_i of Gd (n x R), U = I + triu(mean_b W_b^T W_b, 1): the unit upper-triangular matrix of
+        `_project_one_pass` (T U = mean_b X_b W_b), so that t_i^T g_i = mean_b x_ib^T W_b h_i over a complete row."""
+        be = self.be
+        R = state.n_components
+        nb = len(state.blocks)
+        with self.device_ctx():
+            Gs = be.empty(nb, R * R)
+            for b, blk in enumerate(state.blocks):
+                for m, L in enumerate(blk.loadings):
+                    be.kr_gram(L, Gs[b], first=(m == 0))
+            Gbar = Gs.view(nb, R, R).mean(dim=0)
+            U = torch.eye(R, dtype=torch.float64, device=Gd.device) + torch.triu(Gbar, 1)
+            return torch.linalg.solve_triangular(U, Gd.T, upper=True).T.contiguous()
+
     def _project_one_pass(self, state: FitState, Xs: List[torch.Tensor], mixed: bool = False, centred: bool = True,
                           nan_flag: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """All R scores from ONE read of every NaN-free block (centred: already centred in place; otherwise the centring

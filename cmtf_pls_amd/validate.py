@@ -207,3 +207,24 @@ def sample_diagnostics(pls_tensor, X=None, Y=None, level: float = 0.95, device: 
     from .diagnostics import sample_diagnostics as _run
 
     return _run(pls_tensor, X, Y, level, device)
+
+
+def sample_contributions(pls_tensor, X=None, rows=None, cells: bool = False, device: bool = True) -> dict:
+    """Contribution plot data: for each diagnosed sample, which slice of which mode carries its Q residual (SPE) and its Hotelling
+    T^2.  X=None: the training rows (fitted scores and ``original_X``; ValueError after a copy_X=False fit); otherwise new rows (a
+    ctPLS: a list of blocks), scored as transform scores them.  rows: a 1-D integer array of distinct row indices (ValueError
+    otherwise), None for every row; only those rows are read by the contribution pass.
+    Returns {"rows": (n,), "scores": (n, R), "t2": (n,) as sample_diagnostics, "t2_closure": (n,) t_i^T S^+ (t_i - tbar), "spe",
+    "spe_mode", "t2_mode"}.  For a tPLS spe is (n,) and spe_mode / t2_mode are lists with one (n, D_m) float64 array per trailing
+    mode of X: spe_mode[m][i, j] is the sum of e^2, and t2_mode[m][i, j] the sum of d = x * (W U^-1 S^+ (t - tbar)) / n_blocks, over
+    the observed cells of sample i whose index along mode m is j.  For a ctPLS each of the three is a list over blocks.  Every
+    spe_mode[m] sums over j to spe.  Over a sample without missing values t2_mode[m] sums (over j and blocks) to t2_closure, which
+    equals t2 when the training scores have zero mean (a fit on complete data) and differs from it by tbar^T S^+ (t - tbar)
+    otherwise; for samples WITH missing values the same formula is applied to the observed cells and that closure is not claimed
+    (their scores come from the masked sequence, which is not linear in x).  cells=True adds "spe_cells" (the signed residual e)
+    and "t2_cells" (d), shaped (n, *X.shape[1:]) per block, formed by torch ops: ValueError when n * prod(X.shape[1:]) exceeds
+    2**28 in a block.  On the GPU every block's selected rows are read once (cmtfpls_contrib_rows_*); device=False, R > 16 or a
+    first mode beyond the kernel's LDS takes torch ops instead.  Which form ran: ``contributions_report_`` (contributions.py)."""
+    from .contributions import sample_contributions as _run
+
+    return _run(pls_tensor, X, rows, cells, device)

@@ -459,6 +459,22 @@ int cmtfpls_resid_rows_f32(const float* X, const double* T, int64_t I, int ldt, 
 int cmtfpls_resid_rows_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
                            int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
 
+/* contrib_rows: per-mode contributions of a sample to its Q residual (SPE) and its Hotelling T^2 (validate.sample_contributions), in
+ * ONE read of the uncentred X (I x A*B, storage type, any alignment), nothing of X's size written.  Output row i (0 <= i < n) reads
+ * row src = rows ? rows[i] : i of X (src outside [0, I): NaN outputs, nothing read) with scores T[i*ldt + r] and T^2 direction
+ * H[i*ldh + r].  With x = X[src,c] - mean[c] (mean nullable), c = j*B + k, W = WA[j*R + r] WB[k*R + r], over the entries with x finite:
+ *   e = x - sum_r T W,  d = x sum_r H W;
+ *   speA[i*A + j] = sum_k e^2,  speB[i*B + k] = sum_j e^2,  t2A[i*A + j] = sum_k d,  t2B[i*B + k] = sum_j d.
+ * speA and t2A may both be NULL when A == 1 (a matrix block: they would repeat the row totals).  A NaN row of T or H gives NaN outputs
+ * for that row only.  Deterministic: a workgroup owns whole rows and closes both sums in a fixed order; no atomics, no workspace.
+ * R <= 16 and 2 A (R + 1) doubles (plus 16 KB) within the 160 KB LDS: CMTFPLS_EUNSUPPORTED beyond, before any launch. */
+int cmtfpls_contrib_rows_f32(const float* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                             const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                             double* t2A, double* t2B, void* stream);
+int cmtfpls_contrib_rows_f64(const double* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                             const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                             double* t2A, double* t2B, void* stream);
+
 /* ---- leave-one-out refits, all folds in one launch: validate.get_q2y  (cmtf_pls/validate.py:7-37) ------------
  * For every fold i in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113; R components, tol, max_iter, the
  * reference's loop and convergence test) on the I - 1 samples other than i, then predict (tpls.py:122-143) of sample
