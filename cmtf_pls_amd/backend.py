@@ -825,6 +825,24 @@ class HipBackend:
     def kfold_inner_workspace_bytes(self, A: int, B: int, K: int) -> int:
         return int(self.lib.cmtfpls_kfold_inner_workspace_bytes(A, B, K))
 
+    def kfold_inner_tensor(self, state, B1: int, B2: int, a: int, tol: float, max_iter: int, ws: torch.Tensor,
+                           model_fold: Optional[torch.Tensor] = None, groups: int = 1, Wk: Optional[torch.Tensor] = None,
+                           Wl: Optional[torch.Tensor] = None) -> Optional[bool]:
+        """kfold_inner (model_fold: kfold_inner_grouped) for X of order 4, I x A x B1 x B2 with state.B = B1 * B2: the rank-1 CP of
+        each fold's A x B1 x B2 cross-covariance inside its workgroup (cmtfpls_kfold_inner_tensor_f64).  Wk (K x R x B1) and Wl
+        (K x R x B2) receive component a's mode loadings; `ws` at least kfold_inner_tensor_workspace_bytes.  None when the shape is
+        outside the device form."""
+        assert model_fold is None or (model_fold.dtype == torch.int32 and model_fold.numel() == state.K)
+        rc = self.lib.cmtfpls_kfold_inner_tensor_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(B1), int(B2), int(a),
+                                                     float(tol), int(max_iter), _ptr(Wk), _ptr(Wl), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner_tensor")
+        return True
+
+    def kfold_inner_tensor_workspace_bytes(self, A: int, B1: int, B2: int, K: int) -> int:
+        return int(self.lib.cmtfpls_kfold_inner_tensor_workspace_bytes(A, B1, B2, K))
+
     def kfold_row_tiles(self, I: int) -> Tuple[int, int]:
         """(row tiles of the K-fold epilogue's grid, doubles of partial sums per tile)."""
         return int(self.lib.cmtfpls_kfold_row_tiles(I)), int(self.lib.cmtfpls_kfold_part_stride())

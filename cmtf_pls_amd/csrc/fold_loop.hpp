@@ -83,6 +83,9 @@ __device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, doubl
 
 // Leading singular pair of Z (A x B row-major, global): wA (A), wB (B) unit norm, largest-|.| entry of wB positive.
 // Zt: P doubles of scratch (the transpose when B < A); G0 / G1: n x n each (ping-pong); xs (n), ys (k) in LDS.
+// LONG_GLOBAL (lx_cp3's unfoldings): the same code as an instantiation of its own, whose ys and wB are global scratch, so that the
+// callers with everything in LDS keep the code they had.
+template <bool LONG_GLOBAL = false>
 __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, double* wB, double* G0, double* G1,
                          double* xs, double* ys, double* red, double* bestv, int* besti) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -188,13 +191,170 @@ __device__ __forceinline__ double lx_wave_dot(const double* row, const double* w
   return wave_sum(s);
 }
 
+// ---- rank-1 CP of an order-3 cross-covariance (X of order 4) ---------------------------------------------------------------------
+// The trailing dims of an order-4 block and the scratch of its extraction.  B2 == 0: X of order 2 or 3, Z a matrix (lx_rank1).
+struct LxTensor {
+  int B1 = 0, B2 = 0;
+  double* wK = nullptr;    // LDS: B1, the loading of mode 2 of X
+  double* wL = nullptr;    // LDS: B2, the loading of mode 3 of X
+  double* v = nullptr;     // LDS: B1 * B2, Z x_0 f_A (shared by the contractions of modes 1 and 2)
+  double* tmp = nullptr;   // LDS: max(A, B1, B2), a contraction before its scaling
+  double* part = nullptr;  // LDS: kLxNT, the row groups' partial sums of v
+  double* U = nullptr;     // global: A * B1 * B2, the unfolding of mode 1 or 2
+  double* yl = nullptr;    // global: A * B1 * B2, the long vector of lx_rank1 on an unfolding
+  double* vr = nullptr;    // global: A * B1 * B2, the right singular vector of an unfolding (not used)
+};
+
+// index of the largest |v[i]|, first index on ties, to every thread
+__device__ int lx_argmax_abs(const double* v, int n, double* bestv, int* besti) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double bv = -1.0;
+  int bi = 0;
+  for (int i = tid; i < n; i += kLxNT) { const double d = fabs(v[i]); if (d > bv) { bv = d; bi = i; } }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const double ov = __shfl_xor(bv, m, 64);
+    const int oi = __shfl_xor(bi, m, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
+  __syncthreads();
+  bv = bestv[0];
+  bi = besti[0];
+  for (int w = 1; w < kLxWaves; ++w)
+    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
+  __syncthreads();
+  return bi;
+}
+
+__device__ __forceinline__ double lx_dot(const double* a, const double* b, int n, double* red) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += kLxNT) s = fma(a[i], b[i], s);
+  return lx_sum(s, red);
+}
+
+// Rank-1 CP factors of Z (A x B1 x B2 row-major, global): parafac(Z, 1, tol=tol, init="svd", normalize_factors=True) as
+// rank1_tensor.hip:1-9 and oracle/nipals_oracle.rank1_factors state it, by the fold's workgroup.
+//   init    f_m = the leading left singular vector of the mode-m unfolding (lx_rank1: mode 0 is Z as A x B1 B2, modes 1 and 2 are
+//           unfolded into t.U in the C order of the other modes), largest-|.| entry positive.  The unfolding's long vector and
+//           its right singular vector live in global scratch (t.yl, t.vr): only the short side is bounded (kLxMaxN).
+//   sweep   cp_rank1_als_kernel's, in its order of operations, with two reads of Z instead of three: mode 0 is a dot of every
+//           row of Z with f_K (x) f_L (kl, a wavefront per row); v = Z x_0 f_A with the new f_A then serves mode 1 (v f_L) and
+//           mode 2 (v^T f_K), since f_A does not change between them.  v is built by floor(1024 / B) row groups of B threads
+//           (coalesced over the columns), the groups' partial sums added in group order.
+// fA (A), t.wK (B1), t.wL (B2): the factors as the sweeps leave them (the regular engine applies nothing further to
+// cmtfpls_rank1_tensor_f64's output).  kl: B doubles of LDS, on return f_K (x) f_L.  G0 / G1: n x n for the largest short side n of
+// the three unfoldings; xs: that n.
+__device__ void lx_cp3(const double* Z, double* Zt, int A, double tol, const LxTensor& t, double* fA, double* kl, double* G0, double* G1,
+                       double* xs, double* red, double* bestv, int* besti) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int B1 = t.B1, B2 = t.B2, B = B1 * B2, P = A * B;
+  double* f[3] = {fA, t.wK, t.wL};
+  const int d[3] = {A, B1, B2};
+  lx_rank1<true>(Z, Zt, A, B, fA, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  for (int e = tid; e < P; e += kLxNT) {                                             // mode 1: U[k][a B2 + l] = Z[a][k][l]
+    const int k = e / (A * B2), c = e % (A * B2);
+    t.U[e] = Z[(int64_t)(c / B2) * B + k * B2 + c % B2];
+  }
+  __syncthreads();
+  lx_rank1<true>(t.U, Zt, B1, A * B2, t.wK, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  for (int e = tid; e < P; e += kLxNT) {                                             // mode 2: U[l][a B1 + k] = Z[a][k][l]
+    const int l = e / (A * B1), c = e % (A * B1);
+    t.U[e] = Z[(int64_t)c * B2 + l];
+  }
+  __syncthreads();
+  lx_rank1<true>(t.U, Zt, B2, A * B1, t.wL, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  for (int m = 0; m < 3; ++m) {                                                      // sign rule (cp_rank1_als_kernel:90-103)
+    const int arg = lx_argmax_abs(f[m], d[m], bestv, besti);
+    const bool flip = f[m][arg] < 0.0;
+    __syncthreads();
+    if (flip) for (int i = tid; i < d[m]; i += kLxNT) f[m][i] = -f[m][i];
+    __syncthreads();
+  }
+  double zz = 0.0;
+  for (int e = tid; e < P; e += kLxNT) zz = fma(Z[e], Z[e], zz);
+  const double norm_z = sqrt(lx_sum(zz, red));
+  const int G = B >= kLxNT ? 1 : kLxNT / B;                                         // row groups of v
+  double weight = 1.0, prev_err = 0.0;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double iprod = 0.0;
+    for (int m = 0; m < 3; ++m) {
+      double gram = weight * weight;
+      for (int i = 0; i < 3; ++i)
+        if (i != m) gram *= lx_dot(f[i], f[i], d[i], red);
+      if (m == 0) {                                                                  // tmp[a] = Z[a, :, :] . (f_K (x) f_L)
+        for (int c = tid; c < B; c += kLxNT) kl[c] = t.wK[c / B2] * t.wL[c % B2];
+        __syncthreads();
+        for (int a = wv; a < A; a += kLxWaves) {
+          const double s = lx_wave_dot(Z + (int64_t)a * B, kl, B, lane);
+          if (lane == 0) t.tmp[a] = s;
+        }
+      } else if (m == 1) {                                                           // v = Z x_0 f_A, tmp[k] = v[k, :] . f_L
+        if (G == 1) {
+          for (int c = tid; c < B; c += kLxNT) {
+            double s = 0.0;
+            for (int a = 0; a < A; ++a) s = fma(fA[a], Z[(int64_t)a * B + c], s);
+            t.v[c] = s;
+          }
+        } else {
+          if (tid < G * B) {
+            const int g = tid / B, c = tid % B;
+            double s = 0.0;
+            for (int a = g; a < A; a += G) s = fma(fA[a], Z[(int64_t)a * B + c], s);
+            t.part[tid] = s;
+          }
+          __syncthreads();
+          for (int c = tid; c < B; c += kLxNT) {
+            double s = 0.0;
+            for (int g = 0; g < G; ++g) s += t.part[g * B + c];
+            t.v[c] = s;
+          }
+        }
+        __syncthreads();
+        for (int k = wv; k < B1; k += kLxWaves) {
+          double s = 0.0;
+          for (int l = lane; l < B2; l += 64) s = fma(t.v[k * B2 + l], t.wL[l], s);
+          s = wave_sum(s);
+          if (lane == 0) t.tmp[k] = s;
+        }
+      } else {                                                                       // tmp[l] = v[:, l] . f_K
+        for (int l = wv; l < B2; l += kLxWaves) {
+          double s = 0.0;
+          for (int k = lane; k < B1; k += 64) s = fma(t.v[k * B2 + l], t.wK[k], s);
+          s = wave_sum(s);
+          if (lane == 0) t.tmp[l] = s;
+        }
+      }
+      __syncthreads();
+      if (m == 2) iprod = (weight * weight * lx_dot(t.tmp, t.tmp, d[m], red) / gram) * weight;
+      for (int i = tid; i < d[m]; i += kLxNT) f[m][i] = t.tmp[i] * weight / gram;
+      __syncthreads();
+    }
+    double fn2 = weight * weight;
+    for (int i = 0; i < 3; ++i) fn2 *= lx_dot(f[i], f[i], d[i], red);
+    const double err = sqrt(fabs(norm_z * norm_z + fn2 - 2.0 * iprod)) / norm_z;
+    if (sweep >= 1 && fabs(prev_err - err) < tol) break;                             // (uniform: every thread holds the same sums)
+    prev_err = err;
+    for (int i = 0; i < 3; ++i) {
+      const double nrm = sqrt(lx_dot(f[i], f[i], d[i], red));
+      weight *= nrm;
+      for (int j = tid; j < d[i]; j += kLxNT) f[i][j] = f[i][j] / nrm;
+      __syncthreads();
+    }
+  }
+  for (int c = tid; c < B; c += kLxNT) kl[c] = t.wK[c / B2] * t.wL[c % B2];           // w_B = w_K (x) w_L (C order)
+  __syncthreads();
+}
+
 // The whole inner loop of one component (tpls.py:78-107) on S (M x P, global) from q = e_0 (u = Y[:, 0], tpls.py:78) until
 // sqrt(dq^T G_y dq) < tol (never on the first pass: oldU = inf, tpls.py:77) or max_iter passes.  On return q holds the converged
 // q, wA / wB the loadings and wk (P) their Kronecker product; returns the passes executed.  Z, Zt, wk: P doubles each (global);
 // G0, G1: n x n (global); q, qn, tq (M), xs (n), ys (k), red, bestv, besti: workgroup scratch; Gy: M x M.
+// tn.B2 > 0: X of order 4, Z an A x B1 x B2 tensor (B = B1 B2) whose extraction is lx_cp3; wB is then w_K (x) w_L and ys is unused.
 __device__ __forceinline__ int lx_inner_loop(const double* S, const double* Gy, int64_t P, int M, int A, int B, double tol, int max_iter,
                                              double* q, double* qn, double* tq, double* Z, double* Zt, double* wk, double* wA, double* wB,
-                                             double* G0, double* G1, double* xs, double* ys, double* red, double* bestv, int* besti) {
+                                             double* G0, double* G1, double* xs, double* ys, double* red, double* bestv, int* besti,
+                                             const LxTensor tn = LxTensor()) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   for (int m = tid; m < M; m += kLxNT) q[m] = (m == 0) ? 1.0 : 0.0;                 // u_0 = Y_f[:, 0] = Y_f e_0 (tpls.py:78)
   __syncthreads();
@@ -214,7 +374,9 @@ __device__ __forceinline__ int lx_inner_loop(const double* S, const double* Gy, 
       Z[c] = s;
     }
     __syncthreads();
-    if (A == 1) {                                                                    // tpls.py:84: Z / norm(Z)
+    if (tn.B2 > 0) {                                                                 // tpls.py:86-88 on a tensor Z
+      lx_cp3(Z, Zt, A, tol, tn, wA, wB, G0, G1, xs, red, bestv, besti);
+    } else if (A == 1) {                                                             // tpls.py:84: Z / norm(Z)
       double s = 0.0;
       for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
       const double nz = sqrt(lx_sum(s, red));

@@ -144,13 +144,47 @@ static size_t kf_inner_lds_bytes(int A, int B, int M) {
   return ((size_t)A + B + 3 * (size_t)M + (size_t)M * M + n + k) * sizeof(double);
 }
 
+// X of order 4 (cmtfpls_kfold_inner_tensor_f64): the trailing dims B1 x B2 = B, the mode loadings' outputs (nullable) and the
+// largest short side of the three unfoldings of Z (the Gram scratch of lx_cp3's init).  B2 == 0: order 2 or 3.
+struct KfTensor {
+  int B1, B2, nmax;
+  double* Wk;             // K x R x B1
+  double* Wl;             // K x R x B2
+};
+
+static int kf_tensor_short(int A, int B1, int B2, int mode) {
+  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
+  return (int)(d < rest ? d : rest);
+}
+
+static int kf_tensor_nmax(int A, int B1, int B2) {
+  int n = 0;
+  for (int m = 0; m < 3; ++m) n = kf_tensor_short(A, B1, B2, m) > n ? kf_tensor_short(A, B1, B2, m) : n;
+  return n;
+}
+
+// LDS: wA (A), wB (B), q, qn, tq (M each), G_y (M x M), xs (nmax), then lx_cp3's wK (B1), wL (B2), v (B), tmp (max dim), part
+static size_t kf_inner_tensor_lds_bytes(int A, int B1, int B2, int M) {
+  const size_t B = (size_t)B1 * B2, dmax = (size_t)(A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2));
+  return ((size_t)A + B + 3 * (size_t)M + (size_t)M * M + kf_tensor_nmax(A, B1, B2) + B1 + B2 + B + dmax + kLxNT) * sizeof(double);
+}
+
+// per fold: Z, Zt, wk, then lx_cp3's U, yl, vr (P each), G0, G1 (nmax x nmax each)
+static int64_t kf_inner_tensor_ws_per_fold(int A, int B1, int B2) {
+  const int64_t n = kf_tensor_nmax(A, B1, B2);
+  return 6 * (int64_t)A * B1 * B2 + 2 * n * n;
+}
+
 // a workgroup per fold: G_y from the row tiles' partials, the inner loop, then what the row pass needs of the new loadings:
 // mu_k^T w and g_j = w_j^T w_a (Gram of a Khatri-Rao product = product of the mode Grams).
 // GROUPED (permutation test, see "grouped models" below): the "folds" of the state are models, model m holding out fold
 // model_fold[m]; the training means are those of that fold.  Without it model k is fold k and the code is the one it always was.
-template <bool GROUPED>
+// TENSOR (X of order 4, st.B = tn.B1 tn.B2): the extraction is lx_cp3, wB = wK (x) wL, and the mode loadings go to tn.Wk / tn.Wl;
+// everything after the loop sees the block as I x A x B, as for order 3.
+template <bool GROUPED, bool TENSOR = false>
 __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state st, int a, double tol, int max_iter, double* ws,
-                                                            int64_t ws_per_fold, const int* __restrict__ model_fold) {
+                                                            int64_t ws_per_fold, const int* __restrict__ model_fold,
+                                                            KfTensor tn = KfTensor{0, 0, 0, nullptr, nullptr}) {
   extern __shared__ double sm[];
   __shared__ double red[kLxWaves];
   __shared__ double bestv[kLxWaves];
@@ -158,11 +192,11 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
   const int tid = threadIdx.x, fold = blockIdx.x;
   const int A = st.A, B = st.B, M = st.M, K = st.K, R = st.R;
   const int64_t P = (int64_t)A * B;
-  const int n = A < B ? A : B, NT = kf_tiles(st.I);
+  const int n = TENSOR ? tn.nmax : (A < B ? A : B), NT = kf_tiles(st.I);
   double* Z = ws + (int64_t)fold * ws_per_fold;                  // P
   double* Zt = Z + P;                                             // P
   double* wk = Zt + P;                                            // P
-  double* G0 = wk + P;                                            // n x n
+  double* G0 = wk + (TENSOR ? 4 : 1) * P;                         // n x n (TENSOR: after U, yl, vr)
   double* G1 = G0 + (int64_t)n * n;                               // n x n
   double* wA = sm;
   double* wB = wA + A;
@@ -172,6 +206,19 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
   double* Gy = tq + M;
   double* xs = Gy + M * M;
   double* ys = xs + n;
+  LxTensor lt;
+  if (TENSOR) {
+    lt.B1 = tn.B1;
+    lt.B2 = tn.B2;
+    lt.wK = ys;                                                   // (ys itself is not used: lx_cp3's long vector is lt.yl)
+    lt.wL = lt.wK + tn.B1;
+    lt.v = lt.wL + tn.B2;
+    lt.tmp = lt.v + B;
+    lt.part = lt.tmp + max(A, max(tn.B1, tn.B2));
+    lt.U = wk + P;
+    lt.yl = lt.U + P;
+    lt.vr = lt.yl + P;
+  }
   for (int o = tid; o < M * M; o += kLxNT) {
     double s = 0.0;
     for (int t = 0; t < NT; ++t) s += st.Gy[((int64_t)fold * NT + t) * M * M + o];
@@ -179,8 +226,18 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
   }
   __syncthreads();
   const int it = lx_inner_loop(st.S + (int64_t)fold * M * P, Gy, P, M, A, B, tol, max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs,
-                               ys, red, bestv, besti);
+                               ys, red, bestv, besti, lt);
   bool bad = false;
+  if (TENSOR) {
+    for (int j = tid; j < tn.B1; j += kLxNT) {
+      if (tn.Wk) tn.Wk[((int64_t)fold * R + a) * tn.B1 + j] = lt.wK[j];
+      bad |= !isfinite(lt.wK[j]);
+    }
+    for (int j = tid; j < tn.B2; j += kLxNT) {
+      if (tn.Wl) tn.Wl[((int64_t)fold * R + a) * tn.B2 + j] = lt.wL[j];
+      bad |= !isfinite(lt.wL[j]);
+    }
+  }
   for (int j = tid; j < A; j += kLxNT) {
     st.WA[(int64_t)j * K + fold] = wA[j];
     st.Wa[((int64_t)fold * R + a) * A + j] = wA[j];
@@ -886,6 +943,23 @@ static int kf_inner_launch(const cmtfpls_kfold_state* st, const int* model_fold,
   return check_launch(GROUPED ? "kfold_inner_grouped" : "kfold_inner");
 }
 
+// the launch of the order-4 inner entry, after its argument checks
+template <bool GROUPED>
+static int kf_inner_tensor_launch(const cmtfpls_kfold_state* st, const int* model_fold, const KfTensor& tn, int a, double tol,
+                                  int max_iter, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (!ws || ws_bytes < cmtfpls_kfold_inner_tensor_workspace_bytes(st->A, tn.B1, tn.B2, st->K)) {
+    set_error("kfold_inner_tensor: workspace too small");
+    return CMTFPLS_EWORKSPACE;
+  }
+  const size_t lds = kf_inner_tensor_lds_bytes(st->A, tn.B1, tn.B2, st->M);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<GROUPED, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+  hipLaunchKernelGGL((kfold_inner_kernel<GROUPED, true>), dim3(st->K), dim3(kLxNT), lds, s, *st, a, tol, max_iter,
+                     static_cast<double*>(ws), kf_inner_tensor_ws_per_fold(st->A, tn.B1, tn.B2), model_fold, tn);
+  return check_launch("kfold_inner_tensor");
+}
+
 // the launch of the plain and grouped coupled inner entries, after their argument checks
 template <bool GROUPED>
 static int kf_inner_coupled_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int a, double tol, int max_iter,
@@ -1058,6 +1132,39 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
     return CMTFPLS_EUNSUPPORTED;
   }
   return kf_inner_launch<false>(st, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t cmtfpls_kfold_inner_tensor_workspace_bytes(int A, int B1, int B2, int K) {
+  if (A <= 0 || B1 <= 0 || B2 <= 0 || K <= 0 || (int64_t)A * B1 * B2 > (int64_t)1 << 24) return 0;
+  return (size_t)K * (size_t)kf_inner_tensor_ws_per_fold(A, B1, B2) * sizeof(double);
+}
+
+int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int B1, int B2, int a, double tol,
+                                   int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, void* stream) {
+  if (!kf_state_ok(st) || B1 <= 0 || B2 <= 0 || (int64_t)B1 * B2 != st->B || a < 0 || a >= st->R || max_iter <= 0 || groups < 1 ||
+      (!model_fold && groups != 1)) {
+    set_error("kfold_inner_tensor: bad argument (B1 * B2 == st->B; model_fold NULL with groups == 1, or the grouped layout)");
+    return CMTFPLS_EINVAL;
+  }
+  for (int m = 0; m < 3; ++m)
+    if (kf_tensor_short(st->A, B1, B2, m) > kLxMaxN) {
+      set_error("kfold_inner_tensor: an unfolding of A x B1 x B2 with its shorter side > 256; refit per fold");
+      return CMTFPLS_EUNSUPPORTED;
+    }
+  if (model_fold) {
+    const int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_inner_tensor: bad argument");
+    if (rc) return rc;
+  } else if (!kf_shape_ok(st->I, st->A, st->B, st->M, st->K, st->R)) {
+    set_error("kfold_inner_tensor: shape outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B1 B2) <= 256); refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  if (kf_inner_tensor_lds_bytes(st->A, B1, B2, st->M) > 150 * 1024) {
+    set_error("kfold_inner_tensor: the fold's vectors exceed the LDS of one workgroup; refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const KfTensor tn{B1, B2, kf_tensor_nmax(st->A, B1, B2), Wk, Wl};
+  if (model_fold) return kf_inner_tensor_launch<true>(st, model_fold, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_tensor_launch<false>(st, nullptr, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {

@@ -15,6 +15,10 @@ A ctPLS runs the same steps per block with the score shared (device_predictions,
 the blocks inside each fold's workgroup, one MTTKRP per block, the blocks' scores averaged (kfold_combine_scores), stage 1 once on
 the shared t, one contraction and stage 2 per block: 2R reads of each block.
 
+A tPLS whose X has order 4 (I x A x B1 x B2), with EngineOptions.tensor_folds: every step above on the I x A x B1 B2
+view with the Kronecker loading wB = wK (x) wL; only the inner loop differs (kfold_inner_tensor: the rank-1 CP of each fold's
+A x B1 x B2 cross-covariance inside its workgroup).
+
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
 
 The permutation test (permutation.py), repeated K-fold (repeated.py) and the bootstrap (bootstrap.py) run the same state with
@@ -152,7 +156,44 @@ def refit_fold(pls, X, Y, test: np.ndarray, tol: float, max_iter: int):
 
 
 def _dims(X) -> Tuple[int, int]:
+    """(A, B) of the I x A x B view the passes take: order 2 is 1 x J, order 4 (I x A x B1 x B2) is A x B1 B2."""
+    if X.ndim == 4:
+        return X.shape[1], X.shape[2] * X.shape[3]
     return (1, X.shape[1]) if X.ndim == 2 else (X.shape[1], X.shape[2])
+
+
+TENSOR_RANK1 = "cp3 in the fold loop"         # q2y_report_["rank1"] of an order-4 run
+TENSOR_LDS_CAP = 150 * 1024
+
+
+def _tensor_dims(Xs, coupled: bool = False) -> Optional[Tuple[int, int]]:
+    """(B1, B2) of a tPLS's order-4 X (the inner loop is then cmtfpls_kfold_inner_tensor_f64), else None."""
+    return (int(Xs[0].shape[2]), int(Xs[0].shape[3])) if not coupled and len(Xs) == 1 and Xs[0].ndim == 4 else None
+
+
+def _decline_tensor(be, A: int, B1: int, B2: int, M: int) -> Optional[str]:
+    """Why cmtfpls_kfold_inner_tensor_f64 does not take an A x B1 x B2 cross-covariance (its limits, checked here before a read)."""
+    if not hasattr(be, "kfold_inner_tensor"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no order-4 K-fold kernel"
+    P = A * B1 * B2
+    for mode, d in enumerate((A, B1, B2)):
+        if min(d, P // d) > MAX_SIDE:
+            return f"mode-{mode} unfolding: min({d}, {P // d}) = {min(d, P // d)} > {MAX_SIDE}"
+    nmax = max(min(d, P // d) for d in (A, B1, B2))
+    lds = 8 * (A + 2 * B1 * B2 + 3 * M + M * M + nmax + B1 + B2 + max(A, B1, B2) + 1024)
+    if lds > TENSOR_LDS_CAP:
+        return f"the fold's vectors need {lds} bytes of LDS > {TENSOR_LDS_CAP} (cmtfpls_kfold_inner_tensor_f64)"
+    return None
+
+
+def _with_rank1(rep: dict, tensor, passes=True) -> dict:
+    """The report of a run whose device passes took an order-4 X: the form names the tensor entry, and `rank1` says where the
+    rank-1 CP ran."""
+    if tensor is None or not passes:
+        return rep
+    form = rep["form"].replace("cmtfpls_kfold_inner_grouped_f64", "cmtfpls_kfold_inner_tensor_f64") \
+                      .replace("cmtfpls_kfold_inner_f64", "cmtfpls_kfold_inner_tensor_f64")
+    return dict(rep, form=form, rank1=TENSOR_RANK1)
 
 
 def _training_data(pls):
@@ -185,8 +226,9 @@ def _groups(X, K: int, P: int) -> int:
     return G
 
 
-def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
-    """Why the device form does not take these blocks / this Y (None: it does, as far as can be told before reading them)."""
+def _decline_blocks(pls, Xs, names, Y, K: int, entries, tensor_ok: bool = False) -> Optional[str]:
+    """Why the device form does not take these blocks / this Y (None: it does, as far as can be told before reading them).
+    tensor_ok: the caller's passes take a tPLS's order-4 X under EngineOptions.tensor_folds (_tensor_dims)."""
     eng = pls._get_engine()
     be = eng.be
     if not all(hasattr(be, f) for f in entries):
@@ -196,8 +238,9 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
         return "sharded model (comm)"
     if len(Xs) > MAX_BLOCKS:
         return f"{len(Xs)} blocks > {MAX_BLOCKS}"
+    tensor = _tensor_dims(Xs, any(e.startswith("kfold_inner_coupled") for e in entries)) if tensor_ok and eng.opt.tensor_folds else None
     for X, name in zip(Xs, names):
-        if X.ndim not in (2, 3):
+        if X.ndim not in (2, 3) and tensor is None:
             return f"{name} of order {X.ndim} (the device form takes order 2 and 3)"
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     R = pls.n_components
@@ -210,6 +253,10 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries) -> Optional[str]:
     for X, name in zip(Xs, names):
         A, B = _dims(X)
         pre = "" if name == "X" else f"{name}: "
+        if tensor is not None and M <= MAX_RESPONSES:
+            why = _decline_tensor(be, A, *tensor, M)
+            if why is not None:
+                return why
         if min(A, B) > MAX_SIDE:
             return f"{pre}min(J, K) = {min(A, B)} > {MAX_SIDE}"
         if not _loadings_fit(A, B, K):
@@ -292,13 +339,14 @@ def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: i
 
 
 def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0,
-                weighted: bool = False):
+                weighted: bool = False, tensor=None):
     """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
     ctPLS, one block included: then the blocks' scores averaged), stage 1 and, but for the last, one contraction and stage 2 per
     block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled), kfold_inner_grouped or kfold_inner_coupled_grouped (coupled
     and grouped: every view's mean is per fold); the epilogue: kfold_epilogue,
     kfold_epilogue_grouped (grouped = (model_fold, groups)), kfold_epilogue_splits (splits > 0) or kfold_epilogue_weighted
-    (weighted: fold_of holds the models' row counts).  None, or why a kernel declined."""
+    (weighted: fold_of holds the models' row counts).  tensor = (B1, B2): a tPLS's order-4 X, st[0].B = B1 B2; the inner entry is
+    kfold_inner_tensor in the plain or the grouped layout and everything else is unchanged.  None, or why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled:
         ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
@@ -306,6 +354,10 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
             inner, inner_name = lambda a: be.kfold_inner_coupled_grouped(st, *grouped, a, tol, max_iter, ws), "kfold_inner_coupled_grouped_f64"
         else:
             inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
+    elif tensor is not None:
+        ws = torch.empty(max(be.kfold_inner_tensor_workspace_bytes(st[0].A, *tensor, n), 256), dtype=torch.uint8, device=be.device)
+        mf, groups = grouped if grouped else (None, 1)
+        inner, inner_name = lambda a: be.kfold_inner_tensor(st[0], *tensor, a, tol, max_iter, ws, mf, groups), "kfold_inner_tensor_f64"
     else:
         ws = torch.empty(max(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), 256), dtype=torch.uint8, device=be.device)
         if grouped:
@@ -384,7 +436,8 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
             X2s.append(X2)
             blocks.append((A, B, S, mean))
         st, shared, own = _state(be, _to_dev(ids, dev, torch.int32), _to_dev(Yk, dev), blocks, R, 1)
-        why = _components(be, X2s, st, shared, own, R, tol, max_iter, coupled)
+        tensor = _tensor_dims(Xs, coupled)
+        why = _components(be, X2s, st, shared, own, R, tol, max_iter, coupled, tensor=tensor)
         if why is not None:
             return None, why
         status = shared["status"].cpu().numpy()
@@ -399,7 +452,7 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
     report = {"form": f"K folds from shared reads of {source} "
                       + _form_entries("cmtfpls_kfold_xcov_*", coupled, "cmtfpls_kfold_epilogue_f64"),
               "folds": int(K), "x_reads": [2 * R] * len(Xs) if coupled else 2 * R, "n_iter": n_iter.tolist()}
-    return pred, report
+    return pred, _with_rank1(report, tensor)
 
 
 MASKED_FORM = "cmtfpls_cv_masked_f64"
@@ -676,7 +729,8 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
         why = None if pred is not None else f"the masked form ({COUPLED_FORM}) declined: {rep}"
     else:
         inner = ("kfold_inner_coupled", "kfold_combine_scores") if coupled else ("kfold_inner",)
-        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"))
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"),
+                              tensor_ok=True)
     if why is None and pred is None:
         pred, rep = device_predictions(pls, Xs, Y, ids, K, tol, max_iter, coupled)
         if pred is None:

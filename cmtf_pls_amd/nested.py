@@ -29,7 +29,7 @@ import torch
 
 from .bootstrap import _ENTRIES, _ENTRIES_COUPLED, MAX_COLUMNS
 from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_passes, _form_entries, _groups, _host, _names, _rows,
-                    _state, _stats_why, _to_dev, _training_data, fold_ids, refit_fold, repeated_fold_ids)
+                    _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids, refit_fold, repeated_fold_ids)
 
 PRESS_FORM = "cmtfpls_press_rows_f64"
 
@@ -153,7 +153,8 @@ def _device_nested(pls, Xs, Y, counts: np.ndarray, ev: np.ndarray, tol: float, m
                     return why
             built.append((A, B, S, mean))
         st, shared, own = _state(be, C, Yk, built, R, 1)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True)
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True,
+                          tensor=_tensor_dims(Xs, coupled))
         if why is not None:
             return why
         status = shared["status"][:g].cpu().numpy()
@@ -196,7 +197,7 @@ def nested_kfold(pls, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inne
         tidy = G - G % (Ki + 1)                                                       # an outer model and its inner models in one pass,
         if tidy and -(-n // tidy) == -(-n // G):                                      # where that costs no pass
             G = tidy
-        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES)
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES, tensor_ok=True)
     dev = pls._get_engine().be.device if why is None else torch.device("cpu")
     pred_d = torch.zeros(R, I, M, dtype=torch.float64, device=dev)
     refit_pred, scored = {}, []
@@ -246,6 +247,6 @@ def nested_kfold(pls, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inne
            "models_per_pass": int(G) if passes else None, "x_reads": x_reads, "n_iter": n_iters}
     if why is not None:
         rep["why"] = why
-    pls.q2y_report_ = rep
+    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(Xs, coupled), passes)
     return {"q2y": q2y, "selected": selected.astype(np.int64), "inner_q2y": inner_q2y, "outer_q2y": outer_q2y,
             "predictions": chosen.reshape(tuple(Y.shape)), "outer_folds": outer, "inner_folds": inner}

@@ -68,6 +68,11 @@ class EngineOptions:
     # block (cmtfpls_kfold_wide_xcov_* per block, cmtfpls_kfold_inner_coupled_grouped_f64, permutation._device_null)
     # instead of one regular-engine refit per fold and permutation; opt-in (report: q2y_report_, a decline names its reason)
     coupled_permutations: bool = False
+    # cross-validation of a tPLS whose X has order 4 (I x A x B1 x B2) on the device: K-fold, the permutation test, repeated and
+    # nested K-fold take it as I x A x B1 B2 with the Kronecker loading wK (x) wL, and the rank-1 CP of each fold's A x B1 x B2
+    # cross-covariance runs inside the fold's workgroup (cmtfpls_kfold_inner_tensor_f64) instead of one regular-engine
+    # refit per model; opt-in (report: q2y_report_ with "rank1", a decline names its reason)
+    tensor_folds: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
-                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _training_data, fold_ids, has_missing,
+                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids, has_missing,
                     masked_fold_numerators, wants_masked_coupled)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
@@ -107,7 +107,8 @@ def _device_null(pls, Xs, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: fl
         Yk = torch.where(train, Yp.unsqueeze(0) - nu.permute(1, 0, 2).unsqueeze(2), 0.0).reshape(n, I, M)
         mf = torch.arange(n, dtype=torch.int32, device=dev) // g
         st, shared, own = _state(be, fold_of, Yk, built, R, g)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, grouped=(mf, g))
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, grouped=(mf, g),
+                          tensor=_tensor_dims(Xs, coupled))
         if why is not None:
             return why
         num = _device_numerators(shared["Tout"], shared["coef"], shared["Q"], nu, Yp, rows, K, g, R, M)
@@ -153,7 +154,7 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
             nums, n_iters, masked = got
     else:
         G = _groups(X, K, NP) if K <= MAX_FOLDS else 0
-        why = _decline_blocks(pls, [X], ["X"], Y, K * G if G else K, _ENTRIES)     # the checks with K made with the n models
+        why = _decline_blocks(pls, [X], ["X"], Y, K * G if G else K, _ENTRIES, tensor_ok=True)   # the checks with K made with the n models
     coupled = isinstance(X, list)
     if masked is None:
         nums, n_iters, passes, why = _device_passes(pls, NP, G, "permutations", why,
@@ -185,5 +186,5 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
            "x_reads": x_reads, "n_iter": n_iters, "observed": observed}
     if why is not None:
         rep["why"] = why
-    pls.q2y_report_ = rep
+    pls.q2y_report_ = _with_rank1(rep, _tensor_dims([X], coupled), passes)
     return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}

@@ -28,7 +28,7 @@ import torch
 
 from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes,
                     _fold_means, _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev,
-                    _training_data, has_missing, masked_fold_numerators, repeated_fold_ids, wants_masked_coupled)
+                    _tensor_dims, _training_data, _with_rank1, has_missing, masked_fold_numerators, repeated_fold_ids, wants_masked_coupled)
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
@@ -75,7 +75,8 @@ def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: in
             order_l = order_d.long()
             rows.append([order_l[int(off[k]):int(off[k + 1])] for k in range(K)])
         st, shared, own = _state(be, fold_of, Yk, built, R, g)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, splits=g)
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, splits=g,
+                          tensor=_tensor_dims(Xs, coupled))
         if why is not None:
             return why
         num = torch.cat([_device_numerators(shared["Tout"][j:j + 1], shared["coef"][j * K:(j + 1) * K], shared["Q"][j * K:(j + 1) * K],
@@ -115,7 +116,8 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
             nums, n_iters, masked = got
     else:
         G = min(_groups(X, K, min(NS, I // K)) for X in Xs) if K <= MAX_FOLDS else 0   # n <= I models, the LDS of every block
-        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES)
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES,
+                              tensor_ok=True)
     identity = np.arange(I)
     if masked is None:
         nums, n_iters, passes, why = _device_passes(pls, NS, G, "splits", why,
@@ -141,7 +143,7 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
            "x_reads": x_reads, "n_iter": n_iters}
     if why is not None:
         rep["why"] = why
-    pls.q2y_report_ = rep
+    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(Xs, coupled), passes)
     return dict(summary(q2y), folds=ids)
 
 

@@ -627,6 +627,18 @@ int cmtfpls_kfold_xcov_f64(const double* X, int64_t I, int A, int B, const doubl
  * fold: writes WA / WB (columns k), Q[k, a], n_iter[k, a].  ws >= cmtfpls_kfold_inner_workspace_bytes(A, B, K). */
 size_t cmtfpls_kfold_inner_workspace_bytes(int A, int B, int K);
 int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, int max_iter, void* ws, size_t ws_bytes, void* stream);
+/* kfold_inner_tensor: kfold_inner for X of order 4 (I x A x B1 x B2) seen as I x A x B with st->B == B1 * B2 (CMTFPLS_EINVAL
+ * otherwise) and the Kronecker loading wB = wK (x) wL (C order); every other kfold entry takes that state unchanged.  The rank-1
+ * extraction of the A x B1 x B2 cross-covariance is the rank-1 CP of cmtfpls_rank1_tensor_f64, run inside each fold's workgroup.
+ * model_fold == NULL, groups == 1: the plain layout (also the split-major and weighted models); otherwise the grouped layout of
+ * cmtfpls_kfold_inner_grouped_f64.  Wk (K x R x B1) and Wl (K x R x B2), nullable, receive the mode loadings of component a; all
+ * else it writes is what cmtfpls_kfold_inner_f64 writes.  Limits, checked before the launch (CMTFPLS_EUNSUPPORTED): those of
+ * kfold_inner, the shorter side of each of the three unfoldings of A x B1 x B2 <= 256, and the fold's vectors
+ * (A + 2 B1 B2 + B1 + B2 + max dim + 3 M + M^2 + 1280 doubles at most) within 150 KB of LDS.
+ * ws >= cmtfpls_kfold_inner_tensor_workspace_bytes(A, B1, B2, K). */
+size_t cmtfpls_kfold_inner_tensor_workspace_bytes(int A, int B1, int B2, int K);
+int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int B1, int B2, int a, double tol,
+                                   int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, void* stream);
 /* kfold_epilogue: stage 0 = the partial Gy of every fold (before component 0; `in` unused); stage 1 = component a's epilogue from
  * `in` = the MTTKRP X_0 WA (.) WB (I x K): a grid of row tiles x folds for the row work, a small solve per fold; stage 2 = the down-date of S from `in` = X_0^T tm (K x A*B), not after the last component. */
 int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream);
