@@ -108,6 +108,8 @@ SIGNATURES = {
     "cmtfpls_deflate_f64": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P]),
     "cmtfpls_score_deflate_f32": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "cmtfpls_score_deflate_f64": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "cmtfpls_sweep_form": (c_int, [c_char_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "cmtfpls_sweep_form_list": (c_int, [c_char_p, c_int, c_char_p, c_size_t]),
     "cmtfpls_small_workspace_bytes": (c_size_t, []),
     "cmtfpls_gram_tn_f64": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int64, _P, _P, c_size_t, _P]),
     "cmtfpls_rowdot_f64": (c_int, [_P, c_int, c_int, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),

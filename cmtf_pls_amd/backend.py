@@ -67,6 +67,25 @@ class HipBackend:
         _lib.check(self.lib.cmtfpls_sum_f64(_ptr(part), part.numel(), _ptr(out), self._stream()), "sum")
         return out
 
+    # -- which kernel instance and grid policy a sweep takes (host arithmetic, no GPU call) ------
+    @staticmethod
+    def sweep_form(op: str, dtype, I: int, A: int, B: int, masked: bool = False, M: int = 0, aligned16: bool = True) -> str:
+        """Name of the form the X sweep `op` takes for an (I, A * B) block of `dtype` (cmtfpls_sweep_form); a shape the entry
+        declines gives "unsupported: <reason>".  Needs the library but no device."""
+        buf = ctypes.create_string_buffer(256)
+        elem = 4 if dtype in (torch.float32, "f32", "float32") else 8
+        _lib.check(_lib.load().cmtfpls_sweep_form(op.encode(), elem, int(I), int(A), int(B), int(bool(masked)), int(M), int(bool(aligned16)),
+                                                  buf, len(buf)), "sweep_form")
+        return buf.value.decode()
+
+    @staticmethod
+    def sweep_form_list(op: str, dtype) -> list:
+        """Every name sweep_form can give for `op` and `dtype` (cmtfpls_sweep_form_list)."""
+        buf = ctypes.create_string_buffer(1 << 14)
+        elem = 4 if dtype in (torch.float32, "f32", "float32") else 8
+        _lib.check(_lib.load().cmtfpls_sweep_form_list(op.encode(), elem, buf, len(buf)), "sweep_form_list")
+        return buf.value.decode().splitlines()
+
     # -- measured HBM ceilings (bench.py: roofline denominators measured in the same run) ---------
     def ceiling(self, op: str, buf: torch.Tensor, row_bytes: int = 0, blocks: int = 2048,
                 dst: Optional[torch.Tensor] = None, map: int = 0) -> bool:

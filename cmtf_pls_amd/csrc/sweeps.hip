@@ -10,6 +10,11 @@
 // Khatri-Rao/Kronecker entry w[c] = wA[c / B] * wB[c % B] is formed on the fly.
 #include "common.hpp"
 
+#include <string.h>
+
+#include <set>
+#include <string>
+
 namespace cmtfpls {
 
 // ------------------------------------------------------------------------------------------
@@ -552,6 +557,277 @@ void launch_reduce_rows(const double* part, int nrows, int64_t P, double* out, h
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(grid), dim3(256), 0, st, part, nrows, P, out);
 }
 
+#ifndef CMTFPLS_CONTRACT_ILV
+#define CMTFPLS_CONTRACT_ILV 1
+#endif
+
+// ------------------------------------------------------------------------------------------
+// host-side forms: every run_* below launches what its *_form function chose, and cmtfpls_sweep_form reports the same
+// choice by name without a GPU call -- one copy of every threshold
+// ------------------------------------------------------------------------------------------
+struct ContractForm {
+  int rc;               // CMTFPLS_OK or the status the entry returns without launching
+  const char* reason;   // rc != OK: short reason (the form's name is "unsupported: <reason>")
+  const char* msg;      // rc != OK: the message for set_error
+  int kind;             // 0 narrow, 1 vec, 2 scalar
+  int mode;             // MODE of the kernels
+  int U;                // vec: column groups per thread
+  bool full, ilv;       // vec: guard-free; interleaved row blocks
+  int blocks;           // vec: workgroups aimed at
+  int yq;               // 0: u is read, 1: u = Y q formed in the kernel, 2: formed once up front
+  bool chunks;          // yq == 1: a workgroup's rows take more than one LDS chunk of u
+  ContractPlan p;
+  int ncv, RS;          // narrow: column vectors per row, rows per workgroup pass
+};
+
+// mode: 0 plain, 1 masked, 2 statistics; yq: the entry forms u = Y q itself (M responses)
+static ContractForm contract_form(int mode, int elem, int64_t I, int64_t P, bool yq, int M) {
+  ContractForm f = {};
+  f.mode = mode;
+  // column groups per thread: 4 (wider tiles, half as many partial rows per column: +2.8 % at 65536 rows) when a
+  // workgroup still gets >= 128 rows, else 2 (shards of <= 16 K rows: 94 vs 101 us at 8192 x 128 x 128,
+  // profiles/r02g_tune_small.txt); the statistics pass carries a second set of accumulators and stays at 2
+  const int Vp = 16 / elem;
+  const bool vecp = (P % Vp) == 0;
+  const bool full4 = vecp && (P % ((int64_t)kSweepThreads * Vp * 4)) == 0, full2 = vecp && (P % ((int64_t)kSweepThreads * Vp * 2)) == 0;
+  // very long rows (>= 16 column tiles of 4 groups, e.g. 256 x 256 f32): one workgroup per CU is best (7.2 against 6.95 TB/s
+  // at 32768 x 256 x 256, profiles/r02t_tune_full.txt)
+  const int64_t tiles4 = vecp ? (P + (int64_t)kSweepThreads * Vp * 4 - 1) / ((int64_t)kSweepThreads * Vp * 4) : 0;
+  const bool one_per_cu = tiles4 >= 16 && I * tiles4 <= (int64_t)8192 * (kContractBlocksFull / 2);   // ... while a workgroup's
+  // row block stays <= 8192 rows: at 262144 x 256 x 256, 256 workgroups fall to 6.8 TB/s and 512 hold 7.06 (profiles/r02ad_tune_cfg5.txt)
+  const int blocks4 = !full4 ? kContractBlocks : (one_per_cu ? kContractBlocksFull / 2 : kContractBlocksFull);
+  const ContractPlan p4 = plan_contract(I, P, elem, 4, blocks4);
+  const bool wideU = mode != 2 && kContractU == 4 && p4.rows_per_block >= 128;
+  const int blocks2 = full2 ? kContractBlocksFull : kContractBlocks;
+  f.p = wideU ? p4 : plan_contract(I, P, elem, 2, blocks2);
+  f.U = wideU ? 4 : 2;
+  f.full = wideU ? full4 : full2;
+  f.blocks = wideU ? blocks4 : blocks2;
+  // Wide blocks (>= kYqUnfuseTiles column tiles): every column tile of a row block would repeat the same
+  // u = Y q prologue, so u is formed once by the rowdot kernel into the tail of the workspace instead
+  // (262144 x 256 x 256, M = 32: 2 % of the sweep)
+  const bool yq_pre = yq && f.p.vec && M <= 64 && mode != 2 && f.p.col_tiles >= kYqUnfuseTiles;
+  // interleaved row blocks (see contract_vec_kernel) for wide rows whose u comes from memory
+  f.ilv = mode != 2 && f.p.vec && (CMTFPLS_CONTRACT_ILV == 2 || (CMTFPLS_CONTRACT_ILV == 1 && f.p.col_tiles >= kYqUnfuseTiles));
+  f.yq = yq_pre ? 2 : (yq ? 1 : 0);
+  f.ncv = f.p.vec ? (int)(P / Vp) : 0;
+  const bool narrow = f.p.vec && f.ncv <= kSweepThreads / 2;          // at least two rows per workgroup pass
+  f.RS = narrow ? kSweepThreads / f.ncv : 1;
+  f.kind = narrow ? 0 : (f.p.vec ? 1 : 2);
+  f.chunks = f.yq == 1 && f.p.rows_per_block > kYqChunk;
+  if (f.yq == 1 && (!f.p.vec || M > 64 || mode == 2)) {
+    // supported: vector shape, M <= 64 (one Y row per wavefront pass)
+    f.rc = CMTFPLS_EUNSUPPORTED;
+    f.reason = !f.p.vec ? "scalar shape" : (M > 64 ? "more than 64 responses" : "statistics pass");
+    f.msg = "mode0_contract_yq: shape outside the fused form; form u = Y q with rowdot and use mode0_contract";
+  }
+  return f;
+}
+
+// row sweeps (center / score / deflate / score_deflate) and the fused deflation + contraction
+static inline size_t loadings_lds_bytes(int A, int B) { return ((size_t)((A + 1) & ~1) + (size_t)((B + 1) & ~1)) * sizeof(double); }
+static constexpr size_t kMaxLoadingsLds = 96 * 1024;
+#ifndef CMTFPLS_ROWS_NARROW
+#define CMTFPLS_ROWS_NARROW 1
+#endif
+#ifndef CMTFPLS_DEFLATE_ROWS
+#define CMTFPLS_DEFLATE_ROWS 1
+#endif
+#ifndef CMTFPLS_DEFLATE_ROWS_PAD
+#define CMTFPLS_DEFLATE_ROWS_PAD 81920
+#endif
+#ifndef CMTFPLS_DC_ROWS
+#define CMTFPLS_DC_ROWS 1
+#endif
+
+// vectors per lane per row of the short-row form (0: the row is too long or the shape is not a vector shape)
+static int narrow_nvl(int V, bool aligned, int A, int B) {
+  if (!CMTFPLS_ROWS_NARROW || (B % V) != 0 || !aligned) return 0;
+  const int64_t P = (int64_t)A * B;
+  if (P <= 64 * V) return 1;
+  if (P <= 2 * 64 * V) return 2;
+  if (P <= 4 * 64 * V) return 4;
+  return 0;
+}
+
+enum RowKind { kRowNarrow = 0, kRowWave, kRowGroup, kRowFew, kRowTile };
+struct RowForm {
+  int rc;               // CMTFPLS_OK or the status the entry returns without launching
+  const char* reason;   // rc != OK: short reason (the form's name is "unsupported: <reason>")
+  const char* msg;      // rc != OK: the message for set_error
+  int kind;             // kRowNarrow: a wavefront owns whole short rows; kRowWave: a wavefront per row; kRowGroup: a 256- or
+                        // 1024-thread workgroup per row (segment); kRowFew: score_fewrows_kernel; kRowTile: deflate_contract_kernel
+  int op;               // 0 score, 1 deflate, 2 score + deflate, 3 deflate + contract (narrow: OP of rows_narrow_kernel)
+  int nvl;              // narrow: vectors per lane per row
+  bool vec, gl;         // 16-byte accesses; loadings read from global memory
+  bool masked, gram;
+  int threads, nv;      // group: workgroup size, vectors per lane
+  bool kc, full;        // group: the stride is a multiple of B; and the workgroup covers the row (segment) exactly
+  int nseg;             // group (center, deflate_contract): segments per row
+  bool rowcnt;          // center: the per-row counts are wanted
+  bool pre;             // tile form of deflate_contract: u = Y q formed once, up front
+  size_t lds;           // dynamic LDS bytes of the launch
+  ContractPlan p;       // tile form of deflate_contract
+};
+
+static RowForm score_form(int elem, int64_t I, int A, int B, bool aligned, bool masked, bool gram, int M, bool few_rows_ok) {
+  RowForm f = {};
+  const int V = 16 / elem;
+  f.masked = masked;
+  f.gram = gram;
+  if (gram && M > kWave) {
+    f.rc = CMTFPLS_EUNSUPPORTED;
+    f.reason = "more than 64 responses";
+    f.msg = "score_gram: more than 64 responses; use score + gram_tn";
+    return f;
+  }
+  if (const int nvl = narrow_nvl(V, aligned, A, B)) {            // short rows: a wavefront owns several whole rows at a time
+    f.kind = kRowNarrow;
+    f.nvl = nvl;
+    f.vec = true;
+    return f;
+  }
+  f.lds = loadings_lds_bytes(A, B);
+  f.gl = f.lds > kMaxLoadingsLds;               // loadings longer than the LDS: read them through L2
+  if (f.gl) f.lds = 0;
+  f.vec = (B % V == 0) && aligned;
+  // a few long rows, one 1024-thread workgroup per row: ONLY for the rows of a cross-covariance S (cmtfpls_score_s_f64), whose row
+  // count is the number of responses -- the score of a SAMPLE (cmtfpls_score_*) must not depend on how many samples are
+  // passed with it, and this kernel sums in another order than score_kernel
+  f.kind = (few_rows_ok && !gram && f.vec && !f.gl && I <= 64 && (int64_t)A * B >= 8192) ? kRowFew : kRowWave;
+  return f;
+}
+
+static RowForm deflate_form(int elem, int A, int B, bool aligned) {
+  RowForm f = {};
+  const int V = 16 / elem;
+  f.op = 1;
+  if (const int nvl = narrow_nvl(V, aligned, A, B)) {            // short rows: a wavefront owns several whole rows at a time
+    f.kind = kRowNarrow;
+    f.nvl = nvl;
+    f.vec = true;
+    return f;
+  }
+  f.kind = kRowWave;
+  f.vec = (B % V == 0) && aligned;
+  f.lds = loadings_lds_bytes(A, B);
+  if (f.lds > kMaxLoadingsLds) {                         // loadings longer than the LDS: read them through L2
+    f.gl = true;
+    f.lds = 0;
+    return f;
+  }
+  if (CMTFPLS_DEFLATE_ROWS && f.vec) {
+    const int64_t P = (int64_t)A * B;
+    // > half of the CU's 160 KB of LDS: ONE workgroup (one row) per CU at a time --
+    // with two, the read/write streams of the rows interleave at the HBM and the sweep is 4 % slower
+    const size_t lds_w = f.lds;
+    const int nv = (P > (int64_t)256 * V * 4 && P <= (int64_t)1024 * V * 4) ? 4 : ((P > (int64_t)1024 * V * 4 && P <= (int64_t)1024 * V * 16) ? 16 : 0);
+    if (nv) {
+      f.kind = kRowGroup;
+      f.threads = 1024;
+      f.nv = nv;
+      f.kc = ((1024 * V) % B) == 0;
+      f.lds = lds_w + ((lds_w + CMTFPLS_DEFLATE_ROWS_PAD + 1024 <= 160 * 1024) ? CMTFPLS_DEFLATE_ROWS_PAD : 0);
+    }
+  }
+  return f;
+}
+
+static RowForm center_form(int elem, int64_t P, bool aligned, bool rowcnt) {
+  RowForm f = {};
+  const int Vc = 16 / elem;
+  f.rowcnt = rowcnt;
+  f.kind = kRowWave;
+  f.vec = (P % Vc == 0) && aligned;
+  // rows of more than 256 * V * 4 elements: one workgroup per row segment of <= 1024 * V * 4 elements (read burst,
+  // barrier, write burst); > half of the LDS as dynamic padding keeps it at ONE segment per CU, as for
+  // deflate_rows_kernel
+  if (f.vec && P > (int64_t)256 * Vc * 4 && P < ((int64_t)1 << 31)) {
+    const int64_t segmax = (int64_t)1024 * Vc * 4;
+    int nseg = (int)((P + segmax - 1) / segmax);
+    while (nseg <= 64 && ((P % ((int64_t)nseg * Vc)) != 0 || (kSweepBlocks % nseg) != 0)) ++nseg;
+    if (nseg <= 64) {
+      f.kind = kRowGroup;
+      f.threads = 1024;
+      f.nv = 4;
+      f.nseg = nseg;
+      f.lds = 81920;
+    }
+  }
+  return f;
+}
+
+static RowForm score_deflate_form(int elem, int A, int B, bool aligned, bool masked) {
+  RowForm f = {};
+  f.op = 2;
+  f.masked = masked;
+  if (const int nvl = narrow_nvl(16 / elem, aligned, A, B)) {            // short rows: the rows stay in registers, no workgroup barrier
+    f.kind = kRowNarrow;
+    f.nvl = nvl;
+    f.vec = true;
+    return f;
+  }
+  f.kind = kRowGroup;
+  f.rc = CMTFPLS_EUNSUPPORTED;
+  f.lds = loadings_lds_bytes(A, B);
+  if (f.lds > kMaxLoadingsLds) { f.reason = "loadings exceed LDS"; f.msg = "score_deflate: loadings exceed LDS"; return f; }
+  f.vec = (B % (16 / elem) == 0) && aligned;
+  const int V = f.vec ? 16 / elem : 1;
+  const int64_t P = (int64_t)A * B;
+  // rows of up to 256*V*4 elements: 256 threads, 1 or 4 vectors per lane; up to 1024*V*4: 1024 threads x 4
+  // vectors (16 waves per row hide the latency that 4 waves x 16 vectors could not: 5.0 -> 5.9 TB/s);
+  // up to 1024*V*16: 1024 threads x 16 vectors, half of them parked in LDS
+  int threads = 256, nv = 1;
+  if (P > (int64_t)256 * V * 4) { threads = 1024; nv = 4; }
+  if (P > (int64_t)1024 * V * 16) {
+    f.reason = "row does not fit one workgroup";
+    f.msg = "score_deflate: row does not fit one workgroup; use score + deflate";
+    return f;
+  }
+  while ((int64_t)threads * V * nv < P) nv *= 4;   // 256 threads: 1, 4; 1024 threads: 4, 16
+  if (threads == 1024 && nv == 16 && f.lds + (size_t)1024 * 8 * 16 + 1024 > (size_t)160 * 1024) {
+    f.reason = "loadings + the parked half row exceed the LDS";
+    f.msg = "score_deflate: loadings + the parked half row exceed the LDS; use score + deflate";
+    return f;
+  }
+  f.rc = CMTFPLS_OK;
+  f.threads = threads;
+  f.nv = nv;
+  f.kc = f.vec && ((threads * V) % B == 0);
+  f.full = f.kc && ((int64_t)threads * V * nv == P);
+  return f;
+}
+
+static RowForm deflate_contract_form(int elem, int64_t I, int A, int B, bool aligned, bool masked, int M) {
+  RowForm f = {};
+  const int64_t P = (int64_t)A * B;
+  const int Vt = 16 / elem;
+  f.op = 3;
+  f.masked = masked;
+  f.p = plan_contract(I, P, elem, kDcU);
+  if (!f.p.vec || (B % Vt) != 0 || !aligned || M > 64) {
+    f.rc = CMTFPLS_EUNSUPPORTED;
+    f.reason = M > 64 && f.p.vec && (B % Vt) == 0 && aligned ? "more than 64 responses" : "not a 16-byte vector shape";
+    f.msg = "deflate_contract_yq: shape outside the fused form; use deflate, then mode0_contract";
+    return f;
+  }
+  f.vec = true;
+  const int nseg = CMTFPLS_DC_ROWS ? rows_nseg(P, Vt, kDcRowsGrid) : 0;
+  if (nseg > 0 && I >= 2 * kDcRowsGrid) {
+    f.kind = kRowGroup;
+    f.threads = 1024;
+    f.nv = 4;
+    f.nseg = nseg;
+    f.kc = ((1024 * Vt) % B) == 0 && ((P / nseg) % B) == 0;
+    f.full = f.kc && (P / nseg) == (int64_t)1024 * Vt * 4;
+    return f;
+  }
+  f.kind = kRowTile;
+  f.pre = f.p.col_tiles >= kYqUnfuseTiles;          // wide block: u = Y q once, up front (see run_contract)
+  f.lds = f.pre ? 0 : (size_t)kYqChunk * sizeof(double);
+  return f;
+}
+
 // Y != nullptr: the YQ form (u = Y q formed in the kernel; u itself is not read)
 template <typename T, int MODE>
 static int run_contract(const T* X, int64_t I, int64_t P, const double* u, double* out, double* cnt_out,
@@ -563,22 +839,10 @@ static int run_contract(const T* X, int64_t I, int64_t P, const double* u, doubl
     return CMTFPLS_EINVAL;
   }
   if ((reinterpret_cast<uintptr_t>(X) & 15) != 0) { set_error("X must be 16-byte aligned"); return CMTFPLS_EINVAL; }
-  // column groups per thread: 4 (wider tiles, half as many partial rows per column: +2.8 % at 65536 rows) when a
-  // workgroup still gets >= 128 rows, else 2 (shards of <= 16 K rows: 94 vs 101 us at 8192 x 128 x 128,
-  // profiles/r02g_tune_small.txt); the statistics pass carries a second set of accumulators and stays at 2
-  constexpr int Vp = 16 / (int)sizeof(T);
-  const bool vecp = (P % Vp) == 0;
-  const bool full4 = vecp && (P % ((int64_t)kSweepThreads * Vp * 4)) == 0, full2 = vecp && (P % ((int64_t)kSweepThreads * Vp * 2)) == 0;
-  // very long rows (>= 16 column tiles of 4 groups, e.g. 256 x 256 f32): one workgroup per CU is best (7.2 against 6.95 TB/s
-  // at 32768 x 256 x 256, profiles/r02t_tune_full.txt)
-  const int64_t tiles4 = vecp ? (P + (int64_t)kSweepThreads * Vp * 4 - 1) / ((int64_t)kSweepThreads * Vp * 4) : 0;
-  const bool one_per_cu = tiles4 >= 16 && I * tiles4 <= (int64_t)8192 * (kContractBlocksFull / 2);   // ... while a workgroup's
-  // row block stays <= 8192 rows: at 262144 x 256 x 256, 256 workgroups fall to 6.8 TB/s and 512 hold 7.06 (profiles/r02ad_tune_cfg5.txt)
-  const int blocks4 = !full4 ? kContractBlocks : (one_per_cu ? kContractBlocksFull / 2 : kContractBlocksFull);
-  const ContractPlan p4 = plan_contract(I, P, (int)sizeof(T), 4, blocks4);
-  const bool wideU = MODE != 2 && kContractU == 4 && p4.rows_per_block >= 128;
-  const ContractPlan p = wideU ? p4 : plan_contract(I, P, (int)sizeof(T), 2, full2 ? kContractBlocksFull : kContractBlocks);
-  const bool fullt = wideU ? full4 : full2;
+  const ContractForm f = contract_form(MODE, (int)sizeof(T), I, P, yq, M);
+  const ContractPlan p = f.p;
+  const bool wideU = f.U == 4, fullt = f.full, ilv = f.ilv, yq_pre = f.yq == 2, narrow = f.kind == 0;
+  const int ncv = f.ncv, RS = f.RS;
 #define CV_LAUNCH1(YQF, UU, FF, LDS, UPTR, YP, LDY, MM, QP)                                                                          \
   do {                                                                                                                               \
     if (!YQF && ilv)                                                                                                                 \
@@ -595,36 +859,19 @@ static int run_contract(const T* X, int64_t I, int64_t P, const double* u, doubl
     else if (fullt) CV_LAUNCH1(YQF, 2, true, LDS, UPTR, YP, LDY, MM, QP);                                                            \
     else CV_LAUNCH1(YQF, 2, false, LDS, UPTR, YP, LDY, MM, QP);                                                                      \
   } while (0)
-  // Wide blocks (>= kYqUnfuseTiles column tiles): every column tile of a row block would repeat the same
-  // u = Y q prologue, so u is formed once by the rowdot kernel into the tail of the workspace instead
-  // (262144 x 256 x 256, M = 32: 2 % of the sweep)
-  const bool yq_pre = yq && p.vec && M <= 64 && MODE != 2 && p.col_tiles >= kYqUnfuseTiles;
-  // interleaved row blocks (see contract_vec_kernel) for wide rows whose u comes from memory
-#ifndef CMTFPLS_CONTRACT_ILV
-#define CMTFPLS_CONTRACT_ILV 1
-#endif
-  const bool ilv = MODE != 2 && p.vec && (CMTFPLS_CONTRACT_ILV == 2 || (CMTFPLS_CONTRACT_ILV == 1 && p.col_tiles >= kYqUnfuseTiles));
   const size_t need = (size_t)p.row_blocks * (size_t)P * sizeof(double) * (MODE == 2 ? 2 : 1) + (yq_pre ? (size_t)I * sizeof(double) : 0);
   if (!ws || ws_bytes < need) { set_error("mode0_contract/colstats: workspace too small"); return CMTFPLS_EWORKSPACE; }
   double* part = static_cast<double*>(ws);
   double* cntpart = (MODE == 2) ? part + (size_t)p.row_blocks * P : nullptr;
   const dim3 grid(p.col_tiles, p.row_blocks);
-  constexpr int Vt = 16 / (int)sizeof(T);
-  const int ncv = p.vec ? (int)(P / Vt) : 0;
-  const bool narrow = p.vec && ncv <= kSweepThreads / 2;          // at least two rows per workgroup pass
-  const int RS = narrow ? kSweepThreads / ncv : 1;
   if (yq_pre) {
     double* u_ws = part + (size_t)p.row_blocks * P;
     const int rc = cmtfpls_rowdot_f64(Y, ldy, M, I, q, u_ws, nullptr, nullptr, nullptr, 0, st);
     if (rc != CMTFPLS_OK) return rc;
     CV_LAUNCH(false, 0, u_ws, nullptr, 0, 0, nullptr);
   } else if (yq) {
-    // supported: vector shape, M <= 64 (one Y row per wavefront pass)
     const size_t lds = (size_t)kYqChunk * sizeof(double);
-    if (!p.vec || M > 64 || MODE == 2) {
-      set_error("mode0_contract_yq: shape outside the fused form; form u = Y q with rowdot and use mode0_contract");
-      return CMTFPLS_EUNSUPPORTED;
-    }
+    if (f.rc != CMTFPLS_OK) { set_error(f.msg); return f.rc; }
     if (narrow)
       hipLaunchKernelGGL((contract_narrow_kernel<T, MODE, true>), grid, dim3(kSweepThreads), lds, st, X, I, P, u, part, cntpart,
                          p.rows_per_block, Y, ldy, M, q, ncv, RS);
@@ -654,17 +901,11 @@ static int run_deflate_contract(T* X, int64_t I, int A, int B, const double* t, 
     return CMTFPLS_EINVAL;
   }
   const int64_t P = (int64_t)A * B;
-  constexpr int Vt = 16 / (int)sizeof(T);
-  const ContractPlan p = plan_contract(I, P, (int)sizeof(T), kDcU);
-  if (!p.vec || (B % Vt) != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0 || M > 64) {
-    set_error("deflate_contract_yq: shape outside the fused form; use deflate, then mode0_contract");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-#ifndef CMTFPLS_DC_ROWS
-#define CMTFPLS_DC_ROWS 1
-#endif
-  const int nseg = CMTFPLS_DC_ROWS ? rows_nseg(P, Vt, kDcRowsGrid) : 0;
-  if (nseg > 0 && I >= 2 * kDcRowsGrid) {
+  const RowForm f = deflate_contract_form((int)sizeof(T), I, A, B, (reinterpret_cast<uintptr_t>(X) & 15) == 0, masked != 0, M);
+  if (f.rc != CMTFPLS_OK) { set_error(f.msg); return f.rc; }
+  const ContractPlan p = f.p;
+  const int nseg = f.nseg;
+  if (f.kind == kRowGroup) {
     // workgroup-per-row-segment form: partial rows | ssq partials | u = Y q
     const size_t nrows_part = (size_t)(kDcRowsGrid / nseg);
     const size_t need_r = (nrows_part * (size_t)P + (size_t)kDcRowsGrid + (size_t)I) * sizeof(double);
@@ -674,9 +915,8 @@ static int run_deflate_contract(T* X, int64_t I, int A, int B, const double* t, 
     double* u_ws = sspart + kDcRowsGrid;
     const int rc = cmtfpls_rowdot_f64(Y, ldy, M, I, q, u_ws, nullptr, nullptr, nullptr, 0, st);
     if (rc != CMTFPLS_OK) return rc;
-    const bool kc = ((1024 * Vt) % B) == 0 && ((P / nseg) % B) == 0;
+    const bool kc = f.kc, full = f.full;
     const dim3 g(kDcRowsGrid), b(1024);
-    const bool full = kc && (P / nseg) == (int64_t)1024 * Vt * 4;
 #define DCR(MD, K, F) hipLaunchKernelGGL((deflate_contract_rows_kernel<T, MD, K, F>), g, b, 0, st, X, I, (unsigned)P, B, nseg, t, wA, wB, u_ws, part, sspart)
     if (masked) { if (full) DCR(1, true, true); else if (kc) DCR(1, true, false); else DCR(1, false, false); }
     else        { if (full) DCR(0, true, true); else if (kc) DCR(0, true, false); else DCR(0, false, false); }
@@ -686,7 +926,7 @@ static int run_deflate_contract(T* X, int64_t I, int A, int B, const double* t, 
     return check_launch("deflate_contract_yq");
   }
   const size_t nss = (size_t)p.col_tiles * p.row_blocks;
-  const bool pre = p.col_tiles >= kYqUnfuseTiles;          // wide block: u = Y q once, up front (see run_contract)
+  const bool pre = f.pre;
   const size_t need = ((size_t)p.row_blocks * (size_t)P + nss + (pre ? (size_t)I : 0)) * sizeof(double);
   if (!ws || ws_bytes < need) { set_error("deflate_contract_yq: workspace too small"); return CMTFPLS_EWORKSPACE; }
   double* part = static_cast<double*>(ws);
@@ -720,7 +960,6 @@ __device__ __forceinline__ void stage_loadings(double* sA, double* sB, const dou
   for (int i = threadIdx.x; i < B; i += blockDim.x) sB[i] = wB[i];
   __syncthreads();
 }
-static inline size_t loadings_lds_bytes(int A, int B) { return ((size_t)((A + 1) & ~1) + (size_t)((B + 1) & ~1)) * sizeof(double); }
 
 // sum_e x[e] * wB[k + e]   (V consecutive k: never straddles a j boundary because B % V == 0)
 template <typename T, int V, bool MASKED>
@@ -1246,21 +1485,6 @@ __global__ __launch_bounds__(kSweepThreads) void rows_narrow_kernel(
   }
 }
 
-// vectors per lane per row of the short-row form (0: the row is too long or the shape is not a vector shape)
-template <typename T>
-static int narrow_nvl(const T* X, int A, int B) {
-#ifndef CMTFPLS_ROWS_NARROW
-#define CMTFPLS_ROWS_NARROW 1
-#endif
-  constexpr int V = VecOf<T>::N;
-  if (!CMTFPLS_ROWS_NARROW || (B % V) != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0) return 0;
-  const int64_t P = (int64_t)A * B;
-  if (P <= 64 * V) return 1;
-  if (P <= 2 * 64 * V) return 2;
-  if (P <= 4 * 64 * V) return 4;
-  return 0;
-}
-
 template <typename T, bool MASKED, bool GRAM, int OP>
 static void launch_rows_narrow(int nvl, hipStream_t st, T* X, int64_t I, int A, int B, const double* wA, const double* wB,
                                const double* rowcnt, double* t, const double* Y, int ldy, int M, double* qpart, double* ssq_part) {
@@ -1273,12 +1497,7 @@ static void launch_rows_narrow(int nvl, hipStream_t st, T* X, int64_t I, int A, 
 // ------------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static bool vec_ok(const T* X, int B) {
-  return (B % VecOf<T>::N == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-}
 static bool shape_ok(int64_t I, int A, int B) { return I > 0 && A > 0 && B > 0; }
-static constexpr size_t kMaxLoadingsLds = 96 * 1024;
 
 // Y != nullptr: also writes the kSweepBlocks x M partial sums of Y^T t into qpart
 template <typename T>
@@ -1288,24 +1507,21 @@ static int run_score(const T* X, int64_t I, int A, int B, const double* wA, cons
   if (!X || !wA || !wB || !t || !shape_ok(I, A, B)) { set_error("score: bad argument"); return CMTFPLS_EINVAL; }
   const bool gram = Y != nullptr;
   if (gram && (!qpart || M <= 0 || ldy < M)) { set_error("score_gram: bad argument"); return CMTFPLS_EINVAL; }
-  if (gram && M > kWave) { set_error("score_gram: more than 64 responses; use score + gram_tn"); return CMTFPLS_EUNSUPPORTED; }
-  if (const int nvl = narrow_nvl(X, A, B)) {            // short rows: a wavefront owns several whole rows at a time
+  const RowForm f = score_form((int)sizeof(T), I, A, B, (reinterpret_cast<uintptr_t>(X) & 15) == 0, rowcnt != nullptr, gram, M, few_rows_ok);
+  if (f.rc != CMTFPLS_OK) { set_error(f.msg); return f.rc; }
+  if (f.kind == kRowNarrow) {
+    const int nvl = f.nvl;
     T* Xm = const_cast<T*>(X);                           // OP 0 does not write X
-    const bool msk = rowcnt != nullptr;
+    const bool msk = f.masked;
     if (gram) { if (msk) launch_rows_narrow<T, true, true, 0>(nvl, st, Xm, I, A, B, wA, wB, rowcnt, t, Y, ldy, M, qpart, nullptr);
                 else launch_rows_narrow<T, false, true, 0>(nvl, st, Xm, I, A, B, wA, wB, rowcnt, t, Y, ldy, M, qpart, nullptr); }
     else      { if (msk) launch_rows_narrow<T, true, false, 0>(nvl, st, Xm, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, nullptr);
                 else launch_rows_narrow<T, false, false, 0>(nvl, st, Xm, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, nullptr); }
     return check_launch("score");
   }
-  size_t lds = loadings_lds_bytes(A, B);
-  const bool gl = lds > kMaxLoadingsLds;               // loadings longer than the LDS: read them through L2
-  if (gl) lds = 0;
-  const bool v = vec_ok(X, B), m = rowcnt != nullptr;
-  // a few long rows, one 1024-thread workgroup per row: ONLY for the rows of a cross-covariance S (cmtfpls_score_s_f64), whose row
-  // count is the number of responses -- the score of a SAMPLE (cmtfpls_score_*) must not depend on how many samples are
-  // passed with it, and this kernel sums in another order than score_kernel
-  if (few_rows_ok && !gram && v && !gl && I <= 64 && (int64_t)A * B >= 8192) {
+  const size_t lds = f.lds;
+  const bool gl = f.gl, v = f.vec, m = f.masked;
+  if (f.kind == kRowFew) {
     if (m) hipLaunchKernelGGL((score_fewrows_kernel<T, true>), dim3((unsigned)I), dim3(1024), lds, st, X, A, B, wA, wB, rowcnt, t);
     else hipLaunchKernelGGL((score_fewrows_kernel<T, false>), dim3((unsigned)I), dim3(1024), lds, st, X, A, B, wA, wB, rowcnt, t);
     return check_launch("score");
@@ -1323,43 +1539,29 @@ template <typename T>
 static int run_deflate(T* X, int64_t I, int A, int B, const double* t, const double* wA, const double* wB,
                        double* ssq_part, hipStream_t st) {
   if (!X || !wA || !wB || !t || !shape_ok(I, A, B)) { set_error("deflate: bad argument"); return CMTFPLS_EINVAL; }
-  if (const int nvl = narrow_nvl(X, A, B)) {            // short rows: a wavefront owns several whole rows at a time
-    launch_rows_narrow<T, false, false, 1>(nvl, st, X, I, A, B, wA, wB, nullptr, const_cast<double*>(t), nullptr, 0, 0, nullptr, ssq_part);
+  const RowForm f = deflate_form((int)sizeof(T), A, B, (reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  if (f.kind == kRowNarrow) {
+    launch_rows_narrow<T, false, false, 1>(f.nvl, st, X, I, A, B, wA, wB, nullptr, const_cast<double*>(t), nullptr, 0, 0, nullptr, ssq_part);
     return check_launch("deflate");
   }
-  const size_t lds = loadings_lds_bytes(A, B);
+  const size_t lds = f.lds;
   const dim3 g(kSweepBlocks), b(kSweepThreads);
-  if (lds > kMaxLoadingsLds) {                         // loadings longer than the LDS: read them through L2
-    if (vec_ok(X, B)) hipLaunchKernelGGL((deflate_kernel<T, true, true>), g, b, 0, st, X, I, A, B, t, wA, wB, ssq_part);
+  if (f.gl) {
+    if (f.vec) hipLaunchKernelGGL((deflate_kernel<T, true, true>), g, b, 0, st, X, I, A, B, t, wA, wB, ssq_part);
     else hipLaunchKernelGGL((deflate_kernel<T, false, true>), g, b, 0, st, X, I, A, B, t, wA, wB, ssq_part);
     return check_launch("deflate");
   }
-#ifndef CMTFPLS_DEFLATE_ROWS
-#define CMTFPLS_DEFLATE_ROWS 1
-#endif
-  if (CMTFPLS_DEFLATE_ROWS && vec_ok(X, B)) {
-    const int64_t P = (int64_t)A * B;
-    constexpr int V = VecOf<T>::N;
-    const bool kc = ((1024 * V) % B) == 0;
-#ifndef CMTFPLS_DEFLATE_ROWS_PAD
-#define CMTFPLS_DEFLATE_ROWS_PAD 81920
-#endif
-    // (shadows the outer lds) > half of the CU's 160 KB of LDS: ONE workgroup (one row) per CU at a time --
-    // with two, the read/write streams of the rows interleave at the HBM and the sweep is 4 % slower
-    const size_t lds_w = loadings_lds_bytes(A, B);
-    const size_t lds = lds_w + ((lds_w + CMTFPLS_DEFLATE_ROWS_PAD + 1024 <= 160 * 1024) ? CMTFPLS_DEFLATE_ROWS_PAD : 0);
-    if (P > (int64_t)256 * V * 4 && P <= (int64_t)1024 * V * 4) {
-      if (kc) hipLaunchKernelGGL((deflate_rows_kernel<T, 4, 1024, true>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
+  if (f.kind == kRowGroup) {
+    if (f.nv == 4) {
+      if (f.kc) hipLaunchKernelGGL((deflate_rows_kernel<T, 4, 1024, true>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
       else hipLaunchKernelGGL((deflate_rows_kernel<T, 4, 1024, false>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
-      return check_launch("deflate");
-    }
-    if (P > (int64_t)1024 * V * 4 && P <= (int64_t)1024 * V * 16) {
-      if (kc) hipLaunchKernelGGL((deflate_rows_kernel<T, 16, 1024, true>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
+    } else {
+      if (f.kc) hipLaunchKernelGGL((deflate_rows_kernel<T, 16, 1024, true>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
       else hipLaunchKernelGGL((deflate_rows_kernel<T, 16, 1024, false>), g, dim3(1024), lds, st, X, I, A, B, t, wA, wB, ssq_part);
-      return check_launch("deflate");
     }
+    return check_launch("deflate");
   }
-  if (vec_ok(X, B)) hipLaunchKernelGGL((deflate_kernel<T, true>), g, b, lds, st, X, I, A, B, t, wA, wB, ssq_part);
+  if (f.vec) hipLaunchKernelGGL((deflate_kernel<T, true>), g, b, lds, st, X, I, A, B, t, wA, wB, ssq_part);
   else hipLaunchKernelGGL((deflate_kernel<T, false>), g, b, lds, st, X, I, A, B, t, wA, wB, ssq_part);
   return check_launch("deflate");
 }
@@ -1441,23 +1643,16 @@ template <typename T>
 static int run_center(T* X, int64_t I, int64_t P, const double* mean, double* rowcnt, double* ssq_part, hipStream_t st) {
   if (!X || !mean || I <= 0 || P <= 0) { set_error("center: bad argument"); return CMTFPLS_EINVAL; }
   const dim3 g(kSweepBlocks), b(kSweepThreads);
-  const bool v = (P % VecOf<T>::N == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-  constexpr int Vc = VecOf<T>::N;
-  // rows of more than 256 * V * 4 elements: one workgroup per row segment of <= 1024 * V * 4 elements (read burst,
-  // barrier, write burst); > half of the LDS as dynamic padding keeps it at ONE segment per CU, as for
-  // deflate_rows_kernel
-  if (v && P > (int64_t)256 * Vc * 4 && P < ((int64_t)1 << 31)) {
-    const int64_t segmax = (int64_t)1024 * Vc * 4;
-    int nseg = (int)((P + segmax - 1) / segmax);
-    while (nseg <= 64 && ((P % ((int64_t)nseg * Vc)) != 0 || (kSweepBlocks % nseg) != 0)) ++nseg;
-    if (nseg <= 64) {
-      if (nseg > 1 && rowcnt) {
-        const hipError_t e = hipMemsetAsync(rowcnt, 0, (size_t)I * sizeof(double), st);
-        if (e != hipSuccess) { set_error("center: memset failed"); return CMTFPLS_EHIP; }
-      }
-      hipLaunchKernelGGL((center_rows_kernel<T, 1024>), g, dim3(1024), 81920, st, X, I, (unsigned)P, nseg, mean, rowcnt, ssq_part);
-      return check_launch("center");
+  const RowForm f = center_form((int)sizeof(T), P, (reinterpret_cast<uintptr_t>(X) & 15) == 0, rowcnt != nullptr);
+  const bool v = f.vec;
+  if (f.kind == kRowGroup) {
+    const int nseg = f.nseg;
+    if (nseg > 1 && rowcnt) {
+      const hipError_t e = hipMemsetAsync(rowcnt, 0, (size_t)I * sizeof(double), st);
+      if (e != hipSuccess) { set_error("center: memset failed"); return CMTFPLS_EHIP; }
     }
+    hipLaunchKernelGGL((center_rows_kernel<T, 1024>), g, dim3(1024), f.lds, st, X, I, (unsigned)P, nseg, mean, rowcnt, ssq_part);
+    return check_launch("center");
   }
   if (v) hipLaunchKernelGGL((center_kernel<T, true>), g, b, 0, st, X, I, P, mean, rowcnt, ssq_part);
   else hipLaunchKernelGGL((center_kernel<T, false>), g, b, 0, st, X, I, P, mean, rowcnt, ssq_part);
@@ -1478,29 +1673,16 @@ template <typename T>
 static int run_score_deflate(T* X, int64_t I, int A, int B, const double* wA, const double* wB,
                              const double* rowcnt, double* t, double* ssq_part, hipStream_t st) {
   if (!X || !wA || !wB || !t || !shape_ok(I, A, B)) { set_error("score_deflate: bad argument"); return CMTFPLS_EINVAL; }
-  if (const int nvl = narrow_nvl(X, A, B)) {            // short rows: the rows stay in registers, no workgroup barrier
-    if (rowcnt) launch_rows_narrow<T, true, false, 2>(nvl, st, X, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, ssq_part);
-    else launch_rows_narrow<T, false, false, 2>(nvl, st, X, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, ssq_part);
+  const RowForm f = score_deflate_form((int)sizeof(T), A, B, (reinterpret_cast<uintptr_t>(X) & 15) == 0, rowcnt != nullptr);
+  if (f.kind == kRowNarrow) {
+    if (rowcnt) launch_rows_narrow<T, true, false, 2>(f.nvl, st, X, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, ssq_part);
+    else launch_rows_narrow<T, false, false, 2>(f.nvl, st, X, I, A, B, wA, wB, rowcnt, t, nullptr, 0, 0, nullptr, ssq_part);
     return check_launch("score_deflate");
   }
-  const size_t lds = loadings_lds_bytes(A, B);
-  if (lds > kMaxLoadingsLds) { set_error("score_deflate: loadings exceed LDS"); return CMTFPLS_EUNSUPPORTED; }
-  const bool v = vec_ok(X, B), m = rowcnt != nullptr;
-  const int V = v ? VecOf<T>::N : 1;
-  const int64_t P = (int64_t)A * B;
-  // rows of up to 256*V*4 elements: 256 threads, 1 or 4 vectors per lane; up to 1024*V*4: 1024 threads x 4
-  // vectors (16 waves per row hide the latency that 4 waves x 16 vectors could not: 5.0 -> 5.9 TB/s);
-  // up to 1024*V*16: 1024 threads x 16 vectors, half of them parked in LDS
-  int threads = 256, nv = 1;
-  if (P > (int64_t)256 * V * 4) { threads = 1024; nv = 4; }
-  if (P > (int64_t)1024 * V * 16) { set_error("score_deflate: row does not fit one workgroup; use score + deflate"); return CMTFPLS_EUNSUPPORTED; }
-  while ((int64_t)threads * V * nv < P) nv *= 4;   // 256 threads: 1, 4; 1024 threads: 4, 16
-  if (threads == 1024 && nv == 16 && lds + (size_t)1024 * 8 * 16 + 1024 > (size_t)160 * 1024) {
-    set_error("score_deflate: loadings + the parked half row exceed the LDS; use score + deflate");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const bool kc = v && ((threads * V) % B == 0);
-  const bool full = kc && ((int64_t)threads * V * nv == P);
+  if (f.rc != CMTFPLS_OK) { set_error(f.msg); return f.rc; }
+  const size_t lds = f.lds;
+  const bool v = f.vec, m = f.masked, kc = f.kc, full = f.full;
+  const int threads = f.threads, nv = f.nv;
   if (m && full) launch_sd<T, true, true, 2>(nv, threads, lds, st, X, I, A, B, wA, wB, rowcnt, t, ssq_part);
   else if (m && kc) launch_sd<T, true, true, 1>(nv, threads, lds, st, X, I, A, B, wA, wB, rowcnt, t, ssq_part);
   else if (m && v) launch_sd<T, true, true, 0>(nv, threads, lds, st, X, I, A, B, wA, wB, rowcnt, t, ssq_part);
@@ -1510,6 +1692,163 @@ static int run_score_deflate(T* X, int64_t I, int A, int B, const double* wA, co
   else if (v) launch_sd<T, false, true, 0>(nv, threads, lds, st, X, I, A, B, wA, wB, rowcnt, t, ssq_part);
   else launch_sd<T, false, false, 0>(nv, threads, lds, st, X, I, A, B, wA, wB, rowcnt, t, ssq_part);
   return check_launch("score_deflate");
+}
+
+// ------------------------------------------------------------------------------------------
+// names of the forms (cmtfpls_sweep_form, cmtfpls_sweep_form_list): stable strings, one per kernel instance and grid policy
+// ------------------------------------------------------------------------------------------
+static std::string unsupported_name(const char* reason) { return std::string("unsupported: ") + reason; }
+
+static std::string contract_name(const ContractForm& f) {
+  if (f.rc != CMTFPLS_OK) return unsupported_name(f.reason);
+  std::string s;
+  if (f.kind == 0) s = "narrow";
+  else if (f.kind == 2) s = "scalar";
+  else s = std::string("vec U") + (f.U == 4 ? "4" : "2") + (f.full ? " FULL" : " guarded") + (f.ilv ? " ilv" : "") + " blocks" + std::to_string(f.blocks);
+  if (f.yq == 1) s += f.chunks ? " yq chunks" : " yq";
+  if (f.yq == 2) s += " yqpre";
+  return s;
+}
+
+static std::string row_name(const RowForm& f) {
+  if (f.rc != CMTFPLS_OK) return unsupported_name(f.reason);
+  std::string s;
+  switch (f.kind) {
+    case kRowNarrow: s = "narrow nvl" + std::to_string(f.nvl) + " op" + std::to_string(f.op); break;
+    case kRowWave: s = std::string("wave ") + (f.vec ? "vec" : "scalar") + (f.gl ? " GL" : ""); break;
+    case kRowFew: s = "fewrows1024"; break;
+    case kRowTile: s = std::string("tile ") + (f.pre ? "yqpre" : "yq"); break;
+    default:
+      s = "rows" + std::to_string(f.threads) + " nv" + std::to_string(f.nv);
+      if (f.nseg > 0) s += " nseg" + std::to_string(f.nseg);
+      else s += f.full ? " KC FULL" : (f.kc ? " KC" : (f.vec ? " vec" : " scalar"));
+      if (f.nseg > 0 && f.op == 3) s += f.full ? " KC FULL" : (f.kc ? " KC" : " vec");
+      if (f.threads == 1024 && f.nv == 16 && f.op == 2) s += " parked";
+  }
+  if (f.gram) s += " gram";
+  if (f.rowcnt) s += " rowcnt";
+  if (f.masked) s += " masked";
+  return s;
+}
+
+enum SweepOp { kOpColstats = 0, kOpContract, kOpContractYq, kOpCenter, kOpScore, kOpScoreGram, kOpDeflate, kOpScoreDeflate, kOpDeflateContractYq, kOpCount };
+static const char* const kSweepOpNames[kOpCount] = {"colstats", "mode0_contract", "mode0_contract_yq", "center", "score", "score_gram",
+                                                    "deflate", "score_deflate", "deflate_contract_yq"};
+static int sweep_op(const char* op) {
+  if (op)
+    for (int i = 0; i < kOpCount; ++i)
+      if (strcmp(op, kSweepOpNames[i]) == 0) return i;
+  return -1;
+}
+
+static int write_name(const std::string& s, char* out, size_t n) {
+  if (!out || n < s.size() + 1) { set_error("sweep_form: output buffer too small"); return CMTFPLS_EINVAL; }
+  memcpy(out, s.c_str(), s.size() + 1);
+  return CMTFPLS_OK;
+}
+
+// every name `op` can return for this element size: the name functions above applied to every combination of the fields the
+// *_form functions can produce (the comments say which combinations they cannot)
+static std::set<std::string> sweep_form_names(int op, int elem) {
+  std::set<std::string> out;
+  const bool tf[2] = {false, true};
+  if (op == kOpColstats || op == kOpContract || op == kOpContractYq) {
+    const bool yq = op == kOpContractYq;
+    ContractForm f = {};
+    for (int kind = 0; kind < 3; ++kind) {
+      f.kind = kind;
+      if (kind != 1) {
+        if (yq && kind == 2) continue;                                 // scalar shapes are declined
+        f.yq = yq ? 1 : 0;
+        for (bool ch : tf) { f.chunks = ch; if (ch && !yq) continue; out.insert(contract_name(f)); }
+        continue;
+      }
+      for (int U = 2; U <= (op == kOpColstats ? 2 : 4); U += 2)       // the statistics pass stays at 2 column groups
+        for (bool full : tf)
+          for (bool ilv : tf) {
+            if (ilv && op == kOpColstats) continue;                    // it reads no u
+            f.U = U; f.full = full; f.ilv = ilv;
+            // guarded: 1024 workgroups; FULL: 512, and 256 (one per CU) only from 16 tiles of 4 groups on, where rows interleave
+            const int nb = (full && U == 4 && ilv) ? 2 : 1;
+            for (int b = 0; b < nb; ++b) {
+              f.blocks = !full ? kContractBlocks : (b ? kContractBlocksFull / 2 : kContractBlocksFull);
+              if (!yq) { f.yq = 0; f.chunks = false; out.insert(contract_name(f)); continue; }
+              f.yq = ilv ? 2 : 1;                                       // >= 16 column tiles: u is formed up front, and only then
+              f.chunks = false;
+              out.insert(contract_name(f));
+              // more than kYqChunk rows per workgroup means >= 128 rows: 4 column groups
+              if (f.yq == 1 && U == 4) { f.chunks = true; out.insert(contract_name(f)); }
+            }
+          }
+    }
+    if (yq) { out.insert(unsupported_name("scalar shape")); out.insert(unsupported_name("more than 64 responses")); }
+  } else if (op == kOpScore || op == kOpScoreGram) {
+    RowForm f = {};
+    f.gram = op == kOpScoreGram;
+    for (bool m : tf) {
+      f.masked = m;
+      f.kind = kRowNarrow;
+      for (int nvl = 1; nvl <= 4; nvl *= 2) { f.nvl = nvl; out.insert(row_name(f)); }
+      f.kind = kRowWave;
+      for (bool v : tf) for (bool gl : tf) { f.vec = v; f.gl = gl; out.insert(row_name(f)); }
+    }
+    if (f.gram) out.insert(unsupported_name("more than 64 responses"));
+  } else if (op == kOpDeflate) {
+    RowForm f = {};
+    f.op = 1;
+    f.kind = kRowNarrow;
+    for (int nvl = 1; nvl <= 4; nvl *= 2) { f.nvl = nvl; out.insert(row_name(f)); }
+    f.kind = kRowWave;
+    for (bool v : tf) for (bool gl : tf) { f.vec = v; f.gl = gl; out.insert(row_name(f)); }
+    f.kind = kRowGroup; f.threads = 1024; f.vec = true; f.gl = false;
+    for (int nv = 4; nv <= 16; nv *= 4) for (bool kc : tf) { f.nv = nv; f.kc = kc; out.insert(row_name(f)); }
+  } else if (op == kOpCenter) {
+    RowForm f = {};
+    for (bool rc : tf) {
+      f.rowcnt = rc;
+      f.kind = kRowWave; f.nseg = 0;
+      for (bool v : tf) { f.vec = v; out.insert(row_name(f)); }
+      f.kind = kRowGroup; f.threads = 1024; f.nv = 4; f.vec = true;
+      for (int nseg = 1; nseg <= 64; ++nseg) if (kSweepBlocks % nseg == 0) { f.nseg = nseg; out.insert(row_name(f)); }
+    }
+  } else if (op == kOpScoreDeflate) {
+    RowForm f = {};
+    f.op = 2;
+    for (bool m : tf) {
+      f.masked = m;
+      f.kind = kRowNarrow;
+      for (int nvl = 1; nvl <= 4; nvl *= 2) { f.nvl = nvl; out.insert(row_name(f)); }
+      f.kind = kRowGroup;
+      for (int w = 0; w < 4; ++w) {                                   // scalar, vec, KC, KC FULL
+        f.vec = w > 0; f.kc = w > 1; f.full = w > 2;
+        // 256 x 1 vector rows are short rows (narrow) unless X is misaligned, and then the walk is scalar
+        if (w == 0) { f.threads = 256; f.nv = 1; out.insert(row_name(f)); }
+        f.threads = 256; f.nv = 4; out.insert(row_name(f));
+        f.threads = 1024; f.nv = 4; out.insert(row_name(f));
+        f.threads = 1024; f.nv = 16; out.insert(row_name(f));
+      }
+    }
+    out.insert(unsupported_name("loadings exceed LDS"));
+    out.insert(unsupported_name("row does not fit one workgroup"));
+    out.insert(unsupported_name("loadings + the parked half row exceed the LDS"));
+  } else if (op == kOpDeflateContractYq) {
+    RowForm f = {};
+    f.op = 3;
+    f.vec = true;
+    for (bool m : tf) {
+      f.masked = m;
+      f.kind = kRowTile;
+      for (bool pre : tf) { f.pre = pre; out.insert(row_name(f)); }
+      f.kind = kRowGroup; f.threads = 1024; f.nv = 4;
+      for (int nseg = 1; nseg <= 64; ++nseg)
+        if (kDcRowsGrid % nseg == 0)
+          for (int w = 1; w < 4; ++w) { f.nseg = nseg; f.kc = w > 1; f.full = w > 2; out.insert(row_name(f)); }
+    }
+    out.insert(unsupported_name("not a 16-byte vector shape"));
+    out.insert(unsupported_name("more than 64 responses"));
+  }
+  (void)elem;   // the same names for both storage types; the shapes that select them differ
+  return out;
 }
 
 }  // namespace cmtfpls
@@ -1613,6 +1952,39 @@ int cmtfpls_score_deflate_f32(float* X, int64_t I, int A, int B, const double* w
 }
 int cmtfpls_score_deflate_f64(double* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* rowcnt, double* t, double* ssq_part, void* s) {
   return run_score_deflate<double>(X, I, A, B, wA, wB, rowcnt, t, ssq_part, (hipStream_t)s);
+}
+
+int cmtfpls_sweep_form(const char* op, int elem_bytes, int64_t I, int A, int B, int masked, int M, int aligned16, char* out, size_t n) {
+  const int o = sweep_op(op);
+  if (o < 0 || (elem_bytes != 4 && elem_bytes != 8) || I <= 0 || A <= 0 || B <= 0) { set_error("sweep_form: bad argument"); return CMTFPLS_EINVAL; }
+  const int64_t P = (int64_t)A * B;
+  const bool al = aligned16 != 0, msk = masked != 0;
+  switch (o) {
+    case kOpColstats:
+    case kOpContract:
+    case kOpContractYq:
+      // the contraction entries refuse a misaligned X outright
+      if (!al || (o == kOpContractYq && M <= 0)) { set_error("sweep_form: bad argument"); return CMTFPLS_EINVAL; }
+      return write_name(contract_name(contract_form(o == kOpColstats ? 2 : (msk ? 1 : 0), elem_bytes, I, P, o == kOpContractYq, M)), out, n);
+    case kOpCenter: return write_name(row_name(center_form(elem_bytes, P, al, msk)), out, n);
+    case kOpScore: return write_name(row_name(score_form(elem_bytes, I, A, B, al, msk, false, 0, false)), out, n);
+    case kOpScoreGram:
+      if (M <= 0) { set_error("sweep_form: bad argument"); return CMTFPLS_EINVAL; }
+      return write_name(row_name(score_form(elem_bytes, I, A, B, al, msk, true, M, false)), out, n);
+    case kOpDeflate: return write_name(row_name(deflate_form(elem_bytes, A, B, al)), out, n);
+    case kOpScoreDeflate: return write_name(row_name(score_deflate_form(elem_bytes, A, B, al, msk)), out, n);
+    default:
+      if (M <= 0) { set_error("sweep_form: bad argument"); return CMTFPLS_EINVAL; }
+      return write_name(row_name(deflate_contract_form(elem_bytes, I, A, B, al, msk, M)), out, n);
+  }
+}
+
+int cmtfpls_sweep_form_list(const char* op, int elem_bytes, char* out, size_t n) {
+  const int o = sweep_op(op);
+  if (o < 0 || (elem_bytes != 4 && elem_bytes != 8)) { set_error("sweep_form_list: bad argument"); return CMTFPLS_EINVAL; }
+  std::string all;
+  for (const std::string& s : sweep_form_names(o, elem_bytes)) { all += s; all += '\n'; }
+  return write_name(all, out, n);
 }
 
 }  // extern "C"

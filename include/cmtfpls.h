@@ -324,6 +324,22 @@ int cmtfpls_score_deflate_f32(float* X, int64_t I, int A, int B, const double* w
 int cmtfpls_score_deflate_f64(double* X, int64_t I, int A, int B, const double* wA, const double* wB,
                               const double* rowcnt, double* t, double* ssq_part, void* stream);
 
+/* ---- which form an X sweep takes (host arithmetic only: no GPU call, works without a device) ------
+ * Every sweep entry above picks one of many kernel instances and grid policies from the shape, the storage
+ * type and the alignment of X.  sweep_form writes the name of the form the entry `op` would take into out
+ * (n bytes, NUL-terminated), from the same host function the entry itself launches from:
+ *   op: "colstats", "mode0_contract", "mode0_contract_yq", "center", "score", "score_gram", "deflate",
+ *       "score_deflate", "deflate_contract_yq";  elem_bytes: 4 (f32) or 8 (f64);  X is I x (A * B);
+ *   masked: the entry's masked flag / rowcnt != NULL (center: rowcnt is wanted);  M: responses (yq, score_gram);
+ *   aligned16: X is 16-byte aligned.
+ * Names look like "vec U4 FULL ilv blocks256", "rows1024 nv16 KC FULL parked masked", "narrow nvl2 op2"; a
+ * shape the entry declines with CMTFPLS_EUNSUPPORTED gives "unsupported: <reason>" (status CMTFPLS_OK: the
+ * query succeeded).  CMTFPLS_EINVAL: unknown op, arguments the entry itself refuses as invalid, n too small.
+ * sweep_form_list writes every name `op` can give for that element size, one per line. */
+int cmtfpls_sweep_form(const char* op, int elem_bytes, int64_t I, int A, int B, int masked, int M,
+                       int aligned16, char* out, size_t n);
+int cmtfpls_sweep_form_list(const char* op, int elem_bytes, char* out, size_t n);
+
 /* ---- K4 / K5 / K7 / K11 small f64 algebra on tall-skinny operands ----------------------------
  * gram_tn:     C (a x b, row-major) = A^T B over I rows; A is (I x a) with leading dim lda, B is
  *              (I x b) with ldb.  Y.T @ t (tpls.py:100), T^T T and T^T u (normal equations of the
