@@ -150,6 +150,9 @@ SIGNATURES = {
     "cmtfpls_kfold_epilogue_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, _P, _P]),
     "cmtfpls_kfold_inner_coupled_workspace_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int]),
     "cmtfpls_kfold_inner_coupled_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, c_double, c_int, _P, c_size_t, _P]),
+    "cmtfpls_kfold_inner_coupled_tensor_workspace_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int, ctypes.POINTER(c_int)]),
+    "cmtfpls_kfold_inner_coupled_tensor_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, ctypes.POINTER(c_int), _P, c_int, c_int, c_double,
+                                                       c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_combine_scores_f64": (c_int, [_P, c_int, c_int64, _P, _P]),
     "cmtfpls_kfold_wide_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "cmtfpls_kfold_wide_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),

@@ -20,6 +20,12 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _int_pairs(pairs):
+    """A host int array of the flattened pairs (the `dims` of cmtfpls_kfold_inner_coupled_tensor_f64)."""
+    flat = [int(v) for p in pairs for v in p]
+    return (ctypes.c_int * len(flat))(*flat)
+
+
 class HipBackend:
     name = "hip"
 
@@ -888,6 +894,26 @@ class HipBackend:
 
     def kfold_inner_coupled_workspace_bytes(self, views) -> int:
         return int(self.lib.cmtfpls_kfold_inner_coupled_workspace_bytes(views, len(views)))
+
+    def kfold_inner_coupled_tensor(self, views, dims, a: int, tol: float, max_iter: int, ws: torch.Tensor,
+                                   model_fold: Optional[torch.Tensor] = None, groups: int = 1, Wk: Optional[torch.Tensor] = None,
+                                   Wl: Optional[torch.Tensor] = None) -> Optional[bool]:
+        """kfold_inner_coupled (model_fold: kfold_inner_coupled_grouped) for a coupled model with blocks of order 4
+        (cmtfpls_kfold_inner_coupled_tensor_f64).  dims: (B1, B2) per block, (0, 0) for a matrix block; a tensor block's view has
+        B = B1 * B2 and its extraction is the rank-1 CP inside the fold's workgroup.  Wk / Wl receive component a's mode loadings,
+        the tensor blocks' K x R x B1 (B2) slices one after another in block order; `ws` at least
+        kfold_inner_coupled_tensor_workspace_bytes(views, dims).  None when a block or the LDS is outside the device form."""
+        assert len(dims) == len(views) and (model_fold is None or (model_fold.dtype == torch.int32 and model_fold.numel() == views[0].K))
+        rc = self.lib.cmtfpls_kfold_inner_coupled_tensor_f64(views, len(views), _int_pairs(dims), _ptr(model_fold), int(groups), int(a),
+                                                             float(tol), int(max_iter), _ptr(Wk), _ptr(Wl), _ptr(ws), ws.numel(),
+                                                             self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "kfold_inner_coupled_tensor")
+        return True
+
+    def kfold_inner_coupled_tensor_workspace_bytes(self, views, dims) -> int:
+        return int(self.lib.cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(views, len(views), _int_pairs(dims)))
 
     def kfold_combine_scores(self, sc: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """out = the average of sc's nb leading slices (nb x I x K), added in block order (cmtfpls_kfold_combine_scores_f64)."""

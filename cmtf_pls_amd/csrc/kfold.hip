@@ -579,14 +579,83 @@ static size_t kf_coupled_lds_bytes(const KfCoupledDims& d, int M) {
 // per fold: Z, Zt (pmax each), G0, G1 (nmax x nmax each), then every block's Kronecker loading wk_b (A_b * B_b), one after another
 static int64_t kf_coupled_ws_per_fold(const KfCoupledDims& d) { return 2 * d.pmax + 2 * (int64_t)d.nmax * d.nmax + d.psum; }
 
+// Blocks of order 4 (cmtfpls_kfold_inner_coupled_tensor_f64): per block the trailing dims B1 x B2 = B (B2 == 0: a matrix block, order
+// 2 or 3) and where its slice of the mode loadings' outputs starts; the scratch of lx_cp3 is shared, sized over the tensor blocks.
+struct KfCoupledTensor {
+  int B1[kKfMaxBlocks], B2[kKfMaxBlocks];
+  int64_t ok[kKfMaxBlocks], ol[kKfMaxBlocks];   // block b's K x R x B1_b / K x R x B2_b slice of Wk / Wl starts here (in doubles)
+  int b1max, b2max, btmax, dmax, kmax;          // tensor blocks: largest B1, B2, B1 B2, single dim; matrix blocks: largest max(A, B)
+  int64_t ptmax, psum;                          // largest A B1 B2 of a tensor block; sum of A B over every block
+  double* Wk;                                   // nullable
+  double* Wl;                                   // nullable
+};
+
+struct KfCoupledTensorDims {
+  KfCoupledDims d;      // pmax, psum, amax, bmax over every block (B = B1 B2); nmax over the matrix blocks' min(A, B) and the short
+  KfCoupledTensor tn;   // sides of every unfolding of every tensor block; kmax over the matrix blocks alone (a tensor block has no ys)
+};
+
+static KfCoupledTensorDims kf_coupled_tensor_dims(const cmtfpls_kfold_state* v, int nb, const int* dims) {
+  KfCoupledTensorDims o{};
+  const int64_t KR = (int64_t)v[0].K * v[0].R;
+  int64_t ok = 0, ol = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int A = v[b].A, B = v[b].B, B1 = dims[2 * b], B2 = dims[2 * b + 1];
+    const int64_t P = (int64_t)A * B;
+    o.d.pmax = P > o.d.pmax ? P : o.d.pmax;
+    o.d.psum += P;
+    o.d.amax = A > o.d.amax ? A : o.d.amax;
+    o.d.bmax = B > o.d.bmax ? B : o.d.bmax;
+    o.tn.B1[b] = B1;
+    o.tn.B2[b] = B2;
+    o.tn.ok[b] = ok;
+    o.tn.ol[b] = ol;
+    int n;
+    if (B2 > 0) {
+      n = kf_tensor_nmax(A, B1, B2);
+      const int dm = A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2);
+      o.tn.b1max = B1 > o.tn.b1max ? B1 : o.tn.b1max;
+      o.tn.b2max = B2 > o.tn.b2max ? B2 : o.tn.b2max;
+      o.tn.btmax = B > o.tn.btmax ? B : o.tn.btmax;
+      o.tn.dmax = dm > o.tn.dmax ? dm : o.tn.dmax;
+      o.tn.ptmax = P > o.tn.ptmax ? P : o.tn.ptmax;
+      ok += KR * B1;
+      ol += KR * B2;
+    } else {
+      n = A < B ? A : B;
+      const int k = A < B ? B : A;
+      o.d.kmax = k > o.d.kmax ? k : o.d.kmax;
+    }
+    o.d.nmax = n > o.d.nmax ? n : o.d.nmax;
+  }
+  o.tn.kmax = o.d.kmax;
+  o.tn.psum = o.d.psum;
+  return o;
+}
+
+// LDS: kf_coupled_lds_bytes' wA (amax), wB (bmax), q, qn, tq (M each), G_y (M x M), xs (nmax), ys (kmax), then lx_cp3's wK (b1max),
+// wL (b2max), v (btmax), tmp (dmax) and part (the 1024 row-group partials).  One block of order 4: kf_inner_tensor_lds_bytes.
+static size_t kf_coupled_tensor_lds_bytes(const KfCoupledTensorDims& o, int M) {
+  return kf_coupled_lds_bytes(o.d, M) + ((size_t)o.tn.b1max + o.tn.b2max + o.tn.btmax + o.tn.dmax + kLxNT) * sizeof(double);
+}
+
+// per fold: kf_coupled_ws_per_fold's Z, Zt, G0, G1 and wk_b, then lx_cp3's U, yl, vr (ptmax each).  One block of order 4:
+// kf_inner_tensor_ws_per_fold.
+static int64_t kf_coupled_tensor_ws_per_fold(const KfCoupledTensorDims& o) { return kf_coupled_ws_per_fold(o.d) + 3 * o.tn.ptmax; }
+
 // a workgroup per fold.  With one block every step is the one of kfold_inner_kernel (lx_inner_loop) in the same order, so the
 // result is bitwise that of the tPLS kernel.  GROUPED (permutation test, see "grouped models" below): every view's mean is per
 // fold (folds x P_b) and model m reads row model_fold[m] of it; S, the loadings, Q, vec, n_iter, status and Gy are per model in
 // every layout.  Without it model k is fold k and the code is the one it always was.
-template <bool GROUPED>
+// TENSOR (a block of order 4 among them, tn.B2[b] > 0 with B_b = tn.B1[b] tn.B2[b]): that block's extraction is lx_cp3, its
+// wB = wK (x) wL, and its mode loadings go to its slice of tn.Wk / tn.Wl on every pass (the last pass's stay, as Wa / Wb);
+// everything after the extraction sees the block as I x A x B.  With one such block every step is the one of
+// kfold_inner_kernel<GROUPED, true> in the same order.  Without TENSOR the code is the one it always was.
+template <bool GROUPED, bool TENSOR = false>
 __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl, int a, double tol, int max_iter, double* ws,
                                                                     int64_t ws_per_fold, int64_t pmax, int nmax, int amax, int bmax,
-                                                                    const int* __restrict__ model_fold) {
+                                                                    const int* __restrict__ model_fold,
+                                                                    KfCoupledTensor tn = KfCoupledTensor{}) {
   extern __shared__ double sm[];
   __shared__ double red[kLxWaves];
   __shared__ double bestv[kLxWaves];
@@ -606,6 +675,17 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl,
   double* Gy = tq + M;
   double* xs = Gy + M * M;
   double* ys = xs + nmax;                                         // kmax
+  LxTensor lt;
+  if (TENSOR) {                                                   // lx_cp3's scratch, shared by the tensor blocks
+    lt.wK = ys + tn.kmax;                                         // b1max
+    lt.wL = lt.wK + tn.b1max;                                     // b2max
+    lt.v = lt.wL + tn.b2max;                                      // btmax
+    lt.tmp = lt.v + tn.btmax;                                     // dmax
+    lt.part = lt.tmp + tn.dmax;                                   // kLxNT
+    lt.U = wk0 + tn.psum;                                         // after the blocks' wk: ptmax each
+    lt.yl = lt.U + tn.ptmax;
+    lt.vr = lt.yl + tn.ptmax;
+  }
   for (int o = tid; o < M * M; o += kLxNT) {
     double s = 0.0;
     for (int t = 0; t < NT; ++t) s += bl.b[0].Gy[((int64_t)fold * NT + t) * M * M + o];
@@ -635,7 +715,13 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl,
         Z[c] = s;
       }
       __syncthreads();
-      if (A == 1) {                                                                  // order 2: Z / norm(Z)
+      if (TENSOR && tn.B2[b] > 0) {                                                  // order 4: the rank-1 CP of the A x B1 x B2 Z
+        lt.B1 = tn.B1[b];
+        lt.B2 = tn.B2[b];
+        lx_cp3(Z, Zt, A, tol, lt, wA, wB, G0, G1, xs, red, bestv, besti);
+        if (tn.Wk) for (int j = tid; j < lt.B1; j += kLxNT) tn.Wk[tn.ok[b] + ((int64_t)fold * R + a) * lt.B1 + j] = lt.wK[j];
+        if (tn.Wl) for (int j = tid; j < lt.B2; j += kLxNT) tn.Wl[tn.ol[b] + ((int64_t)fold * R + a) * lt.B2 + j] = lt.wL[j];
+      } else if (A == 1) {                                                           // order 2: Z / norm(Z)
         double s = 0.0;
         for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
         const double nz = sqrt(lx_sum(s, red));
@@ -987,6 +1073,29 @@ static int kf_inner_coupled_launch(const cmtfpls_kfold_state* blocks, int nb, co
   return check_launch(GROUPED ? "kfold_inner_coupled_grouped" : "kfold_inner_coupled");
 }
 
+// the launch of the coupled entry with blocks of order 4, after its argument checks
+template <bool GROUPED>
+static int kf_inner_coupled_tensor_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, KfCoupledTensorDims o, int a,
+                                          double tol, int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, hipStream_t s) {
+  const size_t lds = kf_coupled_tensor_lds_bytes(o, blocks[0].M);
+  const size_t need = (size_t)blocks[0].K * (size_t)kf_coupled_tensor_ws_per_fold(o) * sizeof(double);
+  if (!ws || ws_bytes < need) {
+    set_error("kfold_inner_coupled_tensor: workspace too small");
+    return CMTFPLS_EWORKSPACE;
+  }
+  KfBlocks bl;
+  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
+  bl.nb = nb;
+  o.tn.Wk = Wk;
+  o.tn.Wl = Wl;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel<GROUPED, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((kfold_inner_coupled_kernel<GROUPED, true>), dim3(blocks[0].K), dim3(kLxNT), lds, s, bl, a, tol, max_iter,
+                     static_cast<double*>(ws), kf_coupled_tensor_ws_per_fold(o), o.d.pmax, o.d.nmax, o.d.amax, o.d.bmax, model_fold, o.tn);
+  return check_launch("kfold_inner_coupled_tensor");
+}
+
 // the stage switch of the three epilogue entries, after their argument checks: stage 0 the Y-side Gram, stage 1 the row work, the
 // solve and (but for the last component) the Y deflation, stage 2 the down-date of S.  kKfGrouped: model_fold and its `groups`;
 // kKfSplits: `groups` is the folds per split; kKfPlain: model_fold null, groups 1
@@ -1192,6 +1301,55 @@ int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, i
   if (rc) return rc;
   if (a < 0 || a >= blocks[0].R || max_iter <= 0) { set_error("kfold_inner_coupled: bad argument"); return CMTFPLS_EINVAL; }
   return kf_inner_coupled_launch<false>(blocks, nb, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// dims: (B1_b, B2_b) per block, (0, 0) for a matrix block, B_b = B1_b B2_b for a tensor block
+static bool kf_coupled_tensor_dims_ok(const cmtfpls_kfold_state* blocks, int nb, const int* dims) {
+  if (!blocks || nb < 1 || nb > kKfMaxBlocks || !dims) return false;
+  for (int b = 0; b < nb; ++b) {
+    const int B1 = dims[2 * b], B2 = dims[2 * b + 1];
+    if (B1 == 0 && B2 == 0) continue;
+    if (B1 <= 0 || B2 <= 0 || (int64_t)B1 * B2 != blocks[b].B) return false;
+  }
+  return true;
+}
+
+size_t cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb, const int* dims) {
+  if (!kf_coupled_tensor_dims_ok(blocks, nb, dims) || blocks[0].K <= 0 || blocks[0].R <= 0) return 0;
+  for (int b = 0; b < nb; ++b)
+    if (blocks[b].A <= 0 || blocks[b].B <= 0 || (int64_t)blocks[b].A * blocks[b].B > (int64_t)1 << 24) return 0;
+  return (size_t)blocks[0].K * (size_t)kf_coupled_tensor_ws_per_fold(kf_coupled_tensor_dims(blocks, nb, dims)) * sizeof(double);
+}
+
+int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, int nb, const int* dims, const int* model_fold, int groups,
+                                           int a, double tol, int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes,
+                                           void* stream) {
+  if (!kf_coupled_tensor_dims_ok(blocks, nb, dims) || groups < 1 || (!model_fold && groups != 1)) {   // before any pointer is looked at
+    set_error("kfold_inner_coupled_tensor: bad argument (1 <= nb <= 8 block views; dims (B1, B2) per block with B1 * B2 == B, or "
+              "(0, 0) for a matrix block; model_fold NULL with groups == 1, or the grouped layout)");
+    return CMTFPLS_EINVAL;
+  }
+  if ((model_fold && blocks[0].K % groups != 0) || a < 0 || a >= blocks[0].R || max_iter <= 0) {
+    set_error("kfold_inner_coupled_tensor: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled_tensor: bad block views (the shared fields must be the same in every view)",
+                           model_fold ? blocks[0].K / groups : 0);
+  if (rc) return rc;
+  for (int b = 0; b < nb; ++b)
+    for (int m = 0; m < 3 && dims[2 * b + 1] > 0; ++m)
+      if (kf_tensor_short(blocks[b].A, dims[2 * b], dims[2 * b + 1], m) > kLxMaxN) {
+        set_error("kfold_inner_coupled_tensor: an unfolding of a block's A x B1 x B2 with its shorter side > 256; refit per fold");
+        return CMTFPLS_EUNSUPPORTED;
+      }
+  const KfCoupledTensorDims o = kf_coupled_tensor_dims(blocks, nb, dims);
+  if (kf_coupled_tensor_lds_bytes(o, blocks[0].M) > 150 * 1024) {
+    set_error("kfold_inner_coupled_tensor: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  if (model_fold)
+    return kf_inner_coupled_tensor_launch<true>(blocks, nb, model_fold, o, a, tol, max_iter, Wk, Wl, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_coupled_tensor_launch<false>(blocks, nb, nullptr, o, a, tol, max_iter, Wk, Wl, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream) {

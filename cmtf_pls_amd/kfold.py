@@ -17,7 +17,8 @@ the shared t, one contraction and stage 2 per block: 2R reads of each block.
 
 A tPLS whose X has order 4 (I x A x B1 x B2), with EngineOptions.tensor_folds: every step above on the I x A x B1 B2
 view with the Kronecker loading wB = wK (x) wL; only the inner loop differs (kfold_inner_tensor: the rank-1 CP of each fold's
-A x B1 x B2 cross-covariance inside its workgroup).
+A x B1 x B2 cross-covariance inside its workgroup).  A ctPLS with blocks of order 4, with EngineOptions.tensor_folds_coupled (DESIGN
+8n): the coupled steps with every order-4 block seen that way; only the inner loop differs (kfold_inner_coupled_tensor).
 
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
 
@@ -166,9 +167,15 @@ TENSOR_RANK1 = "cp3 in the fold loop"         # q2y_report_["rank1"] of an order
 TENSOR_LDS_CAP = 150 * 1024
 
 
-def _tensor_dims(Xs, coupled: bool = False) -> Optional[Tuple[int, int]]:
-    """(B1, B2) of a tPLS's order-4 X (the inner loop is then cmtfpls_kfold_inner_tensor_f64), else None."""
-    return (int(Xs[0].shape[2]), int(Xs[0].shape[3])) if not coupled and len(Xs) == 1 and Xs[0].ndim == 4 else None
+def _tensor_dims(Xs, coupled: bool = False):
+    """(B1, B2) of a tPLS's order-4 X (the inner loop is then cmtfpls_kfold_inner_tensor_f64), else None.  coupled (a ctPLS with a
+    block of order 4): a list with (B1, B2) per block, (0, 0) for a block of another order (the inner loop is then
+    cmtfpls_kfold_inner_coupled_tensor_f64), else None."""
+    if coupled:
+        if not any(X.ndim == 4 for X in Xs):
+            return None
+        return [(int(X.shape[2]), int(X.shape[3])) if X.ndim == 4 else (0, 0) for X in Xs]
+    return (int(Xs[0].shape[2]), int(Xs[0].shape[3])) if len(Xs) == 1 and Xs[0].ndim == 4 else None
 
 
 def _decline_tensor(be, A: int, B1: int, B2: int, M: int) -> Optional[str]:
@@ -186,11 +193,44 @@ def _decline_tensor(be, A: int, B1: int, B2: int, M: int) -> Optional[str]:
     return None
 
 
+def coupled_tensor_lds_bytes(dims, tensor, M: int) -> int:
+    """The LDS of a workgroup of cmtfpls_kfold_inner_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with
+    tensor = [(B1, B2), ..] ((0, 0): a matrix block), the library's kf_coupled_tensor_lds_bytes: the coupled kernel's vectors (the
+    Gram seed over every matrix block's short side and every unfolding's, the long vector over the matrix blocks alone), then the
+    CP's wK, wL, v, unscaled contraction and 1024 partials, sized over the tensor blocks."""
+    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
+    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
+    nmax = max([min(A, B) for A, B in mats] + [min(d, A * B1 * B2 // d) for A, B1, B2 in tens for d in (A, B1, B2)])
+    kmax = max([max(A, B) for A, B in mats], default=0)
+    cp = max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens) + 1024
+    return 8 * (max(A for A, _ in dims) + max(B for _, B in dims) + 3 * M + M * M + nmax + kmax + cp)
+
+
+def _decline_coupled_tensor(be, dims, tensor, M: int) -> Optional[str]:
+    """Why cmtfpls_kfold_inner_coupled_tensor_f64 does not take these blocks (its limits, checked here before a read): per tensor
+    block _decline_tensor's unfoldings, then the LDS of all blocks together."""
+    if not hasattr(be, "kfold_inner_coupled_tensor"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no order-4 coupled K-fold kernel"
+    for b, ((A, _), (B1, B2)) in enumerate(zip(dims, tensor)):
+        P = A * B1 * B2
+        for mode, d in enumerate((A, B1, B2) if B2 > 0 else ()):
+            if min(d, P // d) > MAX_SIDE:
+                return f"block {b}: mode-{mode} unfolding: min({d}, {P // d}) = {min(d, P // d)} > {MAX_SIDE}"
+    lds = coupled_tensor_lds_bytes(dims, tensor, M)
+    if lds > TENSOR_LDS_CAP:
+        return f"the blocks' vectors need {lds} bytes of LDS > {TENSOR_LDS_CAP} (cmtfpls_kfold_inner_coupled_tensor_f64)"
+    return None
+
+
 def _with_rank1(rep: dict, tensor, passes=True) -> dict:
     """The report of a run whose device passes took an order-4 X: the form names the tensor entry, and `rank1` says where the
     rank-1 CP ran."""
     if tensor is None or not passes:
         return rep
+    if isinstance(tensor, list):                                                 # a ctPLS: the coupled tensor entry
+        form = rep["form"].replace("cmtfpls_kfold_inner_coupled_grouped_f64", "cmtfpls_kfold_inner_coupled_tensor_f64") \
+                          .replace("cmtfpls_kfold_inner_coupled_f64", "cmtfpls_kfold_inner_coupled_tensor_f64")
+        return dict(rep, form=form, rank1=TENSOR_RANK1)
     form = rep["form"].replace("cmtfpls_kfold_inner_grouped_f64", "cmtfpls_kfold_inner_tensor_f64") \
                       .replace("cmtfpls_kfold_inner_f64", "cmtfpls_kfold_inner_tensor_f64")
     return dict(rep, form=form, rank1=TENSOR_RANK1)
@@ -228,7 +268,8 @@ def _groups(X, K: int, P: int) -> int:
 
 def _decline_blocks(pls, Xs, names, Y, K: int, entries, tensor_ok: bool = False) -> Optional[str]:
     """Why the device form does not take these blocks / this Y (None: it does, as far as can be told before reading them).
-    tensor_ok: the caller's passes take a tPLS's order-4 X under EngineOptions.tensor_folds (_tensor_dims)."""
+    tensor_ok: the caller's passes take a tPLS's order-4 X under EngineOptions.tensor_folds (_tensor_dims) and a
+    ctPLS's blocks of order 4 under EngineOptions.tensor_folds_coupled."""
     eng = pls._get_engine()
     be = eng.be
     if not all(hasattr(be, f) for f in entries):
@@ -238,9 +279,10 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries, tensor_ok: bool = False)
         return "sharded model (comm)"
     if len(Xs) > MAX_BLOCKS:
         return f"{len(Xs)} blocks > {MAX_BLOCKS}"
-    tensor = _tensor_dims(Xs, any(e.startswith("kfold_inner_coupled") for e in entries)) if tensor_ok and eng.opt.tensor_folds else None
+    coupled = any(e.startswith("kfold_inner_coupled") for e in entries)
+    tensor = _tensor_dims(Xs, coupled) if tensor_ok and (eng.opt.tensor_folds_coupled if coupled else eng.opt.tensor_folds) else None
     for X, name in zip(Xs, names):
-        if X.ndim not in (2, 3) and tensor is None:
+        if X.ndim not in (2, 3) and not (tensor is not None and X.ndim == 4):
             return f"{name} of order {X.ndim} (the device form takes order 2 and 3)"
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     R = pls.n_components
@@ -250,10 +292,14 @@ def _decline_blocks(pls, Xs, names, Y, K: int, entries, tensor_ok: bool = False)
         return f"M = {M} responses > {MAX_RESPONSES}"
     if R > MAX_COMPONENTS:
         return f"R = {R} components > {MAX_COMPONENTS}"
+    if coupled and tensor is not None:
+        why = _decline_coupled_tensor(be, [_dims(X) for X in Xs], tensor, M)
+        if why is not None:
+            return why
     for X, name in zip(Xs, names):
         A, B = _dims(X)
         pre = "" if name == "X" else f"{name}: "
-        if tensor is not None and M <= MAX_RESPONSES:
+        if tensor is not None and not coupled:
             why = _decline_tensor(be, A, *tensor, M)
             if why is not None:
                 return why
@@ -346,9 +392,15 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     and grouped: every view's mean is per fold); the epilogue: kfold_epilogue,
     kfold_epilogue_grouped (grouped = (model_fold, groups)), kfold_epilogue_splits (splits > 0) or kfold_epilogue_weighted
     (weighted: fold_of holds the models' row counts).  tensor = (B1, B2): a tPLS's order-4 X, st[0].B = B1 B2; the inner entry is
-    kfold_inner_tensor in the plain or the grouped layout and everything else is unchanged.  None, or why a kernel declined."""
+    kfold_inner_tensor in the plain or the grouped layout and everything else is unchanged.  coupled with tensor = [(B1, B2), ..]
+    (_tensor_dims: a ctPLS with a block of order 4): likewise kfold_inner_coupled_tensor.  None, or why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
-    if coupled:
+    if coupled and tensor is not None:
+        ws = torch.empty(max(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), 256), dtype=torch.uint8, device=be.device)
+        mf, groups = grouped if grouped else (None, 1)
+        inner, inner_name = lambda a: be.kfold_inner_coupled_tensor(st, tensor, a, tol, max_iter, ws, mf, groups), \
+            "kfold_inner_coupled_tensor_f64"
+    elif coupled:
         ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
         if grouped:
             inner, inner_name = lambda a: be.kfold_inner_coupled_grouped(st, *grouped, a, tol, max_iter, ws), "kfold_inner_coupled_grouped_f64"

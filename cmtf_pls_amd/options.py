@@ -73,6 +73,11 @@ class EngineOptions:
     # cross-covariance runs inside the fold's workgroup (cmtfpls_kfold_inner_tensor_f64) instead of one regular-engine
     # refit per model; opt-in (report: q2y_report_ with "rank1", a decline names its reason)
     tensor_folds: bool = False
+    # the same for a ctPLS on complete data with at least one block of order 4 among blocks of order 2, 3 and 4: K-fold, repeated and
+    # nested K-fold (and, together with coupled_permutations, the permutation test) run the coupled passes with the rank-1 CP of
+    # every order-4 block's cross-covariance inside the fold's workgroup (cmtfpls_kfold_inner_coupled_tensor_f64);
+    # opt-in, and separate from tensor_folds, under which a ctPLS keeps its refit routing (report: q2y_report_ with "rank1")
+    tensor_folds_coupled: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

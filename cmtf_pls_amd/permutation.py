@@ -19,7 +19,8 @@ A ctPLS on complete data with EngineOptions.coupled_permutations ("co
 block: the Y side of the pass is built once, kfold_wide_xcov once per block into that block's S (n x M x P_b) and per-fold mean
 (K x P_b), then per component kfold_inner_coupled_grouped (model m reads row model_fold[m] of every block's mean), one MTTKRP per
 block, kfold_combine_scores, kfold_epilogue_grouped stage 1 on the shared score, one contraction and stage 2 per block: 2R reads of
-each block per pass, G the smallest of the blocks' G.
+each block per pass, G the smallest of the blocks' G.  With EngineOptions.tensor_folds_coupled as well, blocks of order 4 are
+taken: the inner entry is then kfold_inner_coupled_tensor in the grouped layout.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators); with EngineOptions.masked_folds_coupled, a ctPLS
@@ -143,7 +144,7 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
             nums, n_iters, masked = got
     elif isinstance(X, list) and pls._get_engine().opt.coupled_permutations:          # EngineOptions.coupled_permutations
         G = min(_groups(b, K, NP) for b in X) if K <= MAX_FOLDS else 0                # the LDS of every block's score pass
-        why = _decline_blocks(pls, X, _names(X, True), Y, K * G if G else K, _ENTRIES_COUPLED)
+        why = _decline_blocks(pls, X, _names(X, True), Y, K * G if G else K, _ENTRIES_COUPLED, tensor_ok=True)
     elif isinstance(X, list):
         why = "coupled model: permutation device form not built"
     elif pls._get_engine().opt.masked_folds and has_missing(X):                       # EngineOptions.masked_folds
@@ -186,5 +187,5 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
            "x_reads": x_reads, "n_iter": n_iters, "observed": observed}
     if why is not None:
         rep["why"] = why
-    pls.q2y_report_ = _with_rank1(rep, _tensor_dims([X], coupled), passes)
+    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(X if coupled else [X], coupled), passes)
     return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}

@@ -673,6 +673,25 @@ int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, 
 size_t cmtfpls_kfold_inner_coupled_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb);
 int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, int a, double tol, int max_iter, void* ws, size_t ws_bytes,
                                     void* stream);
+/* kfold_inner_coupled_tensor: kfold_inner_coupled for a coupled model with blocks of order 4.  `dims` is a HOST array of 2 nb ints,
+ * (B1_b, B2_b) per block: (0, 0) for a matrix block (order 2 or 3, extracted as in kfold_inner_coupled); otherwise block b is
+ * I x A_b x B1_b x B2_b seen as I x A_b x B_b with blocks[b].B == B1_b * B2_b (CMTFPLS_EINVAL otherwise), its extraction is the
+ * rank-1 CP of cmtfpls_kfold_inner_tensor_f64 inside the fold's workgroup and its WB / Wb hold wK (x) wL (C order); B2_b = 1 is a
+ * tensor (the CP runs).  Every other kfold entry takes the views unchanged.  model_fold == NULL, groups == 1: the plain layout (also
+ * the split-major and weighted models); otherwise the grouped layout of cmtfpls_kfold_inner_coupled_grouped_f64 (every view's mean
+ * per fold).  Wk / Wl, nullable, receive the mode loadings of component a: the tensor blocks' slices lie one after another in block
+ * order, that of tensor block b being K x R x B1_b doubles in Wk and K x R x B2_b doubles in Wl (model k, component a at
+ * [(k R + a) B1_b + j] of the slice; a matrix block has no slice); all else it writes is what cmtfpls_kfold_inner_coupled_f64
+ * writes.  With one block of order 4 the result is bitwise that of cmtfpls_kfold_inner_tensor_f64.  Checked on the host before the
+ * launch: CMTFPLS_EINVAL for nb, dims, model_fold / groups (as the grouped entry) and the view checks; CMTFPLS_EUNSUPPORTED for the
+ * limits of kfold_inner_coupled, a tensor block with the shorter side of one of its three unfoldings > 256, and the blocks' vectors
+ * (max A + max B + 3 M + M^2 + n + k + max B1 + max B2 + max B1 B2 + max dim + 1024 doubles: n the largest short side over every
+ * matrix block and every unfolding, k the largest long side of a matrix block, the other maxima over the tensor blocks) beyond
+ * 150 KB of LDS.  ws >= cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(blocks, nb, dims) (0 for bad dims). */
+size_t cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb, const int* dims);
+int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, int nb, const int* dims, const int* model_fold, int groups,
+                                           int a, double tol, int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes,
+                                           void* stream);
 /* kfold_combine_scores: out[i] = (sum_b sc[b * n + i]) / nb for i < n, the blocks added in order; 1 <= nb <= 8. */
 int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream);
 
