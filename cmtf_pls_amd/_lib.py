@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CMTFPLS_LIB overrides the path (used only by tools/tune_sweeps.sh to A/B kernel variants)
@@ -134,6 +134,17 @@ SIGNATURES = {
     "cmtfpls_resid_rows_f64": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_contrib_rows_f32": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "cmtfpls_contrib_rows_f64": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "cmtfpls_holdout_mask_workspace_bytes": (c_size_t, [c_int64]),
+    "cmtfpls_holdout_mask_f32": (c_int, [_P, _P, c_int64, c_double, c_uint64, c_uint32, c_uint64, _P, _P, c_size_t, _P]),
+    "cmtfpls_holdout_mask_f64": (c_int, [_P, _P, c_int64, c_double, c_uint64, c_uint32, c_uint64, _P, _P, c_size_t, _P]),
+    "cmtfpls_heldout_resid_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "cmtfpls_heldout_resid_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, c_double, c_uint64, c_uint32, c_uint64,
+                                          _P, _P, c_size_t, _P]),
+    "cmtfpls_heldout_resid_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, c_double, c_uint64, c_uint32, c_uint64,
+                                          _P, _P, c_size_t, _P]),
+    "cmtfpls_impute_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "cmtfpls_impute_f32": (c_int, [_P, _P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_impute_f64": (c_int, [_P, _P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_tpls_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -651,6 +651,55 @@ class HipBackend:
         _lib.check(rc, "contrib_rows")
         return speA, speB, t2A, t2B
 
+    def holdout_mask(self, X: torch.Tensor, out: torch.Tensor, fraction: float, seed: int, stream: int, offset: int = 0) -> torch.Tensor:
+        """out = X with its held-out entries (the counter rule of include/cmtfpls.h: Philox stream `stream` = 2 + block index keyed by
+        `seed`, element index + `offset`) replaced by NaN; X is only read, out is another tensor of X's shape and type.  Returns
+        counts (2,) = [entries newly hidden, finite entries left].  One read, one write (cmtfpls_holdout_mask_*)."""
+        assert out.is_contiguous() and out.dtype == X.dtype and out.numel() == X.numel() and out.data_ptr() != X.data_ptr()
+        n = X.numel()
+        ws = self._workspace("holdout_mask", self.lib.cmtfpls_holdout_mask_workspace_bytes(n))
+        counts = self.empty(2)
+        _lib.check(self._fn("holdout_mask", X)(_ptr(X), _ptr(out), n, float(fraction), int(seed) & (2 ** 64 - 1), int(stream), int(offset),
+                                               _ptr(counts), _ptr(ws), ws.numel(), self._stream()), "holdout_mask")
+        return counts
+
+    def heldout_resid(self, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+                      fraction: float, seed: int, stream: int, offset: int = 0) -> Optional[torch.Tensor]:
+        """(R + 2,) = [sum (x - xhat_r)^2 for r = 1..R, sum (x - mean)^2, count] over the held-out finite entries of the ORIGINAL X2
+        (uncentred, storage type), xhat_r = mean + the first r components of T (WA (.) WB)^T; the mask is regenerated from the
+        counter.  One read (cmtfpls_heldout_resid_*); None when the shape has no device form (R > 16)."""
+        I, P = X2.shape
+        R = T.shape[1]
+        A, B = WA.shape[0], WB.shape[0]
+        assert X2.is_contiguous() and T.stride(1) == 1 and WA.is_contiguous() and WB.is_contiguous() and P == A * B
+        ws = self._workspace("heldout_resid", self.lib.cmtfpls_heldout_resid_workspace_bytes(I, P, R))
+        out = self.empty(R + 2)
+        rc = self._fn("heldout_resid", X2)(_ptr(X2), I, A, B, _ptr(T), T.stride(0), R, _ptr(WA), _ptr(WB), _ptr(mean), float(fraction),
+                                          int(seed) & (2 ** 64 - 1), int(stream), int(offset), _ptr(out), _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "heldout_resid")
+        return out
+
+    def impute(self, X2: torch.Tensor, out: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+               mean: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """out = X2 with every non-finite entry replaced by mean + T (WA (.) WB)^T there, rounded once to the storage type; finite
+        entries bit for bit.  out may be X2 itself (then only the 16-byte vectors that held a non-finite entry are stored).  Returns
+        count (1,) = entries imputed (cmtfpls_impute_*); None when the shape has no device form (R > 16)."""
+        I, P = X2.shape
+        R = T.shape[1]
+        A, B = WA.shape[0], WB.shape[0]
+        assert X2.is_contiguous() and out.is_contiguous() and out.dtype == X2.dtype and out.numel() == X2.numel()
+        assert T.stride(1) == 1 and WA.is_contiguous() and WB.is_contiguous() and P == A * B
+        ws = self._workspace("impute", self.lib.cmtfpls_impute_workspace_bytes(I, P))
+        count = self.empty(1)
+        rc = self._fn("impute", X2)(_ptr(X2), _ptr(out), I, A, B, _ptr(T), T.stride(0), R, _ptr(WA), _ptr(WB), _ptr(mean), _ptr(count),
+                                   _ptr(ws), ws.numel(), self._stream())
+        if rc == 4:
+            return None
+        _lib.check(rc, "impute")
+        return count
+
     def loo_tpls(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int,
                  max_ws_bytes: Optional[int] = None, forms=("lds", "xcov")) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
         """Leave-one-out predictions of a tPLS model (validate.py:24-33), every fold a workgroup: returns

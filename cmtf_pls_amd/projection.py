@@ -293,6 +293,141 @@ class ProjectionMixin:
                 cols[:, 1] += x2.sum(dim=0)
         return rows, cols
 
+    def _streaming_form(self, kernel: str, device: bool) -> Optional[str]:
+        """Why the streaming kernel `kernel` of the backend is NOT taken before it is tried (None: try it)."""
+        if not device:
+            return "device pass switched off"
+        if not hasattr(self.be, kernel):
+            return f"backend has no {kernel} kernel"
+        return None
+
+    def impute_rows(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, inplace=False,
+                    device: bool = True) -> List[Tuple[torch.Tensor, int]]:
+        """Per block, (the rows Xs[b] with every non-finite entry replaced by X_mean + T W_b^T there, rounded once to the storage type,
+        the number of entries replaced); finite entries keep their bits.  Xs[b]: contiguous, storage type, UNCENTRED, scores T
+        (I x R).  inplace (a bool, or one per block): Xs[b] itself is completed (a private copy of the caller's) and returned.  One read of every block through
+        cmtfpls_impute_* (in place: only the vectors that held a gap are written); where the backend declines (R > 16, no such
+        kernel, device=False) the same from torch ops on row blocks of <= 256 MB.  `last_imputation` records, per block, the form
+        that ran and why."""
+        be = self.be
+        R = state.n_components
+        out, forms = [], []
+        flags = [bool(inplace)] * len(Xs) if isinstance(inplace, bool) else [bool(f) for f in inplace]
+        with self.device_ctx():
+            for blk, X, own in zip(state.blocks, Xs, flags):
+                I = X.shape[0]
+                X2 = X.view(I, -1)
+                WA, WB = (w.contiguous() for w in self._kr_operands(blk, R))
+                dst = X2 if own else torch.empty_like(X2)
+                why = self._streaming_form("impute", device)
+                count = None
+                if why is None and I > 0:
+                    count = be.impute(X2, dst, T, WA, WB, blk.mean)
+                    if count is None:
+                        why = f"R = {R} > 16: outside cmtfpls_impute"
+                if count is None:
+                    count = self._impute_rows_torch(X2, dst, T, WA, WB, blk.mean)
+                out.append((dst.view(X.shape), int(round(float(count.item())))))
+                forms.append({"form": "torch fallback" if why else "imputation pass (cmtfpls_impute)", "why": why})
+        self.last_imputation = forms
+        return out
+
+    @staticmethod
+    def _impute_rows_torch(X2: torch.Tensor, dst: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+                           mean: Optional[torch.Tensor]) -> torch.Tensor:
+        I, P = X2.shape
+        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        count = torch.zeros(1, dtype=torch.float64, device=T.device)
+        step = max(1, (256 << 20) // max(P * 8, 1))
+        for r0 in range(0, I, step):
+            x = X2[r0:r0 + step]
+            gap = ~torch.isfinite(x)
+            xhat = T[r0:r0 + step] @ W.T
+            if mean is not None:
+                xhat = xhat + mean
+            dst[r0:r0 + step] = torch.where(gap, xhat.to(x.dtype), x)
+            count += gap.sum()
+        return count
+
+    def holdout_copies(self, Xs: List[torch.Tensor], fraction: float, seed: int, device: bool = True,
+                       offsets: Optional[List[int]] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """Per block, (a private copy of Xs[b] whose held-out entries are NaN, counts (2,) = [entries newly hidden, finite entries
+        left]).  The hold-out rule is a pure function of (seed, stream 2 + b, offsets[b] + element index) (include/cmtfpls.h;
+        imputation.holdout_mask_host restates it): one read and one write through cmtfpls_holdout_mask_*, else the same mask
+        from the host restatement."""
+        from .imputation import holdout_mask_host
+
+        be = self.be
+        out = []
+        with self.device_ctx():
+            for b, X in enumerate(Xs):
+                off = int(offsets[b]) if offsets is not None else 0
+                dst = torch.empty_like(X)
+                if device and hasattr(be, "holdout_mask") and X.numel() > 0:
+                    counts = be.holdout_mask(X, dst, fraction, seed, 2 + b, off)
+                else:
+                    held = torch.from_numpy(holdout_mask_host(off, X.numel(), seed, 2 + b, fraction)).to(X.device).view(X.shape)
+                    fin = torch.isfinite(X)
+                    dst.copy_(torch.where(held, torch.full_like(X, float("nan")), X))
+                    counts = torch.stack([(held & fin).sum(), (~held & fin).sum()]).to(torch.float64)
+                out.append((dst, counts))
+        return out
+
+    def heldout_sums(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, fraction: float, seed: int, device: bool = True,
+                     offsets: Optional[List[int]] = None) -> List[torch.Tensor]:
+        """Per block, (R + 2,) f64 = [sum (x - xhat_r)^2 for r = 1..R, sum (x - mean)^2, count] over the entries of the ORIGINAL rows
+        Xs[b] (contiguous, storage type, UNCENTRED, read only) that the hold-out rule of `holdout_copies` (same fraction, seed,
+        offsets) hides AND that are finite; xhat_r = X_mean + the first r components of T W_b^T with the scores T (I x R) of `state`.
+        One read of every block through cmtfpls_heldout_resid_*, no mask tensor; where the backend declines (R > 16, no such
+        kernel, device=False) the same sums from torch ops on row blocks of <= 256 MB with the mask of the host restatement.
+        `last_heldout` records, per block, the form that ran and why."""
+        be = self.be
+        R = state.n_components
+        out, forms = [], []
+        with self.device_ctx():
+            for b, (blk, X) in enumerate(zip(state.blocks, Xs)):
+                I = X.shape[0]
+                X2 = X.view(I, -1)
+                off = int(offsets[b]) if offsets is not None else 0
+                WA, WB = (w.contiguous() for w in self._kr_operands(blk, R))
+                why = self._streaming_form("heldout_resid", device)
+                res = None
+                if why is None and I > 0:
+                    res = be.heldout_resid(X2, T, WA, WB, blk.mean, fraction, seed, 2 + b, off)
+                    if res is None:
+                        why = f"R = {R} > 16: outside cmtfpls_heldout_resid"
+                if res is None:
+                    res = self._heldout_sums_torch(X2, T, WA, WB, blk.mean, fraction, seed, 2 + b, off)
+                out.append(res)
+                forms.append({"form": "torch fallback" if why else "held-out residual pass (cmtfpls_heldout_resid)", "why": why})
+        self.last_heldout = forms
+        return out
+
+    @staticmethod
+    def _heldout_sums_torch(X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+                            fraction: float, seed: int, stream: int, offset: int) -> torch.Tensor:
+        from .imputation import holdout_mask_host
+
+        I, P = X2.shape
+        R = T.shape[1]
+        dev = T.device
+        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        out = torch.zeros(R + 2, dtype=torch.float64, device=dev)
+        step = max(1, (256 << 20) // max(P * 8, 1))
+        for r0 in range(0, I, step):
+            x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
+            held = torch.from_numpy(holdout_mask_host(offset + r0 * P, x.numel(), seed, stream, fraction)).to(dev).view(x.shape)
+            use = held & torch.isfinite(x)
+            acc = torch.zeros_like(x) if mean is None else mean.expand_as(x).clone()
+            d = torch.where(use, x - acc, 0.0)
+            out[R] += (d * d).sum()
+            out[R + 1] += use.sum()
+            for r in range(R):
+                acc += torch.outer(T[r0:r0 + step, r], W[:, r])
+                d = torch.where(use, x - acc, 0.0)
+                out[r] += (d * d).sum()
+        return out
+
     def contribution_rows(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, H: torch.Tensor,
                           rows: Optional[torch.Tensor] = None, device: bool = True) -> List[tuple]:
         """Per block, for n samples with scores T and T^2 directions H (both n x R; H already divided by the number of blocks):

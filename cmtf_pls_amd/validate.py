@@ -228,3 +228,38 @@ def sample_contributions(pls_tensor, X=None, rows=None, cells: bool = False, dev
     from .contributions import sample_contributions as _run
 
     return _run(pls_tensor, X, rows, cells, device)
+
+
+def impute(pls_tensor, X=None, device: bool = True):
+    """X with every missing (non-finite) entry filled from the fitted tPLS or ctPLS, X_mean + T W^T there, and every observed entry
+    untouched.  X=None: the training rows (their fitted scores and ``original_X`` / ``original_Xs``; ValueError after a copy_X=False
+    fit); otherwise new rows (a ctPLS: a list of blocks, ValueError for a wrong number of them), scored as transform scores them,
+    rows with missing values included.  NumPy in: NumPy out in the input's dtype; a tensor in: a new tensor of the storage type on
+    the input's device (a device tensor stays on the device, a host tensor comes back to the host), the caller's tensor only read
+    (a ctPLS: the list of blocks).  On the GPU every block is read once and the
+    reconstruction is never materialised (cmtfpls_impute_*; a block uploaded for the call is completed in place, only its gaps
+    written); device=False, or R > 16, takes torch ops instead.  ``imputation_report_``: the form that ran, the number of imputed
+    entries per block and the reads taken (imputation.py)."""
+    from .imputation import impute as _run
+
+    return _run(pls_tensor, X, device)
+
+
+def get_q2x_heldout(pls_tensor, fraction: float = 0.1, n_repeats: int = 5, random_state=0, device: bool = True, tol: float = 1e-8,
+                    max_iter: int = 100) -> dict:
+    """Q2X by held-out entries, the X-side counterpart of the Q2Y family: repeat g hides the share `fraction` of the entries of every
+    training block (i.i.d., the counter rule of include/cmtfpls.h keyed by seeds[g] =
+    np.random.default_rng(random_state).integers(0, 2**63, n_repeats)[g], Philox stream 2 + block), refits a copy of the model
+    (its dtype, device, backend, algorithm and options; tol, max_iter; Y = ``original_Y``) in place on the masked copies, and
+    scores the refit on the hidden observed entries of the original blocks for every component count:
+    Q2X_r = 1 - sum (x - xhat_r)^2 / sum (x - X_mean)^2, xhat_r = X_mean + the first r components, X_mean the refit's.
+    Returns {"q2x": (n_repeats, n_blocks, R), "q2x_all": (n_repeats, R) with the blocks pooled by summing numerators and
+    denominators, "mean" / "std" (ddof 1, NaN for one repeat) of q2x over the repeats and "mean_all" / "std_all" of q2x_all,
+    "n_heldout": (n_repeats, n_blocks) hidden observed entries, "seeds", "report"}.  ValueError unless 0 < fraction < 1 and
+    n_repeats >= 1, after a copy_X=False fit, and for a repeat whose masking leaves some sample without an observed entry in a
+    block (the masked score divides by that count); NotImplementedError for a sharded model.  On the GPU a repeat reads the
+    original blocks twice (cmtfpls_holdout_mask_*, cmtfpls_heldout_resid_*) and no mask tensor exists; device=False, or R > 16,
+    takes torch ops with the same mask.  Which form ran is recorded on the model (``q2x_report_``; imputation.py)."""
+    from .imputation import get_q2x_heldout as _run
+
+    return _run(pls_tensor, fraction, n_repeats, random_state, device, tol, max_iter)

@@ -10,7 +10,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cmtf_pls_amd import ctPLS, tPLS                                   # noqa: E402
 from cmtf_pls_amd.synthetic import import_synthetic, make_synthetic_test   # noqa: E402
-from cmtf_pls_amd.validate import get_q2y                               # noqa: E402
+from cmtf_pls_amd.validate import get_q2x_heldout, get_q2y, impute      # noqa: E402
 
 
 def main():
@@ -37,6 +37,12 @@ def main():
     miss = np.isnan(Xm)
     rec = plsm.X_reconstructed()
     print("imputation R2 at the missing entries", round(1 - ((rec[miss] - X[miss]) ** 2).sum() / (X[miss] ** 2).sum(), 4))
+    # the completed tensor (observed entries untouched, gaps filled from the model) and the entry-wise validation of the X model:
+    # hide 10 % of the observed entries, refit, score the hidden entries -- Q2X for every component count
+    Xc = impute(plsm)
+    print("imputed", plsm.imputation_report_["imputed"], "entries; observed entries untouched:", bool(np.array_equal(Xc[~miss], Xm[~miss])))
+    q2x = get_q2x_heldout(plsm, fraction=0.1, n_repeats=3)
+    print("Q2X by held-out entries, r = 1..3:", np.round(q2x["mean"][0], 4), "+/-", np.round(q2x["std"][0], 4))
 
     # 5. coupled blocks sharing the sample mode: a tensor and a matrix
     X2, Y2, cp2 = import_synthetic((200, 10, 8), 4, 3, error=0.1, seed=1)

@@ -491,6 +491,50 @@ int cmtfpls_contrib_rows_f64(const double* X, int64_t I, const double* T, int ld
                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
                              double* t2A, double* t2B, void* stream);
 
+/* ---- imputation and entry-wise validation of the X model: validate.impute / validate.get_q2x_heldout (no reference counterpart;
+ * the model they use is factors_to_tensor(X_factors) + X_mean, util.py:18-20 with tpls.py:188-189 / cmtf.py:233-237) ------------
+ * THE HOLD-OUT RULE.  Element e of a block (C-order index) is held out iff
+ *   unit_open(philox4x32_10(counter = (offset + e) / 4, stream, key = seed).v[(offset + e) % 4]) < fraction,
+ * the generator of add_noise (Philox4x32-10, unit_open(x) = (x + 0.5) 2^-32).  stream = 2 + block index: streams 0 and 1 are the
+ * noise and the NaN mask of add_noise.  offset = global index of the block's first element, so a row shard [a, b) of a block
+ * with P columns, masked with offset = a P, is rows [a, b) of the whole block's mask.  No mask tensor exists anywhere: holdout_mask
+ * and heldout_resid regenerate it from the counter.
+ * Common to the three entries: X in its storage type (f32 / f64), everything else f64; 16-byte non-temporal vector accesses where
+ * the buffers are 16-byte aligned (and, for heldout_resid / impute, B % (16 / sizeof(T)) == 0), single elements otherwise; sums
+ * closed in a fixed order from per-workgroup partials in `ws` (no atomics: the same bits on every call); counts are doubles
+ * (exact below 2^53).
+ *
+ * holdout_mask: out[e] = NaN where e is held out, else X[e] bit for bit (n elements; X is only read; out must not overlap X:
+ *   CMTFPLS_EINVAL).
+ *   counts[0] = entries newly hidden (held out and finite in X), counts[1] = finite entries left in out.
+ *   One read, one write.  ws: cmtfpls_holdout_mask_workspace_bytes(n). */
+size_t cmtfpls_holdout_mask_workspace_bytes(int64_t n);
+int cmtfpls_holdout_mask_f32(const float* X, float* out, int64_t n, double fraction, uint64_t seed, uint32_t stream, uint64_t offset,
+                             double* counts, void* ws, size_t ws_bytes, void* hipstream);
+int cmtfpls_holdout_mask_f64(const double* X, double* out, int64_t n, double fraction, uint64_t seed, uint32_t stream, uint64_t offset,
+                             double* counts, void* ws, size_t ws_bytes, void* hipstream);
+/* heldout_resid: ONE read of the ORIGINAL X (I x A*B, uncentred).  With c = j*B + k and the prefix models
+ *   xhat_r[i,c] = mean[c] + sum_{a<r} T[i*ldt + a] WA[j*R + a] WB[k*R + a]   (mean nullable; WA, WB as in recon; accumulated in
+ *   component order, the running sum squared after each component),
+ * over the entries that are held out (the rule above, e = i*A*B + c) AND finite:
+ *   out[r-1] = sum (x - xhat_r)^2 for r = 1..R,   out[R] = sum (x - mean[c])^2,   out[R+1] = the number of such entries,
+ * so that Q2X_r = 1 - out[r-1] / out[R].  R <= 16 (CMTFPLS_EUNSUPPORTED beyond); ws: cmtfpls_heldout_resid_workspace_bytes. */
+size_t cmtfpls_heldout_resid_workspace_bytes(int64_t I, int64_t P, int R);
+int cmtfpls_heldout_resid_f32(const float* X, int64_t I, int A, int B, const double* T, int ldt, int R, const double* WA, const double* WB,
+                              const double* mean, double fraction, uint64_t seed, uint32_t stream, uint64_t offset, double* out,
+                              void* ws, size_t ws_bytes, void* hipstream);
+int cmtfpls_heldout_resid_f64(const double* X, int64_t I, int A, int B, const double* T, int ldt, int R, const double* WA, const double* WB,
+                              const double* mean, double fraction, uint64_t seed, uint32_t stream, uint64_t offset, double* out,
+                              void* ws, size_t ws_bytes, void* hipstream);
+/* impute: out[i,c] = X[i,c] bit for bit where X[i,c] is finite, else xhat_R[i,c] (above) rounded once to the storage type.
+ * out == X is allowed (on a private copy): then only the 16-byte vectors that held a non-finite entry are stored; out != X: every
+ * vector is stored.  An out that overlaps X without being X: CMTFPLS_EINVAL.  count[0] = entries imputed.  R <= 16 (CMTFPLS_EUNSUPPORTED beyond); ws: cmtfpls_impute_workspace_bytes. */
+size_t cmtfpls_impute_workspace_bytes(int64_t I, int64_t P);
+int cmtfpls_impute_f32(const float* X, float* out, int64_t I, int A, int B, const double* T, int ldt, int R, const double* WA,
+                       const double* WB, const double* mean, double* count, void* ws, size_t ws_bytes, void* hipstream);
+int cmtfpls_impute_f64(const double* X, double* out, int64_t I, int A, int B, const double* T, int ldt, int R, const double* WA,
+                       const double* WB, const double* mean, double* count, void* ws, size_t ws_bytes, void* hipstream);
+
 /* ---- leave-one-out refits, all folds in one launch: validate.get_q2y  (cmtf_pls/validate.py:7-37) ------------
  * For every fold i in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113; R components, tol, max_iter, the
  * reference's loop and convergence test) on the I - 1 samples other than i, then predict (tpls.py:122-143) of sample
