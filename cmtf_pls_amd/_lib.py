@@ -180,6 +180,9 @@ SIGNATURES = {
     "cmtfpls_press_rows_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "cmtfpls_press_rows_f64": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_loo_xcov_tensor_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cmtfpls_loo_xcov_tensor_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P,
+                                            c_size_t, _P]),
     "cmtfpls_cv_masked_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_f64": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int,
                                       c_int, _P, _P, _P, _P, _P, c_size_t, _P]),

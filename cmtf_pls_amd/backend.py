@@ -745,6 +745,38 @@ class HipBackend:
                 return Ypred, n_iter, form
         return None
 
+    def loo_tpls_tensor(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B1: int, B2: int, R: int, tol: float, max_iter: int,
+                        max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """loo_tpls for X of order 4 (I x A x B1 x B2 as I x A B1 B2): the xcov form with the rank-1 CP of each fold's A x B1 x B2
+        cross-covariance inside its workgroup (cmtfpls_loo_xcov_tensor_f64).  Returns (Ypred (I, M), n_iter (I, R)) or None when the
+        shape is outside the form.  Folds run in chunks as loo_tpls's xcov form (a centred copy of X per resident fold)."""
+        I, P = X2.shape
+        M = Y.shape[1]
+        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
+        colsum_x, _ = self.colstats(X2)
+        colsum_y, _ = self.colstats(Y)
+        Ypred = self.empty(I, M)
+        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
+        fn = self.lib.cmtfpls_loo_xcov_tensor_f64
+        # probe without a workspace: the shape check comes first (status 4 = the form declines, 2 = it only misses the workspace)
+        if fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), 0, 1, _ptr(Ypred),
+              _ptr(n_iter), None, 0, self._stream()) == 4:
+            return None
+        per = self.lib.cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R)
+        budget = max_ws_bytes
+        if budget is None:
+            budget = max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3)
+        chunk = min(max(1, min(I, int(budget // max(per, 1)))), 512)   # two workgroups' worth of folds per CU is all a launch can overlap
+        ws = self._workspace("loo", per * chunk)
+        for f0 in range(0, I, chunk):
+            nf = min(chunk, I - f0)
+            rc = fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), f0, nf,
+                    _ptr(Ypred), _ptr(n_iter), _ptr(ws), ws.numel(), self._stream())
+            if rc == 4:
+                return None
+            _lib.check(rc, "loo_xcov_tensor")
+        return Ypred, n_iter
+
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
                   max_iter: int, max_ws_bytes: Optional[int] = None
                   ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:

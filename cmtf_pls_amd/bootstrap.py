@@ -16,6 +16,10 @@ per pass only the models' loadings, coef_, status and n_iter come back.  A one-m
 K-fold kernels take at least two models).  The passes run through kfold._device_passes: a pass whose status is set refits
 its own resamples; anything outside the device form refits every resample on the regular engine.
 
+A tPLS whose X has order 4 (I x A x B1 x B2), with EngineOptions.tensor_folds: the same passes on the I x A x B1 B2 view
+with the Kronecker loading wB = wK (x) wL (kfold.py); the inner entry is cmtfpls_kfold_inner_tensor_f64 in the plain
+layout, which also leaves every model's wK and wL, so a resample's loadings are [wA, wK, wL] as the refit's are.
+
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every resample as a count-weighted workgroup of
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model.  With
 EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
@@ -29,8 +33,8 @@ import numpy as np
 import torch
 
 from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
-                    _host, _names, _state, _stats_why, _to_dev, _training_data, has_missing, masked_coupled_report, masked_models,
-                    masked_models_coupled, masked_models_report, wants_masked_coupled)
+                    _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1, has_missing,
+                    masked_coupled_report, masked_models, masked_models_coupled, masked_models_report, wants_masked_coupled)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -117,10 +121,11 @@ def refit(pls, X, Y, idx: np.ndarray, oob: np.ndarray, tol: float, max_iter: int
     return blocks, Q, coef, [int(v) for v in m.n_iter_], pred
 
 
-def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int, coupled: bool, res: list, oob_sum):
+def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int, coupled: bool, res: list, oob_sum, tensor=None):
     """The device form's run(pass, e0, g) of kfold._device_passes: resamples e0 .. e0 + g - 1 as the models of one state (a
     one-model pass as two copies of its resample).  Each resample's (blocks, Q, coef_) goes to res[e]; a pass without a status
-    adds its models' OOB predictions to oob_sum = [sums (R, I, M), counts (I,)] on the device."""
+    adds its models' OOB predictions to oob_sum = [sums (R, I, M), counts (I,)] on the device.  tensor = (B1, B2): a tPLS's
+    order-4 X (kfold._tensor_dims); its loadings are [wA, wK, wL]."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
@@ -152,7 +157,9 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
                     return _declined(why)
             built.append((A, B, S, mean))
         st, shared, own = _state(be, C, Yk, built, R, 1)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True)
+        modes_kl = (be.zeros(n, R, tensor[0]), be.zeros(n, R, tensor[1])) if tensor is not None else None
+        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True, tensor=tensor,
+                          tensor_out=modes_kl)
         if why is not None:
             return _declined(why)
         status = shared["status"][:g].cpu().numpy()
@@ -167,8 +174,13 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
             coef_h, Q_h = coef.cpu().numpy(), Q.cpu().numpy()
             Wa = [o["Wa"][:g].cpu().numpy() for o in own]
             Wb = [o["Wb"][:g].cpu().numpy() for o in own]
+            if tensor is not None:
+                Wk, Wl = (w[:g].cpu().numpy() for w in modes_kl)
             for j in range(g):
-                modes = [([wb[j].T] if X.ndim == 2 else [wa[j].T, wb[j].T]) for X, wa, wb in zip(Xs, Wa, Wb)]
+                if tensor is not None:                                                # wB = wK (x) wL: the modes themselves
+                    modes = [[Wa[0][j].T, Wk[j].T, Wl[j].T]]
+                else:
+                    modes = [([wb[j].T] if X.ndim == 2 else [wa[j].T, wb[j].T]) for X, wa, wb in zip(Xs, Wa, Wb)]
                 res[e0 + j] = (modes, Q_h[j].T, coef_h[j])
         return np.zeros((g, R)), [n_iter[j].tolist() for j in range(g)], status
 
@@ -219,7 +231,9 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
             why = f"the masked form ({COUPLED_FORM}) declined: {mwhy}"
     else:
         G = min(_groups(X, 1, min(NB, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for X in Xs)   # the LDS of every block's score pass
-        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES)
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES,
+                              tensor_ok=not coupled)
+    tensor = _tensor_dims(Xs) if not coupled and why is None and masked is None and pls._get_engine().opt.tensor_folds else None
     res = [None] * NB
     dev = pls._get_engine().be.device if why is None and masked is None else torch.device("cpu")
     oob_sum = [torch.zeros(R, I, M, dtype=torch.float64, device=dev), torch.zeros(I, dtype=torch.float64, device=dev)]
@@ -249,7 +263,8 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
             oob_sum[1] += torch.from_numpy((counts[e] == 0).astype(np.float64))
     else:
         _, n_iters, passes, why = _device_passes(pls, NB, G, "resamples", why,
-                                                 lambda: _device_resamples(pls, Xs, Y, counts, tol, max_iter, coupled, res, oob_sum),
+                                                 lambda: _device_resamples(pls, Xs, Y, counts, tol, max_iter, coupled, res, oob_sum,
+                                                                           tensor),
                                                  refit_one)
     aligned = [align_factors(ref, *r) for r in res]
     nmodes = [len(b) for b in ref]
@@ -285,6 +300,6 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
                "x_reads": x_reads, "n_iter": n_iters}
         if why is not None:
             rep["why"] = why
-        pls.bootstrap_report_ = rep
+        pls.bootstrap_report_ = _with_rank1(rep, tensor, passes)
     return {"resamples": idx, **stacks, "se": {k: v[0] for k, v in spread.items()}, "ci": {k: v[1] for k, v in spread.items()},
             "oob_q2y": oob_q2y, "oob_rows": int(rows.sum())}

@@ -20,6 +20,14 @@
 // Arithmetic: float64 throughout, the reference's operation order outside the re-association above.
 // Limits: X of order 2 or 3 without missing values, min(A, B) <= 256, M <= 128, R <= 64, the workgroup's small vectors in
 // 150 KB of LDS; per resident fold a workspace of I P + M P + 3 P + 2 n^2 + I (M + R + 2) + R (A + B) doubles (cmtfpls_loo_xcov_fold_workspace_bytes).
+//
+// X of order 4 (I x A x B1 x B2, cmtfpls_loo_xcov_tensor_f64): the same kernel as its TENSOR instantiation.  The fold sees X as
+// I x A x B with B = B1 B2; only the extraction differs: the rank-1 CP of the A x B1 x B2 cross-covariance (lx_cp3, fold_loop.hpp)
+// in place of the leading singular pair, which leaves wB = wK (x) wL (C order).  The score, the deflation and the held-out
+// prediction see X through wk = wA (x) wB and Wa[c / B] Wb[c % B] alone, so they are the order-3 code unchanged.  n is then the
+// largest short side of the three unfoldings of A x B1 x B2 (each <= 256).  LDS: xs (n), then in place of ys (k) lx_cp3's wK (B1),
+// wL (B2), v (B), tmp (max(A, B1, B2)) and part (1024); workspace: lx_cp3's U, yl, vr (P each) after wk
+// (cmtfpls_loo_xcov_tensor_fold_workspace_bytes).
 #include "fold_loop.hpp"
 
 namespace cmtfpls {
@@ -37,7 +45,19 @@ struct LooXArgs {
   double tol;
 };
 
-__global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
+// the trailing dims of an order-4 X and the largest short side of the three unfoldings of A x B1 x B2 (B == B1 * B2)
+struct LooXTensorArgs : LooXArgs {
+  int B1, B2, nmax;
+};
+
+template <bool TENSOR>
+struct LooXArgsOf { typedef LooXArgs type; };
+template <>
+struct LooXArgsOf<true> { typedef LooXTensorArgs type; };
+
+// TENSOR = false: X of order 2 or 3, the code this kernel always was.  TENSOR = true: see the head of the file.
+template <bool TENSOR>
+__global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(typename LooXArgsOf<TENSOR>::type a) {
   extern __shared__ double sm[];
   __shared__ double red[kLxWaves];
   __shared__ double bestv[kLxWaves];
@@ -46,7 +66,11 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int I = a.I, A = a.A, B = a.B, M = a.M, R = a.R;
   const int64_t P = (int64_t)A * B;
-  const int n = A < B ? A : B, k = A < B ? B : A;
+  int n = A < B ? A : B, k = A < B ? B : A;
+  if constexpr (TENSOR) {                                    // xs, G0, G1: the largest short side of the unfoldings; ys: lx_cp3's vectors
+    n = a.nmax;
+    k = a.B1 + a.B2 + B + max(A, max(a.B1, a.B2)) + kLxNT;
+  }
   if ((int)blockIdx.x >= a.nfolds) return;
   const int fold = a.fold0 + blockIdx.x;
   if (fold >= I) return;
@@ -58,7 +82,7 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
   double* Z = S + (int64_t)M * P;                            // P
   double* Zt = Z + P;                                        // P       (transpose scratch of the rank-1 extraction)
   double* wk = Zt + P;                                       // P       kron(wA, wB) of the current loadings
-  double* G0 = wk + P;                                       // n x n
+  double* G0 = wk + (TENSOR ? 4 : 1) * P;                    // n x n   (TENSOR: after lx_cp3's U, yl, vr)
   double* G1 = G0 + (int64_t)n * n;
   double* u = G1 + (int64_t)n * n;                           // I
   double* t = u + I;                                         // I
@@ -73,7 +97,7 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
   double* my = tq + M;
   double* Gy = my + M;            // M x M   Y_f^T Y_f of the current component
   double* xs = Gy + M * M;        // n
-  double* ys = xs + n;            // k
+  double* ys = xs + n;            // k       (TENSOR: lx_cp3's wK, wL, v, tmp, part instead)
   double* coef = ys + k;          // R x R
   double* Qs = coef + R * R;      // R x M
   double* Gn = Qs + R * M;        // (a+1) x (a+1) normal equations
@@ -139,7 +163,23 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(LooXArgs a) {
       for (int r = 0; r < I; ++r) s = fma(Yf[(int64_t)r * M + m1], Yf[(int64_t)r * M + m2], s);
       Gy[o] = s;
     }
-    const int it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+    int it;
+    if constexpr (TENSOR) {
+      LxTensor lt;
+      lt.B1 = a.B1;
+      lt.B2 = a.B2;
+      lt.wK = ys;
+      lt.wL = lt.wK + a.B1;
+      lt.v = lt.wL + a.B2;
+      lt.tmp = lt.v + B;
+      lt.part = lt.tmp + max(A, max(a.B1, a.B2));
+      lt.U = wk + P;
+      lt.yl = lt.U + P;
+      lt.vr = lt.yl + P;
+      it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti, lt);
+    } else {
+      it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+    }
     if (a.n_iter && tid == 0) a.n_iter[(int64_t)fold * R + comp] = it;
     // ---- the component's score and Y score with the converged loadings (tpls.py:97-102) ----
     for (int r = wv; r < I; r += kLxWaves) {                                             // (wk holds the converged loadings' Kronecker product)
@@ -255,6 +295,25 @@ static size_t lx_lds_bytes(int A, int B, int M, int R) {
   return dbl * sizeof(double);
 }
 
+static int lx_tensor_short(int A, int B1, int B2, int mode) {
+  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
+  return (int)(d < rest ? d : rest);
+}
+
+static int lx_tensor_nmax(int A, int B1, int B2) {
+  int n = 0;
+  for (int m = 0; m < 3; ++m) n = lx_tensor_short(A, B1, B2, m) > n ? lx_tensor_short(A, B1, B2, m) : n;
+  return n;
+}
+
+// lx_lds_bytes with xs (nmax) and, in place of ys, lx_cp3's wK (B1), wL (B2), v (B1 B2), tmp (max dim) and part (kLxNT)
+static size_t lx_tensor_lds_bytes(int A, int B1, int B2, int M, int R) {
+  const size_t B = (size_t)B1 * B2, dmax = (size_t)(A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2));
+  const size_t dbl = (size_t)A + B + 4 * (size_t)M + (size_t)M * M + lx_tensor_nmax(A, B1, B2) + B1 + B2 + B + dmax + kLxNT +
+                     (size_t)R * R + (size_t)R * M + (size_t)R * R + 3 * (size_t)R;
+  return dbl * sizeof(double);
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -288,9 +347,54 @@ int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_
   a.ws_per_fold = (int64_t)(per / sizeof(double));
   a.I = I; a.A = A; a.B = B; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds; a.tol = tol;
   if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(loo_xcov_kernel, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(loo_xcov_kernel<false>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
   return check_launch("loo_xcov");
+}
+
+size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
+  if (I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0) return 0;
+  const size_t B = (size_t)B1 * B2, P = (size_t)A * B, n = (size_t)lx_tensor_nmax(A, B1, B2);
+  return ((size_t)I * P + (size_t)I * M + (size_t)I * R + (size_t)M * P + 6 * P + 2 * n * n + 2 * (size_t)I + (size_t)R * ((size_t)A + B)) * sizeof(double);
+}
+
+int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B1,
+                                int B2, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter,
+                                void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !Y || !colsum_x || !colsum_y || !Ypred || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0 || max_iter <= 0 ||
+      fold0 < 0 || nfolds <= 0 || fold0 + nfolds > I) {
+    set_error("loo_xcov_tensor: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if ((int64_t)A * B1 * B2 > (int64_t)1 << 24) {
+    set_error("loo_xcov_tensor: A * B1 * B2 > 2^24; refit per fold on the regular engine");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  for (int m = 0; m < 3; ++m)
+    if (lx_tensor_short(A, B1, B2, m) > kLxMaxN) {
+      set_error("loo_xcov_tensor: an unfolding of A x B1 x B2 with its shorter side > 256; refit per fold on the regular engine");
+      return CMTFPLS_EUNSUPPORTED;
+    }
+  if (M > kLxMaxM || R > kLxMaxR) {
+    set_error("loo_xcov_tensor: shape outside the workgroup-per-fold form (M <= 128, R <= 64); refit per fold on the regular engine");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t lds = lx_tensor_lds_bytes(A, B1, B2, M, R);
+  if (lds > 150 * 1024) {
+    set_error("loo_xcov_tensor: the fold's vectors exceed 150 KB of LDS; refit per fold on the regular engine");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  const size_t per = cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R);
+  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("loo_xcov_tensor: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  LooXTensorArgs a;
+  a.X = X; a.Y = Y; a.colsum_x = colsum_x; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
+  a.ws_per_fold = (int64_t)(per / sizeof(double));
+  a.I = I; a.A = A; a.B = B1 * B2; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds; a.tol = tol;
+  a.B1 = B1; a.B2 = B2; a.nmax = lx_tensor_nmax(A, B1, B2);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(loo_xcov_kernel<true>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
+  return check_launch("loo_xcov_tensor");
 }
 
 }  // extern "C"

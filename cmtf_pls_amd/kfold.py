@@ -17,7 +17,8 @@ the shared t, one contraction and stage 2 per block: 2R reads of each block.
 
 A tPLS whose X has order 4 (I x A x B1 x B2), with EngineOptions.tensor_folds: every step above on the I x A x B1 B2
 view with the Kronecker loading wB = wK (x) wL; only the inner loop differs (kfold_inner_tensor: the rank-1 CP of each fold's
-A x B1 x B2 cross-covariance inside its workgroup).  A ctPLS with blocks of order 4, with EngineOptions.tensor_folds_coupled (DESIGN
+A x B1 x B2 cross-covariance inside its workgroup).  The bootstrap's weighted models take the same entry and carry wK / wL out of it
+(bootstrap.py).  A ctPLS with blocks of order 4, with EngineOptions.tensor_folds_coupled (DESIGN
 8n): the coupled steps with every order-4 block seen that way; only the inner loop differs (kfold_inner_coupled_tensor).
 
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
@@ -385,7 +386,7 @@ def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: i
 
 
 def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0,
-                weighted: bool = False, tensor=None):
+                weighted: bool = False, tensor=None, tensor_out=None):
     """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
     ctPLS, one block included: then the blocks' scores averaged), stage 1 and, but for the last, one contraction and stage 2 per
     block.  The inner entry: kfold_inner, kfold_inner_coupled (coupled), kfold_inner_grouped or kfold_inner_coupled_grouped (coupled
@@ -393,7 +394,9 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     kfold_epilogue_grouped (grouped = (model_fold, groups)), kfold_epilogue_splits (splits > 0) or kfold_epilogue_weighted
     (weighted: fold_of holds the models' row counts).  tensor = (B1, B2): a tPLS's order-4 X, st[0].B = B1 B2; the inner entry is
     kfold_inner_tensor in the plain or the grouped layout and everything else is unchanged.  coupled with tensor = [(B1, B2), ..]
-    (_tensor_dims: a ctPLS with a block of order 4): likewise kfold_inner_coupled_tensor.  None, or why a kernel declined."""
+    (_tensor_dims: a ctPLS with a block of order 4): likewise kfold_inner_coupled_tensor.  tensor_out = (Wk (n x R x B1), Wl
+    (n x R x B2)): where kfold_inner_tensor leaves the models' mode loadings (the bootstrap's per-mode stacks).  None, or why a kernel
+    declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled and tensor is not None:
         ws = torch.empty(max(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), 256), dtype=torch.uint8, device=be.device)
@@ -409,7 +412,8 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     elif tensor is not None:
         ws = torch.empty(max(be.kfold_inner_tensor_workspace_bytes(st[0].A, *tensor, n), 256), dtype=torch.uint8, device=be.device)
         mf, groups = grouped if grouped else (None, 1)
-        inner, inner_name = lambda a: be.kfold_inner_tensor(st[0], *tensor, a, tol, max_iter, ws, mf, groups), "kfold_inner_tensor_f64"
+        Wk, Wl = tensor_out if tensor_out else (None, None)
+        inner, inner_name = lambda a: be.kfold_inner_tensor(st[0], *tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), "kfold_inner_tensor_f64"
     else:
         ws = torch.empty(max(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), 256), dtype=torch.uint8, device=be.device)
         if grouped:

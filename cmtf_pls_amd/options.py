@@ -71,7 +71,10 @@ class EngineOptions:
     # cross-validation of a tPLS whose X has order 4 (I x A x B1 x B2) on the device: K-fold, the permutation test, repeated and
     # nested K-fold take it as I x A x B1 B2 with the Kronecker loading wK (x) wL, and the rank-1 CP of each fold's A x B1 x B2
     # cross-covariance runs inside the fold's workgroup (cmtfpls_kfold_inner_tensor_f64) instead of one regular-engine
-    # refit per model; opt-in (report: q2y_report_ with "rank1", a decline names its reason)
+    # refit per model; leave-one-out (get_q2y, loo_predictions) takes cmtfpls_loo_xcov_tensor_f64, a workgroup per fold with the
+    # same CP inside, and bootstrap_factors runs its resamples through the weighted passes with the tensor inner entry, every
+    # model's wK and wL coming back for the per-mode stacks; opt-in (report: q2y_report_ / bootstrap_report_ with
+    # "rank1", a decline names its reason)
     tensor_folds: bool = False
     # the same for a ctPLS on complete data with at least one block of order 4 among blocks of order 2, 3 and 4: K-fold, repeated and
     # nested K-fold (and, together with coupled_permutations, the permutation test) run the coupled passes with the rank-1 CP of

@@ -6,15 +6,49 @@ keeps them.  One refit per held-out sample (validate.py:27-33).  On the GPU the 
 fold doing the whole fit for it with the fold's means down-dated from shared column sums: ``cmtfpls_loo_tpls_f64`` when the
 fold's vectors fit the LDS (min(J, K) <= 64), ``cmtfpls_loo_xcov_f64`` beyond (min(J, K) <= 256: the fold's NIPALS loop on its
 cross-covariance, Gram squarings on the matrix cores) -- X of order 2 or 3 without missing values, M <= 64 / R <= 16 (LDS form), M <= 128 / R <= 64 (xcov form).  Anything else
-refits once per fold on the regular engine with the fitted model's storage type, algorithm and backend.  X with missing values
+refits once per fold on the regular engine with the fitted model's storage type, algorithm and backend.  X of order 4 without
+missing values takes ``cmtfpls_loo_xcov_tensor_f64`` when ``EngineOptions.tensor_folds`` is on (the xcov form with the rank-1 CP of
+each fold's cross-covariance inside its workgroup).  X with missing values
 (order 2 or 3, Y complete) takes ``cmtfpls_cv_masked_f64`` when ``EngineOptions.masked_folds`` is on (a workgroup per fold with
 the reference's masked arithmetic, kfold.masked_predictions; K-fold too).  Which form ran is recorded on the model
 (``q2y_report_``).
 """
 import numpy as np
 
-from .kfold import MASKED_FORM, has_missing, masked_predictions
+from .kfold import MASKED_FORM, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, has_missing, masked_predictions
 from .tpls import tPLS
+
+LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
+LOO_MAX_RESPONSES, LOO_MAX_COMPONENTS, LOO_MAX_CELLS = 128, 64, 1 << 24
+
+
+def loo_tensor_lds_bytes(A: int, B1: int, B2: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_loo_xcov_tensor_f64 (the library's lx_tensor_lds_bytes): wA, wB, q, qn, tq, my, G_y, the Gram
+    seed over the unfoldings' short sides, the CP's wK, wL, v, unscaled contraction and 1024 partials, then coef (R x R), Q (R x M)
+    and the normal equations (R x R + 3 R)."""
+    P = A * B1 * B2
+    nmax = max(min(d, P // d) for d in (A, B1, B2))
+    return 8 * (A + 2 * B1 * B2 + 4 * M + M * M + nmax + B1 + B2 + max(A, B1, B2) + 1024 + 2 * R * R + R * M + 3 * R)
+
+
+def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
+    """Why cmtfpls_loo_xcov_tensor_f64 does not take an I x A x B1 x B2 X (its limits, checked here before X is uploaded)."""
+    if not hasattr(be, "loo_tpls_tensor"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no order-4 leave-one-out kernel"
+    P = A * B1 * B2
+    for mode, d in enumerate((A, B1, B2)):
+        if min(d, P // d) > MAX_SIDE:
+            return f"mode-{mode} unfolding: min({d}, {P // d}) = {min(d, P // d)} > {MAX_SIDE}"
+    if M > LOO_MAX_RESPONSES:
+        return f"M = {M} > {LOO_MAX_RESPONSES} responses (cmtfpls_loo_xcov_tensor_f64)"
+    if R > LOO_MAX_COMPONENTS:
+        return f"R = {R} > {LOO_MAX_COMPONENTS} components (cmtfpls_loo_xcov_tensor_f64)"
+    if P > LOO_MAX_CELLS:
+        return f"A B1 B2 = {P} > {LOO_MAX_CELLS} (cmtfpls_loo_xcov_tensor_f64)"
+    lds = loo_tensor_lds_bytes(A, B1, B2, M, R)
+    if lds > TENSOR_LDS_CAP:
+        return f"the fold's vectors need {lds} bytes of LDS > {TENSOR_LDS_CAP} (cmtfpls_loo_xcov_tensor_f64)"
+    return None
 
 
 def loo_predictions(pls_tensor, tol: float = 1e-8, max_iter: int = 100):
@@ -39,6 +73,8 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         pls_tensor.q2y_report_ = rep
         return pred[-1].reshape(Y.shape), None
     be = eng.be
+    if X.ndim == 4 and eng.opt.tensor_folds:                               # EngineOptions.tensor_folds: cmtfpls_loo_xcov_tensor_f64
+        return _loo_device_tensor(pls_tensor, be, X, Y, tol, max_iter)
     if not hasattr(be, "loo_tpls") or X.ndim not in (2, 3):
         return None, None
     Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
@@ -56,6 +92,31 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         pls_tensor.q2y_report_ = {"form": {"lds": "all folds in one launch, a workgroup per fold, vectors in LDS (cmtfpls_loo_tpls_f64)",
                                            "xcov": "a workgroup per fold on the fold's cross-covariance (cmtfpls_loo_xcov_f64)"}[out[2]],
                                   "folds": int(I), "n_iter_total": int(out[1].sum().item())}
+        return out[0].cpu().numpy().reshape(Yh.shape), None
+
+
+def _loo_device_tensor(pls_tensor, be, X, Y, tol: float, max_iter: int):
+    """_loo_device for X of order 4 under EngineOptions.tensor_folds: (Y_pred, None), or (None, why) with the limit that declined;
+    why is None with missing values (get_q2y then names the limits as it always did)."""
+    import torch
+
+    Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+    Yh = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+    if np.isnan(Xh).any() or np.isnan(Yh).any():
+        return None, None
+    I, A, B1, B2 = (int(d) for d in Xh.shape)
+    R = pls_tensor.n_components
+    why = _decline_loo_tensor(be, A, B1, B2, int(Yh.reshape(I, -1).shape[1]), R)
+    if why is not None:
+        return None, why
+    with torch.cuda.device(be.device):
+        Xd = torch.from_numpy(np.ascontiguousarray(Xh.reshape(I, -1), dtype=np.float64)).to(be.device)
+        Yd = torch.from_numpy(np.ascontiguousarray(Yh.reshape(I, -1), dtype=np.float64)).to(be.device)
+        out = be.loo_tpls_tensor(Xd, Yd, A, B1, B2, R, tol, max_iter)
+        if out is None:
+            return None, "cmtfpls_loo_xcov_tensor_f64 declined the shape"
+        pls_tensor.q2y_report_ = {"form": LOO_TENSOR_FORM, "rank1": TENSOR_RANK1, "folds": int(I),
+                                  "n_iter_total": int(out[1].sum().item())}
         return out[0].cpu().numpy().reshape(Yh.shape), None
 
 
@@ -185,7 +246,8 @@ def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random
     predictions) over "oob_rows" rows, those left out at least once}.  On the GPU up to 32 resamples per pass share every read of X
     (2R reads per pass and block, bootstrap.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
     cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every resample is a count-weighted workgroup with the
-    reference's masked arithmetic.  Anything else refits every resample.  Which form ran is recorded on the model
+    reference's masked arithmetic.  A tPLS whose X has order 4 takes the same passes with cmtfpls_kfold_inner_tensor_f64
+    when EngineOptions.tensor_folds is on.  Anything else refits every resample.  Which form ran is recorded on the model
     (``bootstrap_report_``)."""
     from .bootstrap import bootstrap
 

@@ -558,6 +558,22 @@ size_t cmtfpls_loo_xcov_fold_workspace_bytes(int I, int A, int B, int M, int R);
 int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
                          int B, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
                          int* n_iter, void* ws, size_t ws_bytes, void* stream);
+/* loo_xcov_tensor: cmtfpls_loo_xcov_f64 for X of order 4 (I x A x B1 x B2), seen as I x A x B with B = B1 * B2: the same kernel, one
+ * 1024-thread workgroup per fold, whose extraction is the reference's parafac(Z, 1, tol, init="svd", normalize_factors=True) on the
+ * fold's A x B1 x B2 cross-covariance inside the workgroup (the rank-1 CP of cmtfpls_kfold_inner_tensor_f64) and whose loading of the
+ * trailing modes is wK (x) wL (C order); score, deflation and held-out prediction are those of cmtfpls_loo_xcov_f64.  B2 = 1 (or
+ * B1 = 1) is still a tensor: the CP runs, as on the regular engine.  Same arguments and results otherwise.  Checked on the host
+ * before the launch: CMTFPLS_EINVAL for a bad pointer or size (any of A, B1, B2 <= 0); CMTFPLS_EUNSUPPORTED when the shorter side of
+ * one of the three unfoldings of A x B1 x B2 exceeds 256, M > 128, R > 64, A * B1 * B2 > 2^24 or the workgroup's vectors exceed 150 KB
+ * of LDS: (A + 2 B + 4 M + M^2 + n + B1 + B2 + max(A, B1, B2) + 1024 + 2 R^2 + R M + 3 R) doubles, n the largest of those shorter
+ * sides (wA, wB, q, qn, tq, my, G_y, the Gram seed, then the CP's wK, wL, v, unscaled contraction and 1024 row-group partials, then
+ * coef, Q, the normal equations); CMTFPLS_EWORKSPACE below nfolds * cmtfpls_loo_xcov_tensor_fold_workspace_bytes(...): per fold
+ * (I P + I M + I R + M P + 6 P + 2 n^2 + 2 I + R (A + B)) doubles, P = A B (cmtfpls_loo_xcov_f64's with the CP's three length-P
+ * scratch vectors). */
+size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R);
+int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
+                                int B1, int B2, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
+                                int* n_iter, void* ws, size_t ws_bytes, void* stream);
 /* ---- cross-validation refits of a tPLS whose X has missing values, all folds in one launch: validate.get_q2y / kfold_predictions
  * with EngineOptions.masked_folds (cmtf_pls/validate.py:7-37; tpls.py:61-63 X_hasMiss; missingvals.py:7-38) -------------------
  * For every fold f in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113) on the rows r with fold_of[r] != f, with the
