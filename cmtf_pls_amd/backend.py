@@ -651,6 +651,23 @@ class HipBackend:
         _lib.check(rc, "contrib_rows")
         return speA, speB, t2A, t2B
 
+    def selectivity_cols(self, X2: torch.Tensor, Tau: torch.Tensor, mean: Optional[torch.Tensor], masked: bool):
+        """The target-projection sums of every column in one read of X2 (uncentred, storage type): (a (M, P), d (M, P) or None, s (P,),
+        n (P,)) with x = X2 - mean, o = isfinite(x) when masked (else 1): a = sum_i o x tau, d = sum_i o tau^2 (masked only; complete:
+        the caller's sum_i tau^2), s = sum_i o x^2, n = sum_i o (cmtfpls_selectivity_cols_*).  Any number of responses: passes of 64
+        (masked: 32) inside the entry."""
+        I, P = X2.shape
+        M = Tau.shape[1]
+        assert X2.is_contiguous() and Tau.stride(1) == 1 and Tau.shape[0] == I and Tau.dtype == torch.float64
+        assert mean is None or (mean.is_contiguous() and mean.numel() == P and mean.dtype == torch.float64)
+        ws = self._workspace("selectivity", self.lib.cmtfpls_selectivity_cols_workspace_bytes(I, P, M))
+        a = self.empty(M, P)
+        d = self.empty(M, P) if masked else None
+        s, n = self.empty(P), self.empty(P)
+        _lib.check(self._fn("selectivity_cols", X2)(_ptr(X2), I, P, _ptr(Tau), Tau.stride(0), M, _ptr(mean), int(bool(masked)), _ptr(a),
+                                                    _ptr(d), _ptr(s), _ptr(n), _ptr(ws), ws.numel(), self._stream()), "selectivity_cols")
+        return a, d, s, n
+
     def holdout_mask(self, X: torch.Tensor, out: torch.Tensor, fraction: float, seed: int, stream: int, offset: int = 0) -> torch.Tensor:
         """out = X with its held-out entries (the counter rule of include/cmtfpls.h: Philox stream `stream` = 2 + block index keyed by
         `seed`, element index + `offset`) replaced by NaN; X is only read, out is another tensor of X's shape and type.  Returns

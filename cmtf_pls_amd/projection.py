@@ -293,6 +293,60 @@ class ProjectionMixin:
                 cols[:, 1] += x2.sum(dim=0)
         return rows, cols
 
+    def selectivity_cols(self, state: FitState, Xs: List[torch.Tensor], Tau: torch.Tensor, device: bool = True,
+                         masked: Optional[List[bool]] = None) -> List[tuple]:
+        """Per block, for the rows Xs[b] (device, storage type, UNCENTRED, read only) and the fitted response Tau (I x M):
+        (a (M, P), d (M, P) or None, s (P,), n (P,)) with x = X - mean and o = isfinite(x) (the calcR2X mask of `residual_rows`):
+        a = sum_i o x tau, d = sum_i o tau^2, s = sum_i o x^2, n = sum_i o.  masked[b] False (default: the block's has_miss) declares
+        the rows of block b complete: o = 1, d is None (it is sum_i tau^2 for every column) and a missing value shows as a NaN.
+        One read of every block through cmtfpls_selectivity_cols_*; where the backend has no such kernel, and for device=False,
+        the same sums from torch ops on row blocks of <= 256 MB.  `last_selectivity` records, per block, the form and why."""
+        be = self.be
+        out, forms = [], []
+        flags = [bool(blk.has_miss) for blk in state.blocks] if masked is None else [bool(f) for f in masked]
+        with self.device_ctx():
+            if Tau.stride(1) != 1:
+                Tau = Tau.contiguous()
+            for blk, X, msk in zip(state.blocks, Xs, flags):
+                I = X.shape[0]
+                X2 = X.reshape(I, -1)
+                why = self._streaming_form("selectivity_cols", device)
+                if why is None and I > 0:
+                    res = be.selectivity_cols(X2, Tau, blk.mean, msk)
+                else:
+                    res = self._selectivity_cols_torch(X2, Tau, blk.mean, msk)
+                out.append(res)
+                forms.append({"form": "torch fallback" if why else "selectivity pass (cmtfpls_selectivity_cols)", "why": why,
+                              "masked": msk})
+        self.last_selectivity = forms
+        return out
+
+    @staticmethod
+    def _selectivity_cols_torch(X2: torch.Tensor, Tau: torch.Tensor, mean: Optional[torch.Tensor], masked: bool):
+        I, P = X2.shape
+        M = Tau.shape[1]
+        dev = Tau.device
+        a = torch.zeros(M, P, dtype=torch.float64, device=dev)
+        d = torch.zeros(M, P, dtype=torch.float64, device=dev) if masked else None
+        s, n = (torch.zeros(P, dtype=torch.float64, device=dev) for _ in range(2))
+        step = max(1, (256 << 20) // max(P * 8, 1))
+        for r0 in range(0, I, step):
+            x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
+            tau = Tau[r0:r0 + step]
+            if mean is not None:
+                x = x - mean
+            if masked:
+                fin = torch.isfinite(x)
+                x = torch.where(fin, x, 0.0)
+                o = fin.to(torch.float64)
+                d += (tau * tau).T @ o
+                n += o.sum(dim=0)
+            else:
+                n += float(x.shape[0])
+            a += tau.T @ x
+            s += (x * x).sum(dim=0)
+        return a, d, s, n
+
     def _streaming_form(self, kernel: str, device: bool) -> Optional[str]:
         """Why the streaming kernel `kernel` of the backend is NOT taken before it is tried (None: try it)."""
         if not device:

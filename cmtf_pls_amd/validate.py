@@ -292,6 +292,36 @@ def sample_contributions(pls_tensor, X=None, rows=None, cells: bool = False, dev
     return _run(pls_tensor, X, rows, cells, device)
 
 
+def selectivity_ratio(pls_tensor, X=None, level: float = 0.95, cells: bool = True, device: bool = True) -> dict:
+    """Which variables carry the prediction of a fitted tPLS or ctPLS: the selectivity ratio of every cell and of every slice of
+    every mode, by target projection onto the fitted response tau = scores coef_ Q^T (I x M).  X=None: the training rows (fitted
+    scores and ``original_X``; ValueError after a copy_X=False fit); otherwise new rows (a ctPLS: a list of blocks), scored as
+    transform scores them.  With x = X - X_mean over its finite entries, per cell c and response m: a = sum_i x tau_im, d = sum_i
+    tau_im^2 over the observed rows of c, s = sum_i x^2, n = the observed rows.
+    Returns {"tp_loading": a / d, "explained": a^2 / d, "residual": max(s - explained, 0), "sr": explained / residual, each shaped
+    (M, *X.shape[1:]) and left out with cells=False; "n_observed": X.shape[1:]; "sr_mode": one (M, J_k) array per mode k >= 1, the
+    sum of explained over the sum of residual over the cells of slice j; "f_limit": F.ppf(level, I - 2, I - 3), I the training
+    rows (NaN when I <= 3; nominal where values are missing: see n_observed); "level"}.  sr is NaN where d = 0 or n = 0 and inf where
+    residual = 0 < explained; NaN cells are skipped in sr_mode.  A ctPLS gives every value but f_limit and level as a list over its
+    blocks, which share tau.  Any order >= 2.  On the GPU every block is read once (cmtfpls_selectivity_cols_*); device=False takes
+    torch ops instead.  Which form ran: ``importance_report_`` (importance.py)."""
+    from .importance import selectivity_ratio as _run
+
+    return _run(pls_tensor, X, level, cells, device)
+
+
+def vip_scores(pls_tensor, per_component: bool = False) -> dict:
+    """VIP (variable importance in projection) of every slice of every mode k >= 1 of a fitted tPLS or ctPLS, from the fitted factors
+    alone: with s_r = max(R2Y[r] - R2Y[r - 1], 0) and unit-norm loadings W_k (J_k x R), vip[k][j] = sqrt(J_k sum_r s_r W_k[j, r]^2 /
+    sum_r s_r), so that sum_j vip[k][j]^2 = J_k.  Returns {"vip": a list with one (J_k,) array per mode (per_component=True: (R,
+    J_k), row p from the first p + 1 components; a ctPLS: such a list per block), "component_weights": s (R,), "clipped": the
+    components whose R2Y increment was negative and taken as 0, "why": None, or why every value is NaN (sum s = 0)}; the last two
+    also on the model (``vip_report_``)."""
+    from .importance import vip_scores as _run
+
+    return _run(pls_tensor, per_component)
+
+
 def impute(pls_tensor, X=None, device: bool = True):
     """X with every missing (non-finite) entry filled from the fitted tPLS or ctPLS, X_mean + T W^T there, and every observed entry
     untouched.  X=None: the training rows (their fitted scores and ``original_X`` / ``original_Xs``; ValueError after a copy_X=False

@@ -491,6 +491,23 @@ int cmtfpls_contrib_rows_f64(const double* X, int64_t I, const double* T, int ld
                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
                              double* t2A, double* t2B, void* stream);
 
+/* selectivity_cols: the target-projection sums behind the selectivity ratio of every variable (validate.selectivity_ratio), in ONE
+ * read of the uncentred X (I x P, storage type, any alignment), nothing of X's size written or copied.  Tau (I x M, row stride ldtau
+ * >= M) is the fitted response; with x = X[i,c] - mean[c] formed in registers (mean nullable: x = X) and o = isfinite(x) when
+ * masked != 0, o = 1 otherwise:
+ *   a[m*P + c] = sum_i o x Tau[i,m],   d[m*P + c] = sum_i o Tau[i,m]^2,   s[c] = sum_i o x^2,   n[c] = sum_i o.
+ * d is written only when masked != 0 (it may be NULL otherwise: without a mask d[m, c] = sum_i Tau[i,m]^2 for every c, which the
+ * caller forms once).  f64 matrix cores with the tiling of cmtfpls_xcov_*; the masked form runs a second accumulator set (A = Tau^2,
+ * B = the 0 / 1 mask) and so takes 32 responses per pass over X where the complete form takes 64; more responses: more passes
+ * inside the entry, s and n from the first.  Per-row-block partials closed in fixed order: no atomics, the same bits on every
+ * call.  A non-finite row of Tau makes every output of its responses non-finite.  Argument errors (CMTFPLS_EINVAL) and a short
+ * workspace (CMTFPLS_EWORKSPACE; ws: cmtfpls_selectivity_cols_workspace_bytes, enough for either form) are found before any launch. */
+size_t cmtfpls_selectivity_cols_workspace_bytes(int64_t I, int64_t P, int M);
+int cmtfpls_selectivity_cols_f32(const float* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                 int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_selectivity_cols_f64(const double* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                 int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- imputation and entry-wise validation of the X model: validate.impute / validate.get_q2x_heldout (no reference counterpart;
  * the model they use is factors_to_tensor(X_factors) + X_mean, util.py:18-20 with tpls.py:188-189 / cmtf.py:233-237) ------------
  * THE HOLD-OUT RULE.  Element e of a block (C-order index) is held out iff
