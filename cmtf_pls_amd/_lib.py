@@ -33,6 +33,11 @@ class CvCoupledBlock(ctypes.Structure):
     _fields_ = [("X", _P), ("order", c_int), ("A", c_int), ("B", c_int)]
 
 
+class LooCoupledBlock(ctypes.Structure):
+    """cmtfpls_loo_coupled_block (include/cmtfpls.h): one block of cmtfpls_loo_xcov_coupled_f64."""
+    _fields_ = [("X", _P), ("colsum", _P), ("order", c_int), ("A", c_int), ("B", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/cmtfpls.h one to one
 SIGNATURES = {
     "cmtfpls_xcov_iterate_blocks_f64": (c_int, [ctypes.POINTER(XcovBlock), c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
@@ -186,6 +191,10 @@ SIGNATURES = {
     "cmtfpls_loo_xcov_tensor_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_xcov_tensor_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P,
                                             c_size_t, _P]),
+    "cmtfpls_loo_xcov_coupled_fold_workspace_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, c_int, c_int, c_int]),
+    "cmtfpls_loo_xcov_coupled_lds_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, c_int, c_int, c_int]),
+    "cmtfpls_loo_xcov_coupled_f64": (c_int, [ctypes.POINTER(LooCoupledBlock), c_int, _P, _P, c_int, c_int, c_int, c_double, c_int, c_int, c_int,
+                                             _P, _P, _P, c_size_t, _P]),
     "cmtfpls_cv_masked_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_f64": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int,
                                       c_int, _P, _P, _P, _P, _P, c_size_t, _P]),

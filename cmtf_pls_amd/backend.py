@@ -794,6 +794,43 @@ class HipBackend:
             _lib.check(rc, "loo_xcov_tensor")
         return Ypred, n_iter
 
+    def loo_ctpls(self, Xs, Y: torch.Tensor, dims, R: int, tol: float, max_iter: int,
+                  max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
+        """Leave-one-out predictions of a ctPLS model on complete data (validate.py:24-33 over cmtf.py:85-177), every fold a workgroup
+        on the fold's cross-covariances (cmtfpls_loo_xcov_coupled_f64).  Xs: the blocks, each I x P_b float64; dims: (order, A, B) per
+        block (order 2: A = 1).  Returns (Ypred (I, M), n_iter (I, R), "xcov_coupled") or None when the shape is outside the form.
+        Folds run in chunks as loo_tpls's xcov form (a centred copy of every block per resident fold)."""
+        nb = len(Xs)
+        I, M = Y.shape
+        assert nb >= 1 and len(dims) == nb and Y.dtype == torch.float64 and Y.is_contiguous()
+        for X2, (_, A, B) in zip(Xs, dims):
+            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
+        colsums = [self.colstats(X2)[0] for X2 in Xs]
+        colsum_y, _ = self.colstats(Y)
+        blocks = (_lib.LooCoupledBlock * nb)(*[_lib.LooCoupledBlock(_ptr(X2), _ptr(cs), int(o), int(A), int(B))
+                                               for X2, cs, (o, A, B) in zip(Xs, colsums, dims)])
+        Ypred = self.empty(I, M)
+        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
+        fn = self.lib.cmtfpls_loo_xcov_coupled_f64
+        # probe without a workspace: the shape check comes first (status 4 = the form declines, 2 = it only misses the workspace)
+        if fn(blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), 0, 1, _ptr(Ypred), _ptr(n_iter), None, 0,
+              self._stream()) == 4:
+            return None
+        per = self.lib.cmtfpls_loo_xcov_coupled_fold_workspace_bytes(blocks, nb, I, M, R)
+        budget = max_ws_bytes
+        if budget is None:
+            budget = max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3)
+        chunk = min(max(1, min(I, int(budget // max(per, 1)))), 512)   # two workgroups' worth of folds per CU is all a launch can overlap
+        ws = self._workspace("loo", per * chunk)
+        for f0 in range(0, I, chunk):
+            nf = min(chunk, I - f0)
+            rc = fn(blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter),
+                    _ptr(ws), ws.numel(), self._stream())
+            if rc == 4:
+                return None
+            _lib.check(rc, "loo_xcov_coupled")
+        return Ypred, n_iter, "xcov_coupled"
+
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
                   max_iter: int, max_ws_bytes: Optional[int] = None
                   ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:

@@ -8,18 +8,26 @@ fold's vectors fit the LDS (min(J, K) <= 64), ``cmtfpls_loo_xcov_f64`` beyond (m
 cross-covariance, Gram squarings on the matrix cores) -- X of order 2 or 3 without missing values, M <= 64 / R <= 16 (LDS form), M <= 128 / R <= 64 (xcov form).  Anything else
 refits once per fold on the regular engine with the fitted model's storage type, algorithm and backend.  X of order 4 without
 missing values takes ``cmtfpls_loo_xcov_tensor_f64`` when ``EngineOptions.tensor_folds`` is on (the xcov form with the rank-1 CP of
-each fold's cross-covariance inside its workgroup).  X with missing values
+each fold's cross-covariance inside its workgroup).  A fitted ``ctPLS`` on complete data (at most 8 blocks of order 2 or
+3, min(J, K) <= 256 in every block, M <= 128, R <= 64) takes ``cmtfpls_loo_xcov_coupled_f64``: a workgroup per fold on the
+cross-covariances of all blocks, which share the fold's score; with a NaN in a block and
+``EngineOptions.masked_folds_coupled`` it takes ``cmtfpls_cv_masked_coupled_f64``; anything else refits ``ctPLS`` once per fold and
+says why.  X with missing values
 (order 2 or 3, Y complete) takes ``cmtfpls_cv_masked_f64`` when ``EngineOptions.masked_folds`` is on (a workgroup per fold with
 the reference's masked arithmetic, kfold.masked_predictions; K-fold too).  Which form ran is recorded on the model
 (``q2y_report_``).
 """
 import numpy as np
 
-from .kfold import MASKED_FORM, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, has_missing, masked_predictions
+from .kfold import (COUPLED_FORM, MASKED_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host, _training_data,
+                    has_missing, masked_predictions, masked_predictions_coupled, refit_predictions, wants_masked_coupled)
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
+LOO_COUPLED_FORM = "a workgroup per fold on the cross-covariances of the coupled blocks (cmtfpls_loo_xcov_coupled_f64)"
+LOO_REFIT_FORM = "one refit per fold on the regular engine"
 LOO_MAX_RESPONSES, LOO_MAX_COMPONENTS, LOO_MAX_CELLS = 128, 64, 1 << 24
+LOO_COUPLED_LDS_CAP = 150 * 1024
 
 
 def loo_tensor_lds_bytes(A: int, B1: int, B2: int, M: int, R: int) -> int:
@@ -53,8 +61,109 @@ def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
 
 def loo_predictions(pls_tensor, tol: float = 1e-8, max_iter: int = 100):
     """Y_pred[i] = prediction for sample i by the model refitted without it (validate.py:24-33), all folds in one
-    launch; None when the device form does not apply (see get_q2y)."""
+    launch; None when the device form does not apply (see get_q2y).  `pls_tensor` is a fitted tPLS or ctPLS."""
+    if _is_coupled(pls_tensor):
+        return _loo_device_coupled(pls_tensor, tol, max_iter)[0]
     return _loo_device(pls_tensor, tol, max_iter)[0]
+
+
+def _is_coupled(pls) -> bool:
+    from .cmtf import ctPLS
+
+    return isinstance(pls, ctPLS)
+
+
+def loo_coupled_lds_bytes(dims, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_loo_xcov_coupled_f64 for blocks of trailing shape dims = [(A, B), ..] (the library's
+    cmtfpls_loo_xcov_coupled_lds_bytes): every block's wA and wB, q, qn, tq, my, G_y, the extraction's xs and ys sized for the
+    largest block, then coef (R x R), Q (R x M) and the normal equations (R x R + 3 R)."""
+    nmax = max(min(A, B) for A, B in dims)
+    kmax = max(max(A, B) for A, B in dims)
+    return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R)
+
+
+def _decline_loo_coupled(pls, Xs, Y):
+    """Why cmtfpls_loo_xcov_coupled_f64 does not take these blocks (its limits in the entry's order, checked before a block is
+    uploaded); None: it does."""
+    be = pls._get_engine().be
+    name = "cmtfpls_loo_xcov_coupled_f64"
+    if not hasattr(be, "loo_ctpls"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no coupled leave-one-out kernel"
+    if pls._comm is not None:
+        return "sharded model (comm)"
+    if len(Xs) > MAX_BLOCKS:
+        return f"{len(Xs)} blocks > {MAX_BLOCKS} ({name})"
+    for b, X in enumerate(Xs):
+        if X.ndim > 3:
+            return f"block {b} of order {X.ndim} > 3 ({name})"
+    for b, X in enumerate(Xs):
+        if has_missing(X):
+            return f"missing values in block {b} (EngineOptions.masked_folds_coupled is off; {name} is the complete-data form)"
+    if has_missing(Y):
+        return "missing values in Y"
+    dims = [_dims(X) for X in Xs]
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    R = pls.n_components
+    for b, (A, B) in enumerate(dims):
+        if min(A, B) > MAX_SIDE:
+            return f"block {b}: min(J, K) = {min(A, B)} > {MAX_SIDE} ({name})"
+    if M > LOO_MAX_RESPONSES:
+        return f"M = {M} > {LOO_MAX_RESPONSES} responses ({name})"
+    if R > LOO_MAX_COMPONENTS:
+        return f"R = {R} > {LOO_MAX_COMPONENTS} components ({name})"
+    for b, (A, B) in enumerate(dims):
+        if A * B > LOO_MAX_CELLS:
+            return f"block {b}: J K = {A * B} > {LOO_MAX_CELLS} ({name})"
+    lds = loo_coupled_lds_bytes(dims, M, R)
+    if lds > LOO_COUPLED_LDS_CAP:
+        return f"the fold's vectors need {lds} bytes of LDS > {LOO_COUPLED_LDS_CAP} ({name})"
+    return None
+
+
+def _loo_device_coupled(pls, tol: float, max_iter: int):
+    """_loo_device for a fitted ctPLS: (Y_pred, None) from a device form (q2y_report_ set), or (None, why)."""
+    import torch
+
+    Xs, Y = _training_data(pls)
+    I = Y.shape[0]
+    if wants_masked_coupled(pls, Xs):                                     # EngineOptions.masked_folds_coupled: cmtfpls_cv_masked_coupled_f64
+        pred, rep = masked_predictions_coupled(pls, Xs, Y, np.arange(I), I, tol, max_iter)
+        if pred is None:
+            return None, f"the masked form ({COUPLED_FORM}) declined: {rep}"
+        pls.q2y_report_ = dict(rep, blocks=len(Xs), n_iter_total=int(np.sum(rep["n_iter"])))
+        return pred[-1].reshape(Y.shape), None
+    why = _decline_loo_coupled(pls, Xs, Y)
+    if why is not None:
+        return None, why
+    eng = pls._get_engine()
+    be = eng.be
+    with eng.device_ctx():
+        def f64(a):                                                       # the original data in float64, on the device
+            if isinstance(a, torch.Tensor):
+                return a.detach().to(device=be.device, dtype=torch.float64).contiguous().view(I, -1)
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(I, -1), dtype=np.float64)).to(be.device)
+
+        out = be.loo_ctpls([f64(X) for X in Xs], f64(Y), [(X.ndim, *_dims(X)) for X in Xs], pls.n_components, tol, max_iter)
+        if out is None:
+            return None, "cmtfpls_loo_xcov_coupled_f64 declined the shape"
+        pls.q2y_report_ = {"form": LOO_COUPLED_FORM, "folds": int(I), "blocks": len(Xs), "n_iter_total": int(out[1].sum().item())}
+        return out[0].cpu().numpy().reshape(tuple(Y.shape)), None
+
+
+def _get_q2y_coupled(pls, device_folds: bool):
+    """get_q2y of a fitted ctPLS: the device forms of _loo_device_coupled, else one ctPLS refit per fold with the model's storage
+    type, algorithm, backend and options (kfold.refit_predictions), the reason in q2y_report_["why"]."""
+    Xs, Y = _training_data(pls)
+    I = Y.shape[0]
+    Y_pred, why = _loo_device_coupled(pls, 1e-8, 100) if device_folds else (None, "device folds switched off")
+    Y_actual = _host(Y).astype(float)
+    if Y_pred is None:
+        pred, n_iter = refit_predictions(pls, Xs, Y, np.arange(I), I, 1e-8, 100)
+        pls.q2y_report_ = {"form": LOO_REFIT_FORM, "folds": int(I), "blocks": len(Xs), "n_iter_total": int(np.sum(n_iter)), "why": why}
+        Y_pred = pred[-1].reshape(Y_actual.shape)
+    numerator = (Y_pred - Y_actual) ** 2                     # validate.py:35-37
+    denominator = Y_actual ** 2
+    return 1 - numerator.sum() / denominator.sum()
 
 
 def _loo_device(pls_tensor, tol: float, max_iter: int):
@@ -121,6 +230,8 @@ def _loo_device_tensor(pls_tensor, be, X, Y, tol: float, max_iter: int):
 
 
 def get_q2y(pls_tensor, device_folds: bool = True):
+    if _is_coupled(pls_tensor):
+        return _get_q2y_coupled(pls_tensor, device_folds)
     assert getattr(pls_tensor, "original_X", None) is not None, "PLS Tensor must be fit prior to calculating Q2Y"
     X = np.asarray(pls_tensor.original_X) if not hasattr(pls_tensor.original_X, "cpu") else pls_tensor.original_X.cpu().numpy()
     Y = np.asarray(pls_tensor.original_Y) if not hasattr(pls_tensor.original_Y, "cpu") else pls_tensor.original_Y.cpu().numpy()

@@ -591,6 +591,33 @@ size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2
 int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
                                 int B1, int B2, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
                                 int* n_iter, void* ws, size_t ws_bytes, void* stream);
+/* loo_xcov_coupled: cmtfpls_loo_xcov_f64 for a COUPLED model (ctPLS, cmtf.py:85-177) on complete data: one 1024-thread workgroup per
+ * held-out sample runs the whole fit of the other I - 1 samples on up to 8 blocks that share one score, and predicts its own row.
+ * Every block's and Y's means are down-dated from the column sums; per component S_b = Y_f^T X_{b,f} (M x P_b) of every block and
+ * G_y = Y_f^T Y_f are formed once and the inner loop runs on them from q = e_0, blocks in list order: Z_b = S_b^T q, w_b by
+ * Z_b / |Z_b| (order 2) or the leading singular pair (order 3, Gram squarings on the f64 matrix cores),
+ * Y^T t = (1 / nb) sum_b S_b (wA_b (x) wB_b), |u_old - u|^2 = dq^T G_y dq, no stop on the first pass; then t = mean_b X_{b,f} w_b,
+ * every block deflated by its own t (x) w_b, coef from the normal equations of T, Y deflated.  The original blocks are only read.
+ * Only rows fold0 .. fold0 + nfolds - 1 of Ypred (I x M) and n_iter (nullable, I x R) are written.
+ * Checked on the host before the launch, in this order: CMTFPLS_EINVAL for a bad pointer or size (as cmtfpls_loo_xcov_f64; a block
+ * without X or colsum, A or B <= 0, order < 2, or order 2 with A != 1); CMTFPLS_EUNSUPPORTED for nb > 8, a block of order > 3,
+ * min(A_b, B_b) > 256, M > 128, R > 64, P_b = A_b B_b > 2^24, or more than 150 KB of LDS, which cmtfpls_loo_xcov_coupled_lds_bytes
+ * returns: (sum A_b + sum B_b + 4 M + M^2 + nmax + kmax + 2 R^2 + R M + 3 R) doubles with nmax = max_b min(A_b, B_b) and
+ * kmax = max_b max(A_b, B_b) (every block's wA, wB resident; the extraction scratch shared and sized for the largest block);
+ * CMTFPLS_EWORKSPACE below nfolds * cmtfpls_loo_xcov_coupled_fold_workspace_bytes(...): per fold ((I + M) sumP + 3 Pmax + 2 nmax^2 +
+ * I (M + R + 2) + R (sum A_b + sum B_b)) doubles, sumP = sum_b P_b, Pmax = max_b P_b.  With one block both formulas are
+ * cmtfpls_loo_xcov_f64's.  The two size functions return 0 for a bad argument (nb outside 1..8 included). */
+typedef struct {
+  const double* X;        /* I x A*B row-major, the original block, no missing values */
+  const double* colsum;   /* A*B: column sums over all I samples */
+  int order;              /* 2 (a matrix: A = 1) or 3 */
+  int A, B;
+} cmtfpls_loo_coupled_block;
+size_t cmtfpls_loo_xcov_coupled_fold_workspace_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R);
+size_t cmtfpls_loo_xcov_coupled_lds_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R);
+int cmtfpls_loo_xcov_coupled_f64(const cmtfpls_loo_coupled_block* blocks, int nb, const double* Y, const double* colsum_y, int I,
+                                 int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter,
+                                 void* ws, size_t ws_bytes, void* stream);
 /* ---- cross-validation refits of a tPLS whose X has missing values, all folds in one launch: validate.get_q2y / kfold_predictions
  * with EngineOptions.masked_folds (cmtf_pls/validate.py:7-37; tpls.py:61-63 X_hasMiss; missingvals.py:7-38) -------------------
  * For every fold f in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113) on the rows r with fold_of[r] != f, with the
