@@ -170,8 +170,9 @@ class HipBackend:
 
     def rank1_tensor(self, Z: torch.Tensor, dims, tol: float, factors: torch.Tensor,
                      info: Optional[torch.Tensor] = None, n_squarings: Optional[int] = None) -> None:
-        """Rank-1 CP factors of an order-3/4 cross-covariance tensor; factors: (n, ld) f64, row m = mode m."""
-        import ctypes
+        """Rank-1 CP factors of a cross-covariance tensor of order 3 to 7 (X of order 4 to 8), every mode <= 1024; factors: (n, ld)
+        f64, row m = mode m.  info (2 doubles, optional): [1, ALS sweeps run], or [0, -1] with NaN factors when the one-launch
+        chain of squarings of an init gave up (as rank1 reports it: rank1_chain_gave_up, then call again)."""
         arr = (ctypes.c_int * len(dims))(*[int(d) for d in dims])
         ws = self._workspace("rank1t", self.lib.cmtfpls_rank1_tensor_workspace_bytes(arr, len(dims)))
         _lib.check(self.lib.cmtfpls_rank1_tensor_f64(_ptr(Z), arr, len(dims), float(tol), _ptr(factors), factors.stride(0), _ptr(info),

@@ -73,13 +73,26 @@ __device__ double vec_dot(const double* a, const double* b, int n, double* red) 
 }
 
 // init: (N, max d) factor matrix `f0` in global (from the per-mode matrix rank-1 calls); out: f_out
+// init_info: the N info pairs of those calls.  One of them [., -1] (its one-launch chain of squarings gave up, rank1.hip: that
+// init vector is NaN): NaN factors and info = [0, -1] without a sweep -- what cmtfpls_rank1_f64 itself reports, so that the
+// caller switches the chain off and repeats.
 __global__ __launch_bounds__(1024) void cp_rank1_als_kernel(const double* __restrict__ Z, TensorDims td,
-                                                           const double* __restrict__ f_init, int ld_init, double tol,
+                                                           const double* __restrict__ f_init, int ld_init,
+                                                           const double* __restrict__ init_info, double tol,
                                                            int max_sweeps, double* __restrict__ f_out, int ld_out,
                                                            double* __restrict__ info) {
   extern __shared__ double lds[];
   __shared__ double red[16];
   __shared__ int s_arg;
+  bool gave = false;
+  for (int m = 0; m < td.n; ++m) gave = gave || init_info[2 * m + 1] < 0.0;     // (the same words for every thread: uniform)
+  if (gave) {
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    for (int m = 0; m < td.n; ++m)
+      for (int i = threadIdx.x; i < td.d[m]; i += blockDim.x) f_out[(int64_t)m * ld_out + i] = nan;
+    if (info && threadIdx.x == 0) { info[0] = 0.0; info[1] = -1.0; }
+    return;
+  }
   double* f[kMaxOrder];
   double* tmp;
   {
@@ -187,7 +200,8 @@ size_t cmtfpls_rank1_tensor_workspace_bytes(const int* dims, int n) {
     if ((size_t)td.d[m] > maxd) maxd = td.d[m];
   }
   return align_up_t(ws_mat, 256) + align_up_t((size_t)td.total * sizeof(double), 256) /* unfolding */ +
-         align_up_t((size_t)td.total * sizeof(double), 256) /* discarded right vector */ + align_up_t((size_t)n * maxd * sizeof(double), 256);
+         align_up_t((size_t)td.total * sizeof(double), 256) /* discarded right vector */ + align_up_t((size_t)n * maxd * sizeof(double), 256) +
+         align_up_t((size_t)2 * n * sizeof(double), 256) /* info pair of every init */;
 }
 
 int cmtfpls_rank1_tensor_f64(const double* Z, const int* dims, int n, double tol, double* factors, int ld,
@@ -216,6 +230,8 @@ int cmtfpls_rank1_tensor_f64(const double* Z, const int* dims, int n, double tol
   double* vright = reinterpret_cast<double*>(p);
   p += align_up_t((size_t)td.total * sizeof(double), 256);
   double* finit = reinterpret_cast<double*>(p);
+  p += align_up_t((size_t)n * maxd * sizeof(double), 256);
+  double* init_info = reinterpret_cast<double*>(p);
   // init: leading left singular vector of every unfolding (tensorly initialize_cp, init="svd")
   for (int m = 0; m < n; ++m) {
     const int rows = td.d[m], cols = (int)(td.total / td.d[m]);
@@ -224,11 +240,11 @@ int cmtfpls_rank1_tensor_f64(const double* Z, const int* dims, int n, double tol
       hipLaunchKernelGGL(unfold_kernel, dim3((unsigned)((td.total + 255) / 256)), dim3(256), 0, st, Z, td, m, unf);
       M = unf;
     }
-    const int rc = cmtfpls_rank1_f64(M, rows, cols, finit + (size_t)m * maxd, vright, nullptr, nullptr, n_squarings, wsm, ws_mat, stream);
+    const int rc = cmtfpls_rank1_f64(M, rows, cols, finit + (size_t)m * maxd, vright, nullptr, init_info + 2 * m, n_squarings, wsm, ws_mat, stream);
     if (rc != CMTFPLS_OK) return rc;
   }
   const size_t lds = (sumd + ((maxd + 1) & ~(size_t)1)) * sizeof(double);
-  hipLaunchKernelGGL(cp_rank1_als_kernel, dim3(1), dim3(1024), lds, st, Z, td, finit, (int)maxd, tol, 100, factors, ld, info);
+  hipLaunchKernelGGL(cp_rank1_als_kernel, dim3(1), dim3(1024), lds, st, Z, td, finit, (int)maxd, init_info, tol, 100, factors, ld, info);
   return check_launch("rank1_tensor");
 }
 

@@ -122,7 +122,10 @@ int cmtfpls_normalize_f64(double* v, int64_t n, double* nrm, void* stream);
  * exercised by tests/test_cmtf.py:18-21, tests/test_tpls.py:132-155): leading-left-singular-vector
  * init of every unfolding, ALS sweeps, stop when |d rec_error| < tol from the 2nd sweep on (<= 100
  * sweeps), as tensorly 0.9.0 publishes it.  dims: HOST array of the n mode sizes (each <= 1024);
- * factors: device (n x ld) row-major, row m = factor of mode m; info as for rank1 (info[1] = sweeps).
+ * factors: device (n x ld) row-major, row m = factor of mode m (columns past dims[m] are not written).  info (nullable, 2
+ * doubles): [1, sweeps run] -- or [0, -1] with NaN factors and no sweep when the one-launch chain of squarings of one of the n
+ * inits gave up (see cmtfpls_rank1_chain_enable: switch the chain off and repeat the call); the inits report through n info
+ * pairs in the workspace, read by the ALS kernel: no host synchronisation.
  * kron: out[c] = a[c / nb] * b[c % nb] (builds wB of the factored loading from the trailing factors). */
 size_t cmtfpls_rank1_tensor_workspace_bytes(const int* dims, int n);
 int cmtfpls_rank1_tensor_f64(const double* Z, const int* dims, int n, double tol, double* factors, int ld,
