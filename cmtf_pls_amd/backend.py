@@ -26,6 +26,13 @@ def _int_pairs(pairs):
     return (ctypes.c_int * len(flat))(*flat)
 
 
+def chunk_size(n: int, per: int, budget: int, cap: Optional[int] = None) -> int:
+    """Items per launch of a chunked workgroup-per-item call: as many of the n items as `budget` bytes hold at `per` bytes each,
+    at least one, at most `cap`."""
+    chunk = max(1, min(int(n), int(budget) // max(int(per), 1)))
+    return chunk if cap is None else min(chunk, int(cap))
+
+
 class HipBackend:
     name = "hip"
 
@@ -51,6 +58,33 @@ class HipBackend:
             buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
             self._ws[key] = buf
         return buf
+
+    def _chunked_launch(self, name: str, call, n: int, per_fn, budget: int, cap: Optional[int] = None, extra: int = 0,
+                        ws_key: Optional[str] = None) -> Optional[int]:
+        """Run call(first, count, ws_ptr, ws_bytes) -> status over the n items (folds, models) of a workgroup-per-item entry point
+        in chunks whose workspace fits `budget` bytes; the number of launches, or None when the entry point declines the shape
+        (status 4).  The probe without a workspace comes first: the shape check precedes the workspace check (status 2).
+        per_fn() gives the workspace bytes per item; `extra`: further bytes per item counted against the budget; `cap`: most items
+        per launch; ws_key: the cached workspace to use (allocated for this call and released with it otherwise)."""
+        if call(0, 1, None, 0) == 4:
+            return None
+        per = int(per_fn())
+        chunk = chunk_size(n, per + extra, budget, cap)
+        ws = self._workspace(ws_key, per * chunk) if ws_key else torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
+        launches = 0
+        for i0 in range(0, n, chunk):
+            rc = call(i0, min(chunk, n - i0), _ptr(ws), ws.numel())
+            if rc == 4:
+                return None
+            _lib.check(rc, name)
+            launches += 1
+        return launches
+
+    def _ws_budget(self, max_ws_bytes: Optional[int], third_of_free: bool = False) -> int:
+        """The workspace budget of a chunked call: the caller's, else 4 GiB (third_of_free: or a third of the free HBM if more)."""
+        if max_ws_bytes is not None:
+            return int(max_ws_bytes)
+        return max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3) if third_of_free else 4 << 30
 
     def clear_error(self) -> bool:
         """After a failed HIP-graph capture: reset the runtime's pending error so that the next launch is not blamed for it."""
@@ -736,30 +770,13 @@ class HipBackend:
                                  ("xcov", self.lib.cmtfpls_loo_xcov_fold_workspace_bytes, self.lib.cmtfpls_loo_xcov_f64)):
             if form not in forms:
                 continue
-            # probe without a workspace: the shape check comes first (status 4 = this form declines, 2 = it only misses the workspace)
-            if fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B, M, R, float(tol), int(max_iter), 0, 1, _ptr(Ypred),
-                  _ptr(n_iter), None, 0, self._stream()) == 4:
-                continue
-            per = per_fn(I, A, B, M, R)
-            budget = max_ws_bytes
-            if budget is None:
-                budget = (4 << 30) if form == "lds" else max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3)
-            chunk = max(1, min(I, int(budget // max(per, 1))))
-            if form == "xcov":
-                chunk = min(chunk, 512)                      # two workgroups' worth of folds per CU is all a launch can overlap
-            declined = False
-            ws = None
-            for f0 in range(0, I, chunk):
-                nf = min(chunk, I - f0)
-                if ws is None:
-                    ws = self._workspace("loo", per * min(chunk, I))
-                rc = fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B, M, R, float(tol), int(max_iter),
-                        f0, nf, _ptr(Ypred), _ptr(n_iter), _ptr(ws), ws.numel(), self._stream())
-                if rc == 4:
-                    declined = True
-                    break
-                _lib.check(rc, "loo_" + form)
-            if not declined:
+            xcov = form == "xcov"                            # (512: two workgroups' worth of folds per CU is all a launch can overlap)
+            if self._chunked_launch(
+                    "loo_" + form,
+                    lambda f0, nf, ws, nb, fn=fn: fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
+                                                     int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws, nb, self._stream()),
+                    I, lambda per_fn=per_fn: per_fn(I, A, B, M, R), self._ws_budget(max_ws_bytes, xcov),
+                    cap=512 if xcov else None, ws_key="loo") is not None:
                 return Ypred, n_iter, form
         return None
 
@@ -775,24 +792,14 @@ class HipBackend:
         colsum_y, _ = self.colstats(Y)
         Ypred = self.empty(I, M)
         n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
-        fn = self.lib.cmtfpls_loo_xcov_tensor_f64
-        # probe without a workspace: the shape check comes first (status 4 = the form declines, 2 = it only misses the workspace)
-        if fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), 0, 1, _ptr(Ypred),
-              _ptr(n_iter), None, 0, self._stream()) == 4:
+        if self._chunked_launch(
+                "loo_xcov_tensor",
+                lambda f0, nf, ws, nb: self.lib.cmtfpls_loo_xcov_tensor_f64(
+                    _ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), f0, nf,
+                    _ptr(Ypred), _ptr(n_iter), ws, nb, self._stream()),
+                I, lambda: self.lib.cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R),
+                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
             return None
-        per = self.lib.cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R)
-        budget = max_ws_bytes
-        if budget is None:
-            budget = max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3)
-        chunk = min(max(1, min(I, int(budget // max(per, 1)))), 512)   # two workgroups' worth of folds per CU is all a launch can overlap
-        ws = self._workspace("loo", per * chunk)
-        for f0 in range(0, I, chunk):
-            nf = min(chunk, I - f0)
-            rc = fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), f0, nf,
-                    _ptr(Ypred), _ptr(n_iter), _ptr(ws), ws.numel(), self._stream())
-            if rc == 4:
-                return None
-            _lib.check(rc, "loo_xcov_tensor")
         return Ypred, n_iter
 
     def loo_ctpls(self, Xs, Y: torch.Tensor, dims, R: int, tol: float, max_iter: int,
@@ -812,24 +819,14 @@ class HipBackend:
                                                for X2, cs, (o, A, B) in zip(Xs, colsums, dims)])
         Ypred = self.empty(I, M)
         n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
-        fn = self.lib.cmtfpls_loo_xcov_coupled_f64
-        # probe without a workspace: the shape check comes first (status 4 = the form declines, 2 = it only misses the workspace)
-        if fn(blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), 0, 1, _ptr(Ypred), _ptr(n_iter), None, 0,
-              self._stream()) == 4:
+        if self._chunked_launch(
+                "loo_xcov_coupled",
+                lambda f0, nf, ws, nby: self.lib.cmtfpls_loo_xcov_coupled_f64(
+                    blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws, nby,
+                    self._stream()),
+                I, lambda: self.lib.cmtfpls_loo_xcov_coupled_fold_workspace_bytes(blocks, nb, I, M, R),
+                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
             return None
-        per = self.lib.cmtfpls_loo_xcov_coupled_fold_workspace_bytes(blocks, nb, I, M, R)
-        budget = max_ws_bytes
-        if budget is None:
-            budget = max(4 << 30, torch.cuda.mem_get_info(self.device)[0] // 3)
-        chunk = min(max(1, min(I, int(budget // max(per, 1)))), 512)   # two workgroups' worth of folds per CU is all a launch can overlap
-        ws = self._workspace("loo", per * chunk)
-        for f0 in range(0, I, chunk):
-            nf = min(chunk, I - f0)
-            rc = fn(blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter),
-                    _ptr(ws), ws.numel(), self._stream())
-            if rc == 4:
-                return None
-            _lib.check(rc, "loo_xcov_coupled")
         return Ypred, n_iter, "xcov_coupled"
 
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
@@ -854,16 +851,10 @@ class HipBackend:
         args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
                 int(max_iter))
         outs = (_ptr(Ypred), _ptr(n_iter), _ptr(status), _ptr(info))
-        # probe without a workspace: the shape check comes first (4 = declined, 2 = only the workspace is missing)
-        if fn(*args, 0, 1, *outs, None, 0, self._stream()) == 4:
+        if self._chunked_launch("cv_masked", lambda f0, nf, ws, nb: fn(*args, f0, nf, *outs, ws, nb, self._stream()), K,
+                                lambda: self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R),
+                                self._ws_budget(max_ws_bytes)) is None:
             return None
-        per = int(self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R))
-        budget = (4 << 30) if max_ws_bytes is None else int(max_ws_bytes)
-        chunk = max(1, min(K, budget // max(per, 1)))
-        ws = torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
-        for f0 in range(0, K, chunk):
-            nf = min(chunk, K - f0)
-            _lib.check(fn(*args, f0, nf, *outs, _ptr(ws), ws.numel(), self._stream()), "cv_masked")
         return Ypred, n_iter, status, info
 
     def cv_masked_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int, B: int,
@@ -891,19 +882,11 @@ class HipBackend:
                 int(max_iter))
         outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wb", "coef", "Q")) if factors else (None,) * 4),
                 _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
-        # probe without a workspace: the shape check comes first (4 = declined, 2 = only the workspace is missing)
-        if fn(*args, 0, 1, *outs, None, 0, self._stream()) == 4:
-            return None
-        per = int(self.lib.cmtfpls_cv_masked_model_workspace_bytes(I, A, B, M, R))
-        budget = (4 << 30) if max_ws_bytes is None else int(max_ws_bytes)
-        chunk = max(1, min(nm, budget // max(per + R * I * M * 8, 1)))
-        ws = torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
-        launches = 0
-        for m0 in range(0, nm, chunk):
-            _lib.check(fn(*args, m0, min(chunk, nm - m0), *outs, _ptr(ws), ws.numel(), self._stream()), "cv_masked_models")
-            launches += 1
-        out["launches"] = launches
-        return out
+        out["launches"] = self._chunked_launch(
+            "cv_masked_models", lambda m0, n, ws, nb: fn(*args, m0, n, *outs, ws, nb, self._stream()), nm,
+            lambda: self.lib.cmtfpls_cv_masked_model_workspace_bytes(I, A, B, M, R), self._ws_budget(max_ws_bytes),
+            extra=R * I * M * 8)
+        return out if out["launches"] is not None else None
 
     def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
                           max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
@@ -934,18 +917,12 @@ class HipBackend:
         args = (blocks, nb, _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, M, R, float(tol), int(max_iter))
         outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wb", "coef", "Q")) if factors else (None,) * 4),
                 _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
-        # probe without a workspace: the shape check comes first (4 = declined, 2 = only the workspace is missing)
-        if fn(*args, 0, 1, *outs, None, 0, self._stream()) == 4:
+        out["launches"] = self._chunked_launch(
+            "cv_masked_coupled", lambda m0, n, ws, nby: fn(*args, m0, n, *outs, ws, nby, self._stream()), nm,
+            lambda: self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R), self._ws_budget(max_ws_bytes),
+            extra=R * I * M * 8)
+        if out["launches"] is None:
             return None
-        per = int(self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R))
-        budget = (4 << 30) if max_ws_bytes is None else int(max_ws_bytes)
-        chunk = max(1, min(nm, budget // max(per + R * I * M * 8, 1)))
-        ws = torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
-        launches = 0
-        for m0 in range(0, nm, chunk):
-            _lib.check(fn(*args, m0, min(chunk, nm - m0), *outs, _ptr(ws), ws.numel(), self._stream()), "cv_masked_coupled")
-            launches += 1
-        out["launches"] = launches
         if factors:                                                                  # block b's R x A_b at R * (A_0 + .. + A_(b-1))
             oa = ob = 0
             Wa, Wb = [], []

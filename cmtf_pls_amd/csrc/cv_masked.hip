@@ -21,6 +21,7 @@
 // Limits: those of the LDS form (min(A, B) <= 64, M <= 64, R <= 16, the vectors plus the per-row counts and flags within 150 KB
 // of LDS), 1 <= K <= I, at least 2 training rows per fold (status 2 otherwise).
 #include "common.hpp"
+#include "fold_regress.hpp"
 
 namespace cmtfpls {
 
@@ -224,59 +225,9 @@ __global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
       Xf[idx] = Xf[idx] - t[r] * (wA[c / B] * wB[c % B]);
     }
     __syncthreads();
-    // inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112): normal equations, equilibrated Cholesky (held-out rows of T are 0)
-    const int kk = comp + 1;
-    for (int o = tid; o < kk * kk + kk; o += NT) {
-      double s = 0.0;
-      if (o < kk * kk) {
-        const int p = o / kk, s2 = o % kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], T[(int64_t)r * R + s2], s);
-        Gn[o] = s;
-      } else {
-        const int p = o - kk * kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], u[r], s);
-        gn[p] = s;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const double tiny = (double)kk * 2.220446049250313e-16;
-      for (int i = 0; i < kk; ++i) { const double g = Gn[i * kk + i]; dd[i] = (g > 0.0 && isfinite(g)) ? 1.0 / sqrt(g) : 0.0; }
-      for (int i = 0; i < kk; ++i) {
-        for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
-        bb[i] = gn[i] * dd[i];
-      }
-      bool dep[kCvMaxR];
-      for (int c = 0; c < kk; ++c) {
-        const double piv = Gn[c * kk + c];
-        dep[c] = !(piv > tiny);
-        if (dep[c]) { Gn[c * kk + c] = 1.0; for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0; continue; }
-        const double l = sqrt(piv);
-        Gn[c * kk + c] = l;
-        for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
-        for (int i = c + 1; i < kk; ++i)
-          for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
-      }
-      for (int r = 0; r < kk; ++r) {
-        double s = bb[r];
-        for (int j = 0; j < r; ++j) s -= Gn[r * kk + j] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = kk - 1; r >= 0; --r) {
-        double s = bb[r];
-        for (int j = r + 1; j < kk; ++j) s -= Gn[j * kk + r] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; coef[r * R + comp] = bb[r]; }
-    }
-    __syncthreads();
-    // Y -= T b q^T (tpls.py:113); t is free: reuse it for yhat = T b
-    for (int r = tid; r < I; r += NT) {
-      double s = 0.0;
-      for (int j = 0; j < kk; ++j) s = fma(T[(int64_t)r * R + j], bb[j], s);
-      t[r] = s;
-    }
-    __syncthreads();
+    // inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112), fold_regress.hpp (held-out rows of T are 0); then
+    // Y -= T b q^T (tpls.py:113), yhat = T b in t
+    fold_inner_regression<NT, false>(T, u, nullptr, I, R, comp, Gn, gn, bb, dd, coef, t);
     for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
       const int r = (int)(idx / M), m = (int)(idx % M);
       Yf[idx] = Yf[idx] - t[r] * qn[m];

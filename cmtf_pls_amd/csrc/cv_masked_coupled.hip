@@ -32,6 +32,7 @@
 //   + sum_b [(R + 1)(A_b + B_b) + I]  (the current and the R stored loadings, the per-row observed counts o^b)
 // Limits: every block min(A_b, B_b) <= 64 and order 2 or 3, M <= 64, R <= 16, nb <= 8, the LDS above <= 150 KB.
 #include "common.hpp"
+#include "fold_regress.hpp"
 
 namespace cmtfpls {
 
@@ -292,63 +293,9 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
       }
     }
     __syncthreads();
-    // inner regression b = lstsq(T[:, :k], u) on the weighted rows (cmtf.py:136-138): (T^T C T) b = T^T C u, equilibrated Cholesky
-    const int kk = comp + 1;
-    for (int o = tid; o < kk * kk + kk; o += NT) {
-      double s = 0.0;
-      if (o < kk * kk) {
-        const int p = o / kk, s2 = o % kk;
-        for (int r = 0; r < I; ++r) s = fma(cw[r] * T[(int64_t)r * R + p], T[(int64_t)r * R + s2], s);
-        Gn[o] = s;
-      } else {
-        const int p = o - kk * kk;
-        for (int r = 0; r < I; ++r) s = fma(cw[r] * T[(int64_t)r * R + p], u[r], s);
-        gn[p] = s;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const double tiny = (double)kk * 2.220446049250313e-16;
-      for (int i = 0; i < kk; ++i) { const double g = Gn[i * kk + i]; dd[i] = (g > 0.0 && isfinite(g)) ? 1.0 / sqrt(g) : 0.0; }
-      for (int i = 0; i < kk; ++i) {
-        for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
-        bb[i] = gn[i] * dd[i];
-      }
-      unsigned dep = 0u;                                                             // bit c: a dependent column
-      for (int c = 0; c < kk; ++c) {
-        const double piv = Gn[c * kk + c];
-        if (!(piv > tiny)) {
-          dep |= 1u << c;
-          Gn[c * kk + c] = 1.0;
-          for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0;
-          continue;
-        }
-        const double l = sqrt(piv);
-        Gn[c * kk + c] = l;
-        for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
-        for (int i = c + 1; i < kk; ++i)
-          for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
-      }
-      for (int r = 0; r < kk; ++r) {
-        double s = bb[r];
-        for (int j = 0; j < r; ++j) s -= Gn[r * kk + j] * bb[j];
-        bb[r] = ((dep >> r) & 1u) ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = kk - 1; r >= 0; --r) {
-        double s = bb[r];
-        for (int j = r + 1; j < kk; ++j) s -= Gn[j * kk + r] * bb[j];
-        bb[r] = ((dep >> r) & 1u) ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; coef[r * R + comp] = bb[r]; }
-    }
-    __syncthreads();
-    // Y -= T b q^T (cmtf.py:139); held-out rows of T are 0, so their Yf stays 0.  t is free: reuse it for yhat = T b
-    for (int r = tid; r < I; r += NT) {
-      double s = 0.0;
-      for (int j = 0; j < kk; ++j) s = fma(T[(int64_t)r * R + j], bb[j], s);
-      t[r] = s;
-    }
-    __syncthreads();
+    // inner regression b = lstsq(T[:, :k], u) on the weighted rows (cmtf.py:136-138): (T^T C T) b = T^T C u, fold_regress.hpp; then
+    // Y -= T b q^T (cmtf.py:139), yhat = T b in t; held-out rows of T are 0, so their Yf stays 0
+    fold_inner_regression<NT, true>(T, u, cw, I, R, comp, Gn, gn, bb, dd, coef, t);
     for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
       const int r = (int)(idx / M), m = (int)(idx % M);
       Yf[idx] = Yf[idx] - t[r] * qn[m];

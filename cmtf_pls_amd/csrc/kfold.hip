@@ -16,6 +16,7 @@
 // on load).  No workgroup waits on another.  Coupled models (ctPLS): the same steps per block with the score shared, see the
 // section "coupled models" below.
 #include "fold_loop.hpp"
+#include "fold_regress.hpp"
 
 namespace cmtfpls {
 
@@ -361,34 +362,8 @@ __global__ __launch_bounds__(64) void kfold_solve_kernel(cmtfpls_kfold_state st,
   for (int p = 0; p < kk; ++p) { Gt[a * R + p] = tot[p]; Gt[p * R + a] = tot[p]; }
   for (int i = 0; i < kk; ++i)
     for (int j = 0; j < kk; ++j) Gn[i * kk + j] = Gt[i * R + j];
-  const double tiny = (double)kk * 2.220446049250313e-16;
-  for (int i = 0; i < kk; ++i) { const double gi = Gn[i * kk + i]; dd[i] = (gi > 0.0 && isfinite(gi)) ? 1.0 / sqrt(gi) : 0.0; }
-  for (int i = 0; i < kk; ++i) {
-    for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
-    bb[i] = tot[kk + i] * dd[i];
-  }
-  bool dep[kKfMaxR];
-  for (int c = 0; c < kk; ++c) {
-    const double piv = Gn[c * kk + c];
-    dep[c] = !(piv > tiny);
-    if (dep[c]) { Gn[c * kk + c] = 1.0; for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0; continue; }
-    const double l = sqrt(piv);
-    Gn[c * kk + c] = l;
-    for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
-    for (int i = c + 1; i < kk; ++i)
-      for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
-  }
-  for (int r = 0; r < kk; ++r) {
-    double v = bb[r];
-    for (int j = 0; j < r; ++j) v -= Gn[r * kk + j] * bb[j];
-    bb[r] = dep[r] ? 0.0 : v / Gn[r * kk + r];
-  }
-  for (int r = kk - 1; r >= 0; --r) {
-    double v = bb[r];
-    for (int j = r + 1; j < kk; ++j) v -= Gn[j * kk + r] * bb[j];
-    bb[r] = dep[r] ? 0.0 : v / Gn[r * kk + r];
-  }
-  for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; st.coef[((int64_t)k * R + r) * R + a] = bb[r]; vec[r] = bb[r]; }
+  fold_normal_solve(Gn, tot + kk, kk, dd, bb);                      // fold_regress.hpp
+  for (int r = 0; r < kk; ++r) { st.coef[((int64_t)k * R + r) * R + a] = bb[r]; vec[r] = bb[r]; }
   for (int r = 0; r < kk; ++r) {                                  // c = T^T yhat = (T^T T) b, the training Gram
     double v = 0.0;
     for (int j = 0; j < kk; ++j) v = fma(Gt[r * R + j], bb[j], v);

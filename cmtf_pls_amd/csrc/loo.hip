@@ -16,6 +16,7 @@
 // Limits (the caller falls back to one refit per fold on the regular engine otherwise): X of order 2 or 3 without
 // missing values, min(A, B) <= 64, M <= 64, R <= 16, and the per-workgroup vectors must fit 150 KB of LDS.
 #include "common.hpp"
+#include "fold_regress.hpp"
 
 namespace cmtfpls {
 
@@ -236,59 +237,8 @@ __global__ __launch_bounds__(NT) void loo_tpls_kernel(LooArgs a) {
       if (tid == 0) a.ssq_out[2 * (comp + 1)] = ssx;
     }
     __syncthreads();
-    // inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112): normal equations, equilibrated Cholesky
-    const int kk = comp + 1;
-    for (int o = tid; o < kk * kk + kk; o += kLooThreads) {
-      double s = 0.0;
-      if (o < kk * kk) {
-        const int p = o / kk, s2 = o % kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], T[(int64_t)r * R + s2], s);
-        Gn[o] = s;
-      } else {
-        const int p = o - kk * kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], u[r], s);
-        gn[p] = s;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const double tiny = (double)kk * 2.220446049250313e-16;
-      for (int i = 0; i < kk; ++i) { const double g = Gn[i * kk + i]; dd[i] = (g > 0.0 && isfinite(g)) ? 1.0 / sqrt(g) : 0.0; }
-      for (int i = 0; i < kk; ++i) {
-        for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
-        bb[i] = gn[i] * dd[i];
-      }
-      bool dep[kLooMaxR];
-      for (int c = 0; c < kk; ++c) {
-        const double piv = Gn[c * kk + c];
-        dep[c] = !(piv > tiny);
-        if (dep[c]) { Gn[c * kk + c] = 1.0; for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0; continue; }
-        const double l = sqrt(piv);
-        Gn[c * kk + c] = l;
-        for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
-        for (int i = c + 1; i < kk; ++i)
-          for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
-      }
-      for (int r = 0; r < kk; ++r) {
-        double s = bb[r];
-        for (int j = 0; j < r; ++j) s -= Gn[r * kk + j] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = kk - 1; r >= 0; --r) {
-        double s = bb[r];
-        for (int j = r + 1; j < kk; ++j) s -= Gn[j * kk + r] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; coef[r * R + comp] = bb[r]; }
-    }
-    __syncthreads();
-    // Y -= T b q^T (tpls.py:113); t is free: reuse it for yhat = T b
-    for (int r = tid; r < I; r += kLooThreads) {
-      double s = 0.0;
-      for (int j = 0; j < kk; ++j) s = fma(T[(int64_t)r * R + j], bb[j], s);
-      t[r] = s;
-    }
-    __syncthreads();
+    // inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112), fold_regress.hpp; then Y -= T b q^T (tpls.py:113), yhat = T b in t
+    fold_inner_regression<NT, false>(T, u, nullptr, I, R, comp, Gn, gn, bb, dd, coef, t);
     double ssy = 0.0;
     for (int64_t idx = tid; idx < (int64_t)I * M; idx += kLooThreads) {
       const int r = (int)(idx / M), m = (int)(idx % M);

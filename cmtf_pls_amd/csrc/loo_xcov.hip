@@ -29,6 +29,7 @@
 // wL (B2), v (B), tmp (max(A, B1, B2)) and part (1024); workspace: lx_cp3's U, yl, vr (P each) after wk
 // (cmtfpls_loo_xcov_tensor_fold_workspace_bytes).
 #include "fold_loop.hpp"
+#include "fold_regress.hpp"
 
 namespace cmtfpls {
 
@@ -203,59 +204,8 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(typename LooXArgsOf<TEN
       for (int64_t c = tid; c < P; c += kLxNT) xr[c] = fma(-tr, wk[c], xr[c]);
     }
     __syncthreads();
-    // ---- inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112): normal equations, equilibrated Cholesky (as loo.hip) ----
-    const int kk = comp + 1;
-    for (int o = tid; o < kk * kk + kk; o += kLxNT) {
-      double s = 0.0;
-      if (o < kk * kk) {
-        const int p = o / kk, s2 = o % kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], T[(int64_t)r * R + s2], s);
-        Gn[o] = s;
-      } else {
-        const int p = o - kk * kk;
-        for (int r = 0; r < I; ++r) s = fma(T[(int64_t)r * R + p], u[r], s);
-        gn[p] = s;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const double tiny = (double)kk * 2.220446049250313e-16;
-      for (int i = 0; i < kk; ++i) { const double g = Gn[i * kk + i]; dd[i] = (g > 0.0 && isfinite(g)) ? 1.0 / sqrt(g) : 0.0; }
-      for (int i = 0; i < kk; ++i) {
-        for (int j = 0; j < kk; ++j) Gn[i * kk + j] *= dd[i] * dd[j];
-        bb[i] = gn[i] * dd[i];
-      }
-      bool dep[kLxMaxR];
-      for (int c = 0; c < kk; ++c) {
-        const double piv = Gn[c * kk + c];
-        dep[c] = !(piv > tiny);
-        if (dep[c]) { Gn[c * kk + c] = 1.0; for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] = 0.0; continue; }
-        const double l = sqrt(piv);
-        Gn[c * kk + c] = l;
-        for (int i = c + 1; i < kk; ++i) Gn[i * kk + c] /= l;
-        for (int i = c + 1; i < kk; ++i)
-          for (int j = c + 1; j <= i; ++j) Gn[i * kk + j] -= Gn[i * kk + c] * Gn[j * kk + c];
-      }
-      for (int r = 0; r < kk; ++r) {
-        double s = bb[r];
-        for (int j = 0; j < r; ++j) s -= Gn[r * kk + j] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = kk - 1; r >= 0; --r) {
-        double s = bb[r];
-        for (int j = r + 1; j < kk; ++j) s -= Gn[j * kk + r] * bb[j];
-        bb[r] = dep[r] ? 0.0 : s / Gn[r * kk + r];
-      }
-      for (int r = 0; r < kk; ++r) { bb[r] *= dd[r]; coef[r * R + comp] = bb[r]; }
-    }
-    __syncthreads();
-    // ---- Y -= T b q^T (tpls.py:113); t is free: reuse it for yhat = T b ----
-    for (int r = tid; r < I; r += kLxNT) {
-      double s = 0.0;
-      for (int j = 0; j < kk; ++j) s = fma(T[(int64_t)r * R + j], bb[j], s);
-      t[r] = s;
-    }
-    __syncthreads();
+    // ---- inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112), fold_regress.hpp; then Y -= T b q^T (tpls.py:113), yhat = T b in t ----
+    fold_inner_regression<kLxNT, false>(T, u, nullptr, I, R, comp, Gn, gn, bb, dd, coef, t);
     for (int64_t idx = tid; idx < (int64_t)I * M; idx += kLxNT) {
       const int r = (int)(idx / M), m = (int)(idx % M);
       Yf[idx] = fma(-t[r], q[m], Yf[idx]);

@@ -17,7 +17,8 @@ constexpr int kSolveMax = 64;
 // tolerates (rcond = machine precision relative to T's largest singular value); solving the raw normal
 // equations would square that spread.  A column whose pivot falls below k * eps after equilibration is linearly
 // dependent on the earlier ones to working precision (or identically zero): its coefficient is set to 0 and it
-// is dropped from the system, which is what a truncated least-squares solve does with it.
+// is dropped from the system, which is what a truncated least-squares solve does with it.  (The one-thread form of the same
+// rule, used inside the fold kernels, is fold_normal_solve in fold_regress.hpp.)
 __global__ __launch_bounds__(kSolveMax) void normal_solve_kernel(const double* __restrict__ G, const double* __restrict__ g, int k,
                                                                 double* __restrict__ b, int incb) {
   __shared__ double A[kSolveMax][kSolveMax + 1];

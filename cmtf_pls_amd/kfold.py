@@ -514,6 +514,11 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
 MASKED_FORM = "cmtfpls_cv_masked_f64"
 
 
+def _f64(a, dev):
+    """The original data in float64, on the device."""
+    return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
+
+
 def has_missing(X) -> bool:
     """Whether X (a host array or a device tensor) holds a NaN."""
     if isinstance(X, torch.Tensor):
@@ -544,12 +549,9 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
-    def f64(a):                                                                 # the original data in float64, on the device
-        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
-
     with eng.device_ctx():
-        out = be.cv_masked(f64(X).contiguous().view(I, -1), f64(Y).contiguous().view(I, M), _to_dev(ids, dev, torch.int32), K, A, B, R,
-                           tol, max_iter)
+        out = be.cv_masked(_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M),
+                           _to_dev(ids, dev, torch.int32), K, A, B, R, tol, max_iter)
         if out is None:
             return None, (f"shape outside {MASKED_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
                           f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
@@ -590,13 +592,10 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
-    def f64(a):                                                                 # the original data in float64, on the device
-        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
-
     with eng.device_ctx():
-        out = be.cv_masked_models(f64(X).contiguous().view(I, -1), f64(Y).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
-                                  None if yrow is None else _to_dev(yrow, dev, torch.int32), A, B, R, tol, max_iter, factors,
-                                  max_ws_bytes)
+        out = be.cv_masked_models(_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M),
+                                  _to_dev(counts, dev, torch.int32), None if yrow is None else _to_dev(yrow, dev, torch.int32),
+                                  A, B, R, tol, max_iter, factors, max_ws_bytes)
         if out is None:
             return None, (f"shape outside {MODELS_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
                           f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
@@ -699,14 +698,12 @@ def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndar
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
-    def f64(a):                                                                 # the original data in float64, on the device
-        return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
-
     with eng.device_ctx():
         out = None
         if len(Xs) <= MAX_BLOCKS:                                                # (the entry declines more blocks itself)
-            out = be.cv_masked_coupled([f64(X).contiguous().view(I, -1) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
-                                       f64(Y).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+            out = be.cv_masked_coupled([_f64(X, dev).contiguous().view(I, -1) for X in Xs],
+                                       [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
+                                       _f64(Y, dev).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
                                        None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol, max_iter, factors, max_ws_bytes)
         if out is None:
             return None, (f"shape outside {COUPLED_FORM} (it takes at most {MAX_BLOCKS} blocks, min(J, K) <= 64 in every block, "

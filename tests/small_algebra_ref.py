@@ -1,6 +1,7 @@
 """NumPy restatements, input generators, bounds and case tables for the small f64 kernels of csrc/small.hip, csrc/solve.hip,
 csrc/rank1_tensor.hip (kron) and the calcR2X pass of csrc/recon.hip.  No GPU and no torch here: tests/test_small_algebra_ref_cpu.py
-checks this module on the CPU, tests/test_gpu_small_algebra_limits.py runs the kernels against it.
+checks this module on the CPU, tests/test_gpu_small_algebra_limits.py runs the kernels against it.  `fold_normal_solve` restates
+the fold kernels' serial solve (csrc/fold_regress.hpp) operation by operation; tests/test_fold_regress_cpu.py compares the two.
 
 Every restatement takes the arguments of the `HipBackend` method of the same name (as NumPy arrays, views included),
 accumulates in `np.longdouble` (64-bit significand) and returns the value together with the magnitude sum of the same
@@ -233,6 +234,48 @@ def khatri_rao(Am, Bm):
 
 def kron(a, b):
     return (a[:, None] * b[None, :]).reshape(-1)
+
+
+def fold_normal_solve(G, g):
+    """csrc/fold_regress.hpp's fold_normal_solve in plain Python floats, one correctly rounded operation per operator and in the
+    header's order (no fused multiply-add): the header compiled for the host without contraction gives the same bits
+    (tests/test_fold_regress_cpu.py).  Returns (b, dropped columns)."""
+    k = len(g)
+    A = [[float(G[i][j]) for j in range(k)] for i in range(k)]
+    tiny = float(k) * 2.220446049250313e-16
+    d = [1.0 / math.sqrt(A[i][i]) if A[i][i] > 0.0 and math.isfinite(A[i][i]) else 0.0 for i in range(k)]
+    b = [0.0] * k
+    for i in range(k):
+        for j in range(k):
+            A[i][j] = A[i][j] * (d[i] * d[j])
+        b[i] = float(g[i]) * d[i]
+    dropped = []
+    for c in range(k):
+        piv = A[c][c]
+        if not piv > tiny:
+            dropped.append(c)
+            A[c][c] = 1.0
+            for i in range(c + 1, k):
+                A[i][c] = 0.0
+            continue
+        l = math.sqrt(piv)
+        A[c][c] = l
+        for i in range(c + 1, k):
+            A[i][c] = A[i][c] / l
+        for i in range(c + 1, k):
+            for j in range(c + 1, i + 1):
+                A[i][j] = A[i][j] - A[i][c] * A[j][c]
+    for r in range(k):
+        s = b[r]
+        for j in range(r):
+            s = s - A[r][j] * b[j]
+        b[r] = 0.0 if r in dropped else s / A[r][r]
+    for r in range(k - 1, -1, -1):
+        s = b[r]
+        for j in range(r + 1, k):
+            s = s - A[j][r] * b[j]
+        b[r] = 0.0 if r in dropped else s / A[r][r]
+    return np.array([b[r] * d[r] for r in range(k)]), dropped
 
 
 def recon(T, WA, WB, mean):
