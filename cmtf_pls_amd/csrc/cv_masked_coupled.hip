@@ -1,8 +1,8 @@
 // Refits of a small coupled model (ctPLS: nb blocks sharing the sample mode and ONE score) whose blocks have missing values, on
 // count-weighted rows, ALL MODELS OF A CHUNK IN ONE LAUNCH: K-fold and leave-one-out Q2Y, the permutation test, repeated K-fold and
-// the bootstrap of such data (validate.py with EngineOptions.masked_folds_coupled).  The count-weighted model of
-// cv_masked_models.hip generalised to 1 <= nb <= 8 blocks: model m is counts[m, r] >= 0 copies of row r of EVERY block paired with
-// Y[yrow[m, r]] (yrow nullable = identity); its arithmetic is the reference's ctPLS.fit (cmtf.py:87-139) on that literal data, the
+// the bootstrap of such data (validate.py with EngineOptions.masked_folds_coupled).  The count-weighted model of cv_masked.hip
+// for 1 <= nb <= 8 blocks, the steps of masked_fold.hpp once per block: model m is counts[m, r] >= 0 copies of row r of EVERY block
+// paired with Y[yrow[m, r]] (yrow nullable = identity); the reference's ctPLS.fit (cmtf.py:87-139) on that literal data, the
 // missing-value arithmetic switched on BLOCK BY BLOCK (Xs_hasMiss[ti], cmtf.py:77-82, 92-121), every sum over rows weighted by c_r.
 // Then the rows with c_r = 0 are predicted as one batch (cmtf.py:141-175) with every component count.  One 256-thread workgroup per
 // model; the model's centred working copies in the workspace, deflated in place; the vectors in LDS.
@@ -23,7 +23,7 @@
 // by it makes every later score of the row NaN: NaN from that component on, as the reference (and projection.py) give.
 // Status 1: a training row with nothing observed in some block (the reference is NaN everywhere); 2: n < 2; 3: a negative count or
 // a yrow outside 0..I-1.  A model with a status writes nothing else.  info[m] = (bit b: block b's training rows took the masked
-// arithmetic, bit b: block b's held-out batch did).  With nb = 1 a model is a model of cv_masked_models_kernel.
+// arithmetic, bit b: block b's held-out batch did).  With nb = 1 a model is a count-weighted model of cv_masked_kernel.
 //
 // Workspace per resident model (doubles): for each block Xf^b (I P_b) | c^b (P_b) | mu^b (P_b); then Yf (I M) | T (I R).
 // LDS (doubles): 3 I (u, t, c) + 3 M (q, q normalised, nu) + 2 R^2 + R M + 3 R (coef, Q, the normal equations) + 256 (partial rows)
@@ -37,6 +37,7 @@
 namespace cmtfpls {
 
 #include "loo_rank1.hpp"
+#include "masked_fold.hpp"
 
 constexpr int kCvcMaxN = 64, kCvcMaxR = 16, kCvcMaxM = 64, kCvcThreads = 256, kCvcMaxBlocks = 8;
 
@@ -73,7 +74,6 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
   const int I = a.I, M = a.M, R = a.R, nb = a.nb;
   const int model = a.model0 + blockIdx.x;
   if (blockIdx.x >= a.nmodels || model >= a.nm) return;
-  const int* cnt_m = a.counts + (int64_t)model * I;
   const int* yrow_m = a.yrow ? a.yrow + (int64_t)model * I : nullptr;
   double* wsm = a.ws + (int64_t)blockIdx.x * a.ws_per_model;
   // LDS carve-up: the shared part, the per-block scratch sized for the largest block, then each block's own vectors
@@ -130,69 +130,26 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
 
   if (tid == 0) a.status[model] = 0;
   // ---- counts and training size; a bad count or Y row stops the model before Y is read
-  double nt = 0.0, bad = 0.0;
-  for (int r = tid; r < I; r += NT) {
-    const int c = cnt_m[r];
-    const int yr = yrow_m ? yrow_m[r] : r;
-    if (c < 0 || yr < 0 || yr >= I) bad = 1.0;
-    cw[r] = c > 0 ? (double)c : 0.0;
-    nt += c > 0 ? (double)c : 0.0;
-  }
-  const double nf = loo_sum<NT>(nt, red);                                       // (its barriers publish cw)
-  if (loo_sum<NT>(bad, red) > 0.0) { if (tid == 0) a.status[model] = 3; return; }   // uniform
-  if (nf < 2.0) { if (tid == 0) a.status[model] = 2; return; }                 // uniform
+  double nf;
+  const int st = mf_weights<NT>(a.counts + (int64_t)model * I, yrow_m, I, cw, &nf, red);
+  if (st != 0) { if (tid == 0) a.status[model] = st; return; }                  // uniform
   for (int o = tid; o < R * R; o += NT) coef[o] = 0.0;
   // ---- means (cmtf.py:74-75, np.nanmean on the resampled rows), the masked flag per block (cmtf.py:77)
   unsigned missmask = 0u;
   for (int b = 0; b < nb; ++b) {
     CVC_BLOCK(b);
-    double missing = 0.0;
-    for (int c = tid; c < P; c += NT) {
-      double s = 0.0, cp = 0.0;
-      for (int r = 0; r < I; ++r) {
-        const double w = cw[r];
-        if (w == 0.0) continue;
-        const double x = Xo[(int64_t)r * P + c];
-        if (!isnan(x)) { s = fma(w, x, s); cp += w; }
-      }
-      cs[c] = cp;
-      mu[c] = cp > 0.0 ? s / cp : __builtin_nan("");
-      if (cp < nf) missing = 1.0;
-    }
+    const double missing = mf_weighted_means<NT>(Xo, cw, I, P, nf, cs, mu);
     if (loo_sum<NT>(missing, red) > 0.0) missmask |= 1u << b;                  // (its barriers publish cs, mu)
   }
-  for (int m = tid; m < M; m += NT) {
-    double s = 0.0;
-    for (int r = 0; r < I; ++r) {
-      const double w = cw[r];
-      if (w != 0.0) s = fma(w, a.Y[(int64_t)(yrow_m ? yrow_m[r] : r) * M + m], s);
-    }
-    my[m] = s / nf;
-  }
+  mf_weighted_mean_y<NT>(a.Y, yrow_m, cw, I, M, nf, my);
   __syncthreads();
-  // ---- working copies: centred, zero at held-out rows and missing entries; observed entries of every row (a training row
-  // without any in some block makes the reference's block score 0 / 0)
+  // ---- working copies; a training row without an observed entry in some block makes the reference's block score 0 / 0
   double empty = 0.0;
   for (int b = 0; b < nb; ++b) {
     CVC_BLOCK(b);
-    for (int64_t idx = tid; idx < (int64_t)I * P; idx += NT) {
-      const int r = (int)(idx / P), c = (int)(idx % P);
-      const double x = Xo[idx];
-      Xf[idx] = (cw[r] == 0.0 || isnan(x)) ? 0.0 : x - mu[c];
-    }
-    for (int r = wv; r < I; r += NT / 64) {
-      double cnt = 0.0;
-      for (int c = lane; c < P; c += 64) cnt += isnan(Xo[(int64_t)r * P + c]) ? 0.0 : 1.0;
-      cnt = wave_sum(cnt);
-      if (lane == 0) ro[r] = cnt;
-      if (cw[r] != 0.0 && cnt == 0.0) empty = 1.0;
-    }
+    if (mf_working_copy<NT>(Xo, cw, mu, I, P, Xf, ro) != 0.0) empty = 1.0;
   }
-  for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
-    const int r = (int)(idx / M), m = (int)(idx % M);
-    Yf[idx] = (cw[r] == 0.0) ? 0.0 : a.Y[(int64_t)(yrow_m ? yrow_m[r] : r) * M + m] - my[m];
-  }
-  for (int64_t idx = tid; idx < (int64_t)I * R; idx += NT) T[idx] = 0.0;
+  mf_working_copy_y<NT>(a.Y, yrow_m, cw, my, I, M, R, Yf, T);
   if (loo_sum<NT>(empty, red) > 0.0) { if (tid == 0) a.status[model] = 1; return; }   // uniform (its barriers publish Xf, Yf, ro)
   const double inv_nb = 1.0 / (double)nb;
 
@@ -204,48 +161,13 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
       for (int b = 0; b < nb; ++b) {                                                 // cmtf.py:91-118, the blocks in turn
         CVC_BLOCK(b);
         const bool miss = (missmask >> b) & 1u;
-        const int n = A < B ? A : B, k = A < B ? B : A;
-        const int nrg = (P < NT) ? NT / P : 1;
-        // Z = X x_0 u over the weighted rows (cmtf.py:93), or miss_tensordot: the column's sum / c_p * n, 0 when c_p = 0
-        if (nrg == 1) {
-          for (int c = tid; c < P; c += NT) {
-            double s = 0.0;
-            for (int r = 0; r < I; ++r) s = fma(Xf[(int64_t)r * P + c], cw[r] * u[r], s);
-            Z[c] = miss ? (cs[c] > 0.0 ? s / cs[c] * nf : 0.0) : s;
-          }
-        } else {
-          const int rg = tid / P, c = tid % P;
-          if (rg < nrg) {
-            double s = 0.0;
-            for (int r = rg; r < I; r += nrg) s = fma(Xf[(int64_t)r * P + c], cw[r] * u[r], s);
-            part[rg * P + c] = s;
-          }
-          __syncthreads();
-          for (int c2 = tid; c2 < P; c2 += NT) {
-            double s = 0.0;
-            for (int g = 0; g < nrg; ++g) s += part[g * P + c2];
-            Z[c2] = miss ? (cs[c2] > 0.0 ? s / cs[c2] * nf : 0.0) : s;
-          }
-        }
-        __syncthreads();
-        if (A == 1) {                                                                // cmtf.py:97: Z / norm(Z)
-          double s = 0.0;
-          for (int c = tid; c < P; c += NT) s = fma(Z[c], Z[c], s);
-          const double nz = sqrt(loo_sum<NT>(s, red));
-          for (int c = tid; c < P; c += NT) wB[c] = Z[c] / nz;
-          if (tid == 0) wA[0] = 1.0;
-          __syncthreads();
-        } else {
-          if (n <= 8 && k <= 64) loo_rank1_wave(Z, A, B, wA, wB);                      // cmtf.py:98-103
-          else loo_rank1<NT>(Z, A, B, wA, wB, G0, G1, xs, ys, red, ired);
-        }
+        mf_contract<NT, true>(Xf, u, cw, cs, I, P, miss, nf, part, Z);
+        mf_loading<NT>(Z, A, B, wA, wB, G0, G1, xs, ys, red, ired);
         // t^b = X x_1 wA x_2 wB (cmtf.py:106-110), or miss_mmodedot: the row's sum / o_r * P_b; added to the blocks before it
         // by the row's own wavefront; after the last block the average (cmtf.py:119); held-out rows 0
         const double Pd = (double)P;
         for (int r = wv; r < I; r += NT / 64) {
-          double s = 0.0;
-          for (int c = lane; c < P; c += 64) s = fma(Xf[(int64_t)r * P + c], wA[c / B] * wB[c % B], s);
-          s = wave_sum(s);
+          const double s = mf_row_dot(Xf + (int64_t)r * P, wA, wB, P, B);
           if (lane == 0) {
             double v = (b == 0 ? 0.0 : t[r]) + (miss ? s / ro[r] * Pd : s);
             if (b == nb - 1) v *= inv_nb;
@@ -254,76 +176,26 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
         }
       }
       __syncthreads();
-      // q = Y^T C t / |.| (cmtf.py:120-121)
-      if (tid < M) {
-        double s = 0.0;
-        for (int r = 0; r < I; ++r) s = fma(Yf[(int64_t)r * M + tid], cw[r] * t[r], s);
-        q[tid] = s;
-      }
-      __syncthreads();
-      double qs = (tid < M) ? q[tid] * q[tid] : 0.0;
-      const double qnrm = sqrt(loo_sum<NT>(qs, red));
-      if (tid < M) qn[tid] = q[tid] / qnrm;
-      __syncthreads();
-      // u = Y q and the weighted |u_old - u| (cmtf.py:122-123)
-      double du2 = 0.0;
-      for (int r = tid; r < I; r += NT) {
-        double s = 0.0;
-        for (int m = 0; m < M; ++m) s = fma(Yf[(int64_t)r * M + m], qn[m], s);
-        const double d0 = u[r] - s;
-        du2 = fma(cw[r] * d0, d0, du2);
-        u[r] = s;
-      }
-      const double du = sqrt(loo_sum<NT>(du2, red));
+      const double du = mf_y_step<NT, true>(Yf, t, cw, I, M, q, qn, u, red);
       if (it > 0 && du < a.tol) { ++it; break; }                                     // first pass: oldU = inf (cmtf.py:88)
     }
     if (a.n_iter && tid == 0) a.n_iter[(int64_t)model * R + comp] = it;
-    // store the component; deflate the observed training entries of every block by the shared t (cmtf.py:130-131)
+    // store the component; deflate every block by the shared t, then Y after the inner regression
     for (int r = tid; r < I; r += NT) T[(int64_t)r * R + comp] = t[r];
     for (int m = tid; m < M; m += NT) Qs[comp * M + m] = qn[m];
     for (int b = 0; b < nb; ++b) {
       CVC_BLOCK(b);
-      const bool miss = (missmask >> b) & 1u;
-      for (int j = tid; j < A; j += NT) Wa[comp * A + j] = wA[j];
-      for (int j = tid; j < B; j += NT) Wb[comp * B + j] = wB[j];
-      for (int64_t idx = tid; idx < (int64_t)I * P; idx += NT) {
-        const int r = (int)(idx / P), c = (int)(idx % P);
-        if (cw[r] == 0.0 || (miss && isnan(Xo[idx]))) continue;
-        Xf[idx] = Xf[idx] - t[r] * (wA[c / B] * wB[c % B]);
-      }
+      mf_deflate_x<NT>(Xo, cw, t, wA, wB, I, A, B, comp, (missmask >> b) & 1u, Wa, Wb, Xf);
     }
     __syncthreads();
-    // inner regression b = lstsq(T[:, :k], u) on the weighted rows (cmtf.py:136-138): (T^T C T) b = T^T C u, fold_regress.hpp; then
-    // Y -= T b q^T (cmtf.py:139), yhat = T b in t; held-out rows of T are 0, so their Yf stays 0
-    fold_inner_regression<NT, true>(T, u, cw, I, R, comp, Gn, gn, bb, dd, coef, t);
-    for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
-      const int r = (int)(idx / M), m = (int)(idx % M);
-      Yf[idx] = Yf[idx] - t[r] * qn[m];
-    }
-    __syncthreads();
+    mf_regress_deflate_y<NT, true>(T, u, cw, qn, I, M, R, comp, Gn, gn, bb, dd, coef, t, Yf);
   }
 
-  // ---- predict the held-out rows (cmtf.py:141-175): per block centre with the model's means, THEN mask (NaN after centring,
-  // which takes in the columns without a training observation); a block of the batch is masked when any of its entries is
+  // ---- predict the held-out rows (cmtf.py:141-175): a block of the batch is masked when any of its entries is missing
   unsigned hmask = 0u;
   for (int b = 0; b < nb; ++b) {
     CVC_BLOCK(b);
-    const double Pd = (double)P;
-    double hmiss = 0.0;
-    for (int r = wv; r < I; r += NT / 64) {
-      if (cw[r] != 0.0) continue;                                                     // uniform in the wavefront
-      double cnt = 0.0;
-      for (int c = lane; c < P; c += 64) {
-        const double v = Xo[(int64_t)r * P + c] - mu[c];
-        const bool ob = !isnan(v);
-        Xf[(int64_t)r * P + c] = ob ? v : 0.0;
-        cnt += ob ? 1.0 : 0.0;
-      }
-      cnt = wave_sum(cnt);
-      if (lane == 0) ro[r] = cnt;
-      if (cnt < Pd) hmiss = 1.0;
-    }
-    if (loo_sum<NT>(hmiss, red) > 0.0) hmask |= 1u << b;                        // (its barriers publish ro)
+    if (mf_heldout_batch<NT>(Xo, mu, cw, I, P, Xf, ro, red)) hmask |= 1u << b;
   }
   // scores and deflation per component: a wavefront owns a held-out row of every block for all R components (no barrier between
   // them: every lane rereads only the entries it wrote)
@@ -333,45 +205,27 @@ __global__ __launch_bounds__(kCvcThreads) void cv_masked_coupled_kernel(CvMasked
       double sv = 0.0;
       for (int b = 0; b < nb; ++b) {
         CVC_BLOCK(b);
-        double s = 0.0;
-        for (int c = lane; c < P; c += 64) s = fma(Xf[(int64_t)r * P + c], Wa[comp * A + c / B] * Wb[comp * B + c % B], s);
-        s = wave_sum(s);
+        const double s = mf_row_dot(Xf + (int64_t)r * P, Wa + comp * A, Wb + comp * B, P, B);
         sv += ((hmask >> b) & 1u) ? s / ro[r] * (double)P : s;                     // o_r = 0: 0 / 0 = NaN, as the reference
       }
       sv *= inv_nb;
       if (lane == 0) T[(int64_t)r * R + comp] = sv;
       for (int b = 0; b < nb; ++b) {
         CVC_BLOCK(b);
-        const bool hm = (hmask >> b) & 1u;
-        for (int c = lane; c < P; c += 64) {
-          if (hm && isnan(Xo[(int64_t)r * P + c] - mu[c])) continue;
-          Xf[(int64_t)r * P + c] = Xf[(int64_t)r * P + c] - sv * (Wa[comp * A + c / B] * Wb[comp * B + c % B]);
-        }
+        mf_heldout_deflate(Xo + (int64_t)r * P, mu, Wa + comp * A, Wb + comp * B, P, B, sv, (hmask >> b) & 1u, Xf + (int64_t)r * P);
       }
     }
   }
   __syncthreads();
-  // Ypred[m, c - 1] = scores[:, :c] coef_[:c, :c] Q[:, :c]^T + nu for c = 1..R (coef_ upper triangular: one pass over h Q^T)
-  double* yp = a.Ypred + (int64_t)model * R * I * M;
-  for (int64_t o = tid; o < (int64_t)I * M; o += NT) {
-    const int r = (int)(o / M), m = (int)(o % M);
-    if (cw[r] != 0.0) continue;
-    double acc = 0.0;
-    for (int b2 = 0; b2 < R; ++b2) {
-      double h = 0.0;
-      for (int a2 = 0; a2 <= b2; ++a2) h = fma(T[(int64_t)r * R + a2], coef[a2 * R + b2], h);
-      acc = fma(h, Qs[b2 * M + m], acc);
-      yp[((int64_t)b2 * I + r) * M + m] = acc + my[m];
-    }
-  }
+  mf_predict<NT>(T, coef, Qs, my, cw, I, M, R, a.Ypred + (int64_t)model * R * I * M);
   // the model's factors (the bootstrap aligns them on the host)
   for (int b = 0; b < nb; ++b) {
     CVC_BLOCK(b);
-    if (a.Wa) for (int o = tid; o < R * A; o += NT) a.Wa[(int64_t)model * R * a.sumA + (int64_t)R * sOa[b] + o] = Wa[o];
-    if (a.Wb) for (int o = tid; o < R * B; o += NT) a.Wb[(int64_t)model * R * a.sumB + (int64_t)R * sOb[b] + o] = Wb[o];
+    mf_write_factor<NT>(a.Wa, (int64_t)model * R * a.sumA + (int64_t)R * sOa[b], Wa, R * A);
+    mf_write_factor<NT>(a.Wb, (int64_t)model * R * a.sumB + (int64_t)R * sOb[b], Wb, R * B);
   }
-  if (a.coef) for (int o = tid; o < R * R; o += NT) a.coef[(int64_t)model * R * R + o] = coef[o];
-  if (a.Q) for (int o = tid; o < R * M; o += NT) a.Q[(int64_t)model * R * M + o] = Qs[o];
+  mf_write_factor<NT>(a.coef, (int64_t)model * R * R, coef, R * R);
+  mf_write_factor<NT>(a.Q, (int64_t)model * R * M, Qs, R * M);
   if (a.info && tid == 0) {
     a.info[2 * (int64_t)model] = (int)missmask;
     a.info[2 * (int64_t)model + 1] = (int)hmask;

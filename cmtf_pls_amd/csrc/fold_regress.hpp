@@ -1,6 +1,6 @@
 // The inner regression of one component, coef_[:a+1, a] = lstsq(T[:, :a+1], u) (tpls.py:110-112, cmtf.py:135), as the
-// one-workgroup-per-fold kernels run it (loo.hip, loo_xcov.hip, loo_xcov_coupled.hip, cv_masked.hip, cv_masked_models.hip,
-// cv_masked_coupled.hip) and the serial solve inside it, which kfold.hip's kfold_solve_kernel shares.
+// one-workgroup-per-fold kernels run it (loo.hip, loo_xcov.hip, loo_xcov_coupled.hip, and through masked_fold.hpp cv_masked.hip
+// and cv_masked_coupled.hip) and the serial solve inside it, which kfold.hip's kfold_solve_kernel shares.
 #pragma once
 #include <hip/hip_runtime.h>
 

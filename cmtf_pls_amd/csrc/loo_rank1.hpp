@@ -1,6 +1,6 @@
-// Workgroup helpers of the one-workgroup-per-fold kernels (loo.hip: leave-one-out and the whole small fit; cv_masked.hip:
-// folds of X with missing values): a workgroup sum and the rank-1 extraction of a fold's A x B contraction, block and
-// one-wavefront forms.  Include after common.hpp, inside namespace cmtfpls.
+// Workgroup helpers of the one-workgroup-per-fold kernels (loo.hip: leave-one-out and the whole small fit; masked_fold.hpp: the
+// steps of cv_masked.hip and cv_masked_coupled.hip, models of X with missing values): a workgroup sum and the rank-1 extraction
+// of a fold's A x B contraction, block and one-wavefront forms.  Include after common.hpp, inside namespace cmtfpls.
 #pragma once
 
 // sum over the workgroup; every thread gets the same value; two barriers, so back-to-back calls may share `red`

@@ -1,6 +1,6 @@
 """Cross-validation of a ctPLS whose blocks have missing values, every model refitted by one workgroup
 (cmtfpls_cv_masked_coupled_f64, EngineOptions.masked_folds_coupled): one model against the NumPy restatement (coupled_masked_ref),
-one block against cmtfpls_cv_masked_models_f64, chunks of models; then K-fold, leave-one-out, the permutation test, repeated K-fold
+one block equal to cmtfpls_cv_masked_models_f64, chunks of models; then K-fold, leave-one-out, the permutation test, repeated K-fold
 and the bootstrap against literal refits on the regular engine, where the per-block masked arithmetic switches on and off, the
 status paths, the declared limits and one step past them, the declines, and a float32 model.  Every end-to-end test checks the
 report's form and that nothing was refitted, so a silent decline cannot compare refits with refits.  The bound is the family's:
@@ -155,9 +155,10 @@ def test_one_block_equals_the_tpls_kernel(shape):
     got = _kernel(be, [x], y, counts, None, R, factors=True)
     assert not got["status"].any() and torch.equal(got["status"], want["status"])
     assert torch.equal(got["n_iter"], want["n_iter"]) and torch.equal(got["info"], want["info"])
-    assert _rel(got["Ypred"].cpu(), want["Ypred"].cpu()) <= 1e-12
-    for key, g in (("Wa", got["Wa"][0]), ("Wb", got["Wb"][0]), ("coef", got["coef"]), ("Q", got["Q"])):
-        assert _rel(g.cpu(), want[key].cpu()) <= 1e-12, key
+    # the two kernels run the same steps (csrc/masked_fold.hpp); what one block adds, 0.0 + s and * 1.0, is exact
+    for key, g in (("Ypred", got["Ypred"]), ("Wa", got["Wa"][0]), ("Wb", got["Wb"][0]), ("coef", got["coef"]), ("Q", got["Q"])):
+        g, w = g.cpu().numpy(), want[key].cpu().numpy()
+        assert np.array_equal(np.isnan(g), np.isnan(w)) and np.array_equal(g, w, equal_nan=True), key
 
 
 def test_chunked_launches_are_bit_identical():

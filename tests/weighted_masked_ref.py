@@ -1,4 +1,4 @@
-"""NumPy float64 restatement of ONE model of cmtfpls_cv_masked_models_f64 (csrc/cv_masked_models.hip) -- TEST
+"""NumPy float64 restatement of ONE model of cmtfpls_cv_masked_models_f64 (csrc/cv_masked.hip, its count-weighted form) -- TEST
 INFRASTRUCTURE ONLY.  Row r of X appears c_r times in the model's training data, paired with Y row yrow[r]; every sum over rows is
 weighted by c_r, with the reference's missing-value arithmetic (missingvals.py:7-38) when some column has fewer weighted
 observations than n = sum c_r.  The rows with c_r = 0 are predicted as one batch, centred and then masked (tpls.py:122-143).
