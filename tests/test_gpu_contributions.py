@@ -1,6 +1,8 @@
 """Contribution plots on the device (validate.sample_contributions, cmtf_pls_amd/contributions.py): cmtfpls_contrib_rows_* against
 a float64 torch formula (storage types, unaligned shapes, many rows, R 1 / 10 / 16, a row list, the LDS limit, a NaN score row,
-bit-identical repeats, X untouched, the R = 17 and LDS declines), then the estimator on the HIP backend against the float64 NumPy
+bit-identical repeats, X untouched, the R = 17 and LDS declines; both sides of every register-chunk boundary, mean = NULL and a
+misaligned mean, row indices outside X, the rows per workgroup halved by LDS pressure and five rows per workgroup, each with the
+plan restated in tests/resid_rows_ref.py asserted), then the estimator on the HIP backend against the float64 NumPy
 restatement (tests/contributions_ref.py), its report and its agreement with the torch form.
 
 Tolerances.  The squared sums (speA, speB) are sums of non-negative terms: the project's rtol=1e-11, atol=1e-9 for such sums
@@ -16,6 +18,7 @@ from cmtf_pls_amd import ctPLS, tPLS
 from cmtf_pls_amd.backend import HipBackend
 from cmtf_pls_amd.validate import sample_contributions
 from contributions_ref import check, contributions
+from resid_rows_ref import CONTRIB_LDS_CASES, CONTRIB_ODD_G, contrib_g_start, contrib_plan, vec_width
 
 pytestmark = pytest.mark.gpu
 
@@ -121,6 +124,98 @@ def test_contrib_rows_nan_score_row():
     assert torch.isnan(speA[7]).all() and torch.isnan(speB[7]).all() and not torch.isnan(speA[other != 7]).any()
     assert not torch.isnan(speB[other != 7]).any() and not torch.isnan(t2A[7]).any()
     assert torch.isnan(t2A[9]).all() and torch.isnan(t2B[9]).all() and not torch.isnan(t2B[other != 9]).any()
+
+
+def _vec(dtype, B):
+    return vec_width("f32" if dtype == torch.float32 else "f64", B)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("I,A,B", [(300, 5, 7), (257, 6, 8)])      # one element per thread; vector loads
+def test_contrib_rows_register_chunk_boundaries(dtype, I, A, B):
+    """R on both sides of 4 | 5, 8 | 9 and 12 | 13 (R = 5 and 16 run above): the chunks of 4, 8, 12 and 16 registers each at their
+    last width and the next chunk at its first."""
+    be = HipBackend()
+    for R in (4, 8, 9, 12, 13):
+        X2, T, H, WA, WB, mean = _operands(I, A, B, R, dtype, seed=I + R, nan_frac=0.05)
+        got = be.contrib_rows(X2, T, H, WA, WB, mean)
+        _check_kernel(got, _formula(X2, T, H, WA, WB, mean), A, B, R, f"{dtype} {(I, A, B)} R = {R}")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_contrib_rows_without_a_mean_and_with_a_misaligned_one(dtype):
+    """mean = NULL, and a mean one double into its storage while X is 16-byte aligned: the kernel then has to take the
+    one-element path (a vector load of the mean would be misaligned).  Both against the formula; the run with the same mean
+    aligned meets the same bounds."""
+    be = HipBackend()
+    I, A, B, R = 257, 6, 8, 10
+    X2, T, H, WA, WB, mean = _operands(I, A, B, R, dtype, seed=31, nan_frac=0.05)
+    assert X2.data_ptr() % 16 == 0 and mean.data_ptr() % 16 == 0 and _vec(dtype, B) > 1
+    got = be.contrib_rows(X2, T, H, WA, WB, None)
+    _check_kernel(got, _formula(X2, T, H, WA, WB, torch.zeros_like(mean)), A, B, R, f"{dtype} mean = NULL")
+    buf = torch.zeros(A * B + 1, dtype=torch.float64, device="cuda")
+    buf[1:] = mean
+    shifted = buf[1:]
+    assert shifted.data_ptr() % 16 == 8 and torch.equal(shifted, mean)
+    want = _formula(X2, T, H, WA, WB, mean)
+    one = be.contrib_rows(X2, T, H, WA, WB, shifted)
+    _check_kernel(one, want, A, B, R, f"{dtype} misaligned mean")
+    _check_kernel(be.contrib_rows(X2, T, H, WA, WB, mean), want, A, B, R, f"{dtype} aligned mean")
+    assert all(torch.equal(a, b) for a, b in zip(one, be.contrib_rows(X2, T, H, WA, WB, shifted)))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_contrib_rows_row_indices_outside_x(dtype):
+    """Row indices -1 and I among valid ones: NaN in all four outputs of those rows (the guard is in the kernel, the backend
+    passes the list through), every other row as the formula."""
+    be = HipBackend()
+    I, A, B, R, n = 50, 6, 20, 10, 23
+    X2, T, H, WA, WB, mean = _operands(I, A, B, R, dtype, seed=41, nan_frac=0.05)
+    rows = torch.randperm(I, generator=torch.Generator().manual_seed(3))[:n]
+    bad = [0, 4, 11, n - 1]                                          # the first and last row of the list among them
+    rows[bad] = torch.tensor([-1, I, I + 7, -(2 ** 40)])
+    Ts, Hs = T[:n], H[:n].contiguous()
+    got = be.contrib_rows(X2, Ts, Hs, WA, WB, mean, rows=rows.cuda())
+    good = torch.ones(n, dtype=torch.bool)
+    good[bad] = False
+    assert all(bool(torch.isnan(g[bad]).all()) and not bool(torch.isnan(g[good]).any()) for g in got)
+    g = good.cuda()
+    want = _formula(X2, Ts[g], Hs[g], WA, WB, mean, rows=rows[good].cuda())
+    _check_kernel(tuple(t[g] for t in got), want, A, B, R, f"{dtype} row indices outside X")
+
+
+@pytest.mark.parametrize("case,plan", CONTRIB_LDS_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_contrib_rows_group_halved_by_lds_pressure(case, plan):
+    """16385 row indices into an X of 64 rows: 8 rows per workgroup wanted, halved until TH + accumulators + slab fit 160 KB."""
+    be = HipBackend()
+    n, A, B, R, st = case
+    g_start, G, lg = plan
+    assert contrib_g_start(n) == g_start == 8 and contrib_plan(n, R, A, B, vec_width(st, B))[:2] == (G, lg) and G < g_start
+    assert contrib_plan(n, R, A, B, vec_width(st, B))[3] and n % G == 1 % G                      # a ragged last group where G > 1
+    X2, _, _, WA, WB, mean = _operands(64, A, B, R, torch.float32, seed=51 + R, nan_frac=0.02)
+    g = torch.Generator(device="cpu").manual_seed(52)
+    rows = torch.randint(0, 64, (n,), generator=g).cuda()
+    T = torch.randn(n, R, generator=g, dtype=torch.float64).cuda()
+    H = torch.randn(n, R, generator=g, dtype=torch.float64).cuda()
+    got = be.contrib_rows(X2, T, H, WA, WB, mean, rows=rows)
+    _check_kernel(got, _formula(X2, T, H, WA, WB, mean, rows=rows), A, B, R, f"LDS pressure {case} G = {G}")
+    again = be.contrib_rows(X2, T, H, WA, WB, mean, rows=rows)
+    assert all(torch.equal(a, b) for a, b in zip(got, again))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("case,plan", CONTRIB_ODD_G)
+def test_contrib_rows_with_five_rows_per_workgroup(dtype, case, plan):
+    """G = 5, not a power of two: 9000 rows are 1800 whole groups, 9001 leave a last group of one row."""
+    be = HipBackend()
+    n, A, B, R = case
+    G, last = plan
+    assert contrib_plan(n, R, A, B, _vec(dtype, B))[0] == G == 5 and n - (-(-n // G) - 1) * G == last
+    X2, T, H, WA, WB, mean = _operands(n, A, B, R, dtype, seed=n, nan_frac=0.02)
+    got = be.contrib_rows(X2, T, H, WA, WB, mean)
+    _check_kernel(got, _formula(X2, T, H, WA, WB, mean), A, B, R, f"{dtype} {case} G = 5")
+    again = be.contrib_rows(X2, T, H, WA, WB, mean)
+    assert all(torch.equal(a, b) for a, b in zip(got, again))
 
 
 def _fit(shape, R, dtype, nan=0.0, seed=1, coupled=False):

@@ -1,7 +1,8 @@
 """Sample diagnostics on the device (validate.sample_diagnostics, cmtf_pls_amd/diagnostics.py): cmtfpls_resid_rows_* against a
 float64 torch formula (storage types, unaligned shapes, many row blocks, R 1 / 10 / 16, a NaN score row, bit-identical repeats,
 the R = 17 decline), then the estimator on the HIP backend against a float64 NumPy restatement, its read-only behaviour and its
-read counts."""
+read counts.  Every kernel shape here plans to 8 rows per block; tests/test_gpu_resid_rows_forms.py runs the taller plans, and
+the last estimator case runs one of them end to end."""
 import numpy as np
 import pytest
 import torch
@@ -11,6 +12,7 @@ from cmtf_pls_amd import ctPLS, tPLS
 from cmtf_pls_amd.backend import HipBackend
 from cmtf_pls_amd.validate import sample_diagnostics
 from diagnostics_ref import check_against_restatement
+from resid_rows_ref import resid_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -101,8 +103,11 @@ def _fit(shape, R, dtype, nan=0.0, seed=1, coupled=False):
     ((50, 8, 6), 3, 0.1, False),
     ((40, 5, 4, 3), 3, 0.0, False),
     ((45, 7, 6), 3, 0.1, True),
+    ((143357, 2, 4), 3, 0.1, False),       # 70 rows per block in the residual pass: two 64-row chunks, the second of 6 rows
 ])
 def test_estimator_against_restatement(dtype, rtol, shape, R, nan, coupled):
+    if shape[0] > 100000:
+        assert resid_plan(shape[0], int(np.prod(shape[1:])), 4 if dtype == "float32" else 2) == (1, 2048, 70, 67)
     m, X, y = _fit(shape, R, dtype, nan, coupled=coupled)
     d = sample_diagnostics(m)
     assert m.diagnostics_report_["form"] == "fitted scores + residual pass" and m.diagnostics_report_["x_reads"] == [1] * (2 if coupled else 1)
