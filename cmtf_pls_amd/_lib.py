@@ -201,6 +201,12 @@ SIGNATURES = {
     "cmtfpls_cv_masked_model_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_models_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int]
                                      + [_P] * 8 + [_P, c_size_t, _P]),
+    "cmtfpls_cv_masked_tensor_fold_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cmtfpls_cv_masked_tensor_f64": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int,
+                                             c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_cv_masked_tensor_model_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cmtfpls_cv_masked_tensor_models_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int,
+                                                    c_int, c_int] + [_P] * 9 + [_P, c_size_t, _P]),
     "cmtfpls_cv_masked_coupled_workspace_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_coupled_lds_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_coupled_f64": (c_int, [ctypes.POINTER(CvCoupledBlock), c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_double,

@@ -888,6 +888,60 @@ class HipBackend:
             extra=R * I * M * 8)
         return out if out["launches"] is not None else None
 
+    def cv_masked_tensor(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B1: int, B2: int, R: int,
+                         tol: float, max_iter: int, max_ws_bytes: Optional[int] = None
+                         ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, int]]:
+        """cv_masked for X of order 4 (I x A x B1 x B2 as I x A B1 B2, NaN = missing): the rank-1 CP of each fold's A x B1 x B2
+        contraction inside its workgroup (cmtfpls_cv_masked_tensor_f64).  Returns cv_masked's (Ypred, n_iter, status, info) and the
+        number of launches, or None when the shape is outside the form."""
+        I, P = X2.shape
+        M = Y.shape[1]
+        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
+        assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
+        colsum_x, colcnt_x = self.colstats(X2)
+        colsum_y, _ = self.colstats(Y)
+        Ypred = self.zeros(R, I, M)
+        n_iter = torch.zeros(K, R, dtype=torch.int32, device=self.device)
+        status = torch.zeros(K, dtype=torch.int32, device=self.device)
+        info = torch.zeros(K, 2, dtype=torch.int32, device=self.device)
+        fn = self.lib.cmtfpls_cv_masked_tensor_f64
+        args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol),
+                int(max_iter))
+        outs = (_ptr(Ypred), _ptr(n_iter), _ptr(status), _ptr(info))
+        launches = self._chunked_launch("cv_masked_tensor", lambda f0, nf, ws, nb: fn(*args, f0, nf, *outs, ws, nb, self._stream()), K,
+                                        lambda: self.lib.cmtfpls_cv_masked_tensor_fold_workspace_bytes(I, A, B1, B2, M, R),
+                                        self._ws_budget(max_ws_bytes))
+        return None if launches is None else (Ypred, n_iter, status, info, launches)
+
+    def cv_masked_tensor_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int,
+                                B1: int, B2: int, R: int, tol: float, max_iter: int, factors: bool = False,
+                                max_ws_bytes: Optional[int] = None) -> Optional[dict]:
+        """cv_masked_models for X of order 4 (I x A x B1 x B2 as I x A B1 B2, NaN = missing; cmtfpls_cv_masked_tensor_models_f64).
+        Returns cv_masked_models' dict, with `factors` Wa (n, R, A), Wk (n, R, B1), Wl (n, R, B2), coef and Q, or None when the
+        shape is outside the form."""
+        I, P = X2.shape
+        M = Y.shape[1]
+        nm = counts.shape[0]
+        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
+        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
+        out = {"Ypred": self.zeros(nm, R, I, M), "n_iter": torch.zeros(nm, R, dtype=torch.int32, device=self.device),
+               "status": torch.zeros(nm, dtype=torch.int32, device=self.device),
+               "info": torch.zeros(nm, 2, dtype=torch.int32, device=self.device)}
+        if factors:
+            out.update(Wa=self.zeros(nm, R, A), Wk=self.zeros(nm, R, B1), Wl=self.zeros(nm, R, B2), coef=self.zeros(nm, R, R),
+                       Q=self.zeros(nm, R, M))
+        fn = self.lib.cmtfpls_cv_masked_tensor_models_f64
+        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, A, B1, B2, M, R, float(tol),
+                int(max_iter))
+        outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wk", "Wl", "coef", "Q")) if factors else (None,) * 5),
+                _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
+        out["launches"] = self._chunked_launch(
+            "cv_masked_tensor_models", lambda m0, n, ws, nb: fn(*args, m0, n, *outs, ws, nb, self._stream()), nm,
+            lambda: self.lib.cmtfpls_cv_masked_tensor_model_workspace_bytes(I, A, B1, B2, M, R), self._ws_budget(max_ws_bytes),
+            extra=R * I * M * 8)
+        return out if out["launches"] is not None else None
+
     def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
                           max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
         """Refits of a ctPLS whose blocks X2s (each I x P_b, NaN = missing) have missing values on count-weighted rows, a workgroup

@@ -21,7 +21,8 @@ with the Kronecker loading wB = wK (x) wL (kfold.py); the inner entry
 layout, which also leaves every model's wK and wL, so a resample's loadings are [wA, wK, wL] as the refit's are.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every resample as a count-weighted workgroup of
-cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model.  With
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model; X of order 4
+with EngineOptions.masked_tensor_folds takes cmtfpls_cv_masked_tensor_models_f64, its per-mode stacks [wA, wK, wL].  With
 EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
 (kfold.masked_models_coupled), every block's factors aligned by align_factors.
 """
@@ -32,9 +33,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
-                    _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1, has_missing,
-                    masked_coupled_report, masked_models, masked_models_coupled, masked_models_report, wants_masked_coupled)
+from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
+                    _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1, masked_coupled_report,
+                    masked_forms, masked_models, masked_models_coupled, masked_models_report, wants_masked, wants_masked_coupled)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -221,10 +222,10 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
     masked = None
     if not device_folds:
         why = "device folds switched off"
-    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):        # EngineOptions.masked_folds
+    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
         masked, mwhy = masked_models(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
         if masked is None:
-            why = f"the masked form ({MODELS_FORM}) declined: {mwhy}"
+            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {mwhy}"
     elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
         masked, mwhy = masked_models_coupled(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
         if masked is None:
@@ -256,6 +257,8 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
                 continue
             if coupled:
                 modes = [[wb[e].T] if Xb.ndim == 2 else [wa[e].T, wb[e].T] for Xb, wa, wb in zip(Xs, masked["Wa"], masked["Wb"])]
+            elif "tensor" in masked:                                                  # order-4 X: wB = wK (x) wL, the modes themselves
+                modes = [[masked["Wa"][e].T, masked["Wk"][e].T, masked["Wl"][e].T]]
             else:
                 modes = [[masked["Wb"][e].T] if X.ndim == 2 else [masked["Wa"][e].T, masked["Wb"][e].T]]
             res[e] = (modes, masked["Q"][e].T, masked["coef"][e])

@@ -29,7 +29,16 @@
 // 2: n < 2; 3 (count-weighted form): a negative count or a yrow outside 0..I-1.  A model with a status writes nothing else.
 // Limits: those of the LDS form (min(A, B) <= 64, M <= 64, R <= 16, the vectors plus the per-row counts and weights within 150 KB
 // of LDS); the fold form 1 <= K <= I.
+//
+// TENSOR (cmtfpls_cv_masked_tensor_f64, cmtfpls_cv_masked_tensor_models_f64): X of order 4, I x A x B1 x B2.  The same kernel on the
+// I x A x B view with B = B1 B2: Z (A x B1 x B2, in LDS, already rescaled by mf_contract when the model is masked) goes through the
+// rank-1 CP of fold_loop.hpp (lx_cp3, tpls.py:86-88 on a tensor Z) in place of mf_loading, and its wA and wB = wK (x) wL feed the
+// unchanged steps.  lx_cp3 is templated on the thread count; this form runs it, and the mf_* steps, at 512 threads, where a wavefront
+// has 256 registers and the inlined CP spills nothing (at 1024 threads and 128 registers it does); its Zt, U, yl and vr (P doubles each)
+// follow the model's means in the workspace; G0 / G1 and xs are sized for the largest short side n of the three unfoldings of Z,
+// min(A, B1 B2), min(B1, A B2), min(B2, A B1).  Limits: that n <= 64, M <= 64, R <= 16, the LDS within 150 KB, 1 <= K <= I.
 #include "common.hpp"
+#include "fold_loop.hpp"
 #include "fold_regress.hpp"
 
 namespace cmtfpls {
@@ -37,7 +46,7 @@ namespace cmtfpls {
 #include "loo_rank1.hpp"
 #include "masked_fold.hpp"
 
-constexpr int kCvMaxN = 64, kCvMaxR = 16, kCvMaxM = 64, kCvThreads = 256;
+constexpr int kCvMaxN = 64, kCvMaxR = 16, kCvMaxM = 64, kCvThreads = 256, kCvTensorThreads = 512;
 
 struct CvMaskedArgs {
   const double* X;        // (I, P) original, uncentred, NaN = missing
@@ -59,20 +68,35 @@ struct CvMaskedArgs {
   int64_t ws_per_model;   // doubles
   int I, A, B, M, R, nm, max_iter, model0, nmodels;   // nm = K in the fold form
   double tol;
+  int B1, B2;             // TENSOR: the trailing dims of X, B = B1 B2
+  double* Wk;             // TENSOR: (nm, R, B1) (nullable)
+  double* Wl;             // TENSOR: (nm, R, B2) (nullable)
 };
+
+// TENSOR: the largest short side of the three unfoldings of an A x B1 x B2 tensor
+__host__ __device__ inline int cv_tensor_short_side(int A, int B1, int B2) {
+  const int64_t P = (int64_t)A * B1 * B2;
+  int64_t n = 0;
+  for (const int d : {A, B1, B2}) {
+    const int64_t s = d < P / d ? d : P / d;
+    if (s > n) n = s;
+  }
+  return n > INT32_MAX ? INT32_MAX : (int)n;
+}
 
 // The reduction buffers of loo_sum and loo_rank1: one pair for both instantiations.  Declared inside the kernel every instantiation
 // gets its own pair, and the compiler's LDS layout for a module with two such kernels costs each of them 2 VGPRs.
 __shared__ double red[16];
 __shared__ int ired[4];
 
-template <bool MODELS>
-__global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
-  constexpr int NT = kCvThreads;
+template <bool MODELS, bool TENSOR = false>
+__global__ __launch_bounds__(TENSOR ? kCvTensorThreads : kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
+  constexpr int NT = TENSOR ? kCvTensorThreads : kCvThreads;
   extern __shared__ double sm[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int I = a.I, A = a.A, B = a.B, M = a.M, R = a.R, P = A * B;
-  const int n = A < B ? A : B, k = A < B ? B : A;
+  const int n = TENSOR ? cv_tensor_short_side(A, a.B1, a.B2) : (A < B ? A : B);
+  const int k = TENSOR ? 0 : (A < B ? B : A);       // (ys: the CP keeps its long vector in the workspace)
   const int model = a.model0 + blockIdx.x;
   if (blockIdx.x >= a.nmodels || model >= a.nm) return;
   const int* rows_m = MODELS ? a.rows + (int64_t)model * I : a.rows;
@@ -107,6 +131,23 @@ __global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
   double* part = dd + R;          // NT doubles: partial rows of the contraction when P < NT
   double* ro = part + NT;         // I: observed entries of each row (o_r)
   double* cw = ro + I;            // I: 0 = held out, otherwise the row's weight c_r (1 in the fold form)
+  LxTensor tn;                    // TENSOR: the CP's vectors after cw, its unfoldings after mu; part is shared with mf_contract
+  double* bestv = nullptr;
+  int* besti = nullptr;
+  if constexpr (TENSOR) {
+    const int dmax = A > a.B1 ? (A > a.B2 ? A : a.B2) : (a.B1 > a.B2 ? a.B1 : a.B2);
+    tn.B1 = a.B1; tn.B2 = a.B2;
+    tn.wK = cw + I;
+    tn.wL = tn.wK + a.B1;
+    tn.v = tn.wL + a.B2;
+    tn.tmp = tn.v + B;
+    tn.part = part;
+    bestv = tn.tmp + dmax;        // NT / 64 doubles, then NT / 64 ints
+    besti = reinterpret_cast<int*>(bestv + NT / 64);
+    tn.U = mu + 2 * (int64_t)P;
+    tn.yl = tn.U + P;
+    tn.vr = tn.yl + P;
+  }
 
   if (tid == 0) a.status[model] = 0;
   double nf, missing = 0.0;
@@ -163,7 +204,8 @@ __global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
     int it = 0;
     for (; it < a.max_iter; ++it) {                                                  // tpls.py:79
       mf_contract<NT, MODELS>(Xf, u, cw, cs, I, P, miss, nf, part, Z);
-      mf_loading<NT>(Z, A, B, wA, wB, G0, G1, xs, ys, red, ired);
+      if constexpr (TENSOR) lx_cp3<NT>(Z, mu + P, A, a.tol, tn, wA, wB, G0, G1, xs, red, bestv, besti);   // wB = wK (x) wL
+      else mf_loading<NT>(Z, A, B, wA, wB, G0, G1, xs, ys, red, ired);
       // t = X x_1 wA x_2 wB (tpls.py:97-99), or miss_mmodedot (missingvals.py:37): the row's sum / o_r * P; held-out rows 0
       for (int r = wv; r < I; r += NT / 64) {
         const double s = mf_row_dot(Xf + (int64_t)r * P, wA, wB, P, B);
@@ -178,6 +220,10 @@ __global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
     for (int r = tid; r < I; r += NT) T[(int64_t)r * R + comp] = t[r];
     for (int m = tid; m < M; m += NT) Qs[comp * M + m] = qn[m];
     mf_deflate_x<NT>(a.X, cw, t, wA, wB, I, A, B, comp, miss, Wa, Wb, Xf);
+    if constexpr (MODELS && TENSOR) {                                                // the modes of wB, straight to the outputs
+      mf_write_factor<NT>(a.Wk, ((int64_t)model * R + comp) * a.B1, tn.wK, a.B1);
+      mf_write_factor<NT>(a.Wl, ((int64_t)model * R + comp) * a.B2, tn.wL, a.B2);
+    }
     __syncthreads();
     mf_regress_deflate_y<NT, MODELS>(T, u, cw, qn, I, M, R, comp, Gn, gn, bb, dd, coef, t, Yf);
   }
@@ -200,7 +246,7 @@ __global__ __launch_bounds__(kCvThreads) void cv_masked_kernel(CvMaskedArgs a) {
   mf_predict<NT>(T, coef, Qs, my, cw, I, M, R, MODELS ? a.Ypred + (int64_t)model * R * I * M : a.Ypred);
   if constexpr (MODELS) {                                                            // the model's factors (the bootstrap aligns them on the host)
     mf_write_factor<NT>(a.Wa, (int64_t)model * R * A, Wa, R * A);
-    mf_write_factor<NT>(a.Wb, (int64_t)model * R * B, Wb, R * B);
+    if constexpr (!TENSOR) mf_write_factor<NT>(a.Wb, (int64_t)model * R * B, Wb, R * B);
     mf_write_factor<NT>(a.coef, (int64_t)model * R * R, coef, R * R);
     mf_write_factor<NT>(a.Q, (int64_t)model * R * M, Qs, R * M);
   }
@@ -222,11 +268,36 @@ static size_t cv_masked_workspace_bytes(int I, int A, int B, int M, int R) {
   return ((size_t)I * A * B + (size_t)I * M + (size_t)I * R + 2 * (size_t)A * B) * sizeof(double);
 }
 
-template <bool MODELS>
+// TENSOR: the carve-up above with B = B1 B2, n the largest short side, no ys, kCvTensorThreads partials, then wK, wL, v, the CP's unscaled
+// contraction (max(A, B1, B2)) and its argmax scratch (a double and an int per wavefront)
+static size_t cv_masked_tensor_lds_bytes(int I, int A, int B1, int B2, int M, int R) {
+  const size_t B = (size_t)B1 * B2, P = (size_t)A * B, n = (size_t)cv_tensor_short_side(A, B1, B2);
+  const size_t dmax = (size_t)(A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2));
+  const size_t dbl = 2 * (size_t)I + P + A + B + 2 * (size_t)M + 2 * n * n + n + M + (size_t)R * R + (size_t)R * (A + B) +
+                     (size_t)R * M + (size_t)R * R + 3 * (size_t)R + (size_t)kCvTensorThreads + 2 * (size_t)I + B1 + B2 + B + dmax +
+                     kCvTensorThreads / 64 + kCvTensorThreads / 128;
+  return dbl * sizeof(double);
+}
+
+// TENSOR: the order-3 workspace, then Zt | U | yl | vr of the CP (P doubles each)
+static size_t cv_masked_tensor_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
+  if (I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0) return 0;
+  const size_t P = (size_t)A * B1 * B2;
+  return ((size_t)I * P + (size_t)I * M + (size_t)I * R + 6 * P) * sizeof(double);
+}
+
+// Whether the TENSOR form takes the shape (every limit in 64-bit arithmetic, before a pointer is touched)
+static bool cv_masked_tensor_fits(int I, int A, int B1, int B2, int M, int R) {
+  if ((int64_t)A * B1 * B2 > INT32_MAX / 2) return false;
+  return cv_tensor_short_side(A, B1, B2) <= kCvMaxN && M <= kCvMaxM && R <= kCvMaxR &&
+         cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R) <= 150 * 1024;
+}
+
+template <bool MODELS, bool TENSOR = false>
 static void cv_masked_launch(const CvMaskedArgs& a, size_t lds, void* stream) {
-  const auto kernel = cv_masked_kernel<MODELS>;
+  const auto kernel = cv_masked_kernel<MODELS, TENSOR>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kernel, dim3(a.nmodels), dim3(kCvThreads), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, dim3(a.nmodels), dim3(TENSOR ? kCvTensorThreads : kCvThreads), lds, (hipStream_t)stream, a);
 }
 
 }  // namespace cmtfpls
@@ -291,6 +362,67 @@ int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* co
   a.I = I; a.A = A; a.B = B; a.M = M; a.R = R; a.nm = nm; a.max_iter = max_iter; a.model0 = model0; a.nmodels = nmodels; a.tol = tol;
   cv_masked_launch<true>(a, lds, stream);
   return check_launch("cv_masked_models");
+}
+
+size_t cmtfpls_cv_masked_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
+  return cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
+}
+
+size_t cmtfpls_cv_masked_tensor_model_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
+  return cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
+}
+
+int cmtfpls_cv_masked_tensor_f64(const double* X, const double* Y, const int* fold_of, int K, const double* colsum_x,
+                                 const double* colcnt_x, const double* colsum_y, int I, int A, int B1, int B2, int M, int R, double tol,
+                                 int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status, int* info, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (!X || !Y || !fold_of || !colsum_x || !colcnt_x || !colsum_y || !Ypred || !status || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 ||
+      M <= 0 || R <= 0 || max_iter <= 0 || K <= 0 || fold0 < 0 || nfolds <= 0) {
+    set_error("cv_masked_tensor: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if (K > I || !cv_masked_tensor_fits(I, A, B1, B2, M, R)) {
+    set_error("cv_masked_tensor: shape outside the one-workgroup-per-fold form; refit per fold on the regular engine");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  if (fold0 + nfolds > K) { set_error("cv_masked_tensor: folds out of range"); return CMTFPLS_EINVAL; }
+  const size_t per = cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
+  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("cv_masked_tensor: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  CvMaskedArgs a = {};
+  a.X = X; a.Y = Y; a.rows = fold_of; a.colsum_x = colsum_x; a.colcnt_x = colcnt_x; a.colsum_y = colsum_y;
+  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter; a.status = status; a.info = info;
+  a.ws_per_model = (int64_t)(per / sizeof(double));
+  a.I = I; a.A = A; a.B = B1 * B2; a.B1 = B1; a.B2 = B2; a.M = M; a.R = R; a.nm = K; a.max_iter = max_iter; a.model0 = fold0;
+  a.nmodels = nfolds; a.tol = tol;
+  cv_masked_launch<false, true>(a, cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R), stream);
+  return check_launch("cv_masked_tensor");
+}
+
+int cmtfpls_cv_masked_tensor_models_f64(const double* X, const double* Y, const int* counts, const int* yrow, int nm, int I, int A,
+                                        int B1, int B2, int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred,
+                                        double* Wa, double* Wk, double* Wl, double* coef, double* Q, int* n_iter, int* status,
+                                        int* info, void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !Y || !counts || !Ypred || !status || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0 || max_iter <= 0 ||
+      nm <= 0 || model0 < 0 || nmodels <= 0) {
+    set_error("cv_masked_tensor_models: bad argument");
+    return CMTFPLS_EINVAL;
+  }
+  if (!cv_masked_tensor_fits(I, A, B1, B2, M, R)) {
+    set_error("cv_masked_tensor_models: shape outside the one-workgroup-per-model form; refit per model on the regular engine");
+    return CMTFPLS_EUNSUPPORTED;
+  }
+  if (model0 + nmodels > nm) { set_error("cv_masked_tensor_models: models out of range"); return CMTFPLS_EINVAL; }
+  const size_t per = cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
+  if (!ws || ws_bytes < per * (size_t)nmodels) { set_error("cv_masked_tensor_models: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  CvMaskedArgs a = {};
+  a.X = X; a.Y = Y; a.rows = counts; a.yrow = yrow;
+  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.Wa = Wa; a.Wk = Wk; a.Wl = Wl; a.coef = coef; a.Q = Q;
+  a.n_iter = n_iter; a.status = status; a.info = info;
+  a.ws_per_model = (int64_t)(per / sizeof(double));
+  a.I = I; a.A = A; a.B = B1 * B2; a.B1 = B1; a.B2 = B2; a.M = M; a.R = R; a.nm = nm; a.max_iter = max_iter; a.model0 = model0;
+  a.nmodels = nmodels; a.tol = tol;
+  cv_masked_launch<true, true>(a, cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R), stream);
+  return check_launch("cv_masked_tensor_models");
 }
 
 }  // extern "C"

@@ -7,19 +7,20 @@
 
 namespace cmtfpls {
 
-constexpr int kLxNT = 1024, kLxWaves = kLxNT / 64;
+constexpr int kLxNT = 1024, kLxWaves = kLxNT / 64;    // the workgroup of the helpers below unless they are given another (NT)
 constexpr int kLxMaxN = 256, kLxMaxM = 128, kLxMaxR = 64;     // (M: as far as the M x M Gram of the responses fits the LDS next to the rest)
 
 typedef double lx_d4_t __attribute__((ext_vector_type(4)));
 
 // sum over the workgroup; every thread gets the same value; two barriers, so back-to-back calls may share `red`
+template <int NT = kLxNT>
 __device__ __forceinline__ double lx_sum(double v, double* red) {
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = 0.0;
 #pragma unroll
-  for (int w = 0; w < kLxWaves; ++w) s += red[w];
+  for (int w = 0; w < (NT / 64); ++w) s += red[w];
   __syncthreads();
   return s;
 }
@@ -30,6 +31,7 @@ __device__ __forceinline__ double lx_sum(double v, double* red) {
 //   lane group kq takes the 8 consecutive columns c0 + 8 kq + (0..7) of a 32-column chunk, MFMA s multiplies column
 //   c0 + 8 kq + s of row i0 + (l & 15) with the same column of row j0 + (l & 15) (B = Mx^T).
 // The mirrored tile is written from the same registers (C is bitwise symmetric).  Returns tr(C) and |C|_F^2 to every thread.
+template <int NT = kLxNT>
 __device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, double* C_keep, double scale2, double* red,
                         double* tr_out, double* fro_out) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, ri = lane & 15, kq = lane >> 4;
@@ -38,7 +40,7 @@ __device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, doubl
   int idx = 0;
   for (int ti = 0; ti < nt; ++ti)
     for (int tj = 0; tj <= ti; ++tj, ++idx) {
-      if ((idx % kLxWaves) != wv) continue;
+      if ((idx % (NT / 64)) != wv) continue;
       const int i0 = ti * 16, j0 = tj * 16;
       const bool ra = (i0 + ri) < n, rb = (j0 + ri) < n;
       const double* rowa = Mx + (int64_t)(ra ? i0 + ri : 0) * ld;
@@ -77,15 +79,15 @@ __device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, doubl
         }
       }
     }
-  *tr_out = lx_sum(trp, red);        // (the barriers inside also publish C to the whole workgroup)
-  *fro_out = lx_sum(frp, red);
+  *tr_out = lx_sum<NT>(trp, red);        // (the barriers inside also publish C to the whole workgroup)
+  *fro_out = lx_sum<NT>(frp, red);
 }
 
 // Leading singular pair of Z (A x B row-major, global): wA (A), wB (B) unit norm, largest-|.| entry of wB positive.
 // Zt: P doubles of scratch (the transpose when B < A); G0 / G1: n x n each (ping-pong); xs (n), ys (k) in LDS.
 // LONG_GLOBAL (lx_cp3's unfoldings): the same code as an instantiation of its own, whose ys and wB are global scratch, so that the
 // callers with everything in LDS keep the code they had.
-template <bool LONG_GLOBAL = false>
+template <bool LONG_GLOBAL = false, int NT = kLxNT>
 __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, double* wB, double* G0, double* G1,
                          double* xs, double* ys, double* red, double* bestv, int* besti) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -93,12 +95,12 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
   const int n = rowsA ? A : B, k = rowsA ? B : A;
   const double* Mx = Z;
   if (!rowsA) {
-    for (int idx = tid; idx < A * B; idx += kLxNT) { const int b = idx / A, a = idx % A; Zt[idx] = Z[(int64_t)a * B + b]; }
+    for (int idx = tid; idx < A * B; idx += NT) { const int b = idx / A, a = idx % A; Zt[idx] = Z[(int64_t)a * B + b]; }
     __syncthreads();
     Mx = Zt;
   }
   double tr, fro;
-  lx_syrk(Mx, n, k, k, G0, nullptr, 1.0, red, &tr, &fro);                              // G_0 = Mx Mx^T
+  lx_syrk<NT>(Mx, n, k, k, G0, nullptr, 1.0, red, &tr, &fro);                              // G_0 = Mx Mx^T
   double* G = G0;
   double* Gn = G1;
   for (int step = 0; step < 64; ++step) {
@@ -106,13 +108,13 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
     int e;
     frexp(tr, &e);
     const double sc = ldexp(1.0, -e);                                                 // exact power of two
-    lx_syrk(G, n, n, n, Gn, nullptr, sc * sc, red, &tr, &fro);                         // G <- (sc G)^2   (G symmetric: G G = G G^T)
+    lx_syrk<NT>(G, n, n, n, Gn, nullptr, sc * sc, red, &tr, &fro);                         // G <- (sc G)^2   (G symmetric: G G = G G^T)
     double* tmp = G; G = Gn; Gn = tmp;
   }
   // seed = dominant column of G (first index on ties), normalised
   double bv = -1.0;
   int bi = 0;
-  for (int i = tid; i < n; i += kLxNT) { const double d = G[(int64_t)i * n + i]; if (d > bv) { bv = d; bi = i; } }
+  for (int i = tid; i < n; i += NT) { const double d = G[(int64_t)i * n + i]; if (d > bv) { bv = d; bi = i; } }
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) {
     const double ov = __shfl_xor(bv, m, 64);
@@ -123,21 +125,21 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
   __syncthreads();
   bv = bestv[0];
   bi = besti[0];
-  for (int w = 1; w < kLxWaves; ++w)
+  for (int w = 1; w < (NT / 64); ++w)
     if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
   __syncthreads();
   double ss = 0.0;
-  for (int i = tid; i < n; i += kLxNT) { const double g = G[(int64_t)bi * n + i]; ss = fma(g, g, ss); }
-  const double snrm = sqrt(lx_sum(ss, red));
-  for (int i = tid; i < n; i += kLxNT) xs[i] = G[(int64_t)bi * n + i] / snrm;
+  for (int i = tid; i < n; i += NT) { const double g = G[(int64_t)bi * n + i]; ss = fma(g, g, ss); }
+  const double snrm = sqrt(lx_sum<NT>(ss, red));
+  for (int i = tid; i < n; i += NT) xs[i] = G[(int64_t)bi * n + i] / snrm;
   __syncthreads();
-  for (int l = tid; l < k; l += kLxNT) {                                               // y = Mx^T seed
+  for (int l = tid; l < k; l += NT) {                                               // y = Mx^T seed
     double s = 0.0;
     for (int i = 0; i < n; ++i) s = fma(Mx[(int64_t)i * k + l], xs[i], s);
     ys[l] = s;
   }
   __syncthreads();
-  for (int i = wv; i < n; i += kLxWaves) {                                             // x = Mx y: a wavefront per row
+  for (int i = wv; i < n; i += (NT / 64)) {                                             // x = Mx y: a wavefront per row
     double s = 0.0;
     for (int l = lane; l < k; l += 64) s = fma(Mx[(int64_t)i * k + l], ys[l], s);
     s = wave_sum(s);
@@ -145,15 +147,15 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
   }
   __syncthreads();
   double sx = 0.0, sy = 0.0;
-  for (int i = tid; i < n; i += kLxNT) sx = fma(xs[i], xs[i], sx);
-  for (int l = tid; l < k; l += kLxNT) sy = fma(ys[l], ys[l], sy);
-  const double nx = sqrt(lx_sum(sx, red)), ny = sqrt(lx_sum(sy, red));
+  for (int i = tid; i < n; i += NT) sx = fma(xs[i], xs[i], sx);
+  for (int l = tid; l < k; l += NT) sy = fma(ys[l], ys[l], sy);
+  const double nx = sqrt(lx_sum<NT>(sx, red)), ny = sqrt(lx_sum<NT>(sy, red));
   // sign rule on the LAST mode's vector wB: its largest-|.| entry is positive (first index on ties)
   const double* vb = rowsA ? ys : xs;
   const int nb = rowsA ? k : n;
   bv = -1.0;
   bi = 0;
-  for (int i = tid; i < nb; i += kLxNT) { const double d = fabs(vb[i]); if (d > bv) { bv = d; bi = i; } }
+  for (int i = tid; i < nb; i += NT) { const double d = fabs(vb[i]); if (d > bv) { bv = d; bi = i; } }
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) {
     const double ov = __shfl_xor(bv, m, 64);
@@ -164,14 +166,14 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
   __syncthreads();
   bv = bestv[0];
   bi = besti[0];
-  for (int w = 1; w < kLxWaves; ++w)
+  for (int w = 1; w < (NT / 64); ++w)
     if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
   const double sgn = (vb[bi] < 0.0) ? -1.0 : 1.0;
   double* ox = rowsA ? wA : wB;
   double* oy = rowsA ? wB : wA;
   __syncthreads();
-  for (int i = tid; i < n; i += kLxNT) ox[i] = sgn * (xs[i] / nx);
-  for (int l = tid; l < k; l += kLxNT) oy[l] = sgn * (ys[l] / ny);
+  for (int i = tid; i < n; i += NT) ox[i] = sgn * (xs[i] / nx);
+  for (int l = tid; l < k; l += NT) oy[l] = sgn * (ys[l] / ny);
   __syncthreads();
 }
 
@@ -199,18 +201,19 @@ struct LxTensor {
   double* wL = nullptr;    // LDS: B2, the loading of mode 3 of X
   double* v = nullptr;     // LDS: B1 * B2, Z x_0 f_A (shared by the contractions of modes 1 and 2)
   double* tmp = nullptr;   // LDS: max(A, B1, B2), a contraction before its scaling
-  double* part = nullptr;  // LDS: kLxNT, the row groups' partial sums of v
+  double* part = nullptr;  // LDS: NT (the caller's thread count), the row groups' partial sums of v
   double* U = nullptr;     // global: A * B1 * B2, the unfolding of mode 1 or 2
   double* yl = nullptr;    // global: A * B1 * B2, the long vector of lx_rank1 on an unfolding
   double* vr = nullptr;    // global: A * B1 * B2, the right singular vector of an unfolding (not used)
 };
 
 // index of the largest |v[i]|, first index on ties, to every thread
+template <int NT = kLxNT>
 __device__ int lx_argmax_abs(const double* v, int n, double* bestv, int* besti) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   double bv = -1.0;
   int bi = 0;
-  for (int i = tid; i < n; i += kLxNT) { const double d = fabs(v[i]); if (d > bv) { bv = d; bi = i; } }
+  for (int i = tid; i < n; i += NT) { const double d = fabs(v[i]); if (d > bv) { bv = d; bi = i; } }
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) {
     const double ov = __shfl_xor(bv, m, 64);
@@ -221,16 +224,17 @@ __device__ int lx_argmax_abs(const double* v, int n, double* bestv, int* besti) 
   __syncthreads();
   bv = bestv[0];
   bi = besti[0];
-  for (int w = 1; w < kLxWaves; ++w)
+  for (int w = 1; w < (NT / 64); ++w)
     if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
   __syncthreads();
   return bi;
 }
 
+template <int NT = kLxNT>
 __device__ __forceinline__ double lx_dot(const double* a, const double* b, int n, double* red) {
   double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += kLxNT) s = fma(a[i], b[i], s);
-  return lx_sum(s, red);
+  for (int i = threadIdx.x; i < n; i += NT) s = fma(a[i], b[i], s);
+  return lx_sum<NT>(s, red);
 }
 
 // Rank-1 CP factors of Z (A x B1 x B2 row-major, global): parafac(Z, 1, tol=tol, init="svd", normalize_factors=True) as
@@ -245,53 +249,54 @@ __device__ __forceinline__ double lx_dot(const double* a, const double* b, int n
 // fA (A), t.wK (B1), t.wL (B2): the factors as the sweeps leave them (the regular engine applies nothing further to
 // cmtfpls_rank1_tensor_f64's output).  kl: B doubles of LDS, on return f_K (x) f_L.  G0 / G1: n x n for the largest short side n of
 // the three unfoldings; xs: that n.
+template <int NT = kLxNT>
 __device__ void lx_cp3(const double* Z, double* Zt, int A, double tol, const LxTensor& t, double* fA, double* kl, double* G0, double* G1,
                        double* xs, double* red, double* bestv, int* besti) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int B1 = t.B1, B2 = t.B2, B = B1 * B2, P = A * B;
   double* f[3] = {fA, t.wK, t.wL};
   const int d[3] = {A, B1, B2};
-  lx_rank1<true>(Z, Zt, A, B, fA, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
-  for (int e = tid; e < P; e += kLxNT) {                                             // mode 1: U[k][a B2 + l] = Z[a][k][l]
+  lx_rank1<true, NT>(Z, Zt, A, B, fA, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  for (int e = tid; e < P; e += NT) {                                             // mode 1: U[k][a B2 + l] = Z[a][k][l]
     const int k = e / (A * B2), c = e % (A * B2);
     t.U[e] = Z[(int64_t)(c / B2) * B + k * B2 + c % B2];
   }
   __syncthreads();
-  lx_rank1<true>(t.U, Zt, B1, A * B2, t.wK, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
-  for (int e = tid; e < P; e += kLxNT) {                                             // mode 2: U[l][a B1 + k] = Z[a][k][l]
+  lx_rank1<true, NT>(t.U, Zt, B1, A * B2, t.wK, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  for (int e = tid; e < P; e += NT) {                                             // mode 2: U[l][a B1 + k] = Z[a][k][l]
     const int l = e / (A * B1), c = e % (A * B1);
     t.U[e] = Z[(int64_t)c * B2 + l];
   }
   __syncthreads();
-  lx_rank1<true>(t.U, Zt, B2, A * B1, t.wL, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
+  lx_rank1<true, NT>(t.U, Zt, B2, A * B1, t.wL, t.vr, G0, G1, xs, t.yl, red, bestv, besti);
   for (int m = 0; m < 3; ++m) {                                                      // sign rule (cp_rank1_als_kernel:90-103)
-    const int arg = lx_argmax_abs(f[m], d[m], bestv, besti);
+    const int arg = lx_argmax_abs<NT>(f[m], d[m], bestv, besti);
     const bool flip = f[m][arg] < 0.0;
     __syncthreads();
-    if (flip) for (int i = tid; i < d[m]; i += kLxNT) f[m][i] = -f[m][i];
+    if (flip) for (int i = tid; i < d[m]; i += NT) f[m][i] = -f[m][i];
     __syncthreads();
   }
   double zz = 0.0;
-  for (int e = tid; e < P; e += kLxNT) zz = fma(Z[e], Z[e], zz);
-  const double norm_z = sqrt(lx_sum(zz, red));
-  const int G = B >= kLxNT ? 1 : kLxNT / B;                                         // row groups of v
+  for (int e = tid; e < P; e += NT) zz = fma(Z[e], Z[e], zz);
+  const double norm_z = sqrt(lx_sum<NT>(zz, red));
+  const int G = B >= NT ? 1 : NT / B;                                         // row groups of v
   double weight = 1.0, prev_err = 0.0;
   for (int sweep = 0; sweep < 100; ++sweep) {
     double iprod = 0.0;
     for (int m = 0; m < 3; ++m) {
       double gram = weight * weight;
       for (int i = 0; i < 3; ++i)
-        if (i != m) gram *= lx_dot(f[i], f[i], d[i], red);
+        if (i != m) gram *= lx_dot<NT>(f[i], f[i], d[i], red);
       if (m == 0) {                                                                  // tmp[a] = Z[a, :, :] . (f_K (x) f_L)
-        for (int c = tid; c < B; c += kLxNT) kl[c] = t.wK[c / B2] * t.wL[c % B2];
+        for (int c = tid; c < B; c += NT) kl[c] = t.wK[c / B2] * t.wL[c % B2];
         __syncthreads();
-        for (int a = wv; a < A; a += kLxWaves) {
+        for (int a = wv; a < A; a += (NT / 64)) {
           const double s = lx_wave_dot(Z + (int64_t)a * B, kl, B, lane);
           if (lane == 0) t.tmp[a] = s;
         }
       } else if (m == 1) {                                                           // v = Z x_0 f_A, tmp[k] = v[k, :] . f_L
         if (G == 1) {
-          for (int c = tid; c < B; c += kLxNT) {
+          for (int c = tid; c < B; c += NT) {
             double s = 0.0;
             for (int a = 0; a < A; ++a) s = fma(fA[a], Z[(int64_t)a * B + c], s);
             t.v[c] = s;
@@ -304,21 +309,21 @@ __device__ void lx_cp3(const double* Z, double* Zt, int A, double tol, const LxT
             t.part[tid] = s;
           }
           __syncthreads();
-          for (int c = tid; c < B; c += kLxNT) {
+          for (int c = tid; c < B; c += NT) {
             double s = 0.0;
             for (int g = 0; g < G; ++g) s += t.part[g * B + c];
             t.v[c] = s;
           }
         }
         __syncthreads();
-        for (int k = wv; k < B1; k += kLxWaves) {
+        for (int k = wv; k < B1; k += (NT / 64)) {
           double s = 0.0;
           for (int l = lane; l < B2; l += 64) s = fma(t.v[k * B2 + l], t.wL[l], s);
           s = wave_sum(s);
           if (lane == 0) t.tmp[k] = s;
         }
       } else {                                                                       // tmp[l] = v[:, l] . f_K
-        for (int l = wv; l < B2; l += kLxWaves) {
+        for (int l = wv; l < B2; l += (NT / 64)) {
           double s = 0.0;
           for (int k = lane; k < B1; k += 64) s = fma(t.v[k * B2 + l], t.wK[k], s);
           s = wave_sum(s);
@@ -326,23 +331,23 @@ __device__ void lx_cp3(const double* Z, double* Zt, int A, double tol, const LxT
         }
       }
       __syncthreads();
-      if (m == 2) iprod = (weight * weight * lx_dot(t.tmp, t.tmp, d[m], red) / gram) * weight;
-      for (int i = tid; i < d[m]; i += kLxNT) f[m][i] = t.tmp[i] * weight / gram;
+      if (m == 2) iprod = (weight * weight * lx_dot<NT>(t.tmp, t.tmp, d[m], red) / gram) * weight;
+      for (int i = tid; i < d[m]; i += NT) f[m][i] = t.tmp[i] * weight / gram;
       __syncthreads();
     }
     double fn2 = weight * weight;
-    for (int i = 0; i < 3; ++i) fn2 *= lx_dot(f[i], f[i], d[i], red);
+    for (int i = 0; i < 3; ++i) fn2 *= lx_dot<NT>(f[i], f[i], d[i], red);
     const double err = sqrt(fabs(norm_z * norm_z + fn2 - 2.0 * iprod)) / norm_z;
     if (sweep >= 1 && fabs(prev_err - err) < tol) break;                             // (uniform: every thread holds the same sums)
     prev_err = err;
     for (int i = 0; i < 3; ++i) {
-      const double nrm = sqrt(lx_dot(f[i], f[i], d[i], red));
+      const double nrm = sqrt(lx_dot<NT>(f[i], f[i], d[i], red));
       weight *= nrm;
-      for (int j = tid; j < d[i]; j += kLxNT) f[i][j] = f[i][j] / nrm;
+      for (int j = tid; j < d[i]; j += NT) f[i][j] = f[i][j] / nrm;
       __syncthreads();
     }
   }
-  for (int c = tid; c < B; c += kLxNT) kl[c] = t.wK[c / B2] * t.wL[c % B2];           // w_B = w_K (x) w_L (C order)
+  for (int c = tid; c < B; c += NT) kl[c] = t.wK[c / B2] * t.wL[c % B2];           // w_B = w_K (x) w_L (C order)
   __syncthreads();
 }
 

@@ -30,7 +30,9 @@ epilogue entries of the form, and _device_passes runs the passes and refits what
 Missing values in X (opt-in): a tPLS with EngineOptions.masked_folds refits every fold in a workgroup of cmtfpls_cv_masked_f64
 (masked_predictions) or, count-weighted, of cmtfpls_cv_masked_models_f64 (masked_models); a ctPLS with
 EngineOptions.masked_folds_coupled and a NaN in at least one block refits every model in a workgroup of
-cmtfpls_cv_masked_coupled_f64 (masked_models_coupled, masked_predictions_coupled).
+cmtfpls_cv_masked_coupled_f64 (masked_models_coupled, masked_predictions_coupled).  A tPLS whose X has order 4 and a NaN,
+with EngineOptions.masked_tensor_folds: the same two routines through cmtfpls_cv_masked_tensor_f64 and
+cmtfpls_cv_masked_tensor_models_f64, the rank-1 CP of the fold's contraction inside its workgroup.
 """
 from __future__ import annotations
 
@@ -512,6 +514,47 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
 
 
 MASKED_FORM = "cmtfpls_cv_masked_f64"
+MASKED_TENSOR_FORM = "cmtfpls_cv_masked_tensor_f64"           # order-4 X under EngineOptions.masked_tensor_folds
+MODELS_TENSOR_FORM = "cmtfpls_cv_masked_tensor_models_f64"
+MASKED_LDS_CAP = 150 * 1024
+
+
+def masked_tensor_side(A: int, B1: int, B2: int) -> int:
+    """The largest short side of the three unfoldings of an A x B1 x B2 contraction: the Gram matrices of the CP's seeds."""
+    P = A * B1 * B2
+    return max(min(d, P // d) for d in (A, B1, B2))
+
+
+def masked_tensor_lds_bytes(I: int, A: int, B1: int, B2: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of the masked order-4 entries (the library's cv_masked_tensor_lds_bytes): the order-3 form's vectors
+    on the A x B1 B2 view with the Gram seed over the unfoldings' short sides and 512 partials (a 512-thread workgroup), then the CP's wK, wL, v, unscaled
+    contraction and argmax scratch."""
+    B, n = B1 * B2, masked_tensor_side(A, B1, B2)
+    P = A * B
+    return 8 * (2 * I + P + A + B + 2 * M + 2 * n * n + n + M + R * R + R * (A + B) + R * M + R * R + 3 * R + 512 + 2 * I
+                + B1 + B2 + B + max(A, B1, B2) + 12)
+
+
+def wants_masked_tensor(pls, X) -> bool:
+    """Whether the masked order-4 form is asked for: a tPLS whose X has order 4 and holds a NaN, with
+    EngineOptions.masked_tensor_folds."""
+    return not isinstance(X, list) and X.ndim == 4 and pls._get_engine().opt.masked_tensor_folds and has_missing(X)
+
+
+def wants_masked(pls, X) -> bool:
+    """Whether a tPLS's X takes masked_predictions / masked_models: a NaN under EngineOptions.masked_folds, or wants_masked_tensor."""
+    return not isinstance(X, list) and ((pls._get_engine().opt.masked_folds and has_missing(X)) or wants_masked_tensor(pls, X))
+
+
+def masked_forms(pls, X):
+    """(the fold entry, the models entry) that masked_predictions / masked_models take for X."""
+    return (MASKED_TENSOR_FORM, MODELS_TENSOR_FORM) if wants_masked_tensor(pls, X) else (MASKED_FORM, MODELS_FORM)
+
+
+def _masked_tensor_outside(form: str, I: int, A: int, B1: int, B2: int, M: int, R: int) -> str:
+    return (f"shape outside {form} (it takes the short side of every unfolding <= 64, M <= 64, R <= 16 and its vectors within "
+            f"{MASKED_LDS_CAP} bytes of LDS): largest short side = {masked_tensor_side(A, B1, B2)}, M = {M}, R = {R}, LDS = "
+            f"{masked_tensor_lds_bytes(I, A, B1, B2, M, R)} bytes")
 
 
 def _f64(a, dev):
@@ -529,16 +572,18 @@ def has_missing(X) -> bool:
 def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
     """Refits of a tPLS on X with missing values, a workgroup per fold in one launch (cmtfpls_cv_masked_f64), in float64
     on the original data whatever the model's storage type: (pred (R, I, M), report) or (None, why).  Leave-one-out: ids =
-    arange(I), K = I."""
+    arange(I), K = I.  X of order 4 under EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_f64, the report
+    with `rank1` and `launches`."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
     I = ids.shape[0]
-    if not hasattr(be, "cv_masked"):
-        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked fold kernel"
+    tensor = _tensor_dims([X]) if eng.opt.masked_tensor_folds else None
+    if not hasattr(be, "cv_masked_tensor" if tensor else "cv_masked"):
+        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked {'order-4 ' if tensor else ''}fold kernel"
     if pls._comm is not None:
         return None, "sharded model (comm)"
-    if X.ndim not in (2, 3):
+    if X.ndim not in (2, 3) and tensor is None:
         return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
     if has_missing(Y):
         return None, "missing values in Y"
@@ -550,12 +595,18 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
     dev = be.device
 
     with eng.device_ctx():
-        out = be.cv_masked(_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M),
-                           _to_dev(ids, dev, torch.int32), K, A, B, R, tol, max_iter)
-        if out is None:
-            return None, (f"shape outside {MASKED_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
-                          f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
-        pred, n_iter, status, info = (t.cpu().numpy() for t in out)
+        data = (_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M), _to_dev(ids, dev, torch.int32), K)
+        if tensor:
+            out = be.cv_masked_tensor(*data, A, *tensor, R, tol, max_iter)
+            if out is None:
+                return None, _masked_tensor_outside(MASKED_TENSOR_FORM, I, A, *tensor, M, R)
+            launches = out[4]
+        else:
+            out = be.cv_masked(*data, A, B, R, tol, max_iter)
+            if out is None:
+                return None, (f"shape outside {MASKED_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
+                              f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+        pred, n_iter, status, info = (t.cpu().numpy() for t in out[:4])
     if status.any():
         empty, small = np.flatnonzero(status == 1).tolist(), np.flatnonzero(status == 2).tolist()
         return None, "; ".join(w for w in (f"training rows without an observed entry of X in folds {empty}" if empty else "",
@@ -563,6 +614,9 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
     report = {"form": f"a workgroup per fold on X with missing values, all folds in one launch ({MASKED_FORM})", "folds": int(K),
               "x_reads": None, "n_iter": n_iter.tolist(), "masked_folds": int(info[:, 0].sum()),
               "masked_batches": int(info[:, 1].sum())}
+    if tensor:
+        report.update(form=f"a workgroup per fold on order-4 X with missing values, all folds in {launches} launch(es) "
+                           f"({MASKED_TENSOR_FORM})", rank1=TENSOR_RANK1, launches=int(launches))
     return pred, report
 
 
@@ -575,16 +629,19 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
     (cmtfpls_cv_masked_models_f64), in float64 on the original data whatever the model's storage type.  Model m trains on
     counts[m, r] copies of X row r paired with Y row yrow[m, r] (yrow None: identity) and predicts its rows with count 0.  Returns
     (out, None) -- out the backend's dict on the host (Ypred (n, R, I, M), n_iter, status, info, launches, with `factors` Wa, Wb,
-    coef, Q) -- or (None, why) with masked_predictions' declines.  Models with a status are the caller's to refit."""
+    coef, Q) -- or (None, why) with masked_predictions' declines.  Models with a status are the caller's to refit.  X of order 4
+    under EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_models_f64, `factors` then Wa, Wk, Wl in place
+    of Wa, Wb, and out["tensor"] = (B1, B2)."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
     I = counts.shape[1]
-    if not hasattr(be, "cv_masked_models"):
-        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked model kernel"
+    tensor = _tensor_dims([X]) if eng.opt.masked_tensor_folds else None
+    if not hasattr(be, "cv_masked_tensor_models" if tensor else "cv_masked_models"):
+        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked {'order-4 ' if tensor else ''}model kernel"
     if pls._comm is not None:
         return None, "sharded model (comm)"
-    if X.ndim not in (2, 3):
+    if X.ndim not in (2, 3) and tensor is None:
         return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
     if has_missing(Y):
         return None, "missing values in Y"
@@ -593,12 +650,18 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
     dev = be.device
 
     with eng.device_ctx():
-        out = be.cv_masked_models(_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M),
-                                  _to_dev(counts, dev, torch.int32), None if yrow is None else _to_dev(yrow, dev, torch.int32),
-                                  A, B, R, tol, max_iter, factors, max_ws_bytes)
-        if out is None:
-            return None, (f"shape outside {MODELS_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
-                          f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+        data = (_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+                None if yrow is None else _to_dev(yrow, dev, torch.int32))
+        if tensor:
+            out = be.cv_masked_tensor_models(*data, A, *tensor, R, tol, max_iter, factors, max_ws_bytes)
+            if out is None:
+                return None, _masked_tensor_outside(MODELS_TENSOR_FORM, I, A, *tensor, M, R)
+            out["tensor"] = tensor
+        else:
+            out = be.cv_masked_models(*data, A, B, R, tol, max_iter, factors, max_ws_bytes)
+            if out is None:
+                return None, (f"shape outside {MODELS_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
+                              f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
         return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}, None
 
 
@@ -608,9 +671,13 @@ def masked_models_report(out: dict, refitted, what: str) -> dict:
     status = out["status"]
     ok = status == 0
     form = f"a workgroup per model on X with missing values, {len(status)} models in {out['launches']} launch(es) ({MODELS_FORM})"
+    if "tensor" in out:                                                          # order-4 X (masked_tensor_folds)
+        form = form.replace("on X", "on order-4 X").replace(MODELS_FORM, MODELS_TENSOR_FORM)
     rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
            "models": int(len(status)), "launches": int(out["launches"]), "masked_models": int(out["info"][ok, 0].sum()),
            "masked_batches": int(out["info"][ok, 1].sum()), "x_reads": None}
+    if "tensor" in out:
+        rep["rank1"] = TENSOR_RANK1
     if len(refitted):
         names = {1: "a training row without an observed entry of X", 2: "fewer than 2 training rows", 3: "bad counts or Y rows"}
         rep["refitted"] = [int(m) for m in refitted]
@@ -774,9 +841,9 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
     pred = None
     if not device_folds:
         why = "device folds switched off"
-    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):
+    elif wants_masked(pls, X):                                                      # EngineOptions.masked_folds / masked_tensor_folds
         pred, rep = masked_predictions(pls, X, Y, ids, K, tol, max_iter)
-        why = None if pred is not None else f"the masked form ({MASKED_FORM}) declined: {rep}"
+        why = None if pred is not None else f"the masked form ({masked_forms(pls, X)[0]}) declined: {rep}"
     elif wants_masked_coupled(pls, X):                                              # EngineOptions.masked_folds_coupled
         pred, rep = masked_predictions_coupled(pls, X, Y, ids, K, tol, max_iter)
         why = None if pred is not None else f"the masked form ({COUPLED_FORM}) declined: {rep}"

@@ -81,6 +81,12 @@ class EngineOptions:
     # every order-4 block's cross-covariance inside the fold's workgroup (cmtfpls_kfold_inner_coupled_tensor_f64);
     # opt-in, and separate from tensor_folds, under which a ctPLS keeps its refit routing (report: q2y_report_ with "rank1")
     tensor_folds_coupled: bool = False
+    # cross-validation of a tPLS whose X has order 4 AND missing values: the masked workgroup-per-model refits of masked_folds on
+    # the I x A x B1 B2 view with the rank-1 CP of each model's A x B1 x B2 contraction inside its workgroup
+    # (cmtfpls_cv_masked_tensor_f64, cmtfpls_cv_masked_tensor_models_f64): leave-one-out and K-fold Q2Y, the permutation
+    # test, repeated K-fold and the bootstrap; opt-in, and separate from masked_folds and tensor_folds, each of which alone leaves
+    # such an X to the refits (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
+    masked_tensor_folds: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

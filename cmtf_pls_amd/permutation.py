@@ -23,7 +23,8 @@ each block per pass, G the smallest of the blocks' G.  With EngineOptions.tensor
 taken: the inner entry is then kfold_inner_coupled_tensor in the grouped layout.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
-cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators); with EngineOptions.masked_folds_coupled, a ctPLS
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators; X of order 4 with EngineOptions.masked_tensor_folds:
+cmtfpls_cv_masked_tensor_models_f64); with EngineOptions.masked_folds_coupled, a ctPLS
 with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
 """
 from __future__ import annotations
@@ -33,9 +34,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
-                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids, has_missing,
-                    masked_fold_numerators, wants_masked_coupled)
+from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
+                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids,
+                    masked_fold_numerators, masked_forms, wants_masked, wants_masked_coupled)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_wide_xcov", "kfold_inner_coupled_grouped", "kfold_combine_scores", "kfold_epilogue_grouped", "mttkrp", "xcov")
@@ -147,10 +148,10 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
         why = _decline_blocks(pls, X, _names(X, True), Y, K * G if G else K, _ENTRIES_COUPLED, tensor_ok=True)
     elif isinstance(X, list):
         why = "coupled model: permutation device form not built"
-    elif pls._get_engine().opt.masked_folds and has_missing(X):                       # EngineOptions.masked_folds
+    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
         got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter)
         if got[0] is None:
-            why = f"the masked form ({MODELS_FORM}) declined: {got[1]}"
+            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {got[1]}"
         else:
             nums, n_iters, masked = got
     else:

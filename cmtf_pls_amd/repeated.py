@@ -15,7 +15,8 @@ n_iter and G x R numerators come back.  The passes run through kfold._device_pas
 splits; anything outside the device form refits every fold of every split with kfold.refit_predictions.
 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every split x fold as a workgroup of
-cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators); with EngineOptions.masked_folds_coupled, a ctPLS
+cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators; X of order 4 with EngineOptions.masked_tensor_folds:
+cmtfpls_cv_masked_tensor_models_f64); with EngineOptions.masked_folds_coupled, a ctPLS
 with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
 """
 from __future__ import annotations
@@ -26,9 +27,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, MODELS_FORM, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes,
+from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes,
                     _fold_means, _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev,
-                    _tensor_dims, _training_data, _with_rank1, has_missing, masked_fold_numerators, repeated_fold_ids, wants_masked_coupled)
+                    _tensor_dims, _training_data, _with_rank1, masked_fold_numerators, masked_forms, repeated_fold_ids, wants_masked,
+                    wants_masked_coupled)
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
@@ -102,10 +104,10 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
     masked = None
     if not device_folds:
         why = "device folds switched off"
-    elif not coupled and pls._get_engine().opt.masked_folds and has_missing(X):        # EngineOptions.masked_folds
+    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
         got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter)
         if got[0] is None:
-            why = f"the masked form ({MODELS_FORM}) declined: {got[1]}"
+            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {got[1]}"
         else:
             nums, n_iters, masked = got
     elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled

@@ -14,13 +14,16 @@ cross-covariances of all blocks, which share the fold's score; with 
 ``EngineOptions.masked_folds_coupled`` it takes ``cmtfpls_cv_masked_coupled_f64``; anything else refits ``ctPLS`` once per fold and
 says why.  X with missing values
 (order 2 or 3, Y complete) takes ``cmtfpls_cv_masked_f64`` when ``EngineOptions.masked_folds`` is on (a workgroup per fold with
-the reference's masked arithmetic, kfold.masked_predictions; K-fold too).  Which form ran is recorded on the model
-(``q2y_report_``).
+the reference's masked arithmetic, kfold.masked_predictions; K-fold too).  X of order 4 with missing values takes
+``cmtfpls_cv_masked_tensor_f64`` when ``EngineOptions.masked_tensor_folds`` is on: the same workgroup per fold on the I x A x B1 B2
+view, the rank-1 CP of the fold's contraction inside it; ``tensor_folds`` and ``masked_folds`` alone leave such an X to
+the refits.  Which form ran is recorded on the model (``q2y_report_``).
 """
 import numpy as np
 
-from .kfold import (COUPLED_FORM, MASKED_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host, _training_data,
-                    has_missing, masked_predictions, masked_predictions_coupled, refit_predictions, wants_masked_coupled)
+from .kfold import (COUPLED_FORM, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
+                    _training_data, has_missing, masked_predictions, masked_predictions_coupled, refit_predictions,
+                    wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
@@ -173,11 +176,12 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
     X = pls_tensor.original_X
     Y = pls_tensor.original_Y
     eng = pls_tensor._get_engine()
-    if eng.opt.masked_folds and X.ndim in (2, 3) and has_missing(X):       # EngineOptions.masked_folds: cmtfpls_cv_masked_f64
+    tensor = wants_masked_tensor(pls_tensor, X)                            # EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_f64
+    if tensor or (eng.opt.masked_folds and X.ndim in (2, 3) and has_missing(X)):   # EngineOptions.masked_folds: cmtfpls_cv_masked_f64
         I = X.shape[0]
         pred, rep = masked_predictions(pls_tensor, X, Y, np.arange(I), I, tol, max_iter)
         if pred is None:
-            return None, f"the masked form ({MASKED_FORM}) declined: {rep}"
+            return None, f"the masked form ({MASKED_TENSOR_FORM if tensor else MASKED_FORM}) declined: {rep}"
         rep["n_iter_total"] = int(np.sum(rep["n_iter"]))
         pls_tensor.q2y_report_ = rep
         return pred[-1].reshape(Y.shape), None
@@ -265,7 +269,8 @@ def kfold_predictions(pls_tensor, n_splits: int = 5, folds=None, tol: float = 1e
     `pls_tensor` is a fitted tPLS or ctPLS (a coupled model: 2R reads of each block, ``x_reads`` one entry per block).
     With missing values in X a tPLS takes cmtfpls_cv_masked_f64 under EngineOptions.masked_folds, and a ctPLS with a NaN in some
     block takes cmtfpls_cv_masked_coupled_f64 under EngineOptions.masked_folds_coupled (every fold a workgroup, leave-one-out is
-    n_splits = I); the permutation test, repeated K-fold and the bootstrap below route the same way.
+    n_splits = I), and a tPLS whose X has order 4 takes cmtfpls_cv_masked_tensor_f64 under
+    EngineOptions.masked_tensor_folds; the permutation test, repeated K-fold and the bootstrap below route the same way.
     Which form ran is recorded on the model (``q2y_report_``)."""
     from .kfold import kfold_run
 
@@ -292,7 +297,8 @@ def permutation_test_q2y(pls_tensor, n_permutations: int = 99, n_splits: int = 5
     per_component), "null": (P,) or (P, R), "p_value": (1 + #{null >= q2y}) / (P + 1) (per component with per_component),
     "permutations": (P, I)}.  On the GPU a tPLS runs floor(32 / K) permutations x K folds per pass from shared reads of X (2R reads
     per pass, permutation.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes cmtfpls_cv_masked_models_f64 when
-    EngineOptions.masked_folds is on: every permutation x fold is a workgroup with the reference's masked arithmetic.
+    EngineOptions.masked_folds is on: every permutation x fold is a workgroup with the reference's masked arithmetic (DESIGN 8i);
+    X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when EngineOptions.masked_tensor_folds is on.
     Anything else refits every fold of every permutation.  Which form ran is recorded on the model (``q2y_report_``)."""
     from .permutation import permutation_test
 
@@ -310,7 +316,8 @@ def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, f
     On the GPU floor(32 / K) splits x K folds of a tPLS or ctPLS share every MTTKRP and contraction of X (G + 2R - 1 reads
     per pass and block, repeated.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
     cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every split x fold is a workgroup with the reference's
-    masked arithmetic.  Anything else refits every fold of every split.  Which form ran is recorded on the model
+    masked arithmetic; X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when
+    EngineOptions.masked_tensor_folds is on.  Anything else refits every fold of every split.  Which form ran is recorded on the model
     (``q2y_report_``)."""
     from .repeated import repeated_kfold
 
@@ -357,7 +364,8 @@ def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random
     predictions) over "oob_rows" rows, those left out at least once}.  On the GPU up to 32 resamples per pass share every read of X
     (2R reads per pass and block, bootstrap.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
     cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every resample is a count-weighted workgroup with the
-    reference's masked arithmetic.  A tPLS whose X has order 4 takes the same passes with cmtfpls_kfold_inner_tensor_f64
+    reference's masked arithmetic; X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when
+    EngineOptions.masked_tensor_folds is on, its per-mode stacks [wA, wK, wL].  A tPLS whose X has order 4 takes the same passes with cmtfpls_kfold_inner_tensor_f64
     when EngineOptions.tensor_folds is on.  Anything else refits every resample.  Which form ran is recorded on the model
     (``bootstrap_report_``)."""
     from .bootstrap import bootstrap

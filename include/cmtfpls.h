@@ -662,6 +662,34 @@ int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* co
                                  int B, int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred,
                                  double* Wa, double* Wb, double* coef, double* Q, int* n_iter, int* status, int* info,
                                  void* ws, size_t ws_bytes, void* stream);
+/* ---- the same two entries for X of order 4 (I x A x B1 x B2, NaN = missing) with EngineOptions.masked_tensor_folds ---------------
+ * cmtfpls_cv_masked_f64 / cmtfpls_cv_masked_models_f64 on the I x A x B view with B = B1 B2 (tpls.py:73-113 with miss_tensordot /
+ * miss_mmodedot, missingvals.py:7-38, on that view): the fold's or model's Z (A x B1 x B2, already / c_p * n when it is masked)
+ * goes through the rank-1 CP of the complete-data order-4 forms (tpls.py:86-88 on a tensor Z: parafac(Z, 1, init="svd",
+ * normalize_factors=True), as cmtfpls_rank1_tensor_f64 states it), and wA with wB = wK (x) wL (C order) feed every other step
+ * unchanged: means, masked score / o_r * P, deflation on the observed entries, inner regression, the held-out batch centred then
+ * masked, status 1 / 2 / 3, info.  One 512-thread workgroup per fold or model.  Arguments as the order-3 entries with B1, B2 in
+ * place of B; the models entry writes Wk (nm x R x B1) and Wl (nm x R x B2) (both nullable) in place of Wb.
+ * ws >= n * cmtfpls_cv_masked_tensor_{fold,model}_workspace_bytes(...): per resident fold or model I P + I M + I R + 6 P doubles,
+ * P = A B1 B2 (Xf | Yf | T | column counts | means | the CP's transpose, unfolding, long vector and right vector); 0 for I <= 1.
+ * LDS of a workgroup, in doubles, with n the largest of min(A, B1 B2), min(B1, A B2), min(B2, A B1): 4 I + P + A + 2 B + 3 M +
+ * 2 n^2 + n + 2 R^2 + R (A + B) + R M + 3 R + 512 + B1 + B2 + max(A, B1, B2) + 12.
+ * CMTFPLS_EUNSUPPORTED (checked before the workspace and before any pointer is read) when that n > 64, M > 64, R > 16, the LDS
+ * exceeds 150 KB, or, in the fold form, K > I. */
+/* reference: tpls.py:73-113, 122-143 (fit and predict of one fold), missingvals.py:7-38 */
+size_t cmtfpls_cv_masked_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R);
+/* reference: validate.py:24-33 (one refit per fold) over tpls.py:73-143 */
+int cmtfpls_cv_masked_tensor_f64(const double* X, const double* Y, const int* fold_of, int K, const double* colsum_x,
+                                 const double* colcnt_x, const double* colsum_y, int I, int A, int B1, int B2, int M, int R,
+                                 double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status,
+                                 int* info, void* ws, size_t ws_bytes, void* stream);
+/* reference: tpls.py:73-113, 122-143 (fit and predict of one model), missingvals.py:7-38 */
+size_t cmtfpls_cv_masked_tensor_model_workspace_bytes(int I, int A, int B1, int B2, int M, int R);
+/* reference: tpls.py:73-143 on literally repeated rows (X[idx], Y[idx]) */
+int cmtfpls_cv_masked_tensor_models_f64(const double* X, const double* Y, const int* counts, const int* yrow, int nm, int I,
+                                        int A, int B1, int B2, int M, int R, double tol, int max_iter, int model0, int nmodels,
+                                        double* Ypred, double* Wa, double* Wk, double* Wl, double* coef, double* Q, int* n_iter,
+                                        int* status, int* info, void* ws, size_t ws_bytes, void* stream);
 /* ---- refits of a coupled model (ctPLS) whose blocks have missing values on count-weighted rows, all models of a chunk in one
  * launch: K-fold / leave-one-out Q2Y, the permutation test, repeated K-fold and the bootstrap (validate.py) with
  * EngineOptions.masked_folds_coupled (cmtf.py:69-139 fit with the per-block Xs_hasMiss / Xs_miss, cmtf.py:141-175 predict;
