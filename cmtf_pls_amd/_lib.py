@@ -195,6 +195,12 @@ SIGNATURES = {
     "cmtfpls_loo_xcov_coupled_lds_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_xcov_coupled_f64": (c_int, [ctypes.POINTER(LooCoupledBlock), c_int, _P, _P, c_int, c_int, c_int, c_double, c_int, c_int, c_int,
                                              _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, ctypes.POINTER(c_int), c_int,
+                                                                       c_int, c_int]),
+    "cmtfpls_loo_xcov_coupled_tensor_lds_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, ctypes.POINTER(c_int), c_int, c_int,
+                                                            c_int]),
+    "cmtfpls_loo_xcov_coupled_tensor_f64": (c_int, [ctypes.POINTER(LooCoupledBlock), c_int, ctypes.POINTER(c_int), _P, _P, c_int, c_int, c_int,
+                                                    c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_cv_masked_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_f64": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int,
                                       c_int, _P, _P, _P, _P, _P, c_size_t, _P]),

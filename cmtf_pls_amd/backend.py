@@ -829,6 +829,34 @@ class HipBackend:
             return None
         return Ypred, n_iter, "xcov_coupled"
 
+    def loo_ctpls_tensor(self, Xs, Y: torch.Tensor, dims, tensor, R: int, tol: float, max_iter: int,
+                         max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """loo_ctpls for a ctPLS with blocks of order 4 (cmtfpls_loo_xcov_coupled_tensor_f64): a block I x A x B1 x B2 is given as
+        I x A B1 B2 with dims (4, A, B1 B2) and tensor (B1, B2); a block of order 2 or 3 has tensor (0, 0).  The extraction of a tensor
+        block is the rank-1 CP of its cross-covariance inside the fold's workgroup.  Returns (Ypred (I, M), n_iter (I, R)) or None
+        when the shape is outside the form.  Folds run in chunks as loo_ctpls's."""
+        nb = len(Xs)
+        I, M = Y.shape
+        assert nb >= 1 and len(dims) == nb and len(tensor) == nb and Y.dtype == torch.float64 and Y.is_contiguous()
+        for X2, (_, A, B) in zip(Xs, dims):
+            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
+        colsums = [self.colstats(X2)[0] for X2 in Xs]
+        colsum_y, _ = self.colstats(Y)
+        blocks = (_lib.LooCoupledBlock * nb)(*[_lib.LooCoupledBlock(_ptr(X2), _ptr(cs), int(o), int(A), int(B))
+                                               for X2, cs, (o, A, B) in zip(Xs, colsums, dims)])
+        pairs = _int_pairs(tensor)
+        Ypred = self.empty(I, M)
+        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
+        if self._chunked_launch(
+                "loo_xcov_coupled_tensor",
+                lambda f0, nf, ws, nby: self.lib.cmtfpls_loo_xcov_coupled_tensor_f64(
+                    blocks, nb, pairs, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws,
+                    nby, self._stream()),
+                I, lambda: self.lib.cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(blocks, nb, pairs, I, M, R),
+                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
+            return None
+        return Ypred, n_iter
+
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
                   max_iter: int, max_ws_bytes: Optional[int] = None
                   ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:

@@ -23,6 +23,10 @@ layout, which also leaves every model's wK and wL, so a resample's loadings are 
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every resample as a count-weighted workgroup of
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_models): factors and OOB predictions come back per model; X of order 4
 with EngineOptions.masked_tensor_folds takes cmtfpls_cv_masked_tensor_models_f64, its per-mode stacks [wA, wK, wL].  With
+EngineOptions.tensor_resamples_coupled, a ctPLS on complete data with a block of order 4 among blocks of order 2, 3 and 4 runs the
+coupled passes with cmtfpls_kfold_inner_coupled_tensor_f64 as the inner entry: every block is taken as I x A x B (an order-4
+block with B = B1 B2 and wB = wK (x) wL), the entry leaves every model's wK and wL of every order-4 block, and a resample's loadings of
+such a block are [wA, wK, wL].  With
 EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
 (kfold.masked_models_coupled), every block's factors aligned by align_factors.
 """
@@ -33,9 +37,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_passes, _from_scores, _groups,
-                    _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1, masked_coupled_report,
-                    masked_forms, masked_models, masked_models_coupled, masked_models_report, wants_masked, wants_masked_coupled)
+from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_passes,
+                    _dims, _from_scores, _groups, _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1,
+                    masked_coupled_report, masked_forms, masked_models, masked_models_coupled, masked_models_report, wants_masked,
+                    wants_masked_coupled)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -126,7 +131,8 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
     """The device form's run(pass, e0, g) of kfold._device_passes: resamples e0 .. e0 + g - 1 as the models of one state (a
     one-model pass as two copies of its resample).  Each resample's (blocks, Q, coef_) goes to res[e]; a pass without a status
     adds its models' OOB predictions to oob_sum = [sums (R, I, M), counts (I,)] on the device.  tensor = (B1, B2): a tPLS's
-    order-4 X (kfold._tensor_dims); its loadings are [wA, wK, wL]."""
+    order-4 X (kfold._tensor_dims); its loadings are [wA, wK, wL].  tensor = [(B1, B2), ..]: a ctPLS with blocks of order 4 ((0, 0):
+    another order); an order-4 block's loadings are [wA, wK, wL], read from its slice of the entry's Wk / Wl."""
     eng = pls._get_engine()
     be = eng.be
     R = pls.n_components
@@ -158,7 +164,10 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
                     return _declined(why)
             built.append((A, B, S, mean))
         st, shared, own = _state(be, C, Yk, built, R, 1)
-        modes_kl = (be.zeros(n, R, tensor[0]), be.zeros(n, R, tensor[1])) if tensor is not None else None
+        if isinstance(tensor, list):                                                  # coupled: the tensor blocks' n x R x B1_b (B2_b) slices
+            modes_kl = (be.zeros(n * R * sum(B1 for B1, B2 in tensor if B2 > 0)), be.zeros(n * R * sum(B2 for _, B2 in tensor if B2 > 0)))
+        else:
+            modes_kl = (be.zeros(n, R, tensor[0]), be.zeros(n, R, tensor[1])) if tensor is not None else None
         why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True, tensor=tensor,
                           tensor_out=modes_kl)
         if why is not None:
@@ -175,10 +184,15 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
             coef_h, Q_h = coef.cpu().numpy(), Q.cpu().numpy()
             Wa = [o["Wa"][:g].cpu().numpy() for o in own]
             Wb = [o["Wb"][:g].cpu().numpy() for o in own]
-            if tensor is not None:
+            if isinstance(tensor, list):                                              # block b's slice: n x R x B1_b (B2_b), or None
+                Wk, Wl = _mode_slices(modes_kl[0].cpu().numpy(), modes_kl[1].cpu().numpy(), tensor, n, R)
+            elif tensor is not None:
                 Wk, Wl = (w[:g].cpu().numpy() for w in modes_kl)
             for j in range(g):
-                if tensor is not None:                                                # wB = wK (x) wL: the modes themselves
+                if isinstance(tensor, list):
+                    modes = [[wa[j].T, wk[j].T, wl[j].T] if X.ndim == 4 else [wb[j].T] if X.ndim == 2 else [wa[j].T, wb[j].T]
+                             for X, wa, wb, wk, wl in zip(Xs, Wa, Wb, Wk, Wl)]
+                elif tensor is not None:                                              # wB = wK (x) wL: the modes themselves
                     modes = [[Wa[0][j].T, Wk[j].T, Wl[j].T]]
                 else:
                     modes = [([wb[j].T] if X.ndim == 2 else [wa[j].T, wb[j].T]) for X, wa, wb in zip(Xs, Wa, Wb)]
@@ -190,6 +204,28 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
         oob_sum[1].zero_()
         return why
     return run
+
+
+def _mode_slices(Wk: np.ndarray, Wl: np.ndarray, tensor, n: int, R: int):
+    """Per block the n x R x B1_b and n x R x B2_b views of cmtfpls_kfold_inner_coupled_tensor_f64's Wk / Wl (the tensor blocks'
+    slices lie one after another in block order); None for a block of another order."""
+    ks, ls, ok, ol = [], [], 0, 0
+    for B1, B2 in tensor:
+        if B2 == 0:
+            ks.append(None)
+            ls.append(None)
+            continue
+        ks.append(Wk[ok:ok + n * R * B1].reshape(n, R, B1))
+        ls.append(Wl[ol:ol + n * R * B2].reshape(n, R, B2))
+        ok += n * R * B1
+        ol += n * R * B2
+    return ks, ls
+
+
+def _as_blocks_of_order3(Xs):
+    """Order-4 blocks as the coupled passes see them, I x A x B1 B2 (kfold._dims), for the checks of _decline_blocks that do not
+    depend on EngineOptions.tensor_folds_coupled; the other blocks as they are."""
+    return [X.reshape(X.shape[0], X.shape[1], -1) if X.ndim == 4 else X for X in Xs]
 
 
 def _spread(stack, level: float):
@@ -220,6 +256,7 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
     why: Optional[str] = None
     G = 0
     masked = None
+    ctensor = None                                                # (B1, B2) per block of a ctPLS under tensor_resamples_coupled
     if not device_folds:
         why = "device folds switched off"
     elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
@@ -232,9 +269,21 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
             why = f"the masked form ({COUPLED_FORM}) declined: {mwhy}"
     else:
         G = min(_groups(X, 1, min(NB, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for X in Xs)   # the LDS of every block's score pass
-        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES,
-                              tensor_ok=not coupled)
-    tensor = _tensor_dims(Xs) if not coupled and why is None and masked is None and pls._get_engine().opt.tensor_folds else None
+        if coupled and pls._get_engine().opt.tensor_resamples_coupled and _tensor_dims(Xs, coupled=True) is not None:
+            # EngineOptions.tensor_resamples_coupled: the checks of the coupled passes on the I x A x B1 B2 views, then
+            # cmtfpls_kfold_inner_coupled_tensor_f64's own limits, as the K-fold path checks them
+            ctensor = _tensor_dims(Xs, coupled=True)
+            why = _decline_blocks(pls, _as_blocks_of_order3(Xs), _names(Xs, coupled), Y, max(G, 2),
+                                  _ENTRIES_COUPLED + ("kfold_inner_coupled_tensor",))
+            if why is None:
+                why = _decline_coupled_tensor(pls._get_engine().be, [_dims(X) for X in Xs], ctensor, M)
+        else:
+            why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, max(G, 2), _ENTRIES_COUPLED if coupled else _ENTRIES,
+                                  tensor_ok=not coupled)
+    if ctensor is not None and why is None and masked is None:
+        tensor = ctensor
+    else:
+        tensor = _tensor_dims(Xs) if not coupled and why is None and masked is None and pls._get_engine().opt.tensor_folds else None
     res = [None] * NB
     dev = pls._get_engine().be.device if why is None and masked is None else torch.device("cpu")
     oob_sum = [torch.zeros(R, I, M, dtype=torch.float64, device=dev), torch.zeros(I, dtype=torch.float64, device=dev)]

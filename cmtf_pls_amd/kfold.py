@@ -397,13 +397,15 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     (weighted: fold_of holds the models' row counts).  tensor = (B1, B2): a tPLS's order-4 X, st[0].B = B1 B2; the inner entry is
     kfold_inner_tensor in the plain or the grouped layout and everything else is unchanged.  coupled with tensor = [(B1, B2), ..]
     (_tensor_dims: a ctPLS with a block of order 4): likewise kfold_inner_coupled_tensor.  tensor_out = (Wk (n x R x B1), Wl
-    (n x R x B2)): where kfold_inner_tensor leaves the models' mode loadings (the bootstrap's per-mode stacks).  None, or why a kernel
-    declined."""
+    (n x R x B2)): where kfold_inner_tensor leaves the models' mode loadings (the bootstrap's per-mode stacks); coupled: where
+    kfold_inner_coupled_tensor leaves them, the tensor blocks' n x R x B1_b (B2_b) slices one after another in block order.  None, or
+    why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled and tensor is not None:
         ws = torch.empty(max(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), 256), dtype=torch.uint8, device=be.device)
         mf, groups = grouped if grouped else (None, 1)
-        inner, inner_name = lambda a: be.kfold_inner_coupled_tensor(st, tensor, a, tol, max_iter, ws, mf, groups), \
+        Wk, Wl = tensor_out if tensor_out else (None, None)
+        inner, inner_name = lambda a: be.kfold_inner_coupled_tensor(st, tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), \
             "kfold_inner_coupled_tensor_f64"
     elif coupled:
         ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)

@@ -87,6 +87,13 @@ class EngineOptions:
     # test, repeated K-fold and the bootstrap; opt-in, and separate from masked_folds and tensor_folds, each of which alone leaves
     # such an X to the refits (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
     masked_tensor_folds: bool = False
+    # leave-one-out Q2Y (get_q2y, loo_predictions) and the factor bootstrap of a ctPLS on complete data with at least one block of
+    # order 4 among blocks of order 2, 3 and 4 on the device: every fold a workgroup on the cross-covariances of the coupled blocks
+    # with the rank-1 CP of every order-4 block inside it (cmtfpls_loo_xcov_coupled_tensor_f64), and the bootstrap's weighted passes
+    # through cmtfpls_kfold_inner_coupled_tensor_f64 with per-mode stacks [wA, wK, wL]; opt-in, and separate from
+    # tensor_folds_coupled, tensor_folds and masked_folds_coupled, each of which alone leaves these two routines on their refits
+    # (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
+    tensor_resamples_coupled: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

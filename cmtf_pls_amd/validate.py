@@ -12,7 +12,9 @@ each fold's cross-covariance inside its workgroup).  A fitted ``ctPLS
 3, min(J, K) <= 256 in every block, M <= 128, R <= 64) takes ``cmtfpls_loo_xcov_coupled_f64``: a workgroup per fold on the
 cross-covariances of all blocks, which share the fold's score; with a NaN in a block and
 ``EngineOptions.masked_folds_coupled`` it takes ``cmtfpls_cv_masked_coupled_f64``; anything else refits ``ctPLS`` once per fold and
-says why.  X with missing values
+says why.  With ``EngineOptions.tensor_resamples_coupled`` a ``ctPLS`` on complete data with a block of order 4 among blocks of
+order 2, 3 and 4 takes ``cmtfpls_loo_xcov_coupled_tensor_f64``: the same workgroup per fold with the rank-1 CP of every order-4 block's
+cross-covariance inside it.  X with missing values
 (order 2 or 3, Y complete) takes ``cmtfpls_cv_masked_f64`` when ``EngineOptions.masked_folds`` is on (a workgroup per fold with
 the reference's masked arithmetic, kfold.masked_predictions; K-fold too).  X of order 4 with missing values takes
 ``cmtfpls_cv_masked_tensor_f64`` when ``EngineOptions.masked_tensor_folds`` is on: the same workgroup per fold on the I x A x B1 B2
@@ -22,15 +24,18 @@ the refits.  Which form ran is recorded on the model (``q2y_report_``).
 import numpy as np
 
 from .kfold import (COUPLED_FORM, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
-                    _training_data, has_missing, masked_predictions, masked_predictions_coupled, refit_predictions,
+                    _tensor_dims, _training_data, has_missing, masked_predictions, masked_predictions_coupled, refit_predictions,
                     wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
 LOO_COUPLED_FORM = "a workgroup per fold on the cross-covariances of the coupled blocks (cmtfpls_loo_xcov_coupled_f64)"
+LOO_COUPLED_TENSOR_FORM = ("a workgroup per fold on the cross-covariances of the coupled blocks, order-4 blocks among them "
+                           "(cmtfpls_loo_xcov_coupled_tensor_f64)")
 LOO_REFIT_FORM = "one refit per fold on the regular engine"
 LOO_MAX_RESPONSES, LOO_MAX_COMPONENTS, LOO_MAX_CELLS = 128, 64, 1 << 24
 LOO_COUPLED_LDS_CAP = 150 * 1024
+LOO_COUPLED_TENSOR_THREADS = 512          # the workgroup of cmtfpls_loo_xcov_coupled_tensor_f64: the CP's partial sums in its LDS
 
 
 def loo_tensor_lds_bytes(A: int, B1: int, B2: int, M: int, R: int) -> int:
@@ -123,6 +128,69 @@ def _decline_loo_coupled(pls, Xs, Y):
     return None
 
 
+def loo_coupled_tensor_lds_bytes(dims, tensor, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_loo_xcov_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with tensor =
+    [(B1, B2), ..] ((0, 0): a block of order 2 or 3), the library's cmtfpls_loo_xcov_coupled_tensor_lds_bytes: loo_coupled_lds_bytes
+    with the Gram seed over every order-2/3 block's short side and every unfolding's and the long vector over the order-2/3 blocks
+    alone, then the CP's wK, wL, v, unscaled contraction and the workgroup's 512 partials, sized over the tensor blocks."""
+    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
+    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
+    nmax = max([min(A, B) for A, B in mats] + [min(d, A * B1 * B2 // d) for A, B1, B2 in tens for d in (A, B1, B2)])
+    kmax = max([max(A, B) for A, B in mats], default=0)
+    cp = (max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens)
+          + LOO_COUPLED_TENSOR_THREADS)
+    return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R + cp)
+
+
+def _decline_loo_coupled_tensor(pls, Xs, Y):
+    """Why cmtfpls_loo_xcov_coupled_tensor_f64 does not take these blocks, at least one of them of order 4 (its limits in the entry's
+    order, checked before a block is uploaded); None: it does."""
+    be = pls._get_engine().be
+    name = "cmtfpls_loo_xcov_coupled_tensor_f64"
+    if not hasattr(be, "loo_ctpls_tensor"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no order-4 coupled leave-one-out kernel"
+    if pls._comm is not None:
+        return "sharded model (comm)"
+    for b, X in enumerate(Xs):
+        if X.ndim > 4:
+            return f"block {b} of order {X.ndim} > 4 ({name})"
+    if len(Xs) > MAX_BLOCKS:
+        return f"{len(Xs)} blocks > {MAX_BLOCKS} ({name})"
+    for b, X in enumerate(Xs):
+        if has_missing(X):
+            return f"missing values in block {b} ({name} is the complete-data form)"
+    if has_missing(Y):
+        return "missing values in Y"
+    dims = [_dims(X) for X in Xs]
+    tensor = _tensor_dims(Xs, coupled=True)
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    R = pls.n_components
+    for b, ((A, B), (_, B2)) in enumerate(zip(dims, tensor)):
+        if B2 == 0 and min(A, B) > MAX_SIDE:
+            return f"block {b}: min(J, K) = {min(A, B)} > {MAX_SIDE} ({name})"
+    for b, ((A, _), (B1, B2)) in enumerate(zip(dims, tensor)):
+        P = A * B1 * B2
+        for mode, d in enumerate((A, B1, B2) if B2 > 0 else ()):
+            if min(d, P // d) > MAX_SIDE:
+                return f"block {b}: mode-{mode} unfolding: min({d}, {P // d}) = {min(d, P // d)} > {MAX_SIDE} ({name})"
+    if M > LOO_MAX_RESPONSES:
+        return f"M = {M} > {LOO_MAX_RESPONSES} responses ({name})"
+    if R > LOO_MAX_COMPONENTS:
+        return f"R = {R} > {LOO_MAX_COMPONENTS} components ({name})"
+    for b, (A, B) in enumerate(dims):
+        if A * B > LOO_MAX_CELLS:
+            return f"block {b}: J K = {A * B} > {LOO_MAX_CELLS} ({name})"
+    lds = loo_coupled_tensor_lds_bytes(dims, tensor, M, R)
+    if lds > LOO_COUPLED_LDS_CAP:
+        return f"the fold's vectors need {lds} bytes of LDS > {LOO_COUPLED_LDS_CAP} ({name})"
+    return None
+
+
+def _wants_loo_coupled_tensor(pls, Xs) -> bool:
+    """EngineOptions.tensor_resamples_coupled with a block of order 4 (or above: that one declines with its reason)."""
+    return bool(pls._get_engine().opt.tensor_resamples_coupled) and any(X.ndim >= 4 for X in Xs)
+
+
 def _loo_device_coupled(pls, tol: float, max_iter: int):
     """_loo_device for a fitted ctPLS: (Y_pred, None) from a device form (q2y_report_ set), or (None, why)."""
     import torch
@@ -135,7 +203,8 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
             return None, f"the masked form ({COUPLED_FORM}) declined: {rep}"
         pls.q2y_report_ = dict(rep, blocks=len(Xs), n_iter_total=int(np.sum(rep["n_iter"])))
         return pred[-1].reshape(Y.shape), None
-    why = _decline_loo_coupled(pls, Xs, Y)
+    tensor = _wants_loo_coupled_tensor(pls, Xs)                           # EngineOptions.tensor_resamples_coupled
+    why = _decline_loo_coupled_tensor(pls, Xs, Y) if tensor else _decline_loo_coupled(pls, Xs, Y)
     if why is not None:
         return None, why
     eng = pls._get_engine()
@@ -146,6 +215,14 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
                 return a.detach().to(device=be.device, dtype=torch.float64).contiguous().view(I, -1)
             return torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(I, -1), dtype=np.float64)).to(be.device)
 
+        if tensor:
+            out = be.loo_ctpls_tensor([f64(X) for X in Xs], f64(Y), [(X.ndim, *_dims(X)) for X in Xs], _tensor_dims(Xs, coupled=True),
+                                      pls.n_components, tol, max_iter)
+            if out is None:
+                return None, "cmtfpls_loo_xcov_coupled_tensor_f64 declined the shape"
+            pls.q2y_report_ = {"form": LOO_COUPLED_TENSOR_FORM, "rank1": TENSOR_RANK1, "folds": int(I), "blocks": len(Xs),
+                               "n_iter_total": int(out[1].sum().item())}
+            return out[0].cpu().numpy().reshape(tuple(Y.shape)), None
         out = be.loo_ctpls([f64(X) for X in Xs], f64(Y), [(X.ndim, *_dims(X)) for X in Xs], pls.n_components, tol, max_iter)
         if out is None:
             return None, "cmtfpls_loo_xcov_coupled_f64 declined the shape"

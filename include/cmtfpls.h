@@ -613,7 +613,7 @@ int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* 
 typedef struct {
   const double* X;        /* I x A*B row-major, the original block, no missing values */
   const double* colsum;   /* A*B: column sums over all I samples */
-  int order;              /* 2 (a matrix: A = 1) or 3 */
+  int order;              /* 2 (a matrix: A = 1) or 3; 4 (B = B1 B2) for cmtfpls_loo_xcov_coupled_tensor_f64 alone */
   int A, B;
 } cmtfpls_loo_coupled_block;
 size_t cmtfpls_loo_xcov_coupled_fold_workspace_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R);
@@ -621,6 +621,30 @@ size_t cmtfpls_loo_xcov_coupled_lds_bytes(const cmtfpls_loo_coupled_block* block
 int cmtfpls_loo_xcov_coupled_f64(const cmtfpls_loo_coupled_block* blocks, int nb, const double* Y, const double* colsum_y, int I,
                                  int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter,
                                  void* ws, size_t ws_bytes, void* stream);
+/* loo_xcov_coupled_tensor: cmtfpls_loo_xcov_coupled_f64 with blocks of order 4 among blocks of order 2, 3 and 4 (cmtf.py:98-104 on an
+ * order-3 Z_b: parafac(Z_b, 1, init="svd"), as cmtfpls_loo_xcov_tensor_f64).  `dims` is a HOST array of 2 nb ints, (B1_b, B2_b) for a
+ * block of order 4 (blocks[b].order == 4, I x A_b x B1_b x B2_b seen as I x A_b x B_b with B_b = B1_b B2_b; B2_b = 1 is still a tensor)
+ * and (0, 0) for a block of order 2 or 3 (cmtfpls_kfold_inner_coupled_tensor_f64's convention).  A 512-thread workgroup per fold; a
+ * tensor block's extraction is the rank-1 CP of its A x B1 x B2 Z_b inside the workgroup, which leaves wB_b = wK_b (x) wL_b (C order);
+ * everything after the extraction, and every block of order 2 or 3, is cmtfpls_loo_xcov_coupled_f64's arithmetic in its order.
+ * Checked on the host before the launch, in this order: CMTFPLS_EINVAL for what cmtfpls_loo_xcov_coupled_f64 calls a bad argument or
+ * block, dims == NULL, a negative dim, B1 B2 != B in a block of order 4, order 4 with B2 = 0 or another order with B2 > 0, order > 4,
+ * or no block of order 4 at all (that is cmtfpls_loo_xcov_coupled_f64's call); CMTFPLS_EUNSUPPORTED for nb > 8, min(A_b, B_b) > 256 in
+ * a block of order 2 or 3, an unfolding of a tensor block's A x B1 x B2 with its shorter side > 256, M > 128, R > 64,
+ * P_b = A_b B_b > 2^24, or more than 150 KB of LDS, which cmtfpls_loo_xcov_coupled_tensor_lds_bytes returns:
+ * (sum A_b + sum B_b + 4 M + M^2 + nmax + kmax + 2 R^2 + R M + 3 R + max B1 + max B2 + max B1 B2 + max dim + 512) doubles, nmax the
+ * largest of min(A_b, B_b) over the blocks of order 2 or 3 and of the shorter side of each of the three unfoldings of every tensor
+ * block, kmax = max max(A_b, B_b) over the blocks of order 2 or 3 alone (0 without one), the last five terms the CP's wK, wL, v, tmp
+ * (the largest single dim A, B1 or B2) and the workgroup's partial sums, taken over the tensor blocks, which share them;
+ * CMTFPLS_EWORKSPACE below nfolds * cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(...): per fold ((I + M) sumP + 3 Pmax +
+ * 3 Ptmax + 2 nmax^2 + I (M + R + 2) + R (sum A_b + sum B_b)) doubles, Ptmax the largest P_b of a tensor block (the CP's U, yl, vr).
+ * The two size functions return 0 for what the entry answers with CMTFPLS_EINVAL, for nb > 8 and for P_b > 2^24. */
+size_t cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, int I,
+                                                            int M, int R);
+size_t cmtfpls_loo_xcov_coupled_tensor_lds_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, int I, int M, int R);
+int cmtfpls_loo_xcov_coupled_tensor_f64(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, const double* Y,
+                                        const double* colsum_y, int I, int M, int R, double tol, int max_iter, int fold0, int nfolds,
+                                        double* Ypred, int* n_iter, void* ws, size_t ws_bytes, void* stream);
 /* ---- cross-validation refits of a tPLS whose X has missing values, all folds in one launch: validate.get_q2y / kfold_predictions
  * with EngineOptions.masked_folds (cmtf_pls/validate.py:7-37; tpls.py:61-63 X_hasMiss; missingvals.py:7-38) -------------------
  * For every fold f in [fold0, fold0 + nfolds): a complete tPLS fit (tpls.py:73-113) on the rows r with fold_of[r] != f, with the
@@ -720,7 +744,7 @@ int cmtfpls_cv_masked_tensor_models_f64(const double* X, const double* Y, const 
  * a block's min(A, B) > 64, M > 64, R > 16 or the LDS exceeds 150 KB. */
 typedef struct {
   const double* X;        /* I x A*B row-major, the original block, NaN = missing */
-  int order;              /* 2 (a matrix: A = 1) or 3 */
+  int order;              /* 2 (a matrix: A = 1) or 3; 4 (B = B1 B2) for cmtfpls_loo_xcov_coupled_tensor_f64 alone */
   int A, B;
 } cmtfpls_cv_coupled_block;
 size_t cmtfpls_cv_masked_coupled_workspace_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, int I, int M, int R);
