@@ -1,7 +1,10 @@
 // The NIPALS inner loop of one component on a cross-covariance, run by ONE 1024-thread workgroup (tpls.py:78-107 re-associated:
 // np.einsum(X, u) = S^T q, Y.T @ t = S (wA (x) wB), |u_old - u|^2 = dq^T G_y dq with S = Y^T X (M x P) and G_y = Y^T Y), with the
-// product's rank-1 extraction (Gram squarings on the f64 matrix cores, sign rule on the last mode).  Shared by the leave-one-out
-// folds (loo_xcov.hip) and the K-fold folds (kfold.hip): one workgroup per fold, no workgroup waits on another.
+// product's rank-1 extraction (Gram squarings on the f64 matrix cores, sign rule on the last mode).  One workgroup per fold, no
+// workgroup waits on another.  A pass is five steps, each written once: lx_z_from_s, lx_extract, lx_kron, lx_row_dots, lx_q_step.
+// lx_inner_loop is the loop over them for one block (loo_xcov.hip, kfold.hip's kfold_inner_kernel); the coupled kernels
+// (loo_xcov_coupled.hip, kfold.hip's kfold_inner_coupled_kernel) call the first four once per block and keep what is their own: how
+// a block's sum enters tq, and their stores between the Kronecker product and its barrier.  cv_masked.hip takes lx_cp3 alone.
 #pragma once
 #include "common.hpp"
 
@@ -83,6 +86,36 @@ __device__ void lx_syrk(const double* Mx, int n, int k, int ld, double* C, doubl
   *fro_out = lx_sum<NT>(frp, red);
 }
 
+// index of the largest key(i), i < n (keys >= 0), first index on ties, to every thread; ends on a barrier, so bestv / besti may be
+// reused at once
+template <int NT = kLxNT, typename Key>
+__device__ __forceinline__ int lx_argmax(int n, Key key, double* bestv, int* besti) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double bv = -1.0;
+  int bi = 0;
+  for (int i = tid; i < n; i += NT) { const double d = key(i); if (d > bv) { bv = d; bi = i; } }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const double ov = __shfl_xor(bv, m, 64);
+    const int oi = __shfl_xor(bi, m, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
+  __syncthreads();
+  bv = bestv[0];
+  bi = besti[0];
+  for (int w = 1; w < (NT / 64); ++w)
+    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
+  __syncthreads();
+  return bi;
+}
+
+// index of the largest |v[i]|, first index on ties, to every thread
+template <int NT = kLxNT>
+__device__ int lx_argmax_abs(const double* v, int n, double* bestv, int* besti) {
+  return lx_argmax<NT>(n, [v](int i) { return fabs(v[i]); }, bestv, besti);
+}
+
 // Leading singular pair of Z (A x B row-major, global): wA (A), wB (B) unit norm, largest-|.| entry of wB positive.
 // Zt: P doubles of scratch (the transpose when B < A); G0 / G1: n x n each (ping-pong); xs (n), ys (k) in LDS.
 // LONG_GLOBAL (lx_cp3's unfoldings): the same code as an instantiation of its own, whose ys and wB are global scratch, so that the
@@ -112,22 +145,7 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
     double* tmp = G; G = Gn; Gn = tmp;
   }
   // seed = dominant column of G (first index on ties), normalised
-  double bv = -1.0;
-  int bi = 0;
-  for (int i = tid; i < n; i += NT) { const double d = G[(int64_t)i * n + i]; if (d > bv) { bv = d; bi = i; } }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const double ov = __shfl_xor(bv, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
-  __syncthreads();
-  bv = bestv[0];
-  bi = besti[0];
-  for (int w = 1; w < (NT / 64); ++w)
-    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
-  __syncthreads();
+  const int bi = lx_argmax<NT>(n, [G, n](int i) { return G[(int64_t)i * n + i]; }, bestv, besti);
   double ss = 0.0;
   for (int i = tid; i < n; i += NT) { const double g = G[(int64_t)bi * n + i]; ss = fma(g, g, ss); }
   const double snrm = sqrt(lx_sum<NT>(ss, red));
@@ -153,25 +171,9 @@ __device__ void lx_rank1(const double* Z, double* Zt, int A, int B, double* wA, 
   // sign rule on the LAST mode's vector wB: its largest-|.| entry is positive (first index on ties)
   const double* vb = rowsA ? ys : xs;
   const int nb = rowsA ? k : n;
-  bv = -1.0;
-  bi = 0;
-  for (int i = tid; i < nb; i += NT) { const double d = fabs(vb[i]); if (d > bv) { bv = d; bi = i; } }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const double ov = __shfl_xor(bv, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
-  __syncthreads();
-  bv = bestv[0];
-  bi = besti[0];
-  for (int w = 1; w < (NT / 64); ++w)
-    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
-  const double sgn = (vb[bi] < 0.0) ? -1.0 : 1.0;
+  const double sgn = (vb[lx_argmax_abs<NT>(vb, nb, bestv, besti)] < 0.0) ? -1.0 : 1.0;
   double* ox = rowsA ? wA : wB;
   double* oy = rowsA ? wB : wA;
-  __syncthreads();
   for (int i = tid; i < n; i += NT) ox[i] = sgn * (xs[i] / nx);
   for (int l = tid; l < k; l += NT) oy[l] = sgn * (ys[l] / ny);
   __syncthreads();
@@ -207,34 +209,24 @@ struct LxTensor {
   double* vr = nullptr;    // global: A * B1 * B2, the right singular vector of an unfolding (not used)
 };
 
-// index of the largest |v[i]|, first index on ties, to every thread
-template <int NT = kLxNT>
-__device__ int lx_argmax_abs(const double* v, int n, double* bestv, int* besti) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  double bv = -1.0;
-  int bi = 0;
-  for (int i = tid; i < n; i += NT) { const double d = fabs(v[i]); if (d > bv) { bv = d; bi = i; } }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const double ov = __shfl_xor(bv, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { bestv[wv] = bv; besti[wv] = bi; }
-  __syncthreads();
-  bv = bestv[0];
-  bi = besti[0];
-  for (int w = 1; w < (NT / 64); ++w)
-    if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) { bv = bestv[w]; bi = besti[w]; }
-  __syncthreads();
-  return bi;
-}
-
 template <int NT = kLxNT>
 __device__ __forceinline__ double lx_dot(const double* a, const double* b, int n, double* red) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += NT) s = fma(a[i], b[i], s);
   return lx_sum<NT>(s, red);
+}
+
+// host: the shorter side of the mode-`mode` unfolding of A x B1 x B2 (what lx_rank1 squares), and the largest of the three, which
+// sizes xs, G0 and G1 of an order-4 block
+inline int lx_tensor_short(int A, int B1, int B2, int mode) {
+  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
+  return (int)(d < rest ? d : rest);
+}
+
+inline int lx_tensor_nmax(int A, int B1, int B2) {
+  int n = 0;
+  for (int m = 0; m < 3; ++m) n = lx_tensor_short(A, B1, B2, m) > n ? lx_tensor_short(A, B1, B2, m) : n;
+  return n;
 }
 
 // Rank-1 CP factors of Z (A x B1 x B2 row-major, global): parafac(Z, 1, tol=tol, init="svd", normalize_factors=True) as
@@ -351,11 +343,116 @@ __device__ void lx_cp3(const double* Z, double* Zt, int A, double tol, const LxT
   __syncthreads();
 }
 
+// lx_cp3's scratch as an LxTensor: wK (b1), wL (b2), v (bt), tmp (dmax) and part (NT, the caller's thread count) from `lds` on, U,
+// yl and vr (pt each) from `glb` on.  A single block gives its own B1, B2, B1 B2, max(A, B1, B2) and A B1 B2; a coupled kernel the
+// maxima over its tensor blocks, and sets B1 / B2 per block.
+__device__ __forceinline__ LxTensor lx_tensor_scratch(double* lds, double* glb, int b1, int b2, int bt, int dmax, int64_t pt, int NT) {
+  LxTensor t;
+  t.B1 = b1;
+  t.B2 = b2;
+  t.wK = lds;
+  t.wL = t.wK + b1;
+  t.v = t.wL + b2;
+  t.tmp = t.v + bt;
+  t.part = t.tmp + dmax;
+  t.U = glb;
+  t.yl = t.U + pt;
+  t.vr = t.yl + pt;
+  return t;
+}
+
+// ---- the steps of one pass of the inner loop (tpls.py:79-107, cmtf.py:91-128), by the fold's workgroup of NT threads ---------------
+// Z = X x_0 u = S^T q (tpls.py:83) for S (M x P, global), four rows of S in flight in the order of the plain sum.  Ends on a
+// barrier: Z is published.
+template <int NT = kLxNT>
+__device__ __forceinline__ void lx_z_from_s(const double* S, const double* q, double* Z, int64_t P, int M) {
+  const int tid = threadIdx.x;
+  for (int64_t c = tid; c < P; c += NT) {
+    double s = 0.0;
+    int m = 0;
+    for (; m + 4 <= M; m += 4) {
+      const double s0 = S[(int64_t)m * P + c], s1 = S[(int64_t)(m + 1) * P + c], s2 = S[(int64_t)(m + 2) * P + c], s3 = S[(int64_t)(m + 3) * P + c];
+      s = fma(q[m], s0, s);
+      s = fma(q[m + 1], s1, s);
+      s = fma(q[m + 2], s2, s);
+      s = fma(q[m + 3], s3, s);
+    }
+    for (; m < M; ++m) s = fma(q[m], S[(int64_t)m * P + c], s);
+    Z[c] = s;
+  }
+  __syncthreads();
+}
+
+// The loadings wA (A), wB (B) of Z (A x B, P = A B; tpls.py:84-88): t.B2 > 0 (TENSOR callers only: the others never instantiate
+// lx_cp3): the rank-1 CP of the A x B1 x B2 Z, wB = wK (x) wL; A == 1: Z / |Z|; else lx_rank1.  Ends on a barrier: wA and wB (and
+// t.wK, t.wL) are published.
+template <bool TENSOR, int NT = kLxNT>
+__device__ __forceinline__ void lx_extract(const double* Z, double* Zt, int A, int B, int64_t P, double tol, const LxTensor& t, double* wA,
+                                           double* wB, double* G0, double* G1, double* xs, double* ys, double* red, double* bestv,
+                                           int* besti) {
+  const int tid = threadIdx.x;
+  bool cp = false;
+  if constexpr (TENSOR) cp = t.B2 > 0;
+  if (cp) {
+    if constexpr (TENSOR) lx_cp3<NT>(Z, Zt, A, tol, t, wA, wB, G0, G1, xs, red, bestv, besti);
+  } else if (A == 1) {
+    double s = 0.0;
+    for (int64_t c = tid; c < P; c += NT) s = fma(Z[c], Z[c], s);
+    const double nz = sqrt(lx_sum<NT>(s, red));
+    for (int64_t c = tid; c < P; c += NT) wB[c] = Z[c] / nz;
+    if (tid == 0) wA[0] = 1.0;
+    __syncthreads();
+  } else {
+    lx_rank1<false, NT>(Z, Zt, A, B, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+  }
+}
+
+// wk = wA (x) wB (P = A B), the Kronecker loading.  No barrier: every thread writes the entries c = tid, tid + NT, ..., and may read
+// those back at once; the caller's barrier publishes wk.
+template <int NT = kLxNT>
+__device__ __forceinline__ void lx_kron(double* wk, const double* wA, const double* wB, int64_t P, int B) {
+  const int tid = threadIdx.x;
+  for (int64_t c = tid; c < P; c += NT) wk[c] = wA[c / B] * wB[c % B];
+}
+
+// put(r, Mx[r, :] . wk) for the rows r < rows of Mx (rows x P, global), a wavefront per row and its lane 0 calling put: Y^T t = S wk
+// (tpls.py:97-100) on the rows of S, the score X wk on the rows of the fold's X.  Row r is always the same wavefront's, so put may add
+// to what an earlier call left in its slot.  lane, wv: the caller's tid & 63 and tid >> 6, handed in as lx_wave_dot's lane is
+// (computed in here, kfold_inner_kernel spills 16 bytes more).  No barrier.
+template <int NT = kLxNT, typename Put>
+__device__ __forceinline__ void lx_row_dots(const double* Mx, const double* wk, int64_t P, int rows, int lane, int wv, Put put) {
+  for (int r = wv; r < rows; r += NT / 64) {
+    const double s = lx_wave_dot(Mx + (int64_t)r * P, wk, P, lane);
+    if (lane == 0) put(r, s);
+  }
+}
+
+// q <- (tq / nb) / |tq / nb| (tpls.py:101; nb: the blocks whose S wk were added into tq, np.average of cmtf.py:120, 1.0 for a
+// tPLS: x / 1.0 is x) and whether the loop stops: sqrt(dq^T G_y dq) = |u_old - u| < tol (tpls.py:102-103), never on the first pass
+// (oldU = inf, tpls.py:77).  Starts from a published tq, ends on a barrier: q is published.
+template <int NT = kLxNT>
+__device__ __forceinline__ bool lx_q_step(const double* tq, double nb, double* q, double* qn, const double* Gy, int M, double tol, int it,
+                                          double* red) {
+  const int tid = threadIdx.x;
+  double qs = 0.0;
+  for (int m = tid; m < M; m += NT) { const double v = tq[m] / nb; qs = fma(v, v, qs); }
+  const double qnrm = sqrt(lx_sum<NT>(qs, red));
+  for (int m = tid; m < M; m += NT) qn[m] = (tq[m] / nb) / qnrm;
+  __syncthreads();
+  double d2 = 0.0;
+  for (int o = tid; o < M * M; o += NT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
+  d2 = lx_sum<NT>(d2, red);
+  for (int m = tid; m < M; m += NT) q[m] = qn[m];
+  __syncthreads();
+  return it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < tol;
+}
+
 // The whole inner loop of one component (tpls.py:78-107) on S (M x P, global) from q = e_0 (u = Y[:, 0], tpls.py:78) until
-// sqrt(dq^T G_y dq) < tol (never on the first pass: oldU = inf, tpls.py:77) or max_iter passes.  On return q holds the converged
-// q, wA / wB the loadings and wk (P) their Kronecker product; returns the passes executed.  Z, Zt, wk: P doubles each (global);
-// G0, G1: n x n (global); q, qn, tq (M), xs (n), ys (k), red, bestv, besti: workgroup scratch; Gy: M x M.
+// lx_q_step stops it or max_iter passes.  On return q holds the converged q, wA / wB the loadings and wk (P) their Kronecker product;
+// returns the passes executed.  Z, Zt, wk: P doubles each (global); G0, G1: n x n (global); q, qn, tq (M), xs (n), ys (k), red,
+// bestv, besti: workgroup scratch; Gy: M x M.
 // tn.B2 > 0: X of order 4, Z an A x B1 x B2 tensor (B = B1 B2) whose extraction is lx_cp3; wB is then w_K (x) w_L and ys is unused.
+// (A caller without a tensor passes none, and the constant B2 = 0 removes lx_cp3 from its code.)
 __device__ __forceinline__ int lx_inner_loop(const double* S, const double* Gy, int64_t P, int M, int A, int B, double tol, int max_iter,
                                              double* q, double* qn, double* tq, double* Z, double* Zt, double* wk, double* wA, double* wB,
                                              double* G0, double* G1, double* xs, double* ys, double* red, double* bestv, int* besti,
@@ -365,50 +462,13 @@ __device__ __forceinline__ int lx_inner_loop(const double* S, const double* Gy, 
   __syncthreads();
   int it = 0;
   for (; it < max_iter; ++it) {                                                    // tpls.py:79
-    for (int64_t c = tid; c < P; c += kLxNT) {                                       // Z = X x_0 u = S^T q (tpls.py:83)
-      double s = 0.0;
-      int m = 0;
-      for (; m + 4 <= M; m += 4) {                                                   // (four rows of S in flight; same order of the sum)
-        const double s0 = S[(int64_t)m * P + c], s1 = S[(int64_t)(m + 1) * P + c], s2 = S[(int64_t)(m + 2) * P + c], s3 = S[(int64_t)(m + 3) * P + c];
-        s = fma(q[m], s0, s);
-        s = fma(q[m + 1], s1, s);
-        s = fma(q[m + 2], s2, s);
-        s = fma(q[m + 3], s3, s);
-      }
-      for (; m < M; ++m) s = fma(q[m], S[(int64_t)m * P + c], s);
-      Z[c] = s;
-    }
+    lx_z_from_s(S, q, Z, P, M);
+    lx_extract<true>(Z, Zt, A, B, P, tol, tn, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+    lx_kron(wk, wA, wB, P, B);                                                     // once per extraction
     __syncthreads();
-    if (tn.B2 > 0) {                                                                 // tpls.py:86-88 on a tensor Z
-      lx_cp3(Z, Zt, A, tol, tn, wA, wB, G0, G1, xs, red, bestv, besti);
-    } else if (A == 1) {                                                             // tpls.py:84: Z / norm(Z)
-      double s = 0.0;
-      for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
-      const double nz = sqrt(lx_sum(s, red));
-      for (int64_t c = tid; c < P; c += kLxNT) wB[c] = Z[c] / nz;
-      if (tid == 0) wA[0] = 1.0;
-      __syncthreads();
-    } else {
-      lx_rank1(Z, Zt, A, B, wA, wB, G0, G1, xs, ys, red, bestv, besti);          // tpls.py:86-88
-    }
-    for (int64_t c = tid; c < P; c += kLxNT) wk[c] = wA[c / B] * wB[c % B];          // the Kronecker loading, once per extraction
+    lx_row_dots(S, wk, P, M, lane, wv, [tq](int m, double s) { tq[m] = s; });
     __syncthreads();
-    for (int m = wv; m < M; m += kLxWaves) {                                         // Y^T t = S (wA (x) wB) (tpls.py:97-100)
-      const double s = lx_wave_dot(S + (int64_t)m * P, wk, P, lane);
-      if (lane == 0) tq[m] = s;
-    }
-    __syncthreads();
-    double qs = 0.0;
-    for (int m = tid; m < M; m += kLxNT) qs = fma(tq[m], tq[m], qs);
-    const double qnrm = sqrt(lx_sum(qs, red));
-    for (int m = tid; m < M; m += kLxNT) qn[m] = tq[m] / qnrm;                       // tpls.py:101
-    __syncthreads();
-    double d2 = 0.0;                                                                 // |u_old - u|^2 = dq^T G_y dq (tpls.py:102-103)
-    for (int o = tid; o < M * M; o += kLxNT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
-    d2 = lx_sum(d2, red);
-    for (int m = tid; m < M; m += kLxNT) q[m] = qn[m];
-    __syncthreads();
-    if (it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < tol) { ++it; break; }              // first pass: oldU = inf (tpls.py:77)
+    if (lx_q_step(tq, 1.0, q, qn, Gy, M, tol, it, red)) { ++it; break; }
   }
   return it;
 }

@@ -153,26 +153,15 @@ struct KfTensor {
   double* Wl;             // K x R x B2
 };
 
-static int kf_tensor_short(int A, int B1, int B2, int mode) {
-  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
-  return (int)(d < rest ? d : rest);
-}
-
-static int kf_tensor_nmax(int A, int B1, int B2) {
-  int n = 0;
-  for (int m = 0; m < 3; ++m) n = kf_tensor_short(A, B1, B2, m) > n ? kf_tensor_short(A, B1, B2, m) : n;
-  return n;
-}
-
 // LDS: wA (A), wB (B), q, qn, tq (M each), G_y (M x M), xs (nmax), then lx_cp3's wK (B1), wL (B2), v (B), tmp (max dim), part
 static size_t kf_inner_tensor_lds_bytes(int A, int B1, int B2, int M) {
   const size_t B = (size_t)B1 * B2, dmax = (size_t)(A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2));
-  return ((size_t)A + B + 3 * (size_t)M + (size_t)M * M + kf_tensor_nmax(A, B1, B2) + B1 + B2 + B + dmax + kLxNT) * sizeof(double);
+  return ((size_t)A + B + 3 * (size_t)M + (size_t)M * M + lx_tensor_nmax(A, B1, B2) + B1 + B2 + B + dmax + kLxNT) * sizeof(double);
 }
 
 // per fold: Z, Zt, wk, then lx_cp3's U, yl, vr (P each), G0, G1 (nmax x nmax each)
 static int64_t kf_inner_tensor_ws_per_fold(int A, int B1, int B2) {
-  const int64_t n = kf_tensor_nmax(A, B1, B2);
+  const int64_t n = lx_tensor_nmax(A, B1, B2);
   return 6 * (int64_t)A * B1 * B2 + 2 * n * n;
 }
 
@@ -207,19 +196,8 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_kernel(cmtfpls_kfold_state 
   double* Gy = tq + M;
   double* xs = Gy + M * M;
   double* ys = xs + n;
-  LxTensor lt;
-  if (TENSOR) {
-    lt.B1 = tn.B1;
-    lt.B2 = tn.B2;
-    lt.wK = ys;                                                   // (ys itself is not used: lx_cp3's long vector is lt.yl)
-    lt.wL = lt.wK + tn.B1;
-    lt.v = lt.wL + tn.B2;
-    lt.tmp = lt.v + B;
-    lt.part = lt.tmp + max(A, max(tn.B1, tn.B2));
-    lt.U = wk + P;
-    lt.yl = lt.U + P;
-    lt.vr = lt.yl + P;
-  }
+  LxTensor lt;                                                    // (ys itself is not used by lx_cp3: its long vector is lt.yl)
+  if (TENSOR) lt = lx_tensor_scratch(ys, wk + P, tn.B1, tn.B2, B, max(A, max(tn.B1, tn.B2)), P, kLxNT);
   for (int o = tid; o < M * M; o += kLxNT) {
     double s = 0.0;
     for (int t = 0; t < NT; ++t) s += st.Gy[((int64_t)fold * NT + t) * M * M + o];
@@ -587,7 +565,7 @@ static KfCoupledTensorDims kf_coupled_tensor_dims(const cmtfpls_kfold_state* v, 
     o.tn.ol[b] = ol;
     int n;
     if (B2 > 0) {
-      n = kf_tensor_nmax(A, B1, B2);
+      n = lx_tensor_nmax(A, B1, B2);
       const int dm = A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2);
       o.tn.b1max = B1 > o.tn.b1max ? B1 : o.tn.b1max;
       o.tn.b2max = B2 > o.tn.b2max ? B2 : o.tn.b2max;
@@ -618,7 +596,9 @@ static size_t kf_coupled_tensor_lds_bytes(const KfCoupledTensorDims& o, int M) {
 // kf_inner_tensor_ws_per_fold.
 static int64_t kf_coupled_tensor_ws_per_fold(const KfCoupledTensorDims& o) { return kf_coupled_ws_per_fold(o.d) + 3 * o.tn.ptmax; }
 
-// a workgroup per fold.  With one block every step is the one of kfold_inner_kernel (lx_inner_loop) in the same order, so the
+// a workgroup per fold.  A pass is lx_inner_loop's steps (fold_loop.hpp) once per block, with tq zeroed, every block's S_b w_b added
+// to it in block order and the average taken in lx_q_step; Wa / Wb and Wk / Wl are stored between a block's extraction and the
+// barrier after its Kronecker product.  With one block every step is the one of kfold_inner_kernel in the same order, so the
 // result is bitwise that of the tPLS kernel.  GROUPED (permutation test, see "grouped models" below): every view's mean is per
 // fold (folds x P_b) and model m reads row model_fold[m] of it; S, the loadings, Q, vec, n_iter, status and Gy are per model in
 // every layout.  Without it model k is fold k and the code is the one it always was.
@@ -650,17 +630,9 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl,
   double* Gy = tq + M;
   double* xs = Gy + M * M;
   double* ys = xs + nmax;                                         // kmax
-  LxTensor lt;
-  if (TENSOR) {                                                   // lx_cp3's scratch, shared by the tensor blocks
-    lt.wK = ys + tn.kmax;                                         // b1max
-    lt.wL = lt.wK + tn.b1max;                                     // b2max
-    lt.v = lt.wL + tn.b2max;                                      // btmax
-    lt.tmp = lt.v + tn.btmax;                                     // dmax
-    lt.part = lt.tmp + tn.dmax;                                   // kLxNT
-    lt.U = wk0 + tn.psum;                                         // after the blocks' wk: ptmax each
-    lt.yl = lt.U + tn.ptmax;
-    lt.vr = lt.yl + tn.ptmax;
-  }
+  LxTensor lt;                                                    // lx_cp3's scratch, shared by the tensor blocks: LDS after ys, global
+  if (TENSOR)                                                     // after the blocks' wk
+    lt = lx_tensor_scratch(ys + tn.kmax, wk0 + tn.psum, tn.b1max, tn.b2max, tn.btmax, tn.dmax, tn.ptmax, kLxNT);
   for (int o = tid; o < M * M; o += kLxNT) {
     double s = 0.0;
     for (int t = 0; t < NT; ++t) s += bl.b[0].Gy[((int64_t)fold * NT + t) * M * M + o];
@@ -676,61 +648,27 @@ __global__ __launch_bounds__(kLxNT) void kfold_inner_coupled_kernel(KfBlocks bl,
       const int A = bl.b[b].A, B = bl.b[b].B;
       const int64_t P = (int64_t)A * B;
       const double* S = bl.b[b].S + (int64_t)fold * M * P;
-      for (int64_t c = tid; c < P; c += kLxNT) {                                     // Z_b = X_b x_0 u = S_b^T q
-        double s = 0.0;
-        int m = 0;
-        for (; m + 4 <= M; m += 4) {
-          const double s0 = S[(int64_t)m * P + c], s1 = S[(int64_t)(m + 1) * P + c], s2 = S[(int64_t)(m + 2) * P + c], s3 = S[(int64_t)(m + 3) * P + c];
-          s = fma(q[m], s0, s);
-          s = fma(q[m + 1], s1, s);
-          s = fma(q[m + 2], s2, s);
-          s = fma(q[m + 3], s3, s);
-        }
-        for (; m < M; ++m) s = fma(q[m], S[(int64_t)m * P + c], s);
-        Z[c] = s;
-      }
-      __syncthreads();
-      if (TENSOR && tn.B2[b] > 0) {                                                  // order 4: the rank-1 CP of the A x B1 x B2 Z
+      lx_z_from_s(S, q, Z, P, M);                                                    // Z_b = X_b x_0 u = S_b^T q
+      if (TENSOR) {                                                                  // B2 > 0: order 4, the rank-1 CP of the A x B1 x B2 Z
         lt.B1 = tn.B1[b];
         lt.B2 = tn.B2[b];
-        lx_cp3(Z, Zt, A, tol, lt, wA, wB, G0, G1, xs, red, bestv, besti);
+      }
+      lx_extract<TENSOR>(Z, Zt, A, B, P, tol, lt, wA, wB, G0, G1, xs, ys, red, bestv, besti);
+      if (TENSOR && lt.B2 > 0) {
         if (tn.Wk) for (int j = tid; j < lt.B1; j += kLxNT) tn.Wk[tn.ok[b] + ((int64_t)fold * R + a) * lt.B1 + j] = lt.wK[j];
         if (tn.Wl) for (int j = tid; j < lt.B2; j += kLxNT) tn.Wl[tn.ol[b] + ((int64_t)fold * R + a) * lt.B2 + j] = lt.wL[j];
-      } else if (A == 1) {                                                           // order 2: Z / norm(Z)
-        double s = 0.0;
-        for (int64_t c = tid; c < P; c += kLxNT) s = fma(Z[c], Z[c], s);
-        const double nz = sqrt(lx_sum(s, red));
-        for (int64_t c = tid; c < P; c += kLxNT) wB[c] = Z[c] / nz;
-        if (tid == 0) wA[0] = 1.0;
-        __syncthreads();
-      } else {
-        lx_rank1(Z, Zt, A, B, wA, wB, G0, G1, xs, ys, red, bestv, besti);
       }
-      for (int64_t c = tid; c < P; c += kLxNT) wk[c] = wA[c / B] * wB[c % B];
+      lx_kron(wk, wA, wB, P, B);
       double* oa = bl.b[b].Wa + ((int64_t)fold * R + a) * A;                         // (the last pass's loadings stay)
       double* ob = bl.b[b].Wb + ((int64_t)fold * R + a) * B;
       for (int j = tid; j < A; j += kLxNT) oa[j] = wA[j];
       for (int j = tid; j < B; j += kLxNT) ob[j] = wB[j];
       __syncthreads();
-      for (int m = wv; m < M; m += kLxWaves) {                                       // Y^T t_b = S_b w_b, added in block order
-        const double s = lx_wave_dot(S + (int64_t)m * P, wk, P, lane);
-        if (lane == 0) tq[m] += s;
-      }
+      lx_row_dots(S, wk, P, M, lane, wv, [tq](int m, double s) { tq[m] += s; });     // Y^T t_b = S_b w_b, added to 0.0 in block order
       __syncthreads();
       wk += P;
     }
-    for (int m = tid; m < M; m += kLxNT) tq[m] /= (double)nb;                        // Y^T t, t the blocks' average (cmtf.py:126-127)
-    double qs = 0.0;
-    for (int m = tid; m < M; m += kLxNT) qs = fma(tq[m], tq[m], qs);
-    const double qnrm = sqrt(lx_sum(qs, red));
-    for (int m = tid; m < M; m += kLxNT) qn[m] = tq[m] / qnrm;                       // cmtf.py:128
-    __syncthreads();
-    double d2 = 0.0;                                                                 // |u_old - u|^2 = dq^T G_y dq (cmtf.py:129-130)
-    for (int o = tid; o < M * M; o += kLxNT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
-    d2 = lx_sum(d2, red);
-    for (int m = tid; m < M; m += kLxNT) q[m] = qn[m];
-    __syncthreads();
-    if (it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < tol) { ++it; break; }              // first pass: oldU = inf
+    if (lx_q_step(tq, (double)nb, q, qn, Gy, M, tol, it, red)) { ++it; break; }     // t the blocks' average (cmtf.py:126-130)
   }
   bool bad = false;
   for (int m = tid; m < M; m += kLxNT) { bl.b[0].Q[((int64_t)fold * R + a) * M + m] = q[m]; bad |= !isfinite(q[m]); }
@@ -1231,7 +1169,7 @@ int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* mod
     return CMTFPLS_EINVAL;
   }
   for (int m = 0; m < 3; ++m)
-    if (kf_tensor_short(st->A, B1, B2, m) > kLxMaxN) {
+    if (lx_tensor_short(st->A, B1, B2, m) > kLxMaxN) {
       set_error("kfold_inner_tensor: an unfolding of A x B1 x B2 with its shorter side > 256; refit per fold");
       return CMTFPLS_EUNSUPPORTED;
     }
@@ -1246,7 +1184,7 @@ int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* mod
     set_error("kfold_inner_tensor: the fold's vectors exceed the LDS of one workgroup; refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  const KfTensor tn{B1, B2, kf_tensor_nmax(st->A, B1, B2), Wk, Wl};
+  const KfTensor tn{B1, B2, lx_tensor_nmax(st->A, B1, B2), Wk, Wl};
   if (model_fold) return kf_inner_tensor_launch<true>(st, model_fold, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
   return kf_inner_tensor_launch<false>(st, nullptr, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -1313,7 +1251,7 @@ int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, in
   if (rc) return rc;
   for (int b = 0; b < nb; ++b)
     for (int m = 0; m < 3 && dims[2 * b + 1] > 0; ++m)
-      if (kf_tensor_short(blocks[b].A, dims[2 * b], dims[2 * b + 1], m) > kLxMaxN) {
+      if (lx_tensor_short(blocks[b].A, dims[2 * b], dims[2 * b + 1], m) > kLxMaxN) {
         set_error("kfold_inner_coupled_tensor: an unfolding of a block's A x B1 x B2 with its shorter side > 256; refit per fold");
         return CMTFPLS_EUNSUPPORTED;
       }

@@ -18,6 +18,8 @@
 //    (v_mfma_f64_16x16x4_f64, operands straight from L2 in the MFMA layout, the 16 wavefronts of the workgroup dealing the
 //    lower-triangular 16 x 16 tiles among themselves), one exact pass with Z, sign rule on the last mode.
 // Arithmetic: float64 throughout, the reference's operation order outside the re-association above.
+// The fold's steps (means and centred copies, the S build, G_y, the Y score, the deflation, the regression with the Y deflation, the
+// held-out row and the prediction tail) are loo_xcov_fold.hpp's, shared with loo_xcov_coupled.hip; the inner loop is fold_loop.hpp's.
 // Limits: X of order 2 or 3 without missing values, min(A, B) <= 256, M <= 128, R <= 64, the workgroup's small vectors in
 // 150 KB of LDS; per resident fold a workspace of I P + M P + 3 P + 2 n^2 + I (M + R + 2) + R (A + B) doubles (cmtfpls_loo_xcov_fold_workspace_bytes).
 //
@@ -28,8 +30,7 @@
 // largest short side of the three unfoldings of A x B1 x B2 (each <= 256).  LDS: xs (n), then in place of ys (k) lx_cp3's wK (B1),
 // wL (B2), v (B), tmp (max(A, B1, B2)) and part (1024); workspace: lx_cp3's U, yl, vr (P each) after wk
 // (cmtfpls_loo_xcov_tensor_fold_workspace_bytes).
-#include "fold_loop.hpp"
-#include "fold_regress.hpp"
+#include "loo_xcov_fold.hpp"
 
 namespace cmtfpls {
 
@@ -109,115 +110,37 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(typename LooXArgsOf<TEN
 
   // ---- preprocess (tpls.py:61-71): the fold's means by down-dating the column sums; centred copies with the held-out row zero
   for (int o = tid; o < R * R; o += kLxNT) coef[o] = 0.0;
-  for (int m = tid; m < M; m += kLxNT) my[m] = (a.colsum_y[m] - a.Y[(int64_t)fold * M + m]) * inv;
-  for (int64_t c = tid; c < P; c += kLxNT) Z[c] = (a.colsum_x[c] - a.X[(int64_t)fold * P + c]) * inv;
-  __syncthreads();
-  for (int r = 0; r < I; ++r) {
-    const double* xr = a.X + (int64_t)r * P;
-    double* xo = Xf + (int64_t)r * P;
-    if (r == fold) { for (int64_t c = tid; c < P; c += kLxNT) xo[c] = 0.0; }
-    else { for (int64_t c = tid; c < P; c += kLxNT) xo[c] = xr[c] - Z[c]; }
-  }
-  for (int64_t idx = tid; idx < (int64_t)I * M; idx += kLxNT) {
-    const int r = (int)(idx / M), m = (int)(idx % M);
-    Yf[idx] = (r == fold) ? 0.0 : a.Y[idx] - my[m];
-  }
-  __syncthreads();
+  lxf_mean_y<kLxNT>(a.Y, a.colsum_y, fold, M, inv, my);
+  lxf_centre_block<kLxNT>(a.X, a.colsum_x, fold, I, P, inv, Z, Xf);
+  lxf_centre_y<kLxNT>(a.Y, my, fold, I, M, Yf);
 
   for (int comp = 0; comp < R; ++comp) {
-    // ---- S = Y_f^T X_f and G_y = Y_f^T Y_f of this component (X_f, Y_f as deflated so far) ----
-    for (int64_t c = tid; c < P; c += kLxNT) {
-      for (int mc = 0; mc < M; mc += 16) {
-        double acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.0;
-        // four rows of the column in flight at a time (one row per trip leaves a single load per lane outstanding: the pass
-        // is then bound by memory latency, 16 ms per component and fold at 512 x 16384 instead of 2)
-        int r = 0;
-        for (; r + 4 <= I; r += 4) {
-          double x[4];
-#pragma unroll
-          for (int u4 = 0; u4 < 4; ++u4) x[u4] = Xf[(int64_t)(r + u4) * P + c];
-#pragma unroll
-          for (int u4 = 0; u4 < 4; ++u4) {
-            const double* yr = Yf + (int64_t)(r + u4) * M + mc;
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-              if (mc + j < M) acc[j] = fma(yr[j], x[u4], acc[j]);
-          }
-        }
-        for (; r < I; ++r) {
-          const double x = Xf[(int64_t)r * P + c];
-          const double* yr = Yf + (int64_t)r * M + mc;
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (mc + j < M) acc[j] = fma(yr[j], x, acc[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (mc + j < M) S[(int64_t)(mc + j) * P + c] = acc[j];
-      }
-    }
-    for (int o = tid; o < M * M; o += kLxNT) {
-      const int m1 = o / M, m2 = o % M;
-      double s = 0.0;
-      for (int r = 0; r < I; ++r) s = fma(Yf[(int64_t)r * M + m1], Yf[(int64_t)r * M + m2], s);
-      Gy[o] = s;
-    }
+    // ---- S = Y_f^T X_f and G_y = Y_f^T Y_f of this component (X_f, Y_f as deflated so far), then the inner loop on them ----
+    lxf_build_s<kLxNT>(Xf, Yf, I, P, M, S);
+    lxf_gram_y<kLxNT>(Yf, I, M, Gy);
     int it;
     if constexpr (TENSOR) {
-      LxTensor lt;
-      lt.B1 = a.B1;
-      lt.B2 = a.B2;
-      lt.wK = ys;
-      lt.wL = lt.wK + a.B1;
-      lt.v = lt.wL + a.B2;
-      lt.tmp = lt.v + B;
-      lt.part = lt.tmp + max(A, max(a.B1, a.B2));
-      lt.U = wk + P;
-      lt.yl = lt.U + P;
-      lt.vr = lt.yl + P;
+      const LxTensor lt = lx_tensor_scratch(ys, wk + P, a.B1, a.B2, B, max(A, max(a.B1, a.B2)), P, kLxNT);
       it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti, lt);
     } else {
       it = lx_inner_loop(S, Gy, P, M, A, B, a.tol, a.max_iter, q, qn, tq, Z, Zt, wk, wA, wB, G0, G1, xs, ys, red, bestv, besti);
     }
     if (a.n_iter && tid == 0) a.n_iter[(int64_t)fold * R + comp] = it;
-    // ---- the component's score and Y score with the converged loadings (tpls.py:97-102) ----
-    for (int r = wv; r < I; r += kLxWaves) {                                             // (wk holds the converged loadings' Kronecker product)
-      const double s = lx_wave_dot(Xf + (int64_t)r * P, wk, P, lane);
-      if (lane == 0) t[r] = s;
-    }
-    for (int r = tid; r < I; r += kLxNT) {
-      double s = 0.0;
-      for (int m = 0; m < M; ++m) s = fma(Yf[(int64_t)r * M + m], q[m], s);
-      u[r] = s;
-    }
+    // ---- the component's score and Y score with the converged loadings (tpls.py:97-102); wk holds their Kronecker product ----
+    lx_row_dots(Xf, wk, P, I, lane, wv, [t](int r, double s) { t[r] = s; });
+    lxf_y_score<kLxNT>(Yf, q, I, M, u);
     __syncthreads();
     for (int r = tid; r < I; r += kLxNT) T[(int64_t)r * R + comp] = t[r];
     for (int j = tid; j < A; j += kLxNT) Wa[comp * A + j] = wA[j];
     for (int j = tid; j < B; j += kLxNT) Wb[comp * B + j] = wB[j];
     for (int m = tid; m < M; m += kLxNT) Qs[comp * M + m] = q[m];
-    // ---- deflate X (tpls.py:109) ----
-    for (int r = 0; r < I; ++r) {
-      const double tr = t[r];
-      double* xr = Xf + (int64_t)r * P;
-      for (int64_t c = tid; c < P; c += kLxNT) xr[c] = fma(-tr, wk[c], xr[c]);
-    }
+    lxf_deflate<kLxNT>(Xf, t, wk, I, P);                                              // tpls.py:109
     __syncthreads();
-    // ---- inner regression b = lstsq(T[:, :k], u) (tpls.py:110-112), fold_regress.hpp; then Y -= T b q^T (tpls.py:113), yhat = T b in t ----
-    fold_inner_regression<kLxNT, false>(T, u, nullptr, I, R, comp, Gn, gn, bb, dd, coef, t);
-    for (int64_t idx = tid; idx < (int64_t)I * M; idx += kLxNT) {
-      const int r = (int)(idx / M), m = (int)(idx % M);
-      Yf[idx] = fma(-t[r], q[m], Yf[idx]);
-    }
-    __syncthreads();
+    lxf_regress_deflate_y<kLxNT>(T, u, I, M, R, comp, Gn, gn, bb, dd, coef, t, q, Yf);
   }
 
   // ---- predict the held-out sample (tpls.py:122-143): centre with the fold's means, project and deflate ----
-  for (int64_t c = tid; c < P; c += kLxNT) {
-    const double xv = a.X[(int64_t)fold * P + c];
-    Z[c] = xv - (a.colsum_x[c] - xv) * inv;
-  }
+  lxf_heldout_row<kLxNT>(a.X, a.colsum_x, fold, P, inv, Z);
   __syncthreads();
   double* sc = scv;                                                                     // scores of the held-out row (R)
   for (int comp = 0; comp < R; ++comp) {
@@ -228,32 +151,13 @@ __global__ __launch_bounds__(kLxNT) void loo_xcov_kernel(typename LooXArgsOf<TEN
     for (int64_t c = tid; c < P; c += kLxNT) Z[c] = fma(-sv, Wa[comp * A + c / B] * Wb[comp * B + c % B], Z[c]);
     __syncthreads();
   }
-  for (int m = tid; m < M; m += kLxNT) {
-    double yv = 0.0;
-    for (int b2 = 0; b2 < R; ++b2) {
-      double sb = 0.0;
-      for (int a2 = 0; a2 < R; ++a2) sb = fma(sc[a2], coef[a2 * R + b2], sb);        // (scores @ coef_)[b]
-      yv = fma(sb, Qs[b2 * M + m], yv);                                             // @ Q^T
-    }
-    a.Ypred[(int64_t)fold * M + m] = yv + my[m];
-  }
+  lxf_predict<kLxNT>(sc, coef, Qs, my, R, M, a.Ypred + (int64_t)fold * M);
 }
 
 static size_t lx_lds_bytes(int A, int B, int M, int R) {
   const size_t n = (size_t)(A < B ? A : B), k = (size_t)(A < B ? B : A);
   const size_t dbl = (size_t)A + B + 4 * (size_t)M + (size_t)M * M + n + k + (size_t)R * R + (size_t)R * M + (size_t)R * R + 3 * (size_t)R;
   return dbl * sizeof(double);
-}
-
-static int lx_tensor_short(int A, int B1, int B2, int mode) {
-  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
-  return (int)(d < rest ? d : rest);
-}
-
-static int lx_tensor_nmax(int A, int B1, int B2) {
-  int n = 0;
-  for (int m = 0; m < 3; ++m) n = lx_tensor_short(A, B1, B2, m) > n ? lx_tensor_short(A, B1, B2, m) : n;
-  return n;
 }
 
 // lx_lds_bytes with xs (nmax) and, in place of ys, lx_cp3's wK (B1), wL (B2), v (B1 B2), tmp (max dim) and part (kLxNT)

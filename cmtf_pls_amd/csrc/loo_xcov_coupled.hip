@@ -16,6 +16,9 @@
 //    pass (oldU = inf, cmtf.py:89).  The extraction of a block (cmtf.py:98-104) is Z_b / |Z_b| for a matrix block and lx_rank1
 //    (fold_loop.hpp: Gram squarings on the f64 matrix cores, sign rule on the last mode) for an order-3 block.
 //  * coef[:, a] from the normal equations of T (equilibrated Cholesky, as loo_xcov.hip), then Y_f -= T b q^T (cmtf.py:135-138).
+// The steps are loo_xcov.hip's, called once per block: loo_xcov_fold.hpp for the fold's own, fold_loop.hpp for a pass of the inner
+// loop.  This kernel keeps the block descriptors in LDS, the block-order sums into tq and t with their / nb, the Kronecker loading
+// recomputed per block (one wk buffer serves all blocks), and the 512-thread TENSOR instantiation.
 // Held-out prediction: the sequential form of cmtf.py:154-177 on the held-out rows of all blocks -- per component the block average
 // of the projections, then each block's row deflated with its own loadings -- written to row `fold` of Ypred.
 //
@@ -47,8 +50,8 @@
 // Limits: at most 8 blocks, min(A_b, B_b) <= 256 in a block of order 2 or 3, the shorter side of every unfolding of a tensor block
 // <= 256, M <= 128, R <= 64, P_b <= 2^24, LDS <= 150 KB.  A description without a block of order 4 is a bad argument (EINVAL): that
 // call is cmtfpls_loo_xcov_coupled_f64's.
-#include "fold_loop.hpp"
-#include "fold_regress.hpp"
+#include <string>
+#include "loo_xcov_fold.hpp"
 
 namespace cmtfpls {
 
@@ -155,16 +158,9 @@ __global__ __launch_bounds__(TENSOR ? kLxcTensorNT : kLxNT) void loo_xcov_couple
   double* ys = xs + n;            // kmax
   double* coef = ys + a.maxk;     // R x R   (TENSOR: after lx_cp3's wK, wL, v, tmp, part)
   LxTensor lt;
-  if constexpr (TENSOR) {         // lx_cp3's scratch, shared by the tensor blocks
-    lt.wK = ys + a.maxk;          // b1max
-    lt.wL = lt.wK + a.b1max;      // b2max
-    lt.v = lt.wL + a.b2max;       // btmax
-    lt.tmp = lt.v + a.btmax;      // dmax
-    lt.part = lt.tmp + a.dmax;    // NT
+  if constexpr (TENSOR) {         // lx_cp3's scratch, shared by the tensor blocks: LDS after ys, global after wk
+    lt = lx_tensor_scratch(ys + a.maxk, wk + a.maxP, a.b1max, a.b2max, a.btmax, a.dmax, a.ptmax, NT);
     coef = lt.part + NT;
-    lt.U = wk + a.maxP;           // ptmax each
-    lt.yl = lt.U + a.ptmax;
-    lt.vr = lt.yl + a.ptmax;
   }
   double* Qs = coef + R * R;      // R x M
   double* Gn = Qs + R * M;        // (a+1) x (a+1) normal equations
@@ -176,73 +172,19 @@ __global__ __launch_bounds__(TENSOR ? kLxcTensorNT : kLxNT) void loo_xcov_couple
 
   // ---- preprocess (cmtf.py:44-83): the fold's means by down-dating the column sums; centred copies with the held-out row zero
   for (int o = tid; o < R * R; o += NT) coef[o] = 0.0;
-  for (int m = tid; m < M; m += NT) my[m] = (a.colsum_y[m] - a.Y[(int64_t)fold * M + m]) * inv;
+  lxf_mean_y<NT>(a.Y, a.colsum_y, fold, M, inv, my);
   __syncthreads();
   for (int b = 0; b < nb; ++b) {
-    const int64_t P = (int64_t)sA[b] * sB[b];
-    const double* Xb = sX[b];
-    const double* csb = sCs[b];
-    double* Xfb = Xf + (int64_t)I * sOp[b];
-    for (int64_t c = tid; c < P; c += NT) Z[c] = (csb[c] - Xb[(int64_t)fold * P + c]) * inv;
-    __syncthreads();
-    for (int r = 0; r < I; ++r) {
-      const double* xr = Xb + (int64_t)r * P;
-      double* xo = Xfb + (int64_t)r * P;
-      if (r == fold) { for (int64_t c = tid; c < P; c += NT) xo[c] = 0.0; }
-      else { for (int64_t c = tid; c < P; c += NT) xo[c] = xr[c] - Z[c]; }
-    }
+    lxf_centre_block<NT>(sX[b], sCs[b], fold, I, (int64_t)sA[b] * sB[b], inv, Z, Xf + (int64_t)I * sOp[b]);
     __syncthreads();
   }
-  for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
-    const int r = (int)(idx / M), m = (int)(idx % M);
-    Yf[idx] = (r == fold) ? 0.0 : a.Y[idx] - my[m];
-  }
-  __syncthreads();
+  lxf_centre_y<NT>(a.Y, my, fold, I, M, Yf);
 
   for (int comp = 0; comp < R; ++comp) {
     // ---- S_b = Y_f^T X_{b,f} of every block and G_y = Y_f^T Y_f of this component (X_{b,f}, Y_f as deflated so far) ----
-    for (int b = 0; b < nb; ++b) {
-      const int64_t P = (int64_t)sA[b] * sB[b];
-      const double* Xfb = Xf + (int64_t)I * sOp[b];
-      double* Sb = S + (int64_t)M * sOp[b];
-      for (int64_t c = tid; c < P; c += NT) {
-        for (int mc = 0; mc < M; mc += 16) {
-          double acc[16];
-#pragma unroll
-          for (int j = 0; j < 16; ++j) acc[j] = 0.0;
-          // four rows of the column in flight at a time (loo_xcov.hip: one row per trip leaves the pass bound by memory latency)
-          int r = 0;
-          for (; r + 4 <= I; r += 4) {
-            double x[4];
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) x[u4] = Xfb[(int64_t)(r + u4) * P + c];
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) {
-              const double* yr = Yf + (int64_t)(r + u4) * M + mc;
-#pragma unroll
-              for (int j = 0; j < 16; ++j)
-                if (mc + j < M) acc[j] = fma(yr[j], x[u4], acc[j]);
-            }
-          }
-          for (; r < I; ++r) {
-            const double x = Xfb[(int64_t)r * P + c];
-            const double* yr = Yf + (int64_t)r * M + mc;
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-              if (mc + j < M) acc[j] = fma(yr[j], x, acc[j]);
-          }
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (mc + j < M) Sb[(int64_t)(mc + j) * P + c] = acc[j];
-        }
-      }
-    }
-    for (int o = tid; o < M * M; o += NT) {
-      const int m1 = o / M, m2 = o % M;
-      double s = 0.0;
-      for (int r = 0; r < I; ++r) s = fma(Yf[(int64_t)r * M + m1], Yf[(int64_t)r * M + m2], s);
-      Gy[o] = s;
-    }
+    for (int b = 0; b < nb; ++b)
+      lxf_build_s<NT>(Xf + (int64_t)I * sOp[b], Yf, I, (int64_t)sA[b] * sB[b], M, S + (int64_t)M * sOp[b]);
+    lxf_gram_y<NT>(Yf, I, M, Gy);
     // ---- the inner loop on the S_b (cmtf.py:89-128) ----
     for (int m = tid; m < M; m += NT) q[m] = (m == 0) ? 1.0 : 0.0;                 // u_0 = Y_f[:, 0] = Y_f e_0 (cmtf.py:90)
     __syncthreads();
@@ -254,75 +196,30 @@ __global__ __launch_bounds__(TENSOR ? kLxcTensorNT : kLxNT) void loo_xcov_couple
         const double* Sb = S + (int64_t)M * sOp[b];
         double* wAb = wA + sOa[b];
         double* wBb = wB + sOb[b];
-        for (int64_t c = tid; c < P; c += NT) {                                     // Z_b = X_b x_0 u = S_b^T q (cmtf.py:94)
-          double s = 0.0;
-          int m = 0;
-          for (; m + 4 <= M; m += 4) {                                                 // (four rows of S_b in flight; same order of the sum)
-            const double s0 = Sb[(int64_t)m * P + c], s1 = Sb[(int64_t)(m + 1) * P + c], s2 = Sb[(int64_t)(m + 2) * P + c], s3 = Sb[(int64_t)(m + 3) * P + c];
-            s = fma(q[m], s0, s);
-            s = fma(q[m + 1], s1, s);
-            s = fma(q[m + 2], s2, s);
-            s = fma(q[m + 3], s3, s);
-          }
-          for (; m < M; ++m) s = fma(q[m], Sb[(int64_t)m * P + c], s);
-          Z[c] = s;
+        lx_z_from_s<NT>(Sb, q, Z, P, M);                                               // cmtf.py:94
+        if constexpr (TENSOR) {                                                        // B2 > 0: order 4, lx_cp3 leaves wB_b = wK_b (x) wL_b
+          lt.B1 = sB1[b];
+          lt.B2 = sB2[b];
         }
+        lx_extract<TENSOR, NT>(Z, Zt, A, B, P, a.tol, lt, wAb, wBb, G0, G1, xs, ys, red, bestv, besti);   // cmtf.py:98-104
+        lx_kron<NT>(wk, wAb, wBb, P, B);                                               // once per extraction
         __syncthreads();
-        bool cp = false;
-        if constexpr (TENSOR) cp = sB2[b] > 0;
-        if (cp) {                                                                      // order 4: the rank-1 CP of the A x B1 x B2 Z_b
-          if constexpr (TENSOR) {
-            lt.B1 = sB1[b];
-            lt.B2 = sB2[b];
-            lx_cp3<NT>(Z, Zt, A, a.tol, lt, wAb, wBb, G0, G1, xs, red, bestv, besti);   // leaves wB_b = wK_b (x) wL_b
-          }
-        } else if (A == 1) {                                                           // cmtf.py:98: Z / norm(Z)
-          double s = 0.0;
-          for (int64_t c = tid; c < P; c += NT) s = fma(Z[c], Z[c], s);
-          const double nz = sqrt(lx_sum<NT>(s, red));
-          for (int64_t c = tid; c < P; c += NT) wBb[c] = Z[c] / nz;
-          if (tid == 0) wAb[0] = 1.0;
-          __syncthreads();
-        } else {
-          lx_rank1<false, NT>(Z, Zt, A, B, wAb, wBb, G0, G1, xs, ys, red, bestv, besti);   // cmtf.py:100-102
-        }
-        for (int64_t c = tid; c < P; c += NT) wk[c] = wAb[c / B] * wBb[c % B];      // the Kronecker loading, once per extraction
-        __syncthreads();
-        for (int m = wv; m < M; m += NW) {                                       // Y^T t: + S_b (wA_b (x) wB_b) (cmtf.py:106-121)
-          const double s = lx_wave_dot(Sb + (int64_t)m * P, wk, P, lane);
-          if (lane == 0) tq[m] = (b == 0) ? s : tq[m] + s;                             // (row m is always this wavefront's)
-        }
+        // Y^T t: + S_b (wA_b (x) wB_b) (cmtf.py:106-121), assigned by block 0 and added in block order; / nb in lx_q_step
+        lx_row_dots<NT>(Sb, wk, P, M, lane, wv, [tq, b](int m, double s) { tq[m] = (b == 0) ? s : tq[m] + s; });
         __syncthreads();
       }
-      double qs = 0.0;
-      for (int m = tid; m < M; m += NT) { const double v = tq[m] / nbd; qs = fma(v, v, qs); }   // np.average over the blocks (cmtf.py:120)
-      const double qnrm = sqrt(lx_sum<NT>(qs, red));
-      for (int m = tid; m < M; m += NT) qn[m] = (tq[m] / nbd) / qnrm;               // cmtf.py:122
-      __syncthreads();
-      double d2 = 0.0;                                                                 // |u_old - u|^2 = dq^T G_y dq (cmtf.py:123-124)
-      for (int o = tid; o < M * M; o += NT) d2 = fma((qn[o / M] - q[o / M]) * Gy[o], qn[o % M] - q[o % M], d2);
-      d2 = lx_sum<NT>(d2, red);
-      for (int m = tid; m < M; m += NT) q[m] = qn[m];
-      __syncthreads();
-      if (it > 0 && sqrt(d2 > 0.0 ? d2 : 0.0) < a.tol) { ++it; break; }               // first pass: oldU = inf (cmtf.py:89)
+      if (lx_q_step<NT>(tq, nbd, q, qn, Gy, M, a.tol, it, red)) { ++it; break; }     // np.average over the blocks (cmtf.py:120-124)
     }
     if (a.n_iter && tid == 0) a.n_iter[(int64_t)fold * R + comp] = it;
     // ---- the component's score t = mean_b X_{b,f} (wA_b (x) wB_b) (cmtf.py:106-120) and Y score with the converged loadings ----
     for (int b = 0; b < nb; ++b) {
-      const int B = sB[b];
-      const int64_t P = (int64_t)sA[b] * B;
-      const double* Xfb = Xf + (int64_t)I * sOp[b];
-      const double* wAb = wA + sOa[b];
-      const double* wBb = wB + sOb[b];
-      for (int64_t c = tid; c < P; c += NT) wk[c] = wAb[c / B] * wBb[c % B];
+      const int64_t P = (int64_t)sA[b] * sB[b];
+      lx_kron<NT>(wk, wA + sOa[b], wB + sOb[b], P, sB[b]);
       __syncthreads();
-      for (int r = wv; r < I; r += NW) {
-        const double s = lx_wave_dot(Xfb + (int64_t)r * P, wk, P, lane);
-        if (lane == 0) t[r] = (b == 0) ? s : t[r] + s;                                 // (row r is always this wavefront's)
-      }
+      lx_row_dots<NT>(Xf + (int64_t)I * sOp[b], wk, P, I, lane, wv, [t, b](int r, double s) { t[r] = (b == 0) ? s : t[r] + s; });
       __syncthreads();
     }
-    for (int r = tid; r < I; r += NT) {
+    for (int r = tid; r < I; r += NT) {                // (the Y score stays in this loop: as lxf_y_score in a loop of its own it spills)
       const double tr = t[r] / nbd;
       t[r] = tr;
       T[(int64_t)r * R + comp] = tr;
@@ -339,39 +236,16 @@ __global__ __launch_bounds__(TENSOR ? kLxcTensorNT : kLxNT) void loo_xcov_couple
     __syncthreads();
     // ---- deflate every block by its own t (x) wA_b (x) wB_b (cmtf.py:130-131) ----
     for (int b = 0; b < nb; ++b) {
-      const int B = sB[b];
-      const int64_t P = (int64_t)sA[b] * B;
-      double* Xfb = Xf + (int64_t)I * sOp[b];
-      const double* wAb = wA + sOa[b];
-      const double* wBb = wB + sOb[b];
-      for (int64_t c = tid; c < P; c += NT) wk[c] = wAb[c / B] * wBb[c % B];   // (each thread reads back only what it wrote)
-      for (int r = 0; r < I; ++r) {
-        const double tr = t[r];
-        double* xr = Xfb + (int64_t)r * P;
-        for (int64_t c = tid; c < P; c += NT) xr[c] = fma(-tr, wk[c], xr[c]);
-      }
+      const int64_t P = (int64_t)sA[b] * sB[b];
+      lx_kron<NT>(wk, wA + sOa[b], wB + sOb[b], P, sB[b]);                             // (each thread reads back only what it wrote)
+      lxf_deflate<NT>(Xf + (int64_t)I * sOp[b], t, wk, I, P);
     }
     __syncthreads();
-    // ---- inner regression b = lstsq(T[:, :k], u) (cmtf.py:135), fold_regress.hpp; then Y -= T b q^T (cmtf.py:138), yhat = T b in t ----
-    fold_inner_regression<NT, false>(T, u, nullptr, I, R, comp, Gn, gn, bb, dd, coef, t);
-    for (int64_t idx = tid; idx < (int64_t)I * M; idx += NT) {
-      const int r = (int)(idx / M), m = (int)(idx % M);
-      Yf[idx] = fma(-t[r], q[m], Yf[idx]);
-    }
-    __syncthreads();
+    lxf_regress_deflate_y<NT>(T, u, I, M, R, comp, Gn, gn, bb, dd, coef, t, q, Yf);   // cmtf.py:135-138
   }
 
   // ---- predict the held-out sample (cmtf.py:142-177): centre every block's row with the fold's means, project and deflate ----
-  for (int b = 0; b < nb; ++b) {
-    const int64_t P = (int64_t)sA[b] * sB[b];
-    const double* Xb = sX[b];
-    const double* csb = sCs[b];
-    double* Hb = H + sOp[b];
-    for (int64_t c = tid; c < P; c += NT) {
-      const double xv = Xb[(int64_t)fold * P + c];
-      Hb[c] = xv - (csb[c] - xv) * inv;
-    }
-  }
+  for (int b = 0; b < nb; ++b) lxf_heldout_row<NT>(sX[b], sCs[b], fold, (int64_t)sA[b] * sB[b], inv, H + sOp[b]);
   __syncthreads();
   double* sc = scv;                                                                     // scores of the held-out row (R)
   for (int comp = 0; comp < R; ++comp) {
@@ -398,38 +272,57 @@ __global__ __launch_bounds__(TENSOR ? kLxcTensorNT : kLxNT) void loo_xcov_couple
     }
     __syncthreads();
   }
-  for (int m = tid; m < M; m += NT) {
-    double yv = 0.0;
-    for (int b2 = 0; b2 < R; ++b2) {
-      double sb = 0.0;
-      for (int a2 = 0; a2 < R; ++a2) sb = fma(sc[a2], coef[a2 * R + b2], sb);        // (scores @ coef_)[b]
-      yv = fma(sb, Qs[b2 * M + m], yv);                                             // @ Q^T
-    }
-    a.Ypred[(int64_t)fold * M + m] = yv + my[m];
-  }
+  lxf_predict<NT>(sc, coef, Qs, my, R, M, a.Ypred + (int64_t)fold * M);
 }
 
+// what the kernel's LDS and workspace are sized by: sums and maxima over the blocks; maxn over the order-2/3 blocks' min(A, B) and
+// the shorter side of every unfolding of every tensor block, maxk over the order-2/3 blocks' max(A, B) alone (a tensor block has no
+// ys); lx_cp3's shared scratch by the largest B1, B2, B1 B2, single dim and A B1 B2 over the tensor blocks
 struct LxcShape {
   size_t sumA, sumB, sumP, maxP, maxn, maxk;
+  size_t b1max, b2max, btmax, dmax, ptmax;
 };
 
-static LxcShape lxc_shape(const cmtfpls_loo_coupled_block* blocks, int nb) {
-  LxcShape s = {0, 0, 0, 0, 0, 0};
+// dims: (B1, B2) per block, B2 > 0 a block of order 4; null: no such block (cmtfpls_loo_xcov_coupled_f64)
+static LxcShape lxc_shape(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims) {
+  LxcShape o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = 0; b < nb; ++b) {
-    const size_t A = (size_t)blocks[b].A, B = (size_t)blocks[b].B, n = A < B ? A : B, k = A < B ? B : A;
-    s.sumA += A;
-    s.sumB += B;
-    s.sumP += A * B;
-    s.maxP = A * B > s.maxP ? A * B : s.maxP;
-    s.maxn = n > s.maxn ? n : s.maxn;
-    s.maxk = k > s.maxk ? k : s.maxk;
+    const size_t A = (size_t)blocks[b].A, B = (size_t)blocks[b].B, B1 = dims ? (size_t)dims[2 * b] : 0, B2 = dims ? (size_t)dims[2 * b + 1] : 0;
+    size_t n;
+    o.sumA += A;
+    o.sumB += B;
+    o.sumP += A * B;
+    o.maxP = A * B > o.maxP ? A * B : o.maxP;
+    if (B2 > 0) {
+      n = (size_t)lx_tensor_nmax((int)A, (int)B1, (int)B2);
+      const size_t dm = A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2);
+      o.b1max = B1 > o.b1max ? B1 : o.b1max;
+      o.b2max = B2 > o.b2max ? B2 : o.b2max;
+      o.btmax = B > o.btmax ? B : o.btmax;
+      o.dmax = dm > o.dmax ? dm : o.dmax;
+      o.ptmax = A * B > o.ptmax ? A * B : o.ptmax;
+    } else {
+      n = A < B ? A : B;
+      const size_t k = A < B ? B : A;
+      o.maxk = k > o.maxk ? k : o.maxk;
+    }
+    o.maxn = n > o.maxn ? n : o.maxn;
   }
-  return s;
+  return o;
 }
 
+// the kernel's LDS carve-up; TENSOR: then lx_cp3's wK (b1max), wL (b2max), v (btmax), tmp (dmax) and part (the workgroup's 512 threads)
+template <bool TENSOR>
 static size_t lxc_lds_bytes(const LxcShape& s, int M, int R) {
   const size_t dbl = s.sumA + s.sumB + 4 * (size_t)M + (size_t)M * M + s.maxn + s.maxk + 2 * (size_t)R * R + (size_t)R * M + 3 * (size_t)R;
-  return dbl * sizeof(double);
+  return (dbl + (TENSOR ? s.b1max + s.b2max + s.btmax + s.dmax + kLxcTensorNT : 0)) * sizeof(double);
+}
+
+// the kernel's global carve-up per resident fold; TENSOR: with lx_cp3's U, yl, vr (ptmax each)
+template <bool TENSOR>
+static size_t lxc_ws_bytes(const LxcShape& s, int I, int M, int R) {
+  return (((size_t)I + M) * s.sumP + 3 * s.maxP + (TENSOR ? 3 * s.ptmax : 0) + 2 * s.maxn * s.maxn + (size_t)I * ((size_t)M + R + 2) +
+          (size_t)R * (s.sumA + s.sumB)) * sizeof(double);
 }
 
 static bool lxc_sizes_ok(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R) {
@@ -439,59 +332,8 @@ static bool lxc_sizes_ok(const cmtfpls_loo_coupled_block* blocks, int nb, int I,
   return true;
 }
 
-// ---- blocks of order 4 (cmtfpls_loo_xcov_coupled_tensor_f64) ---------------------------------------------------------------------
-static int lxc_tensor_short(int A, int B1, int B2, int mode) {
-  const int64_t d = mode == 0 ? A : mode == 1 ? B1 : B2, rest = (int64_t)A * B1 * B2 / d;
-  return (int)(d < rest ? d : rest);
-}
-
-// LxcShape with maxn over the order-2/3 blocks' min(A, B) and the shorter side of every unfolding of every tensor block, maxk over
-// the order-2/3 blocks alone (a tensor block has no ys), and what lx_cp3's shared scratch is sized by
-struct LxcTensorShape {
-  LxcShape s;
-  size_t b1max, b2max, btmax, dmax, ptmax;
-  int tensors;
-};
-
-static LxcTensorShape lxc_tensor_shape(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims) {
-  LxcTensorShape o = {{0, 0, 0, 0, 0, 0}, 0, 0, 0, 0, 0, 0};
-  for (int b = 0; b < nb; ++b) {
-    const size_t A = (size_t)blocks[b].A, B = (size_t)blocks[b].B, B1 = (size_t)dims[2 * b], B2 = (size_t)dims[2 * b + 1];
-    size_t n;
-    o.s.sumA += A;
-    o.s.sumB += B;
-    o.s.sumP += A * B;
-    o.s.maxP = A * B > o.s.maxP ? A * B : o.s.maxP;
-    if (B2 > 0) {
-      n = 0;
-      for (int m = 0; m < 3; ++m) {
-        const size_t sh = (size_t)lxc_tensor_short((int)A, (int)B1, (int)B2, m);
-        n = sh > n ? sh : n;
-      }
-      const size_t dm = A > B1 ? (A > B2 ? A : B2) : (B1 > B2 ? B1 : B2);
-      o.b1max = B1 > o.b1max ? B1 : o.b1max;
-      o.b2max = B2 > o.b2max ? B2 : o.b2max;
-      o.btmax = B > o.btmax ? B : o.btmax;
-      o.dmax = dm > o.dmax ? dm : o.dmax;
-      o.ptmax = A * B > o.ptmax ? A * B : o.ptmax;
-      ++o.tensors;
-    } else {
-      n = A < B ? A : B;
-      const size_t k = A < B ? B : A;
-      o.s.maxk = k > o.s.maxk ? k : o.s.maxk;
-    }
-    o.s.maxn = n > o.s.maxn ? n : o.s.maxn;
-  }
-  return o;
-}
-
-// lxc_lds_bytes, then lx_cp3's wK (b1max), wL (b2max), v (btmax), tmp (dmax) and part (the workgroup's 512 threads)
-static size_t lxc_tensor_lds_bytes(const LxcTensorShape& o, int M, int R) {
-  return lxc_lds_bytes(o.s, M, R) + (o.b1max + o.b2max + o.btmax + o.dmax + kLxcTensorNT) * sizeof(double);
-}
-
-// what the size functions and the entry call a well-formed description: lxc_sizes_ok, dims without a negative entry, order 4 exactly
-// where B2 > 0 (then B1 B2 == B), no order above 4 and at least one block of order 4; P_b <= 2^24 keeps the sums in range
+// what the tensor size functions and entry call a well-formed description: lxc_sizes_ok, dims without a negative entry, order 4
+// exactly where B2 > 0 (then B1 B2 == B), no order above 4 and at least one block of order 4; P_b <= 2^24 keeps the sums in range
 static bool lxc_tensor_dims_ok(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims) {
   if (!dims) return false;
   int tensors = 0;
@@ -510,6 +352,76 @@ static bool lxc_cells_ok(const cmtfpls_loo_coupled_block* blocks, int nb) {
   return true;
 }
 
+// The checks, argument fill and launch of the two entries: cmtfpls_loo_xcov_coupled_f64 (TENSOR = false, dims null) and
+// cmtfpls_loo_xcov_coupled_tensor_f64.  Each keeps the order of its checks: only where "more than 8 blocks" is tested differs, and
+// what a block's short side is.
+template <bool TENSOR>
+static int lxc_run(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, const double* Y, const double* colsum_y, int I, int M,
+                   int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws, size_t ws_bytes,
+                   void* stream) {
+  const std::string who = TENSOR ? "loo_xcov_coupled_tensor" : "loo_xcov_coupled";
+  const std::string refit = "; refit per fold on the regular engine";
+  auto fail = [&](int code, const std::string& what) { set_error((who + ": " + what).c_str()); return code; };
+  if (!blocks || (TENSOR && !dims) || !Y || !colsum_y || !Ypred || nb <= 0 || I <= 1 || M <= 0 || R <= 0 || max_iter <= 0 || fold0 < 0 ||
+      nfolds <= 0 || fold0 + nfolds > I)
+    return fail(CMTFPLS_EINVAL, "bad argument");
+  if (!TENSOR && nb > kLxcMaxBlocks) return fail(CMTFPLS_EUNSUPPORTED, "more than 8 blocks" + refit);
+  for (int b = 0; b < nb; ++b) {
+    const cmtfpls_loo_coupled_block& k = blocks[b];
+    if (!k.X || !k.colsum || k.A <= 0 || k.B <= 0 || k.order < 2 || (k.order == 2 && k.A != 1)) return fail(CMTFPLS_EINVAL, "bad block");
+  }
+  if constexpr (TENSOR) {
+    if (!lxc_tensor_dims_ok(blocks, nb, dims))
+      return fail(CMTFPLS_EINVAL, "bad dims ((B1, B2) with B1 * B2 == B for every block of order 4 and at least one such block, "
+                                  "(0, 0) for a block of order 2 or 3; no order above 4)");
+    if (nb > kLxcMaxBlocks) return fail(CMTFPLS_EUNSUPPORTED, "more than 8 blocks" + refit);
+  } else {
+    for (int b = 0; b < nb; ++b)
+      if (blocks[b].order > 3) return fail(CMTFPLS_EUNSUPPORTED, "a block of order > 3" + refit);
+  }
+  for (int b = 0; b < nb; ++b)
+    if (!(TENSOR && dims[2 * b + 1] > 0) && (blocks[b].A < blocks[b].B ? blocks[b].A : blocks[b].B) > kLxMaxN)
+      return fail(CMTFPLS_EUNSUPPORTED, (TENSOR ? "min(A, B) > 256 in a block of order 2 or 3" : "min(A, B) > 256 in a block") + refit);
+  if constexpr (TENSOR)
+    for (int b = 0; b < nb; ++b)
+      for (int m = 0; m < 3 && dims[2 * b + 1] > 0; ++m)
+        if (lx_tensor_short(blocks[b].A, dims[2 * b], dims[2 * b + 1], m) > kLxMaxN)
+          return fail(CMTFPLS_EUNSUPPORTED, "an unfolding of a block's A x B1 x B2 with its shorter side > 256" + refit);
+  if (M > kLxMaxM) return fail(CMTFPLS_EUNSUPPORTED, "M > 128" + refit);
+  if (R > kLxMaxR) return fail(CMTFPLS_EUNSUPPORTED, "R > 64" + refit);
+  if (!lxc_cells_ok(blocks, nb)) return fail(CMTFPLS_EUNSUPPORTED, "A * B > 2^24 in a block" + refit);
+  const LxcShape s = lxc_shape(blocks, nb, dims);
+  const size_t lds = lxc_lds_bytes<TENSOR>(s, M, R);
+  if (lds > 150 * 1024) return fail(CMTFPLS_EUNSUPPORTED, "the fold's vectors exceed 150 KB of LDS" + refit);
+  const size_t per = lxc_ws_bytes<TENSOR>(s, I, M, R);
+  if (!ws || ws_bytes < per * (size_t)nfolds) return fail(CMTFPLS_EWORKSPACE, "workspace too small");
+  typename LooXCoupledArgsOf<TENSOR>::type a;
+  for (int b = 0; b < kLxcMaxBlocks; ++b) {
+    a.X[b] = b < nb ? blocks[b].X : nullptr;
+    a.cs[b] = b < nb ? blocks[b].colsum : nullptr;
+    a.A[b] = b < nb ? blocks[b].A : 0;
+    a.B[b] = b < nb ? blocks[b].B : 0;
+    if constexpr (TENSOR) {
+      a.B1[b] = b < nb ? dims[2 * b] : 0;
+      a.B2[b] = b < nb ? dims[2 * b + 1] : 0;
+    }
+  }
+  a.Y = Y; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
+  a.ws_per_fold = (int64_t)(per / sizeof(double));
+  a.sumP = (int64_t)s.sumP;
+  a.nb = nb; a.I = I; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds;
+  a.sumA = (int)s.sumA; a.sumB = (int)s.sumB; a.maxP = (int)s.maxP; a.maxn = (int)s.maxn; a.maxk = (int)s.maxk;
+  if constexpr (TENSOR) {
+    a.b1max = (int)s.b1max; a.b2max = (int)s.b2max; a.btmax = (int)s.btmax; a.dmax = (int)s.dmax; a.ptmax = (int)s.ptmax;
+  }
+  a.tol = tol;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_coupled_kernel<TENSOR>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+  hipLaunchKernelGGL(loo_xcov_coupled_kernel<TENSOR>, dim3(nfolds), dim3(TENSOR ? kLxcTensorNT : kLxNT), lds, (hipStream_t)stream, a);
+  return check_launch(who.c_str());
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -518,164 +430,35 @@ extern "C" {
 
 size_t cmtfpls_loo_xcov_coupled_fold_workspace_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R) {
   if (!lxc_sizes_ok(blocks, nb, I, M, R)) return 0;
-  const LxcShape s = lxc_shape(blocks, nb);
-  return (((size_t)I + M) * s.sumP + 3 * s.maxP + 2 * s.maxn * s.maxn + (size_t)I * ((size_t)M + R + 2) + (size_t)R * (s.sumA + s.sumB)) *
-         sizeof(double);
+  return lxc_ws_bytes<false>(lxc_shape(blocks, nb, nullptr), I, M, R);
 }
 
 size_t cmtfpls_loo_xcov_coupled_lds_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, int I, int M, int R) {
   if (!lxc_sizes_ok(blocks, nb, I, M, R)) return 0;
-  return lxc_lds_bytes(lxc_shape(blocks, nb), M, R);
+  return lxc_lds_bytes<false>(lxc_shape(blocks, nb, nullptr), M, R);
 }
 
 int cmtfpls_loo_xcov_coupled_f64(const cmtfpls_loo_coupled_block* blocks, int nb, const double* Y, const double* colsum_y, int I, int M,
                                  int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (!blocks || !Y || !colsum_y || !Ypred || nb <= 0 || I <= 1 || M <= 0 || R <= 0 || max_iter <= 0 || fold0 < 0 || nfolds <= 0 ||
-      fold0 + nfolds > I) {
-    set_error("loo_xcov_coupled: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  if (nb > kLxcMaxBlocks) {
-    set_error("loo_xcov_coupled: more than 8 blocks; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  for (int b = 0; b < nb; ++b) {
-    const cmtfpls_loo_coupled_block& k = blocks[b];
-    if (!k.X || !k.colsum || k.A <= 0 || k.B <= 0 || k.order < 2 || (k.order == 2 && k.A != 1)) {
-      set_error("loo_xcov_coupled: bad block");
-      return CMTFPLS_EINVAL;
-    }
-  }
-  for (int b = 0; b < nb; ++b)
-    if (blocks[b].order > 3) {
-      set_error("loo_xcov_coupled: a block of order > 3; refit per fold on the regular engine");
-      return CMTFPLS_EUNSUPPORTED;
-    }
-  for (int b = 0; b < nb; ++b)
-    if ((blocks[b].A < blocks[b].B ? blocks[b].A : blocks[b].B) > kLxMaxN) {
-      set_error("loo_xcov_coupled: min(A, B) > 256 in a block; refit per fold on the regular engine");
-      return CMTFPLS_EUNSUPPORTED;
-    }
-  if (M > kLxMaxM) { set_error("loo_xcov_coupled: M > 128; refit per fold on the regular engine"); return CMTFPLS_EUNSUPPORTED; }
-  if (R > kLxMaxR) { set_error("loo_xcov_coupled: R > 64; refit per fold on the regular engine"); return CMTFPLS_EUNSUPPORTED; }
-  for (int b = 0; b < nb; ++b)
-    if ((int64_t)blocks[b].A * blocks[b].B > (int64_t)1 << 24) {
-      set_error("loo_xcov_coupled: A * B > 2^24 in a block; refit per fold on the regular engine");
-      return CMTFPLS_EUNSUPPORTED;
-    }
-  const LxcShape s = lxc_shape(blocks, nb);
-  const size_t lds = lxc_lds_bytes(s, M, R);
-  if (lds > 150 * 1024) {
-    set_error("loo_xcov_coupled: the fold's vectors exceed 150 KB of LDS; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t per = cmtfpls_loo_xcov_coupled_fold_workspace_bytes(blocks, nb, I, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("loo_xcov_coupled: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  LooXCoupledArgs a;
-  for (int b = 0; b < kLxcMaxBlocks; ++b) {
-    a.X[b] = b < nb ? blocks[b].X : nullptr;
-    a.cs[b] = b < nb ? blocks[b].colsum : nullptr;
-    a.A[b] = b < nb ? blocks[b].A : 0;
-    a.B[b] = b < nb ? blocks[b].B : 0;
-  }
-  a.Y = Y; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
-  a.ws_per_fold = (int64_t)(per / sizeof(double));
-  a.sumP = (int64_t)s.sumP;
-  a.nb = nb; a.I = I; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds;
-  a.sumA = (int)s.sumA; a.sumB = (int)s.sumB; a.maxP = (int)s.maxP; a.maxn = (int)s.maxn; a.maxk = (int)s.maxk;
-  a.tol = tol;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_coupled_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  hipLaunchKernelGGL(loo_xcov_coupled_kernel<false>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
-  return check_launch("loo_xcov_coupled");
+  return lxc_run<false>(blocks, nb, nullptr, Y, colsum_y, I, M, R, tol, max_iter, fold0, nfolds, Ypred, n_iter, ws, ws_bytes, stream);
 }
 
 size_t cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, int I, int M,
                                                             int R) {
   if (!lxc_sizes_ok(blocks, nb, I, M, R) || !lxc_tensor_dims_ok(blocks, nb, dims) || !lxc_cells_ok(blocks, nb)) return 0;
-  const LxcTensorShape o = lxc_tensor_shape(blocks, nb, dims);
-  return (((size_t)I + M) * o.s.sumP + 3 * o.s.maxP + 3 * o.ptmax + 2 * o.s.maxn * o.s.maxn + (size_t)I * ((size_t)M + R + 2) +
-          (size_t)R * (o.s.sumA + o.s.sumB)) * sizeof(double);
+  return lxc_ws_bytes<true>(lxc_shape(blocks, nb, dims), I, M, R);
 }
 
 size_t cmtfpls_loo_xcov_coupled_tensor_lds_bytes(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, int I, int M, int R) {
   if (!lxc_sizes_ok(blocks, nb, I, M, R) || !lxc_tensor_dims_ok(blocks, nb, dims) || !lxc_cells_ok(blocks, nb)) return 0;
-  return lxc_tensor_lds_bytes(lxc_tensor_shape(blocks, nb, dims), M, R);
+  return lxc_lds_bytes<true>(lxc_shape(blocks, nb, dims), M, R);
 }
 
 int cmtfpls_loo_xcov_coupled_tensor_f64(const cmtfpls_loo_coupled_block* blocks, int nb, const int* dims, const double* Y,
                                         const double* colsum_y, int I, int M, int R, double tol, int max_iter, int fold0, int nfolds,
                                         double* Ypred, int* n_iter, void* ws, size_t ws_bytes, void* stream) {
-  if (!blocks || !dims || !Y || !colsum_y || !Ypred || nb <= 0 || I <= 1 || M <= 0 || R <= 0 || max_iter <= 0 || fold0 < 0 ||
-      nfolds <= 0 || fold0 + nfolds > I) {
-    set_error("loo_xcov_coupled_tensor: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  for (int b = 0; b < nb; ++b) {
-    const cmtfpls_loo_coupled_block& k = blocks[b];
-    if (!k.X || !k.colsum || k.A <= 0 || k.B <= 0 || k.order < 2 || (k.order == 2 && k.A != 1)) {
-      set_error("loo_xcov_coupled_tensor: bad block");
-      return CMTFPLS_EINVAL;
-    }
-  }
-  if (!lxc_tensor_dims_ok(blocks, nb, dims)) {
-    set_error("loo_xcov_coupled_tensor: bad dims ((B1, B2) with B1 * B2 == B for every block of order 4 and at least one such block, "
-              "(0, 0) for a block of order 2 or 3; no order above 4)");
-    return CMTFPLS_EINVAL;
-  }
-  if (nb > kLxcMaxBlocks) {
-    set_error("loo_xcov_coupled_tensor: more than 8 blocks; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  for (int b = 0; b < nb; ++b)
-    if (dims[2 * b + 1] == 0 && (blocks[b].A < blocks[b].B ? blocks[b].A : blocks[b].B) > kLxMaxN) {
-      set_error("loo_xcov_coupled_tensor: min(A, B) > 256 in a block of order 2 or 3; refit per fold on the regular engine");
-      return CMTFPLS_EUNSUPPORTED;
-    }
-  for (int b = 0; b < nb; ++b)
-    for (int m = 0; m < 3 && dims[2 * b + 1] > 0; ++m)
-      if (lxc_tensor_short(blocks[b].A, dims[2 * b], dims[2 * b + 1], m) > kLxMaxN) {
-        set_error("loo_xcov_coupled_tensor: an unfolding of a block's A x B1 x B2 with its shorter side > 256; refit per fold on the "
-                  "regular engine");
-        return CMTFPLS_EUNSUPPORTED;
-      }
-  if (M > kLxMaxM) { set_error("loo_xcov_coupled_tensor: M > 128; refit per fold on the regular engine"); return CMTFPLS_EUNSUPPORTED; }
-  if (R > kLxMaxR) { set_error("loo_xcov_coupled_tensor: R > 64; refit per fold on the regular engine"); return CMTFPLS_EUNSUPPORTED; }
-  if (!lxc_cells_ok(blocks, nb)) {
-    set_error("loo_xcov_coupled_tensor: A * B > 2^24 in a block; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const LxcTensorShape o = lxc_tensor_shape(blocks, nb, dims);
-  const size_t lds = lxc_tensor_lds_bytes(o, M, R);
-  if (lds > 150 * 1024) {
-    set_error("loo_xcov_coupled_tensor: the fold's vectors exceed 150 KB of LDS; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t per = cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(blocks, nb, dims, I, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("loo_xcov_coupled_tensor: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  LooXCoupledTensorArgs a;
-  for (int b = 0; b < kLxcMaxBlocks; ++b) {
-    a.X[b] = b < nb ? blocks[b].X : nullptr;
-    a.cs[b] = b < nb ? blocks[b].colsum : nullptr;
-    a.A[b] = b < nb ? blocks[b].A : 0;
-    a.B[b] = b < nb ? blocks[b].B : 0;
-    a.B1[b] = b < nb ? dims[2 * b] : 0;
-    a.B2[b] = b < nb ? dims[2 * b + 1] : 0;
-  }
-  a.Y = Y; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
-  a.ws_per_fold = (int64_t)(per / sizeof(double));
-  a.sumP = (int64_t)o.s.sumP;
-  a.nb = nb; a.I = I; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds;
-  a.sumA = (int)o.s.sumA; a.sumB = (int)o.s.sumB; a.maxP = (int)o.s.maxP; a.maxn = (int)o.s.maxn; a.maxk = (int)o.s.maxk;
-  a.b1max = (int)o.b1max; a.b2max = (int)o.b2max; a.btmax = (int)o.btmax; a.dmax = (int)o.dmax; a.ptmax = (int)o.ptmax;
-  a.tol = tol;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_coupled_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  hipLaunchKernelGGL(loo_xcov_coupled_kernel<true>, dim3(nfolds), dim3(kLxcTensorNT), lds, (hipStream_t)stream, a);
-  return check_launch("loo_xcov_coupled_tensor");
+  return lxc_run<true>(blocks, nb, dims, Y, colsum_y, I, M, R, tol, max_iter, fold0, nfolds, Ypred, n_iter, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

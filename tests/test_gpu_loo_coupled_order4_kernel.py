@@ -44,7 +44,11 @@ tests/golden/loo_xcov_coupled_order23.npz holds two runs of cmtfpls_loo_xcov_cou
 on an MI355X from the library built at the commit before the kernel became a template: the first case of loo_coupled_ref.BASIC_CASES
 (I 12, blocks 5 x 7 and 9, M 3, R 3) and loo_coupled_ref.case_data(8, ((17, 5), (5, 17), (11,)), 2, latent 3, noise 0.3, seed 5) with
 R 2 (three blocks, both transposes, a tile edge past 16).  Per run c: nb, order, A, B (per block), the blocks X{c}_{b} (I x P_b) and
-their column sums colsum_x{c}_{b} (NumPy sums over the rows), Y{c}, colsum_y{c}, and the entry's Ypred{c} and n_iter{c}."""
+their column sums colsum_x{c}_{b} (NumPy sums over the rows), Y{c}, colsum_y{c}, and the entry's Ypred{c} and n_iter{c}.
+
+tests/golden/loo_xcov_tensor_parent.npz holds the order-4 cases of tools/xcov_folds_dump.py (its head gives the layout) run through
+cmtfpls_loo_xcov_coupled_tensor_f64 on an MI355X by the library of the commit before the fold's steps moved into fold_loop.hpp and
+loo_xcov_fold.hpp: every order-4 trailing shape as one block, and the sets of two and three blocks with a block of order 4."""
 import ctypes
 import os
 
@@ -62,6 +66,7 @@ EINVAL, EWORKSPACE, EUNSUPPORTED = 1, 2, 4
 RUNS = [(T.TOL, T.MAX_ITER), (T.CAP_TOL, T.CAP_ITER)]
 TAIL = 4096
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loo_xcov_coupled_order23.npz")
+PARENT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loo_xcov_tensor_parent.npz")
 
 
 @pytest.fixture(scope="module")
@@ -272,3 +277,26 @@ def test_order23_entry_keeps_the_bits_of_the_untemplated_kernel(be):
         assert rc == 0
         assert np.array_equal(pred.cpu().numpy(), g[f"Ypred{c}"]), (c, np.abs(pred.cpu().numpy() - g[f"Ypred{c}"]).max())
         assert np.array_equal(n_iter.cpu().numpy(), g[f"n_iter{c}"])
+
+
+def test_tensor_entry_keeps_the_bits_of_the_kernel_before_the_shared_steps(be):
+    g = np.load(PARENT)
+    runs = 0
+    for s in range(int(g["n_sets"])):
+        nb = sum(f"s{s}/shape{b}" in g.files for b in range(8))
+        trail = [tuple(int(v) for v in g[f"s{s}/shape{b}"]) for b in range(nb)]
+        I = g[f"s{s}/Y"].shape[0]
+        Xs = [_dev(g[f"s{s}/X{b}"], I) for b in range(nb)]
+        dims = [(2, 1, t[1]) if t[0] == 1 and len(t) == 2 else (3, *t) if len(t) == 2 else (4, t[0], t[1] * t[2]) for t in trail]
+        tensor = [(t[1], t[2]) if len(t) == 3 else (0, 0) for t in trail]
+        R4 = int(g["R"])
+        for j, M in enumerate(g["Ms"]):                                               # the runs' outputs lie side by side in M order
+            Y = _dev(g[f"s{s}/Y"][:, :M], I)
+            c0 = int(g["Ms"][:j].sum())
+            for stop, (tol, max_iter) in zip(g["stops"], g["stop_values"]):
+                pred, n_iter = be.loo_ctpls_tensor(Xs, Y, dims, tensor, R4, float(tol), int(max_iter))
+                want = g[f"s{s}/c/{stop}/Ypred"][:, c0:c0 + M]
+                assert np.array_equal(pred.cpu().numpy(), want), (trail, M, stop, np.abs(pred.cpu().numpy() - want).max())
+                assert np.array_equal(n_iter.cpu().numpy(), g[f"s{s}/c/{stop}/n_iter"][:, R4 * j:R4 * (j + 1)]), (trail, M, stop)
+                runs += 1
+    assert runs == 48                                                                 # five single blocks and three sets, M = 1, 5, 17, two stops

@@ -2,7 +2,9 @@
 cross-covariance inside it) against float64 oracle refits whose extraction is oracle.rank1_factors
 (tests/loo_order4_ref.py): Ypred at DESIGN 8m's order-4 prediction tolerance (1e-7 relative to max|Y|), n_iter equal per fold and
 component, a chunked call bitwise the whole one, the limits; and cmtfpls_loo_xcov_f64 through the templated kernel against the bits
-the order-2/3 kernel gave before it was a template (tests/golden/loo_xcov_order3.npz, recorded on the GPU at the parent commit)."""
+the order-2/3 kernel gave before it was a template (tests/golden/loo_xcov_order3.npz, recorded on the GPU at the parent commit);
+and the order-4 entry against the bits it gave before the fold's steps moved into fold_loop.hpp and loo_xcov_fold.hpp
+(tests/golden/loo_xcov_tensor_parent.npz, written by tools/xcov_folds_dump.py on the GPU from the library of the commit before)."""
 import ctypes
 import os
 
@@ -23,6 +25,7 @@ SHAPES = [(9, 5, 7, 3),        # the general case
           (8, 6, 5, 1),
           (10, 4, 17, 2)]      # a tile remainder
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loo_xcov_order3.npz")
+PARENT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loo_xcov_tensor_parent.npz")
 
 
 def _dev(a, dtype=torch.float64):
@@ -82,6 +85,30 @@ def test_order3_entry_keeps_the_bits_of_the_untemplated_kernel():
         assert rc == 0
         assert np.array_equal(pred.cpu().numpy(), g[f"Ypred{c}"]), (c, np.abs(pred.cpu().numpy() - g[f"Ypred{c}"]).max())
         assert np.array_equal(n_iter.cpu().numpy(), g[f"n_iter{c}"])
+
+
+def test_order4_entry_keeps_the_bits_of_the_kernel_before_the_shared_steps():
+    from cmtf_pls_amd.backend import HipBackend
+    be = HipBackend(torch.device("cuda:0"))
+    g = np.load(PARENT)
+    assert os.path.getsize(PARENT) < 128 * 1024
+    runs = 0
+    for s in range(int(g["n_sets"])):
+        if f"s{s}/shape1" in g.files:                                                 # several blocks: the coupled entry's
+            continue
+        A, B1, B2 = (int(v) for v in g[f"s{s}/shape0"])
+        X = _dev(g[f"s{s}/X0"])
+        R4 = int(g["R"])
+        for j, M in enumerate(g["Ms"]):                                               # the runs' outputs lie side by side in M order
+            Y = _dev(g[f"s{s}/Y"][:, :M])
+            c0 = int(g["Ms"][:j].sum())
+            for stop, (tol, max_iter) in zip(g["stops"], g["stop_values"]):
+                pred, n_iter = be.loo_tpls_tensor(X, Y, A, B1, B2, R4, float(tol), int(max_iter))
+                want = g[f"s{s}/t/{stop}/Ypred"][:, c0:c0 + M]
+                assert np.array_equal(pred.cpu().numpy(), want), ((A, B1, B2), M, stop, np.abs(pred.cpu().numpy() - want).max())
+                assert np.array_equal(n_iter.cpu().numpy(), g[f"s{s}/t/{stop}/n_iter"][:, R4 * j:R4 * (j + 1)]), ((A, B1, B2), M, stop)
+                runs += 1
+    assert runs == 30                                                                 # five shapes, M = 1, 5, 17, two stops
 
 
 def _limit(I, A, B1, B2, M, Rr, ws_bytes):
