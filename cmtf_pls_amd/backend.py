@@ -26,6 +26,11 @@ def _int_pairs(pairs):
     return (ctypes.c_int * len(flat))(*flat)
 
 
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """A byte buffer for a workspace: at least nbytes, never empty."""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 def chunk_size(n: int, per: int, budget: int, cap: Optional[int] = None) -> int:
     """Items per launch of a chunked workgroup-per-item call: as many of the n items as `budget` bytes hold at `per` bytes each,
     at least one, at most `cap`."""
@@ -55,9 +60,16 @@ class HipBackend:
     def _workspace(self, key: str, nbytes: int) -> torch.Tensor:
         buf = self._ws.get(key)
         if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
-            self._ws[key] = buf
+            buf = self._ws[key] = _scratch(nbytes, self.device)
         return buf
+
+    @staticmethod
+    def _form(rc: int, name: str, value=True):
+        """The answer of an entry that may decline the shape: None on status 4, else `value` once the status is checked."""
+        if rc == 4:
+            return None
+        _lib.check(rc, name)
+        return value
 
     def _chunked_launch(self, name: str, call, n: int, per_fn, budget: int, cap: Optional[int] = None, extra: int = 0,
                         ws_key: Optional[str] = None) -> Optional[int]:
@@ -70,13 +82,11 @@ class HipBackend:
             return None
         per = int(per_fn())
         chunk = chunk_size(n, per + extra, budget, cap)
-        ws = self._workspace(ws_key, per * chunk) if ws_key else torch.empty(max(per * chunk, 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(ws_key, per * chunk) if ws_key else _scratch(per * chunk, self.device)
         launches = 0
         for i0 in range(0, n, chunk):
-            rc = call(i0, min(chunk, n - i0), _ptr(ws), ws.numel())
-            if rc == 4:
+            if self._form(call(i0, min(chunk, n - i0), _ptr(ws), ws.numel()), name) is None:
                 return None
-            _lib.check(rc, name)
             launches += 1
         return launches
 
@@ -142,10 +152,7 @@ class HipBackend:
             rc = self.lib.cmtfpls_ceiling_copy(_ptr(buf), _ptr(dst), nbytes, int(row_bytes), int(map), int(blocks), self._stream())
         else:
             raise ValueError(op)
-        if rc == 4:
-            return False
-        _lib.check(rc, "ceiling_" + op)
-        return True
+        return self._form(rc, "ceiling_" + op, False) is not None
 
     # -- preprocess: tpls.py:61-71 -----------------------------------------------------------
     def colstats(self, X2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -178,10 +185,7 @@ class HipBackend:
         ws = self._workspace("contract", self.lib.cmtfpls_mode0_contract_workspace_bytes(I, P))
         rc = self._fn("mode0_contract_yq", X2)(_ptr(X2), I, P, _ptr(Y), Y.stride(0), Y.shape[1], _ptr(q), _ptr(out), int(masked),
                                                _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "mode0_contract_yq")
-        return out
+        return self._form(rc, "mode0_contract_yq", out)
 
     def colscale(self, Z: torch.Tensor, colcnt: torch.Tensor, n_samples: float) -> None:
         _lib.check(self.lib.cmtfpls_colscale_f64(_ptr(Z), Z.numel(), _ptr(colcnt), float(n_samples), self._stream()), "colscale")
@@ -246,10 +250,7 @@ class HipBackend:
         ssq = self.empty(1)
         rc = self._fn("xcov_deflate", X2)(_ptr(X2), I, A, B, _ptr(Y), Y.stride(0), M, _ptr(t), _ptr(wA), _ptr(wB), _ptr(out), _ptr(ssq),
                                           _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "xcov_deflate")
-        return ssq
+        return self._form(rc, "xcov_deflate", ssq)
 
     def rank1_score(self, Z: torch.Tensor, A: int, B: int, wA: torch.Tensor, wB: torch.Tensor, S: torch.Tensor, tq: torch.Tensor,
                     info: Optional[torch.Tensor] = None, n_squarings: Optional[int] = None) -> torch.Tensor:
@@ -285,10 +286,7 @@ class HipBackend:
         ws = self._workspace("contract", self.lib.cmtfpls_xcov_stats_workspace_bytes(I, P, M))
         stats = self.empty(2 * P)
         rc = self._fn("xcov_stats", X2)(_ptr(X2), I, P, _ptr(Y), Y.stride(0), M, _ptr(out), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "xcov_stats")
-        return out, stats
+        return self._form(rc, "xcov_stats", (out, stats))
 
     def status_snapshot(self, status: torch.Tensor, slot: int, slots: Optional[dict] = None):
         """Enqueue a copy of a few status words to pinned host memory behind the work issued so far (cmtfpls_status_to_host);
@@ -410,10 +408,7 @@ class HipBackend:
         assert WA.is_contiguous() and WB.is_contiguous() and out.stride(1) == 1
         fn = self.lib.cmtfpls_mttkrp_f32_mixed if (mixed and X2.dtype == torch.float32) else self._fn("mttkrp", X2)
         rc = fn(_ptr(X2), X2.shape[0], A, B, _ptr(WA), _ptr(WB), R, _ptr(out), out.stride(0), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "mttkrp")
-        return out
+        return self._form(rc, "mttkrp", out)
 
     # -- K3: tpls.py:92-99 / missingvals.py:23-38 --------------------------------------------
     def score(self, X2, A, B, wA, wB, rowcnt, out) -> torch.Tensor:
@@ -440,20 +435,14 @@ class HipBackend:
         ws = self._workspace("score_contract", max(nbytes, 256))
         rc = self._fn("score_contract", X2)(_ptr(X2), I, A, B, _ptr(wA), _ptr(wB), _ptr(shift), _ptr(sub_own), _ptr(add_other), float(alpha),
                                             _ptr(t), _ptr(Z), _ptr(csum), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "score_contract")
-        return Z
+        return self._form(rc, "score_contract", Z)
 
     def score_gram(self, X2, A, B, wA, wB, rowcnt, out, Y: torch.Tensor, qpart: torch.Tensor) -> Optional[torch.Tensor]:
         """score + the per-workgroup partial sums of Y^T t into qpart (n_partials x M); None when M > 64."""
         assert qpart.numel() >= self.n_partials * Y.shape[1] and qpart.is_contiguous()
         rc = self._fn("score_gram", X2)(_ptr(X2), X2.shape[0], A, B, _ptr(wA), _ptr(wB), _ptr(rowcnt), _ptr(out),
                                         _ptr(Y), Y.stride(0), Y.shape[1], _ptr(qpart), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "score_gram")
-        return out
+        return self._form(rc, "score_gram", out)
 
     def q_update(self, q: torch.Tensor, qpart: Optional[torch.Tensor] = None, normalize: bool = True,
                  G: Optional[torch.Tensor] = None, q_prev: Optional[torch.Tensor] = None,
@@ -481,18 +470,14 @@ class HipBackend:
         ssq = self.empty(1)
         rc = self._fn("deflate_contract_yq", X2)(_ptr(X2), I, A, B, _ptr(t), _ptr(wA), _ptr(wB), _ptr(Y), Y.stride(0), Y.shape[1],
                                                  _ptr(q), _ptr(out), int(masked), _ptr(ssq), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "deflate_contract_yq")
-        return ssq
+        return self._form(rc, "deflate_contract_yq", ssq)
 
     def score_deflate(self, X2, A, B, wA, wB, rowcnt, out) -> Optional[torch.Tensor]:
         """Fused K3+K6; returns None when the row does not fit (caller then uses score + deflate)."""
         part = self.empty(self.n_partials)
         rc = self._fn("score_deflate", X2)(_ptr(X2), X2.shape[0], A, B, _ptr(wA), _ptr(wB), _ptr(rowcnt), _ptr(out), _ptr(part), self._stream())
-        if rc == 4:
+        if self._form(rc, "score_deflate") is None:
             return None
-        _lib.check(rc, "score_deflate")
         return self._close_partials(part)
 
     # -- K4/K5/K7/K11 small algebra ----------------------------------------------------------
@@ -581,10 +566,7 @@ class HipBackend:
                                                   out.stride(0), self._stream())
         else:
             rc = self._fn("project_rows", X2)(_ptr(X2), I, A, B, R, _ptr(WA), _ptr(WB), _ptr(mean), _ptr(out), out.stride(0), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "project_rows")
-        return out
+        return self._form(rc, "project_rows", out)
 
     def project_rows2(self, X2s, As, Bs, WAs, WBs, means, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """project_rows for TWO COUPLED blocks (lists of two): the sample's row of both blocks in one workgroup, the score
@@ -601,10 +583,7 @@ class HipBackend:
             rc = self._fn("project_rows2_idx", X2s[0])(*head, _ptr(rows), rows.numel(), R, _ptr(out), out.stride(0), self._stream())
         else:
             rc = self._fn("project_rows2", X2s[0])(*head, I, R, _ptr(out), out.stride(0), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "project_rows2")
-        return out
+        return self._form(rc, "project_rows2", out)
 
     def predict_rows(self, S: torch.Tensor, Bm: torch.Tensor, mean: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """out (I, M) = S (I, R) @ Bm (R, M) + mean: the last line of predict (tpls.py:143) on the device-resident scores."""
@@ -613,10 +592,7 @@ class HipBackend:
         assert S.stride(1) == 1 and Bm.is_contiguous() and Bm.shape[0] == R
         out = self.empty(I, M)
         rc = self.lib.cmtfpls_predict_rows_f64(_ptr(S), I, S.stride(0), R, _ptr(Bm), M, _ptr(mean), _ptr(out), M, self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "predict_rows")
-        return out
+        return self._form(rc, "predict_rows", out)
 
     def recon(self, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor], out: torch.Tensor) -> Optional[torch.Tensor]:
         """out (I, A*B) = T (WA (.) WB)^T + mean in out's dtype (factors_to_tensor util.py:18-20 + X_mean);
@@ -625,10 +601,7 @@ class HipBackend:
         A, B = WA.shape[0], WB.shape[0]
         assert T.stride(1) == 1 and WA.is_contiguous() and WB.is_contiguous() and out.is_contiguous() and out.numel() == I * A * B
         rc = self._fn("recon", out)(_ptr(T), I, T.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean), _ptr(out), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "recon")
-        return out
+        return self._form(rc, "recon", out)
 
     def recon_r2(self, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """[sum (xhat - x)^2, sum x^2] over the finite entries of x = X2 - mean: calcR2X's two sums (util.py:7-15) against
@@ -641,10 +614,7 @@ class HipBackend:
         out = self.empty(2)
         rc = self._fn("recon_r2", X2)(_ptr(X2), _ptr(T), I, T.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean), _ptr(out),
                                      _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "recon_r2")
-        return out
+        return self._form(rc, "recon_r2", out)
 
     def resid_rows(self, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
                    want_cols: bool) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
@@ -660,10 +630,7 @@ class HipBackend:
         cols = self.empty(P, 2) if want_cols else None
         rc = self._fn("resid_rows", X2)(_ptr(X2), _ptr(T), I, T.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean), _ptr(rows),
                                        _ptr(cols), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "resid_rows")
-        return rows, cols
+        return self._form(rc, "resid_rows", (rows, cols))
 
     def contrib_rows(self, X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
                      mean: Optional[torch.Tensor], rows: Optional[torch.Tensor] = None):
@@ -681,10 +648,7 @@ class HipBackend:
         speA, t2A = (self.empty(n, A), self.empty(n, A)) if A > 1 else (None, None)
         rc = self._fn("contrib_rows", X2)(_ptr(X2), I, _ptr(T), T.stride(0), _ptr(H), H.stride(0), R, _ptr(WA), _ptr(WB), A, B, _ptr(mean),
                                          _ptr(rows), n, _ptr(speA), _ptr(speB), _ptr(t2A), _ptr(t2B), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "contrib_rows")
-        return speA, speB, t2A, t2B
+        return self._form(rc, "contrib_rows", (speA, speB, t2A, t2B))
 
     def selectivity_cols(self, X2: torch.Tensor, Tau: torch.Tensor, mean: Optional[torch.Tensor], masked: bool):
         """The target-projection sums of every column in one read of X2 (uncentred, storage type): (a (M, P), d (M, P) or None, s (P,),
@@ -728,10 +692,7 @@ class HipBackend:
         out = self.empty(R + 2)
         rc = self._fn("heldout_resid", X2)(_ptr(X2), I, A, B, _ptr(T), T.stride(0), R, _ptr(WA), _ptr(WB), _ptr(mean), float(fraction),
                                           int(seed) & (2 ** 64 - 1), int(stream), int(offset), _ptr(out), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "heldout_resid")
-        return out
+        return self._form(rc, "heldout_resid", out)
 
     def impute(self, X2: torch.Tensor, out: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
                mean: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -747,10 +708,20 @@ class HipBackend:
         count = self.empty(1)
         rc = self._fn("impute", X2)(_ptr(X2), _ptr(out), I, A, B, _ptr(T), T.stride(0), R, _ptr(WA), _ptr(WB), _ptr(mean), _ptr(count),
                                    _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
+        return self._form(rc, "impute", count)
+
+    def _loo_folds(self, name: str, fn, head, per_fn, per_args, I: int, M: int, R: int, tol: float, max_iter: int, budget: int,
+                   cap: Optional[int] = 512, outs=None) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """The chunked launch of a workgroup-per-fold leave-one-out entry `fn`: head are its arguments before tol (the inputs, their
+        column sums and the sizes), per_fn(*per_args) its workspace bytes per fold.  Returns (Ypred (I, M), n_iter (I, R)) -- `outs`
+        when given -- or None when the entry declines the shape.  (cap 512: two workgroups' worth of folds per CU is all a launch can
+        overlap.)"""
+        Ypred, n_iter = outs or (self.empty(I, M), torch.zeros(I, R, dtype=torch.int32, device=self.device))
+        if self._chunked_launch(name, lambda f0, nf, ws, nb: fn(*head, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws,
+                                                                nb, self._stream()),
+                                I, lambda: per_fn(*per_args), budget, cap=cap, ws_key="loo") is None:
             return None
-        _lib.check(rc, "impute")
-        return count
+        return Ypred, n_iter
 
     def loo_tpls(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int,
                  max_ws_bytes: Optional[int] = None, forms=("lds", "xcov")) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
@@ -764,20 +735,16 @@ class HipBackend:
         assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
         colsum_x, _ = self.colstats(X2)
         colsum_y, _ = self.colstats(Y)
-        Ypred = self.empty(I, M)
-        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
+        outs = self.empty(I, M), torch.zeros(I, R, dtype=torch.int32, device=self.device)
         for form, per_fn, fn in (("lds", self.lib.cmtfpls_loo_fold_workspace_bytes, self.lib.cmtfpls_loo_tpls_f64),
                                  ("xcov", self.lib.cmtfpls_loo_xcov_fold_workspace_bytes, self.lib.cmtfpls_loo_xcov_f64)):
             if form not in forms:
                 continue
-            xcov = form == "xcov"                            # (512: two workgroups' worth of folds per CU is all a launch can overlap)
-            if self._chunked_launch(
-                    "loo_" + form,
-                    lambda f0, nf, ws, nb, fn=fn: fn(_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
-                                                     int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws, nb, self._stream()),
-                    I, lambda per_fn=per_fn: per_fn(I, A, B, M, R), self._ws_budget(max_ws_bytes, xcov),
-                    cap=512 if xcov else None, ws_key="loo") is not None:
-                return Ypred, n_iter, form
+            xcov = form == "xcov"                            # (the lds form: no cap, the 4 GiB budget)
+            if self._loo_folds("loo_" + form, fn, (_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B, M, R), per_fn,
+                               (I, A, B, M, R), I, M, R, tol, max_iter, self._ws_budget(max_ws_bytes, xcov),
+                               cap=512 if xcov else None, outs=outs) is not None:
+                return (*outs, form)
         return None
 
     def loo_tpls_tensor(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B1: int, B2: int, R: int, tol: float, max_iter: int,
@@ -790,24 +757,15 @@ class HipBackend:
         assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
         colsum_x, _ = self.colstats(X2)
         colsum_y, _ = self.colstats(Y)
-        Ypred = self.empty(I, M)
-        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
-        if self._chunked_launch(
-                "loo_xcov_tensor",
-                lambda f0, nf, ws, nb: self.lib.cmtfpls_loo_xcov_tensor_f64(
-                    _ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol), int(max_iter), f0, nf,
-                    _ptr(Ypred), _ptr(n_iter), ws, nb, self._stream()),
-                I, lambda: self.lib.cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R),
-                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
-            return None
-        return Ypred, n_iter
+        return self._loo_folds("loo_xcov_tensor", self.lib.cmtfpls_loo_xcov_tensor_f64,
+                               (_ptr(X2), _ptr(Y), _ptr(colsum_x), _ptr(colsum_y), I, A, B1, B2, M, R),
+                               self.lib.cmtfpls_loo_xcov_tensor_fold_workspace_bytes, (I, A, B1, B2, M, R), I, M, R, tol, max_iter,
+                               self._ws_budget(max_ws_bytes, True))
 
-    def loo_ctpls(self, Xs, Y: torch.Tensor, dims, R: int, tol: float, max_iter: int,
-                  max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
-        """Leave-one-out predictions of a ctPLS model on complete data (validate.py:24-33 over cmtf.py:85-177), every fold a workgroup
-        on the fold's cross-covariances (cmtfpls_loo_xcov_coupled_f64).  Xs: the blocks, each I x P_b float64; dims: (order, A, B) per
-        block (order 2: A = 1).  Returns (Ypred (I, M), n_iter (I, R), "xcov_coupled") or None when the shape is outside the form.
-        Folds run in chunks as loo_tpls's xcov form (a centred copy of every block per resident fold)."""
+    def _loo_coupled(self, name: str, Xs, Y: torch.Tensor, dims, pairs, R: int, tol: float, max_iter: int,
+                     max_ws_bytes: Optional[int]) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """loo_ctpls (pairs = ()) and loo_ctpls_tensor (pairs = (the (B1, B2) int array,)): cmtfpls_<name>_f64 on the blocks' description,
+        through _loo_folds."""
         nb = len(Xs)
         I, M = Y.shape
         assert nb >= 1 and len(dims) == nb and Y.dtype == torch.float64 and Y.is_contiguous()
@@ -817,17 +775,19 @@ class HipBackend:
         colsum_y, _ = self.colstats(Y)
         blocks = (_lib.LooCoupledBlock * nb)(*[_lib.LooCoupledBlock(_ptr(X2), _ptr(cs), int(o), int(A), int(B))
                                                for X2, cs, (o, A, B) in zip(Xs, colsums, dims)])
-        Ypred = self.empty(I, M)
-        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
-        if self._chunked_launch(
-                "loo_xcov_coupled",
-                lambda f0, nf, ws, nby: self.lib.cmtfpls_loo_xcov_coupled_f64(
-                    blocks, nb, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws, nby,
-                    self._stream()),
-                I, lambda: self.lib.cmtfpls_loo_xcov_coupled_fold_workspace_bytes(blocks, nb, I, M, R),
-                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
-            return None
-        return Ypred, n_iter, "xcov_coupled"
+        return self._loo_folds("loo_" + name, getattr(self.lib, f"cmtfpls_loo_{name}_f64"),
+                               (blocks, nb, *pairs, _ptr(Y), _ptr(colsum_y), I, M, R),
+                               getattr(self.lib, f"cmtfpls_loo_{name}_fold_workspace_bytes"), (blocks, nb, *pairs, I, M, R), I, M, R, tol,
+                               max_iter, self._ws_budget(max_ws_bytes, True))
+
+    def loo_ctpls(self, Xs, Y: torch.Tensor, dims, R: int, tol: float, max_iter: int,
+                  max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor, str]]:
+        """Leave-one-out predictions of a ctPLS model on complete data (validate.py:24-33 over cmtf.py:85-177), every fold a workgroup
+        on the fold's cross-covariances (cmtfpls_loo_xcov_coupled_f64).  Xs: the blocks, each I x P_b float64; dims: (order, A, B) per
+        block (order 2: A = 1).  Returns (Ypred (I, M), n_iter (I, R), "xcov_coupled") or None when the shape is outside the form.
+        Folds run in chunks as loo_tpls's xcov form (a centred copy of every block per resident fold)."""
+        res = self._loo_coupled("xcov_coupled", Xs, Y, dims, (), R, tol, max_iter, max_ws_bytes)
+        return None if res is None else (*res, "xcov_coupled")
 
     def loo_ctpls_tensor(self, Xs, Y: torch.Tensor, dims, tensor, R: int, tol: float, max_iter: int,
                          max_ws_bytes: Optional[int] = None) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
@@ -835,27 +795,27 @@ class HipBackend:
         I x A B1 B2 with dims (4, A, B1 B2) and tensor (B1, B2); a block of order 2 or 3 has tensor (0, 0).  The extraction of a tensor
         block is the rank-1 CP of its cross-covariance inside the fold's workgroup.  Returns (Ypred (I, M), n_iter (I, R)) or None
         when the shape is outside the form.  Folds run in chunks as loo_ctpls's."""
-        nb = len(Xs)
-        I, M = Y.shape
-        assert nb >= 1 and len(dims) == nb and len(tensor) == nb and Y.dtype == torch.float64 and Y.is_contiguous()
-        for X2, (_, A, B) in zip(Xs, dims):
-            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
-        colsums = [self.colstats(X2)[0] for X2 in Xs]
-        colsum_y, _ = self.colstats(Y)
-        blocks = (_lib.LooCoupledBlock * nb)(*[_lib.LooCoupledBlock(_ptr(X2), _ptr(cs), int(o), int(A), int(B))
-                                               for X2, cs, (o, A, B) in zip(Xs, colsums, dims)])
-        pairs = _int_pairs(tensor)
-        Ypred = self.empty(I, M)
-        n_iter = torch.zeros(I, R, dtype=torch.int32, device=self.device)
-        if self._chunked_launch(
-                "loo_xcov_coupled_tensor",
-                lambda f0, nf, ws, nby: self.lib.cmtfpls_loo_xcov_coupled_tensor_f64(
-                    blocks, nb, pairs, _ptr(Y), _ptr(colsum_y), I, M, R, float(tol), int(max_iter), f0, nf, _ptr(Ypred), _ptr(n_iter), ws,
-                    nby, self._stream()),
-                I, lambda: self.lib.cmtfpls_loo_xcov_coupled_tensor_fold_workspace_bytes(blocks, nb, pairs, I, M, R),
-                self._ws_budget(max_ws_bytes, True), cap=512, ws_key="loo") is None:
-            return None
-        return Ypred, n_iter
+        assert len(tensor) == len(Xs)
+        return self._loo_coupled("xcov_coupled_tensor", Xs, Y, dims, (_int_pairs(tensor),), R, tol, max_iter, max_ws_bytes)
+
+    def _masked_outputs(self, n: int, I: int, M: int, R: int, per_model: bool, factors) -> dict:
+        """The zeroed outputs of a masked cross-validation entry over n folds or models: Ypred (R, I, M), per_model: (n, R, I, M),
+        n_iter (n, R), status (n), info (n, 2) and a (n, *shape) tensor per entry of `factors` (name -> shape)."""
+        out = {"Ypred": self.zeros(*((n,) if per_model else ()), R, I, M), "n_iter": torch.zeros(n, R, dtype=torch.int32, device=self.device),
+               "status": torch.zeros(n, dtype=torch.int32, device=self.device),
+               "info": torch.zeros(n, 2, dtype=torch.int32, device=self.device)}
+        out.update({k: self.zeros(n, *shape) for k, shape in factors.items()})
+        return out
+
+    def _masked_launch(self, name: str, args, out: dict, factors, n: int, per_fn, max_ws_bytes: Optional[int], extra: int = 0):
+        """The chunked launch of cmtfpls_<name>_f64(*args, first, count, Ypred, the outputs named in `factors` (NULL where `out` has
+        none), n_iter, status, info, ws, ws_bytes, stream) over n folds or models: `out` with its "launches", or None when the entry
+        declines the shape."""
+        fn = getattr(self.lib, f"cmtfpls_{name}_f64")
+        outs = tuple(_ptr(out.get(k)) for k in ("Ypred", *factors, "n_iter", "status", "info"))
+        out["launches"] = self._chunked_launch(name, lambda i0, cnt, ws, nb: fn(*args, i0, cnt, *outs, ws, nb, self._stream()), n, per_fn,
+                                               self._ws_budget(max_ws_bytes), extra=extra)
+        return out if out["launches"] is not None else None
 
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
                   max_iter: int, max_ws_bytes: Optional[int] = None
@@ -871,19 +831,11 @@ class HipBackend:
         assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
         colsum_x, colcnt_x = self.colstats(X2)
         colsum_y, _ = self.colstats(Y)
-        Ypred = self.zeros(R, I, M)
-        n_iter = torch.zeros(K, R, dtype=torch.int32, device=self.device)
-        status = torch.zeros(K, dtype=torch.int32, device=self.device)
-        info = torch.zeros(K, 2, dtype=torch.int32, device=self.device)
-        fn = self.lib.cmtfpls_cv_masked_f64
         args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
                 int(max_iter))
-        outs = (_ptr(Ypred), _ptr(n_iter), _ptr(status), _ptr(info))
-        if self._chunked_launch("cv_masked", lambda f0, nf, ws, nb: fn(*args, f0, nf, *outs, ws, nb, self._stream()), K,
-                                lambda: self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R),
-                                self._ws_budget(max_ws_bytes)) is None:
-            return None
-        return Ypred, n_iter, status, info
+        out = self._masked_launch("cv_masked", args, self._masked_outputs(K, I, M, R, False, {}), (), K,
+                                  lambda: self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R), max_ws_bytes)
+        return None if out is None else (out["Ypred"], out["n_iter"], out["status"], out["info"])
 
     def cv_masked_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int, B: int,
                          R: int, tol: float, max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None
@@ -900,21 +852,11 @@ class HipBackend:
         assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
         assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
         assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
-        out = {"Ypred": self.zeros(nm, R, I, M), "n_iter": torch.zeros(nm, R, dtype=torch.int32, device=self.device),
-               "status": torch.zeros(nm, dtype=torch.int32, device=self.device),
-               "info": torch.zeros(nm, 2, dtype=torch.int32, device=self.device)}
-        if factors:
-            out.update(Wa=self.zeros(nm, R, A), Wb=self.zeros(nm, R, B), coef=self.zeros(nm, R, R), Q=self.zeros(nm, R, M))
-        fn = self.lib.cmtfpls_cv_masked_models_f64
-        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, A, B, M, R, float(tol),
-                int(max_iter))
-        outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wb", "coef", "Q")) if factors else (None,) * 4),
-                _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
-        out["launches"] = self._chunked_launch(
-            "cv_masked_models", lambda m0, n, ws, nb: fn(*args, m0, n, *outs, ws, nb, self._stream()), nm,
-            lambda: self.lib.cmtfpls_cv_masked_model_workspace_bytes(I, A, B, M, R), self._ws_budget(max_ws_bytes),
-            extra=R * I * M * 8)
-        return out if out["launches"] is not None else None
+        shapes = {"Wa": (R, A), "Wb": (R, B), "coef": (R, R), "Q": (R, M)}
+        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, A, B, M, R, float(tol), int(max_iter))
+        return self._masked_launch("cv_masked_models", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
+                                   lambda: self.lib.cmtfpls_cv_masked_model_workspace_bytes(I, A, B, M, R), max_ws_bytes,
+                                   extra=R * I * M * 8)
 
     def cv_masked_tensor(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B1: int, B2: int, R: int,
                          tol: float, max_iter: int, max_ws_bytes: Optional[int] = None
@@ -928,18 +870,11 @@ class HipBackend:
         assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
         colsum_x, colcnt_x = self.colstats(X2)
         colsum_y, _ = self.colstats(Y)
-        Ypred = self.zeros(R, I, M)
-        n_iter = torch.zeros(K, R, dtype=torch.int32, device=self.device)
-        status = torch.zeros(K, dtype=torch.int32, device=self.device)
-        info = torch.zeros(K, 2, dtype=torch.int32, device=self.device)
-        fn = self.lib.cmtfpls_cv_masked_tensor_f64
         args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol),
                 int(max_iter))
-        outs = (_ptr(Ypred), _ptr(n_iter), _ptr(status), _ptr(info))
-        launches = self._chunked_launch("cv_masked_tensor", lambda f0, nf, ws, nb: fn(*args, f0, nf, *outs, ws, nb, self._stream()), K,
-                                        lambda: self.lib.cmtfpls_cv_masked_tensor_fold_workspace_bytes(I, A, B1, B2, M, R),
-                                        self._ws_budget(max_ws_bytes))
-        return None if launches is None else (Ypred, n_iter, status, info, launches)
+        out = self._masked_launch("cv_masked_tensor", args, self._masked_outputs(K, I, M, R, False, {}), (), K,
+                                  lambda: self.lib.cmtfpls_cv_masked_tensor_fold_workspace_bytes(I, A, B1, B2, M, R), max_ws_bytes)
+        return None if out is None else (out["Ypred"], out["n_iter"], out["status"], out["info"], out["launches"])
 
     def cv_masked_tensor_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int,
                                 B1: int, B2: int, R: int, tol: float, max_iter: int, factors: bool = False,
@@ -953,22 +888,11 @@ class HipBackend:
         assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
         assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
         assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
-        out = {"Ypred": self.zeros(nm, R, I, M), "n_iter": torch.zeros(nm, R, dtype=torch.int32, device=self.device),
-               "status": torch.zeros(nm, dtype=torch.int32, device=self.device),
-               "info": torch.zeros(nm, 2, dtype=torch.int32, device=self.device)}
-        if factors:
-            out.update(Wa=self.zeros(nm, R, A), Wk=self.zeros(nm, R, B1), Wl=self.zeros(nm, R, B2), coef=self.zeros(nm, R, R),
-                       Q=self.zeros(nm, R, M))
-        fn = self.lib.cmtfpls_cv_masked_tensor_models_f64
-        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, A, B1, B2, M, R, float(tol),
-                int(max_iter))
-        outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wk", "Wl", "coef", "Q")) if factors else (None,) * 5),
-                _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
-        out["launches"] = self._chunked_launch(
-            "cv_masked_tensor_models", lambda m0, n, ws, nb: fn(*args, m0, n, *outs, ws, nb, self._stream()), nm,
-            lambda: self.lib.cmtfpls_cv_masked_tensor_model_workspace_bytes(I, A, B1, B2, M, R), self._ws_budget(max_ws_bytes),
-            extra=R * I * M * 8)
-        return out if out["launches"] is not None else None
+        shapes = {"Wa": (R, A), "Wk": (R, B1), "Wl": (R, B2), "coef": (R, R), "Q": (R, M)}
+        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, A, B1, B2, M, R, float(tol), int(max_iter))
+        return self._masked_launch("cv_masked_tensor_models", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}),
+                                   shapes, nm, lambda: self.lib.cmtfpls_cv_masked_tensor_model_workspace_bytes(I, A, B1, B2, M, R),
+                                   max_ws_bytes, extra=R * I * M * 8)
 
     def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
                           max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
@@ -990,22 +914,12 @@ class HipBackend:
         assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
         blocks = (_lib.CvCoupledBlock * nb)(*[_lib.CvCoupledBlock(_ptr(X2), int(o), int(A), int(B)) for X2, (o, A, B) in zip(X2s, dims)])
         sumA, sumB = sum(A for _, A, _ in dims), sum(B for _, _, B in dims)
-        out = {"Ypred": self.zeros(nm, R, I, M), "n_iter": torch.zeros(nm, R, dtype=torch.int32, device=self.device),
-               "status": torch.zeros(nm, dtype=torch.int32, device=self.device),
-               "info": torch.zeros(nm, 2, dtype=torch.int32, device=self.device)}
-        if factors:
-            out.update(Wa=self.zeros(nm, R * sumA), Wb=self.zeros(nm, R * sumB), coef=self.zeros(nm, R, R), Q=self.zeros(nm, R, M))
-        fn = self.lib.cmtfpls_cv_masked_coupled_f64
-        args = (blocks, nb, _ptr(Y), _ptr(counts), _ptr(yrow) if yrow is not None else None, nm, I, M, R, float(tol), int(max_iter))
-        outs = (_ptr(out["Ypred"]), *((_ptr(out[k]) for k in ("Wa", "Wb", "coef", "Q")) if factors else (None,) * 4),
-                _ptr(out["n_iter"]), _ptr(out["status"]), _ptr(out["info"]))
-        out["launches"] = self._chunked_launch(
-            "cv_masked_coupled", lambda m0, n, ws, nby: fn(*args, m0, n, *outs, ws, nby, self._stream()), nm,
-            lambda: self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R), self._ws_budget(max_ws_bytes),
-            extra=R * I * M * 8)
-        if out["launches"] is None:
-            return None
-        if factors:                                                                  # block b's R x A_b at R * (A_0 + .. + A_(b-1))
+        shapes = {"Wa": (R * sumA,), "Wb": (R * sumB,), "coef": (R, R), "Q": (R, M)}
+        args = (blocks, nb, _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, M, R, float(tol), int(max_iter))
+        out = self._masked_launch("cv_masked_coupled", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
+                                  lambda: self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R), max_ws_bytes,
+                                  extra=R * I * M * 8)
+        if out is not None and factors:                                              # block b's R x A_b at R * (A_0 + .. + A_(b-1))
             oa = ob = 0
             Wa, Wb = [], []
             for _, A, B in dims:
@@ -1024,23 +938,17 @@ class HipBackend:
         I, P = X2.shape
         M = Y.shape[1]
         assert Y.dtype == torch.float64 and Y.is_contiguous() and order.dtype == torch.int32 and fold_off.dtype == torch.int32 and P == A * B
-        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K)), 256), dtype=torch.uint8, device=self.device)
+        ws = _scratch(self.lib.cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K), self.device)
         stats = self.empty(2 * P)
         rc = self._fn("kfold_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), M, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S), _ptr(mean),
                                         _ptr(stats), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_xcov")
-        return stats
+        return self._form(rc, "kfold_xcov", stats)
 
     def kfold_inner(self, state, a: int, tol: float, max_iter: int, ws: torch.Tensor) -> Optional[bool]:
         """Component a's inner loop for every fold, a workgroup per fold (cmtfpls_kfold_inner_f64); `state` is a
         _lib.KfoldState, `ws` at least kfold_inner_workspace_bytes.  None when the shape is outside the device form."""
         rc = self.lib.cmtfpls_kfold_inner_f64(ctypes.byref(state), int(a), float(tol), int(max_iter), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner")
-        return True
+        return self._form(rc, "kfold_inner")
 
     def kfold_inner_workspace_bytes(self, A: int, B: int, K: int) -> int:
         return int(self.lib.cmtfpls_kfold_inner_workspace_bytes(A, B, K))
@@ -1055,10 +963,7 @@ class HipBackend:
         assert model_fold is None or (model_fold.dtype == torch.int32 and model_fold.numel() == state.K)
         rc = self.lib.cmtfpls_kfold_inner_tensor_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(B1), int(B2), int(a),
                                                      float(tol), int(max_iter), _ptr(Wk), _ptr(Wl), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner_tensor")
-        return True
+        return self._form(rc, "kfold_inner_tensor")
 
     def kfold_inner_tensor_workspace_bytes(self, A: int, B1: int, B2: int, K: int) -> int:
         return int(self.lib.cmtfpls_kfold_inner_tensor_workspace_bytes(A, B1, B2, K))
@@ -1071,10 +976,7 @@ class HipBackend:
         """Stage 0: every fold's Gy; 1: component a's epilogue from the MTTKRP scores (I x K); 2: the down-date of S from the
         contraction (K x P) -- cmtfpls_kfold_epilogue_f64.  None when the shape is outside the device form."""
         rc = self.lib.cmtfpls_kfold_epilogue_f64(ctypes.byref(state), int(stage), int(a), _ptr(src), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_epilogue")
-        return True
+        return self._form(rc, "kfold_epilogue")
 
     def kfold_inner_coupled(self, views, a: int, tol: float, max_iter: int, ws: torch.Tensor) -> Optional[bool]:
         """Component a's inner loop for every fold of a coupled model, a workgroup per fold going through the blocks
@@ -1082,10 +984,7 @@ class HipBackend:
         kfold_inner_coupled_workspace_bytes(views).  None when a block or the LDS is outside the device form."""
         rc = self.lib.cmtfpls_kfold_inner_coupled_f64(views, len(views), int(a), float(tol), int(max_iter), _ptr(ws), ws.numel(),
                                                       self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner_coupled")
-        return True
+        return self._form(rc, "kfold_inner_coupled")
 
     def kfold_inner_coupled_workspace_bytes(self, views) -> int:
         return int(self.lib.cmtfpls_kfold_inner_coupled_workspace_bytes(views, len(views)))
@@ -1102,10 +1001,7 @@ class HipBackend:
         rc = self.lib.cmtfpls_kfold_inner_coupled_tensor_f64(views, len(views), _int_pairs(dims), _ptr(model_fold), int(groups), int(a),
                                                              float(tol), int(max_iter), _ptr(Wk), _ptr(Wl), _ptr(ws), ws.numel(),
                                                              self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner_coupled_tensor")
-        return True
+        return self._form(rc, "kfold_inner_coupled_tensor")
 
     def kfold_inner_coupled_tensor_workspace_bytes(self, views, dims) -> int:
         return int(self.lib.cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(views, len(views), _int_pairs(dims)))
@@ -1127,14 +1023,11 @@ class HipBackend:
         W = Y.shape[1]
         assert Y.dtype == torch.float64 and Y.is_contiguous() and ydev.is_contiguous() and S.is_contiguous() and P == A * B
         assert order.dtype == torch.int32 and fold_off.dtype == torch.int32 and S.numel() == K * W * P and mean.numel() == K * P
-        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K)), 256), dtype=torch.uint8, device=self.device)
+        ws = _scratch(self.lib.cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K), self.device)
         stats = self.empty(2 * P)
         rc = self._fn("kfold_wide_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), W, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S),
                                              _ptr(mean), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_wide_xcov")
-        return stats
+        return self._form(rc, "kfold_wide_xcov", stats)
 
     def kfold_inner_grouped(self, state, model_fold: torch.Tensor, groups: int, a: int, tol: float, max_iter: int,
                             ws: torch.Tensor) -> Optional[bool]:
@@ -1142,10 +1035,7 @@ class HipBackend:
         assert model_fold.dtype == torch.int32 and model_fold.numel() == state.K
         rc = self.lib.cmtfpls_kfold_inner_grouped_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(a), float(tol), int(max_iter),
                                                       _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner_grouped")
-        return True
+        return self._form(rc, "kfold_inner_grouped")
 
     def kfold_epilogue_grouped(self, state, model_fold: torch.Tensor, groups: int, stage: int, a: int,
                                src: Optional[torch.Tensor]) -> Optional[bool]:
@@ -1154,10 +1044,7 @@ class HipBackend:
         assert model_fold.dtype == torch.int32 and model_fold.numel() == state.K
         rc = self.lib.cmtfpls_kfold_epilogue_grouped_f64(ctypes.byref(state), _ptr(model_fold), int(groups), int(stage), int(a), _ptr(src),
                                                          self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_epilogue_grouped")
-        return True
+        return self._form(rc, "kfold_epilogue_grouped")
 
     def kfold_inner_coupled_grouped(self, views, model_fold: torch.Tensor, groups: int, a: int, tol: float, max_iter: int,
                                     ws: torch.Tensor) -> Optional[bool]:
@@ -1166,20 +1053,14 @@ class HipBackend:
         assert model_fold.dtype == torch.int32 and model_fold.numel() == views[0].K
         rc = self.lib.cmtfpls_kfold_inner_coupled_grouped_f64(views, len(views), _ptr(model_fold), int(groups), int(a), float(tol),
                                                               int(max_iter), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_inner_coupled_grouped")
-        return True
+        return self._form(rc, "kfold_inner_coupled_grouped")
 
     # -- repeated K-fold Q2Y (validate.get_q2y_repeated_kfold, repeated.py): G shuffled splits x K folds per pass ----------------
     def kfold_epilogue_splits(self, state, splits: int, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
         """kfold_epilogue for state.K models in `splits` split-major splits (cmtfpls_kfold_epilogue_splits_f64): fold_of is
         splits x I, and the held-out scores of split m // (K / splits) go to that split's I x R slice of Tout."""
         rc = self.lib.cmtfpls_kfold_epilogue_splits_f64(ctypes.byref(state), int(splits), int(stage), int(a), _ptr(src), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_epilogue_splits")
-        return True
+        return self._form(rc, "kfold_epilogue_splits")
 
     # -- bootstrap of the factors (validate.bootstrap_factors, bootstrap.py): n weighted resamples per pass ------------------
     def kfold_weighted_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, n: int, M: int, S: torch.Tensor,
@@ -1191,24 +1072,17 @@ class HipBackend:
         I, P = X2.shape
         assert Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape == (I, n * (M + 1)) and P == A * B
         assert S.is_contiguous() and S.numel() == n * M * P and mean.is_contiguous() and mean.numel() == n * P
-        ws = torch.empty(max(int(self.lib.cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M)), 256), dtype=torch.uint8,
-                         device=self.device)
+        ws = _scratch(self.lib.cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M), self.device)
         stats = self.empty(2 * P)
         rc = self._fn("kfold_weighted_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), n, M, _ptr(S), _ptr(mean), _ptr(stats), _ptr(ws),
                                                  ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_weighted_xcov")
-        return stats
+        return self._form(rc, "kfold_weighted_xcov", stats)
 
     def kfold_epilogue_weighted(self, state, stage: int, a: int, src: Optional[torch.Tensor]) -> Optional[bool]:
         """kfold_epilogue for state.K weighted models (cmtfpls_kfold_epilogue_weighted_f64): fold_of is the n x I row counts,
         every training-row sum is weighted by them; the rows with count 0 keep their projection in T."""
         rc = self.lib.cmtfpls_kfold_epilogue_weighted_f64(ctypes.byref(state), int(stage), int(a), _ptr(src), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "kfold_epilogue_weighted")
-        return True
+        return self._form(rc, "kfold_epilogue_weighted")
 
     def press_rows(self, T: torch.Tensor, coef: torch.Tensor, Q: torch.Tensor, nu: torch.Tensor, Y: torch.Tensor, ev: torch.Tensor,
                    pred: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -1227,10 +1101,7 @@ class HipBackend:
         press = self.empty(n, R)
         rc = self.lib.cmtfpls_press_rows_f64(_ptr(T), _ptr(coef), _ptr(Q), _ptr(nu), _ptr(Y), _ptr(ev), n, I, R, M, _ptr(press),
                                              _ptr(pred), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
-            return None
-        _lib.check(rc, "press_rows")
-        return press
+        return self._form(rc, "press_rows", press)
 
     def fit_small(self, X2: torch.Tensor, Y: torch.Tensor, A: int, B: int, R: int, tol: float, max_iter: int):
         """The complete tPLS.fit of a small float64 problem without missing values in ONE launch (cmtfpls_fit_small_f64):
@@ -1250,9 +1121,8 @@ class HipBackend:
         rc = self.lib.cmtfpls_fit_small_f64(_ptr(X2), _ptr(Y), I, A, B, M, R, float(tol), int(max_iter), _ptr(T), _ptr(U), _ptr(WA), _ptr(WB),
                                             _ptr(Q), _ptr(small), small[R * R:].data_ptr(), _ptr(xm), _ptr(ym), _ptr(ints),
                                             ints[R:].data_ptr(), _ptr(ws), ws.numel(), self._stream())
-        if rc == 4:
+        if self._form(rc, "fit_small") is None:
             return None
-        _lib.check(rc, "fit_small")
         ih = ints.cpu().numpy()
         if ih[R] != 0:
             return None                                              # a NaN / inf somewhere: the regular (masked) engine takes it

@@ -37,6 +37,8 @@
 // has 256 registers and the inlined CP spills nothing (at 1024 threads and 128 registers it does); its Zt, U, yl and vr (P doubles each)
 // follow the model's means in the workspace; G0 / G1 and xs are sized for the largest short side n of the three unfoldings of Z,
 // min(A, B1 B2), min(B1, A B2), min(B2, A B1).  Limits: that n <= 64, M <= 64, R <= 16, the LDS within 150 KB, 1 <= K <= I.
+#include <string>
+
 #include "common.hpp"
 #include "fold_loop.hpp"
 #include "fold_regress.hpp"
@@ -300,6 +302,39 @@ static void cv_masked_launch(const CvMaskedArgs& a, size_t lds, void* stream) {
   hipLaunchKernelGGL(kernel, dim3(a.nmodels), dim3(TENSOR ? kCvTensorThreads : kCvThreads), lds, (hipStream_t)stream, a);
 }
 
+// The checks and the launch of the four entries.  `a` is the entry's call as it stands: its pointers (the fold entries' fold_of, or
+// the model entries' counts, in rows), nm = K or the number of models, model0 / nmodels the first item and the count, and for
+// TENSOR B1, B2 with B left 0; ws_per_model and the tensor form's B = B1 B2 are filled in here, after the checks.  The fold entries
+// (MODELS = false) also need the column sums and counts and K <= I.
+template <bool MODELS, bool TENSOR>
+static int cv_masked_run(const std::string& who, CvMaskedArgs a, size_t ws_bytes, void* stream) {
+  const std::string item = MODELS ? "model" : "fold";
+  auto fail = [&](int code, const std::string& what) { set_error((who + ": " + what).c_str()); return code; };
+  if (!a.X || !a.Y || !a.rows || (!MODELS && (!a.colsum_x || !a.colcnt_x || !a.colsum_y)) || !a.Ypred || !a.status || a.I <= 1 ||
+      a.A <= 0 || (TENSOR ? a.B1 <= 0 || a.B2 <= 0 : a.B <= 0) || a.M <= 0 || a.R <= 0 || a.max_iter <= 0 || a.nm <= 0 ||
+      a.model0 < 0 || a.nmodels <= 0)
+    return fail(CMTFPLS_EINVAL, "bad argument");
+  size_t lds, per;
+  bool fits;
+  if constexpr (TENSOR) {
+    fits = cv_masked_tensor_fits(a.I, a.A, a.B1, a.B2, a.M, a.R);
+    lds = cv_masked_tensor_lds_bytes(a.I, a.A, a.B1, a.B2, a.M, a.R);
+    per = cv_masked_tensor_workspace_bytes(a.I, a.A, a.B1, a.B2, a.M, a.R);
+  } else {
+    lds = cv_masked_lds_bytes(a.I, a.A, a.B, a.M, a.R);
+    fits = (a.A < a.B ? a.A : a.B) <= kCvMaxN && a.M <= kCvMaxM && a.R <= kCvMaxR && lds <= 150 * 1024;
+    per = cv_masked_workspace_bytes(a.I, a.A, a.B, a.M, a.R);
+  }
+  if ((!MODELS && a.nm > a.I) || !fits)
+    return fail(CMTFPLS_EUNSUPPORTED, "shape outside the one-workgroup-per-" + item + " form; refit per " + item + " on the regular engine");
+  if (a.model0 + a.nmodels > a.nm) return fail(CMTFPLS_EINVAL, item + "s out of range");
+  if (!a.ws || ws_bytes < per * (size_t)a.nmodels) return fail(CMTFPLS_EWORKSPACE, "workspace too small");
+  a.ws_per_model = (int64_t)(per / sizeof(double));
+  if constexpr (TENSOR) a.B = a.B1 * a.B2;
+  cv_masked_launch<MODELS, TENSOR>(a, lds, stream);
+  return check_launch(who.c_str());
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -310,58 +345,23 @@ size_t cmtfpls_cv_masked_fold_workspace_bytes(int I, int A, int B, int M, int R)
 
 size_t cmtfpls_cv_masked_model_workspace_bytes(int I, int A, int B, int M, int R) { return cv_masked_workspace_bytes(I, A, B, M, R); }
 
+// (the braces follow CvMaskedArgs' fields: X, Y, rows, yrow, the column sums and counts, ws, Ypred, Wa, Wb, coef, Q, n_iter, status,
+// info, ws_per_model, I, A, B, M, R, nm, max_iter, model0, nmodels, tol, then B1, B2, Wk, Wl)
 int cmtfpls_cv_masked_f64(const double* X, const double* Y, const int* fold_of, int K, const double* colsum_x, const double* colcnt_x,
                           const double* colsum_y, int I, int A, int B, int M, int R, double tol, int max_iter, int fold0, int nfolds,
                           double* Ypred, int* n_iter, int* status, int* info, void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !Y || !fold_of || !colsum_x || !colcnt_x || !colsum_y || !Ypred || !status || I <= 1 || A <= 0 || B <= 0 || M <= 0 ||
-      R <= 0 || max_iter <= 0 || K <= 0 || fold0 < 0 || nfolds <= 0) {
-    set_error("cv_masked: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  const int n = A < B ? A : B;
-  const size_t lds = cv_masked_lds_bytes(I, A, B, M, R);
-  if (K > I || n > kCvMaxN || M > kCvMaxM || R > kCvMaxR || lds > 150 * 1024) {
-    set_error("cv_masked: shape outside the one-workgroup-per-fold form; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  if (fold0 + nfolds > K) { set_error("cv_masked: folds out of range"); return CMTFPLS_EINVAL; }
-  const size_t per = cv_masked_workspace_bytes(I, A, B, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("cv_masked: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  CvMaskedArgs a = {};
-  a.X = X; a.Y = Y; a.rows = fold_of; a.colsum_x = colsum_x; a.colcnt_x = colcnt_x; a.colsum_y = colsum_y;
-  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter; a.status = status; a.info = info;
-  a.ws_per_model = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B; a.M = M; a.R = R; a.nm = K; a.max_iter = max_iter; a.model0 = fold0; a.nmodels = nfolds; a.tol = tol;
-  cv_masked_launch<false>(a, lds, stream);
-  return check_launch("cv_masked");
+  return cv_masked_run<false, false>("cv_masked", {X, Y, fold_of, nullptr, colsum_x, colcnt_x, colsum_y, static_cast<double*>(ws), Ypred,
+                                                   nullptr, nullptr, nullptr, nullptr, n_iter, status, info, 0, I, A, B, M, R, K,
+                                                   max_iter, fold0, nfolds, tol, 0, 0, nullptr, nullptr}, ws_bytes, stream);
 }
 
 int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* counts, const int* yrow, int nm, int I, int A, int B,
                                  int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred, double* Wa,
                                  double* Wb, double* coef, double* Q, int* n_iter, int* status, int* info, void* ws, size_t ws_bytes,
                                  void* stream) {
-  if (!X || !Y || !counts || !Ypred || !status || I <= 1 || A <= 0 || B <= 0 || M <= 0 || R <= 0 || max_iter <= 0 || nm <= 0 ||
-      model0 < 0 || nmodels <= 0) {
-    set_error("cv_masked_models: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  const int n = A < B ? A : B;
-  const size_t lds = cv_masked_lds_bytes(I, A, B, M, R);
-  if (n > kCvMaxN || M > kCvMaxM || R > kCvMaxR || lds > 150 * 1024) {
-    set_error("cv_masked_models: shape outside the one-workgroup-per-model form; refit per model on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  if (model0 + nmodels > nm) { set_error("cv_masked_models: models out of range"); return CMTFPLS_EINVAL; }
-  const size_t per = cv_masked_workspace_bytes(I, A, B, M, R);
-  if (!ws || ws_bytes < per * (size_t)nmodels) { set_error("cv_masked_models: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  CvMaskedArgs a = {};
-  a.X = X; a.Y = Y; a.rows = counts; a.yrow = yrow;
-  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.Wa = Wa; a.Wb = Wb; a.coef = coef; a.Q = Q;
-  a.n_iter = n_iter; a.status = status; a.info = info;
-  a.ws_per_model = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B; a.M = M; a.R = R; a.nm = nm; a.max_iter = max_iter; a.model0 = model0; a.nmodels = nmodels; a.tol = tol;
-  cv_masked_launch<true>(a, lds, stream);
-  return check_launch("cv_masked_models");
+  return cv_masked_run<true, false>("cv_masked_models", {X, Y, counts, yrow, nullptr, nullptr, nullptr, static_cast<double*>(ws), Ypred,
+                                                         Wa, Wb, coef, Q, n_iter, status, info, 0, I, A, B, M, R, nm, max_iter, model0,
+                                                         nmodels, tol, 0, 0, nullptr, nullptr}, ws_bytes, stream);
 }
 
 size_t cmtfpls_cv_masked_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
@@ -376,53 +376,18 @@ int cmtfpls_cv_masked_tensor_f64(const double* X, const double* Y, const int* fo
                                  const double* colcnt_x, const double* colsum_y, int I, int A, int B1, int B2, int M, int R, double tol,
                                  int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status, int* info, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (!X || !Y || !fold_of || !colsum_x || !colcnt_x || !colsum_y || !Ypred || !status || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 ||
-      M <= 0 || R <= 0 || max_iter <= 0 || K <= 0 || fold0 < 0 || nfolds <= 0) {
-    set_error("cv_masked_tensor: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  if (K > I || !cv_masked_tensor_fits(I, A, B1, B2, M, R)) {
-    set_error("cv_masked_tensor: shape outside the one-workgroup-per-fold form; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  if (fold0 + nfolds > K) { set_error("cv_masked_tensor: folds out of range"); return CMTFPLS_EINVAL; }
-  const size_t per = cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("cv_masked_tensor: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  CvMaskedArgs a = {};
-  a.X = X; a.Y = Y; a.rows = fold_of; a.colsum_x = colsum_x; a.colcnt_x = colcnt_x; a.colsum_y = colsum_y;
-  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter; a.status = status; a.info = info;
-  a.ws_per_model = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B1 * B2; a.B1 = B1; a.B2 = B2; a.M = M; a.R = R; a.nm = K; a.max_iter = max_iter; a.model0 = fold0;
-  a.nmodels = nfolds; a.tol = tol;
-  cv_masked_launch<false, true>(a, cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R), stream);
-  return check_launch("cv_masked_tensor");
+  return cv_masked_run<false, true>("cv_masked_tensor", {X, Y, fold_of, nullptr, colsum_x, colcnt_x, colsum_y, static_cast<double*>(ws),
+                                                         Ypred, nullptr, nullptr, nullptr, nullptr, n_iter, status, info, 0, I, A, 0, M, R,
+                                                         K, max_iter, fold0, nfolds, tol, B1, B2, nullptr, nullptr}, ws_bytes, stream);
 }
 
 int cmtfpls_cv_masked_tensor_models_f64(const double* X, const double* Y, const int* counts, const int* yrow, int nm, int I, int A,
                                         int B1, int B2, int M, int R, double tol, int max_iter, int model0, int nmodels, double* Ypred,
                                         double* Wa, double* Wk, double* Wl, double* coef, double* Q, int* n_iter, int* status,
                                         int* info, void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !Y || !counts || !Ypred || !status || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0 || max_iter <= 0 ||
-      nm <= 0 || model0 < 0 || nmodels <= 0) {
-    set_error("cv_masked_tensor_models: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  if (!cv_masked_tensor_fits(I, A, B1, B2, M, R)) {
-    set_error("cv_masked_tensor_models: shape outside the one-workgroup-per-model form; refit per model on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  if (model0 + nmodels > nm) { set_error("cv_masked_tensor_models: models out of range"); return CMTFPLS_EINVAL; }
-  const size_t per = cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
-  if (!ws || ws_bytes < per * (size_t)nmodels) { set_error("cv_masked_tensor_models: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  CvMaskedArgs a = {};
-  a.X = X; a.Y = Y; a.rows = counts; a.yrow = yrow;
-  a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.Wa = Wa; a.Wk = Wk; a.Wl = Wl; a.coef = coef; a.Q = Q;
-  a.n_iter = n_iter; a.status = status; a.info = info;
-  a.ws_per_model = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B1 * B2; a.B1 = B1; a.B2 = B2; a.M = M; a.R = R; a.nm = nm; a.max_iter = max_iter; a.model0 = model0;
-  a.nmodels = nmodels; a.tol = tol;
-  cv_masked_launch<true, true>(a, cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R), stream);
-  return check_launch("cv_masked_tensor_models");
+  return cv_masked_run<true, true>("cv_masked_tensor_models", {X, Y, counts, yrow, nullptr, nullptr, nullptr, static_cast<double*>(ws),
+                                                               Ypred, Wa, nullptr, coef, Q, n_iter, status, info, 0, I, A, 0, M, R, nm,
+                                                               max_iter, model0, nmodels, tol, B1, B2, Wk, Wl}, ws_bytes, stream);
 }
 
 }  // extern "C"

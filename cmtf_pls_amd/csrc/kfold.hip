@@ -879,6 +879,18 @@ static void kf_wide_launch(dim3 g, hipStream_t st, const T* X, int64_t P, const 
     hipLaunchKernelGGL((kfold_wide_kernel<T, MT, false>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);
 }
 
+// the MT (MFMA tiles per wavefront) instance of the plan
+template <typename T>
+static void kf_wide_dispatch(const KfWidePlan& pl, dim3 g, hipStream_t st, const T* X, int64_t P, const double* Y, int W, const int* order,
+                             const int* off, double* part) {
+  switch (pl.mt) {
+    case 1: kf_wide_launch<T, 1>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    case 2: kf_wide_launch<T, 2>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    case 3: kf_wide_launch<T, 3>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+    default: kf_wide_launch<T, 4>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
+  }
+}
+
 template <typename T>
 static int run_kfold_wide(const T* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off, int K,
                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -897,12 +909,7 @@ static int run_kfold_wide(const T* X, int64_t I, int A, int B, const double* Y, 
   double* part = static_cast<double*>(ws);
   const int64_t ct = (P + kKfWideCols - 1) / kKfWideCols;
   const dim3 g((unsigned)(ct * pl.nyb), (unsigned)(K * pl.nch));
-  switch (pl.mt) {
-    case 1: kf_wide_launch<T, 1>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
-    case 2: kf_wide_launch<T, 2>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
-    case 3: kf_wide_launch<T, 3>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
-    default: kf_wide_launch<T, 4>(g, st, X, P, Y, W, order, fold_off, pl.nyb, pl.nch, part); break;
-  }
+  kf_wide_dispatch<T>(pl, g, st, X, P, Y, W, order, fold_off, part);
   int rc = check_launch("kfold_wide_xcov");
   if (rc) return rc;
   hipLaunchKernelGGL(kfold_finish_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols)), dim3(kKfCols), 0, st, P, W, K, pl.nch, (int)I,
@@ -925,88 +932,62 @@ static int kf_grouped_check(const cmtfpls_kfold_state* st, const int* model_fold
   return CMTFPLS_OK;
 }
 
-// the launch of the plain and grouped inner entries, after their argument checks
-template <bool GROUPED>
-static int kf_inner_launch(const cmtfpls_kfold_state* st, const int* model_fold, int a, double tol, int max_iter, void* ws,
-                           size_t ws_bytes, hipStream_t s) {
-  const size_t need = cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
-  if (!ws || ws_bytes < need) {
-    set_error(GROUPED ? "kfold_inner_grouped: workspace too small" : "kfold_inner: workspace too small");
+// the launch of the inner entries (plain, grouped, order 4), after their argument checks; tn: KfTensor{} unless TENSOR
+template <bool GROUPED, bool TENSOR>
+static int kf_inner_launch(const cmtfpls_kfold_state* st, const int* model_fold, const KfTensor& tn, int a, double tol, int max_iter,
+                           void* ws, size_t ws_bytes, hipStream_t s) {
+  const size_t need = TENSOR ? cmtfpls_kfold_inner_tensor_workspace_bytes(st->A, tn.B1, tn.B2, st->K)
+                             : cmtfpls_kfold_inner_workspace_bytes(st->A, st->B, st->K);
+  if (!ws || ws_bytes < need) {                                   // behaviour: the order-4 entry's texts have no grouped variant
+    set_error(TENSOR ? "kfold_inner_tensor: workspace too small"
+                     : GROUPED ? "kfold_inner_grouped: workspace too small" : "kfold_inner: workspace too small");
     return CMTFPLS_EWORKSPACE;
   }
-  const size_t lds = kf_inner_lds_bytes(st->A, st->B, st->M);
+  const size_t lds = TENSOR ? kf_inner_tensor_lds_bytes(st->A, tn.B1, tn.B2, st->M) : kf_inner_lds_bytes(st->A, st->B, st->M);
+  const int64_t per = TENSOR ? kf_inner_tensor_ws_per_fold(st->A, tn.B1, tn.B2) : (int64_t)(need / st->K / sizeof(double));
+  const auto kernel = kfold_inner_kernel<GROUPED, TENSOR>;
   if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfold_inner_kernel<GROUPED>, dim3(st->K), dim3(kLxNT), lds, s, *st, a, tol, max_iter, static_cast<double*>(ws),
-                     (int64_t)(need / st->K / sizeof(double)), model_fold);
-  return check_launch(GROUPED ? "kfold_inner_grouped" : "kfold_inner");
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(st->K), dim3(kLxNT), lds, s, *st, a, tol, max_iter, static_cast<double*>(ws), per, model_fold, tn);
+  return check_launch(TENSOR ? "kfold_inner_tensor" : GROUPED ? "kfold_inner_grouped" : "kfold_inner");
 }
 
-// the launch of the order-4 inner entry, after its argument checks
-template <bool GROUPED>
-static int kf_inner_tensor_launch(const cmtfpls_kfold_state* st, const int* model_fold, const KfTensor& tn, int a, double tol,
-                                  int max_iter, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!ws || ws_bytes < cmtfpls_kfold_inner_tensor_workspace_bytes(st->A, tn.B1, tn.B2, st->K)) {
-    set_error("kfold_inner_tensor: workspace too small");
-    return CMTFPLS_EWORKSPACE;
-  }
-  const size_t lds = kf_inner_tensor_lds_bytes(st->A, tn.B1, tn.B2, st->M);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_kernel<GROUPED, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  hipLaunchKernelGGL((kfold_inner_kernel<GROUPED, true>), dim3(st->K), dim3(kLxNT), lds, s, *st, a, tol, max_iter,
-                     static_cast<double*>(ws), kf_inner_tensor_ws_per_fold(st->A, tn.B1, tn.B2), model_fold, tn);
-  return check_launch("kfold_inner_tensor");
+static KfBlocks kf_blocks_of(const cmtfpls_kfold_state* blocks, int nb) {
+  KfBlocks bl;
+  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
+  bl.nb = nb;
+  return bl;
 }
 
-// the launch of the plain and grouped coupled inner entries, after their argument checks
-template <bool GROUPED>
-static int kf_inner_coupled_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int a, double tol, int max_iter,
-                                   void* ws, size_t ws_bytes, hipStream_t s) {
-  const KfCoupledDims d = kf_coupled_dims(blocks, nb);
-  const size_t lds = kf_coupled_lds_bytes(d, blocks[0].M);
-  if (lds > 150 * 1024) {
+// the launch of the coupled inner entries (plain, grouped, blocks of order 4), after their argument checks; o: kf_coupled_dims in
+// o.d and nothing else unless TENSOR (then kf_coupled_tensor_dims with the outputs Wk, Wl in o.tn)
+template <bool GROUPED, bool TENSOR>
+static int kf_inner_coupled_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, const KfCoupledTensorDims& o, int a,
+                                   double tol, int max_iter, void* ws, size_t ws_bytes, hipStream_t s) {
+  const size_t lds = TENSOR ? kf_coupled_tensor_lds_bytes(o, blocks[0].M) : kf_coupled_lds_bytes(o.d, blocks[0].M);
+  if (!TENSOR && lds > 150 * 1024) {                              // behaviour: the order-4 entry checks the LDS before it comes here
     set_error(GROUPED ? "kfold_inner_coupled_grouped: the blocks' vectors exceed the LDS of one workgroup; refit per fold"
                       : "kfold_inner_coupled: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  const size_t need = cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb);
-  if (!ws || ws_bytes < need) {
-    set_error(GROUPED ? "kfold_inner_coupled_grouped: workspace too small" : "kfold_inner_coupled: workspace too small");
+  const size_t need = TENSOR ? (size_t)blocks[0].K * (size_t)kf_coupled_tensor_ws_per_fold(o) * sizeof(double)
+                             : cmtfpls_kfold_inner_coupled_workspace_bytes(blocks, nb);
+  if (!ws || ws_bytes < need) {                                   // behaviour: the order-4 entry's texts have no grouped variant
+    set_error(TENSOR ? "kfold_inner_coupled_tensor: workspace too small"
+                     : GROUPED ? "kfold_inner_coupled_grouped: workspace too small" : "kfold_inner_coupled: workspace too small");
     return CMTFPLS_EWORKSPACE;
   }
-  KfBlocks bl;
-  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
-  bl.nb = nb;
+  const auto kernel = kfold_inner_coupled_kernel<GROUPED, TENSOR>;
   if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel<GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  hipLaunchKernelGGL(kfold_inner_coupled_kernel<GROUPED>, dim3(blocks[0].K), dim3(kLxNT), lds, s, bl, a, tol, max_iter,
-                     static_cast<double*>(ws), kf_coupled_ws_per_fold(d), d.pmax, d.nmax, d.amax, d.bmax, model_fold);
-  return check_launch(GROUPED ? "kfold_inner_coupled_grouped" : "kfold_inner_coupled");
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(blocks[0].K), dim3(kLxNT), lds, s, kf_blocks_of(blocks, nb), a, tol, max_iter, static_cast<double*>(ws),
+                     kf_coupled_tensor_ws_per_fold(o), o.d.pmax, o.d.nmax, o.d.amax, o.d.bmax, model_fold, o.tn);   // (3 ptmax = 0 unless TENSOR)
+  return check_launch(TENSOR ? "kfold_inner_coupled_tensor" : GROUPED ? "kfold_inner_coupled_grouped" : "kfold_inner_coupled");
 }
 
-// the launch of the coupled entry with blocks of order 4, after its argument checks
-template <bool GROUPED>
-static int kf_inner_coupled_tensor_launch(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, KfCoupledTensorDims o, int a,
-                                          double tol, int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, hipStream_t s) {
-  const size_t lds = kf_coupled_tensor_lds_bytes(o, blocks[0].M);
-  const size_t need = (size_t)blocks[0].K * (size_t)kf_coupled_tensor_ws_per_fold(o) * sizeof(double);
-  if (!ws || ws_bytes < need) {
-    set_error("kfold_inner_coupled_tensor: workspace too small");
-    return CMTFPLS_EWORKSPACE;
-  }
-  KfBlocks bl;
-  for (int b = 0; b < kKfMaxBlocks; ++b) bl.b[b] = blocks[b < nb ? b : 0];
-  bl.nb = nb;
-  o.tn.Wk = Wk;
-  o.tn.Wl = Wl;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfold_inner_coupled_kernel<GROUPED, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((kfold_inner_coupled_kernel<GROUPED, true>), dim3(blocks[0].K), dim3(kLxNT), lds, s, bl, a, tol, max_iter,
-                     static_cast<double*>(ws), kf_coupled_tensor_ws_per_fold(o), o.d.pmax, o.d.nmax, o.d.amax, o.d.bmax, model_fold, o.tn);
-  return check_launch("kfold_inner_coupled_tensor");
+// the argument test of the epilogue entries
+static bool kf_epilogue_args_ok(const cmtfpls_kfold_state* st, int stage, int a, const double* in) {
+  return kf_state_ok(st) && stage >= 0 && stage <= 2 && a >= 0 && a < st->R && (stage == 0 || in);
 }
 
 // the stage switch of the three epilogue entries, after their argument checks: stage 0 the Y-side Gram, stage 1 the row work, the
@@ -1103,12 +1084,7 @@ static int run_kfold_weighted(const T* X, int64_t I, int A, int B, const double*
   if (rc) return rc;
   const int64_t ct = (P + kKfWideCols - 1) / kKfWideCols;
   const dim3 g((unsigned)(ct * pl.nyb), (unsigned)pl.nch);
-  switch (pl.mt) {
-    case 1: kf_wide_launch<T, 1>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
-    case 2: kf_wide_launch<T, 2>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
-    case 3: kf_wide_launch<T, 3>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
-    default: kf_wide_launch<T, 4>(g, st, X, P, Y, W, order, off, pl.nyb, pl.nch, part); break;
-  }
+  kf_wide_dispatch<T>(pl, g, st, X, P, Y, W, order, off, part);
   rc = check_launch("kfold_weighted_xcov");
   if (rc) return rc;
   hipLaunchKernelGGL(kfold_weighted_finish_kernel, dim3((unsigned)((P + kKfCols - 1) / kKfCols)), dim3(kKfCols), 0, st, P, n, M,
@@ -1153,7 +1129,7 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
     set_error("kfold_inner: shape outside the device form (2 <= K <= 32, M <= 64, R <= 64, min(A, B) <= 256); refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  return kf_inner_launch<false>(st, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_launch<false, false>(st, nullptr, KfTensor{}, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t cmtfpls_kfold_inner_tensor_workspace_bytes(int A, int B1, int B2, int K) {
@@ -1185,12 +1161,12 @@ int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* mod
     return CMTFPLS_EUNSUPPORTED;
   }
   const KfTensor tn{B1, B2, lx_tensor_nmax(st->A, B1, B2), Wk, Wl};
-  if (model_fold) return kf_inner_tensor_launch<true>(st, model_fold, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
-  return kf_inner_tensor_launch<false>(st, nullptr, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  if (model_fold) return kf_inner_launch<true, true>(st, model_fold, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_launch<false, true>(st, nullptr, tn, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {
-  if (!kf_state_ok(st) || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+  if (!kf_epilogue_args_ok(st, stage, a, in)) {
     set_error("kfold_epilogue: bad argument");
     return CMTFPLS_EINVAL;
   }
@@ -1213,7 +1189,9 @@ int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, i
   int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled: bad block views (the shared fields must be the same in every view)");
   if (rc) return rc;
   if (a < 0 || a >= blocks[0].R || max_iter <= 0) { set_error("kfold_inner_coupled: bad argument"); return CMTFPLS_EINVAL; }
-  return kf_inner_coupled_launch<false>(blocks, nb, nullptr, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  KfCoupledTensorDims o{};
+  o.d = kf_coupled_dims(blocks, nb);
+  return kf_inner_coupled_launch<false, false>(blocks, nb, nullptr, o, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // dims: (B1_b, B2_b) per block, (0, 0) for a matrix block, B_b = B1_b B2_b for a tensor block
@@ -1255,14 +1233,15 @@ int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, in
         set_error("kfold_inner_coupled_tensor: an unfolding of a block's A x B1 x B2 with its shorter side > 256; refit per fold");
         return CMTFPLS_EUNSUPPORTED;
       }
-  const KfCoupledTensorDims o = kf_coupled_tensor_dims(blocks, nb, dims);
-  if (kf_coupled_tensor_lds_bytes(o, blocks[0].M) > 150 * 1024) {
+  KfCoupledTensorDims o = kf_coupled_tensor_dims(blocks, nb, dims);
+  if (kf_coupled_tensor_lds_bytes(o, blocks[0].M) > 150 * 1024) {         // behaviour: checked here, ahead of the launch helper
     set_error("kfold_inner_coupled_tensor: the blocks' vectors exceed the LDS of one workgroup; refit per fold");
     return CMTFPLS_EUNSUPPORTED;
   }
-  if (model_fold)
-    return kf_inner_coupled_tensor_launch<true>(blocks, nb, model_fold, o, a, tol, max_iter, Wk, Wl, ws, ws_bytes, (hipStream_t)stream);
-  return kf_inner_coupled_tensor_launch<false>(blocks, nb, nullptr, o, a, tol, max_iter, Wk, Wl, ws, ws_bytes, (hipStream_t)stream);
+  o.tn.Wk = Wk;
+  o.tn.Wl = Wl;
+  if (model_fold) return kf_inner_coupled_launch<true, true>(blocks, nb, model_fold, o, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_coupled_launch<false, true>(blocks, nb, nullptr, o, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_combine_scores_f64(const double* sc, int nb, int64_t n, double* out, void* stream) {
@@ -1293,7 +1272,7 @@ int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* mo
   int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_inner_grouped: bad argument");
   if (rc) return rc;
   if (max_iter <= 0) { set_error("kfold_inner_grouped: bad argument"); return CMTFPLS_EINVAL; }
-  return kf_inner_launch<true>(st, model_fold, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  return kf_inner_launch<true, false>(st, model_fold, KfTensor{}, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_inner_coupled_grouped_f64(const cmtfpls_kfold_state* blocks, int nb, const int* model_fold, int groups, int a, double tol,
@@ -1309,7 +1288,9 @@ int cmtfpls_kfold_inner_coupled_grouped_f64(const cmtfpls_kfold_state* blocks, i
   int rc = kf_blocks_check(blocks, nb, "kfold_inner_coupled_grouped: bad block views (the shared fields must be the same in every view)",
                            blocks[0].K / groups);
   if (rc) return rc;
-  return kf_inner_coupled_launch<true>(blocks, nb, model_fold, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
+  KfCoupledTensorDims o{};
+  o.d = kf_coupled_dims(blocks, nb);
+  return kf_inner_coupled_launch<true, false>(blocks, nb, model_fold, o, a, tol, max_iter, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int stage, int a, const double* in,
@@ -1321,7 +1302,7 @@ int cmtfpls_kfold_epilogue_grouped_f64(const cmtfpls_kfold_state* st, const int*
 }
 
 int cmtfpls_kfold_epilogue_splits_f64(const cmtfpls_kfold_state* st, int splits, int stage, int a, const double* in, void* stream) {
-  if (!kf_state_ok(st) || splits < 1 || st->K % splits != 0 || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+  if (!kf_epilogue_args_ok(st, stage, a, in) || splits < 1 || st->K % splits != 0) {
     set_error("kfold_epilogue_splits: bad argument");
     return CMTFPLS_EINVAL;
   }
@@ -1349,7 +1330,7 @@ int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, co
 }
 
 int cmtfpls_kfold_epilogue_weighted_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {
-  if (!kf_state_ok(st) || stage < 0 || stage > 2 || a < 0 || a >= st->R || (stage > 0 && !in)) {
+  if (!kf_epilogue_args_ok(st, stage, a, in)) {
     set_error("kfold_epilogue_weighted: bad argument");
     return CMTFPLS_EINVAL;
   }

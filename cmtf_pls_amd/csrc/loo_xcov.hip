@@ -30,6 +30,8 @@
 // largest short side of the three unfoldings of A x B1 x B2 (each <= 256).  LDS: xs (n), then in place of ys (k) lx_cp3's wK (B1),
 // wL (B2), v (B), tmp (max(A, B1, B2)) and part (1024); workspace: lx_cp3's U, yl, vr (P each) after wk
 // (cmtfpls_loo_xcov_tensor_fold_workspace_bytes).
+#include <string>
+
 #include "loo_xcov_fold.hpp"
 
 namespace cmtfpls {
@@ -168,6 +170,48 @@ static size_t lx_tensor_lds_bytes(int A, int B1, int B2, int M, int R) {
   return dbl * sizeof(double);
 }
 
+// The checks, argument fill and launch of the two entries: cmtfpls_loo_xcov_f64 (TENSOR = false: the trailing dim B as B1, B2 = 1)
+// and cmtfpls_loo_xcov_tensor_f64.  The shape checks are each entry's own, with its texts in its order.
+template <bool TENSOR>
+static int lx_run(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B1, int B2, int M,
+                  int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws, size_t ws_bytes,
+                  void* stream) {
+  const std::string who = TENSOR ? "loo_xcov_tensor" : "loo_xcov";
+  const std::string refit = "; refit per fold on the regular engine";
+  auto fail = [&](int code, const std::string& what) { set_error((who + ": " + what).c_str()); return code; };
+  if (!X || !Y || !colsum_x || !colsum_y || !Ypred || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0 || max_iter <= 0 ||
+      fold0 < 0 || nfolds <= 0 || fold0 + nfolds > I)
+    return fail(CMTFPLS_EINVAL, "bad argument");
+  size_t lds, per;
+  if constexpr (TENSOR) {
+    if ((int64_t)A * B1 * B2 > (int64_t)1 << 24) return fail(CMTFPLS_EUNSUPPORTED, "A * B1 * B2 > 2^24" + refit);
+    for (int m = 0; m < 3; ++m)
+      if (lx_tensor_short(A, B1, B2, m) > kLxMaxN)
+        return fail(CMTFPLS_EUNSUPPORTED, "an unfolding of A x B1 x B2 with its shorter side > 256" + refit);
+    if (M > kLxMaxM || R > kLxMaxR)
+      return fail(CMTFPLS_EUNSUPPORTED, "shape outside the workgroup-per-fold form (M <= 128, R <= 64)" + refit);
+    lds = lx_tensor_lds_bytes(A, B1, B2, M, R);
+    if (lds > 150 * 1024) return fail(CMTFPLS_EUNSUPPORTED, "the fold's vectors exceed 150 KB of LDS" + refit);
+    per = cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R);
+  } else {
+    lds = lx_lds_bytes(A, B1, M, R);
+    if ((A < B1 ? A : B1) > kLxMaxN || M > kLxMaxM || R > kLxMaxR || lds > 150 * 1024 || (int64_t)A * B1 > (int64_t)1 << 24)
+      return fail(CMTFPLS_EUNSUPPORTED, "shape outside the workgroup-per-fold form (min(A, B) <= 256, M <= 128, R <= 64, small vectors "
+                                        "within 150 KB of LDS)" + refit);
+    per = cmtfpls_loo_xcov_fold_workspace_bytes(I, A, B1, M, R);
+  }
+  if (!ws || ws_bytes < per * (size_t)nfolds) return fail(CMTFPLS_EWORKSPACE, "workspace too small");
+  typename LooXArgsOf<TENSOR>::type a;
+  a.X = X; a.Y = Y; a.colsum_x = colsum_x; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
+  a.ws_per_fold = (int64_t)(per / sizeof(double));
+  a.I = I; a.A = A; a.B = B1 * B2; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds; a.tol = tol;
+  if constexpr (TENSOR) { a.B1 = B1; a.B2 = B2; a.nmax = lx_tensor_nmax(A, B1, B2); }
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel<TENSOR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(loo_xcov_kernel<TENSOR>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
+  return check_launch(who.c_str());
+}
+
 }  // namespace cmtfpls
 
 using namespace cmtfpls;
@@ -180,75 +224,22 @@ size_t cmtfpls_loo_xcov_fold_workspace_bytes(int I, int A, int B, int M, int R) 
   return ((size_t)I * P + (size_t)I * M + (size_t)I * R + (size_t)M * P + 3 * P + 2 * n * n + 2 * (size_t)I + (size_t)R * ((size_t)A + B)) * sizeof(double);
 }
 
-int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B, int M,
-                         int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws,
-                         size_t ws_bytes, void* stream) {
-  if (!X || !Y || !colsum_x || !colsum_y || !Ypred || I <= 1 || A <= 0 || B <= 0 || M <= 0 || R <= 0 || max_iter <= 0 || fold0 < 0 ||
-      nfolds <= 0 || fold0 + nfolds > I) {
-    set_error("loo_xcov: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  const int n = A < B ? A : B;
-  const size_t lds = lx_lds_bytes(A, B, M, R);
-  if (n > kLxMaxN || M > kLxMaxM || R > kLxMaxR || lds > 150 * 1024 || (int64_t)A * B > (int64_t)1 << 24) {
-    set_error("loo_xcov: shape outside the workgroup-per-fold form (min(A, B) <= 256, M <= 128, R <= 64, small vectors within 150 KB of LDS); refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t per = cmtfpls_loo_xcov_fold_workspace_bytes(I, A, B, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("loo_xcov: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  LooXArgs a;
-  a.X = X; a.Y = Y; a.colsum_x = colsum_x; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
-  a.ws_per_fold = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds; a.tol = tol;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(loo_xcov_kernel<false>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
-  return check_launch("loo_xcov");
-}
-
 size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R) {
   if (I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0) return 0;
   const size_t B = (size_t)B1 * B2, P = (size_t)A * B, n = (size_t)lx_tensor_nmax(A, B1, B2);
   return ((size_t)I * P + (size_t)I * M + (size_t)I * R + (size_t)M * P + 6 * P + 2 * n * n + 2 * (size_t)I + (size_t)R * ((size_t)A + B)) * sizeof(double);
 }
 
+int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B, int M,
+                         int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws,
+                         size_t ws_bytes, void* stream) {
+  return lx_run<false>(X, Y, colsum_x, colsum_y, I, A, B, 1, M, R, tol, max_iter, fold0, nfolds, Ypred, n_iter, ws, ws_bytes, stream);
+}
+
 int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B1,
                                 int B2, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter,
                                 void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !Y || !colsum_x || !colsum_y || !Ypred || I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0 || max_iter <= 0 ||
-      fold0 < 0 || nfolds <= 0 || fold0 + nfolds > I) {
-    set_error("loo_xcov_tensor: bad argument");
-    return CMTFPLS_EINVAL;
-  }
-  if ((int64_t)A * B1 * B2 > (int64_t)1 << 24) {
-    set_error("loo_xcov_tensor: A * B1 * B2 > 2^24; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  for (int m = 0; m < 3; ++m)
-    if (lx_tensor_short(A, B1, B2, m) > kLxMaxN) {
-      set_error("loo_xcov_tensor: an unfolding of A x B1 x B2 with its shorter side > 256; refit per fold on the regular engine");
-      return CMTFPLS_EUNSUPPORTED;
-    }
-  if (M > kLxMaxM || R > kLxMaxR) {
-    set_error("loo_xcov_tensor: shape outside the workgroup-per-fold form (M <= 128, R <= 64); refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t lds = lx_tensor_lds_bytes(A, B1, B2, M, R);
-  if (lds > 150 * 1024) {
-    set_error("loo_xcov_tensor: the fold's vectors exceed 150 KB of LDS; refit per fold on the regular engine");
-    return CMTFPLS_EUNSUPPORTED;
-  }
-  const size_t per = cmtfpls_loo_xcov_tensor_fold_workspace_bytes(I, A, B1, B2, M, R);
-  if (!ws || ws_bytes < per * (size_t)nfolds) { set_error("loo_xcov_tensor: workspace too small"); return CMTFPLS_EWORKSPACE; }
-  LooXTensorArgs a;
-  a.X = X; a.Y = Y; a.colsum_x = colsum_x; a.colsum_y = colsum_y; a.ws = static_cast<double*>(ws); a.Ypred = Ypred; a.n_iter = n_iter;
-  a.ws_per_fold = (int64_t)(per / sizeof(double));
-  a.I = I; a.A = A; a.B = B1 * B2; a.M = M; a.R = R; a.max_iter = max_iter; a.fold0 = fold0; a.nfolds = nfolds; a.tol = tol;
-  a.B1 = B1; a.B2 = B2; a.nmax = lx_tensor_nmax(A, B1, B2);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(loo_xcov_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(loo_xcov_kernel<true>, dim3(nfolds), dim3(kLxNT), lds, (hipStream_t)stream, a);
-  return check_launch("loo_xcov_tensor");
+  return lx_run<true>(X, Y, colsum_x, colsum_y, I, A, B1, B2, M, R, tol, max_iter, fold0, nfolds, Ypred, n_iter, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .backend import _scratch
 
 MAX_FOLDS, MAX_RESPONSES, MAX_COMPONENTS, MAX_SIDE = 32, 64, 64, 256
 MAX_BLOCKS = 8                    # blocks of a coupled model (cmtfpls_kfold_inner_coupled_f64)
@@ -402,24 +403,24 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
     if coupled and tensor is not None:
-        ws = torch.empty(max(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), 256), dtype=torch.uint8, device=be.device)
+        ws = _scratch(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), be.device)
         mf, groups = grouped if grouped else (None, 1)
         Wk, Wl = tensor_out if tensor_out else (None, None)
         inner, inner_name = lambda a: be.kfold_inner_coupled_tensor(st, tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), \
             "kfold_inner_coupled_tensor_f64"
     elif coupled:
-        ws = torch.empty(max(be.kfold_inner_coupled_workspace_bytes(st), 256), dtype=torch.uint8, device=be.device)
+        ws = _scratch(be.kfold_inner_coupled_workspace_bytes(st), be.device)
         if grouped:
             inner, inner_name = lambda a: be.kfold_inner_coupled_grouped(st, *grouped, a, tol, max_iter, ws), "kfold_inner_coupled_grouped_f64"
         else:
             inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
     elif tensor is not None:
-        ws = torch.empty(max(be.kfold_inner_tensor_workspace_bytes(st[0].A, *tensor, n), 256), dtype=torch.uint8, device=be.device)
+        ws = _scratch(be.kfold_inner_tensor_workspace_bytes(st[0].A, *tensor, n), be.device)
         mf, groups = grouped if grouped else (None, 1)
         Wk, Wl = tensor_out if tensor_out else (None, None)
         inner, inner_name = lambda a: be.kfold_inner_tensor(st[0], *tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), "kfold_inner_tensor_f64"
     else:
-        ws = torch.empty(max(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), 256), dtype=torch.uint8, device=be.device)
+        ws = _scratch(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), be.device)
         if grouped:
             inner, inner_name = lambda a: be.kfold_inner_grouped(st[0], *grouped, a, tol, max_iter, ws), "kfold_inner_grouped_f64"
         else:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Dump everything the three masked cross-validation entry points return on a fixed table of small inputs, to compare two builds
+"""Dump everything the five masked cross-validation entry points return on a fixed table of small inputs, to compare two builds
 of the library bit for bit: HipBackend.cv_masked (cmtfpls_cv_masked_f64), cv_masked_models (cmtfpls_cv_masked_models_f64,
-factors=True) and cv_masked_coupled (cmtfpls_cv_masked_coupled_f64, factors=True).  Every returned tensor (Ypred, n_iter, status,
+factors=True), cv_masked_coupled (cmtfpls_cv_masked_coupled_f64, factors=True) and, for X of order 4, cv_masked_tensor
+(cmtfpls_cv_masked_tensor_f64) and cv_masked_tensor_models (cmtfpls_cv_masked_tensor_models_f64, factors=True).  Every returned tensor (Ypred, n_iter, status,
 info, the factors) goes into one .npz under "<case>/<name>".  The library is the one CMTFPLS_LIB names (else the in-tree build).
 Not a test: it carries no expected values.  The table is the smallest that reaches every branch of csrc/masked_fold.hpp:
   trailing shapes  (1, 9) matrix block, partial-row contraction | (6, 5) one-wavefront rank-1 | (12, 10) workgroup rank-1, two
@@ -12,6 +13,7 @@ Not a test: it carries no expected values.  The table is the smallest that reach
   stops            tol 1e-8 within 100 iterations | max_iter = 2 (the cap ends the loop)
   statuses         1 a training row with nothing observed | 2 fewer than two training rows | 3 a negative count, a yrow out of range
   coupled          each trailing shape as one block | tensor + complete tensor | matrix + tensor + tensor
+  order 4          (3, 4, 2) | (6, 1, 5) | (2, 9, 3): every NaN pattern and stop, 4 folds and 4 models; one chunked call
 Usage: python tools/masked_forms_dump.py OUT.npz      then      python tools/masked_forms_dump.py --compare A.npz B.npz
 --compare: every array of A and B by name; float arrays as their 64-bit integer views (NaN payloads and signed zeros count);
 prints the number of arrays and cases, every difference, and exits 1 on any."""
@@ -21,6 +23,7 @@ import numpy as np
 SHAPES = [(1, 9), (6, 5), (12, 10), (20, 16), (4, 70)]
 PATTERNS = ("random", "one_row", "heldout_column")
 STOPS = {"tol": (1e-8, 100), "cap": (1e-8, 2)}
+TENSOR_SHAPES = [(3, 4, 2), (6, 1, 5), (2, 9, 3)]
 M = R = 3
 NM = 4
 
@@ -161,6 +164,27 @@ def main(out_path):
         keep(f"models/{case}", be.cv_masked_models(d(Xc), Y, d(cc, torch.int32), d(yc, torch.int32), A, B, R, 1e-8, 100, factors=True))
         keep(f"coupled/{case}", be.cv_masked_coupled([d(Xm), d(Xc)], two_dims, Y, d(cc, torch.int32), d(yc, torch.int32), R, 1e-8, 100,
                                                      factors=True))
+
+    # ---- X of order 4 (I x A x B1 x B2 as I x A B1 B2): 4 folds and 4 models per pattern and stop, then one chunked call
+    ids = np.arange(I) % 4
+    for ti, (A, B1, B2) in enumerate(TENSOR_SHAPES):
+        for pattern in PATTERNS:
+            seed = 2000 + 10 * ti + PATTERNS.index(pattern)
+            rng = np.random.default_rng(seed)
+            T = rng.standard_normal((I, R + 1))
+            Y = d(T @ rng.standard_normal((R + 1, M)) + 0.3 * rng.standard_normal((I, M)))
+            counts, yrow = models(rng, I)
+            for stop, (tol, max_iter) in STOPS.items():
+                X = d(block(np.random.default_rng(seed), I, (A, B1 * B2), T, pattern, ids == 0))
+                keep(f"tensor_folds/{A}x{B1}x{B2}/{pattern}/{stop}",
+                     be.cv_masked_tensor(X, Y, d(ids, torch.int32), 4, A, B1, B2, R, tol, max_iter))
+                X = d(block(np.random.default_rng(seed), I, (A, B1 * B2), T, pattern, counts[0] == 0))
+                keep(f"tensor_models/{A}x{B1}x{B2}/{pattern}/{stop}",
+                     be.cv_masked_tensor_models(X, Y, d(counts, torch.int32), d(yrow, torch.int32), A, B1, B2, R, tol, max_iter, factors=True))
+    per = int(be.lib.cmtfpls_cv_masked_tensor_model_workspace_bytes(I, A, B1, B2, M, R)) + R * I * M * 8
+    res = be.cv_masked_tensor_models(X, Y, d(counts, torch.int32), d(yrow, torch.int32), A, B1, B2, R, 1e-8, 100, factors=True, max_ws_bytes=per)
+    assert res["launches"] == NM >= 3
+    keep("tensor_models/chunked", res)
     torch.cuda.synchronize()
     np.savez(out_path, **out)
     status = np.concatenate([v.ravel() for k, v in out.items() if k.endswith("/status")])
