@@ -29,6 +29,9 @@ block with B = B1 B2 and wB = wK (x) wL), the entry leaves every model's wK and 
 such a block are [wA, wK, wL].  With
 EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
 (kfold.masked_models_coupled), every block's factors aligned by align_factors.
+
+The route (kfold._route), the body of a pass (kfold._device_pass over kfold._weighted_models with kfold_weighted_xcov as the read; it
+allocates the per-mode stacks Wk / Wl) and the report (kfold._passes_report, kfold._masked_run_report) are the shared ones of kfold.py.
 """
 from __future__ import annotations
 
@@ -37,10 +40,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_passes,
-                    _dims, _from_scores, _groups, _host, _names, _state, _stats_why, _tensor_dims, _to_dev, _training_data, _with_rank1,
-                    masked_coupled_report, masked_forms, masked_models, masked_models_coupled, masked_models_report, wants_masked,
-                    wants_masked_coupled)
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_pass,
+                    _device_passes, _dims, _from_scores, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
+                    _route, _tensor_dims, _to_dev, _training_data, _weighted_models, masked_coupled_report, masked_models,
+                    masked_models_coupled, masked_models_report)
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -133,45 +136,27 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
     adds its models' OOB predictions to oob_sum = [sums (R, I, M), counts (I,)] on the device.  tensor = (B1, B2): a tPLS's
     order-4 X (kfold._tensor_dims); its loadings are [wA, wK, wL].  tensor = [(B1, B2), ..]: a ctPLS with blocks of order 4 ((0, 0):
     another order); an order-4 block's loadings are [wA, wK, wL], read from its slice of the entry's Wk / Wl."""
-    eng = pls._get_engine()
-    be = eng.be
+    be = pls._get_engine().be
     R = pls.n_components
     dev = be.device
     I = counts.shape[1]
     Yd = _to_dev(_host(Y).reshape(I, -1).astype(np.float64), dev)
     M = Yd.shape[1]
     blocks = _device_blocks(pls, Xs, dev)
-    names = _names(Xs, coupled)
     counts_d = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int32)).to(dev)  # one upload of the counts
 
     def run(passes, e0, g):
-        n = max(g, 2)
-        C = counts_d[e0:e0 + g] if g > 1 else counts_d[e0:e0 + 1].expand(2, I).contiguous()
-        Cf = C.to(torch.float64)
+        n, C, Cf = _weighted_models(counts_d, e0, g)
         nu = (Cf @ Yd) / I                                                            # n x M: the resamples' means of Y
         Yc = Yd.unsqueeze(0) - nu.unsqueeze(1)                                        # n x I x M
         Yw = torch.cat([(Cf.unsqueeze(2) * Yc).permute(1, 0, 2).reshape(I, n * M), Cf.t()], dim=1).contiguous()   # Y''
         Yk = torch.where(C.unsqueeze(2) > 0, Yc, 0.0).contiguous()                    # rows with c = 0 are 0
-        built = []
-        for (X2, A, B), name in zip(blocks, names):                                   # one read of each block
-            S, mean = be.empty(n, M, A * B), be.empty(n, A * B)
-            stats = be.kfold_weighted_xcov(X2, A, B, Yw, n, M, S, mean)
-            if stats is None:
-                return _declined(f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_weighted_xcov")
-            if passes == 0:
-                why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
-                if why is not None:
-                    return _declined(why)
-            built.append((A, B, S, mean))
-        st, shared, own = _state(be, C, Yk, built, R, 1)
-        if isinstance(tensor, list):                                                  # coupled: the tensor blocks' n x R x B1_b (B2_b) slices
-            modes_kl = (be.zeros(n * R * sum(B1 for B1, B2 in tensor if B2 > 0)), be.zeros(n * R * sum(B2 for _, B2 in tensor if B2 > 0)))
-        else:
-            modes_kl = (be.zeros(n, R, tensor[0]), be.zeros(n, R, tensor[1])) if tensor is not None else None
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True, tensor=tensor,
-                          tensor_out=modes_kl)
-        if why is not None:
-            return _declined(why)
+        got = _device_pass(pls, Xs, blocks, coupled, "kfold_weighted_xcov",           # one read of each block
+                           [lambda X2, A, B, S, mean: be.kfold_weighted_xcov(X2, A, B, Yw, n, M, S, mean)],
+                           C, Yk, 1, passes == 0, tol, max_iter, tensor, mode_loadings=True, weighted=True)
+        if isinstance(got, str):
+            return _declined(got)
+        shared, own = got
         status = shared["status"][:g].cpu().numpy()
         n_iter = shared["n_iter"][:g].cpu().numpy()
         if not status.any():
@@ -185,9 +170,9 @@ def _device_resamples(pls, Xs, Y, counts: np.ndarray, tol: float, max_iter: int,
             Wa = [o["Wa"][:g].cpu().numpy() for o in own]
             Wb = [o["Wb"][:g].cpu().numpy() for o in own]
             if isinstance(tensor, list):                                              # block b's slice: n x R x B1_b (B2_b), or None
-                Wk, Wl = _mode_slices(modes_kl[0].cpu().numpy(), modes_kl[1].cpu().numpy(), tensor, n, R)
+                Wk, Wl = _mode_slices(shared["Wk"].cpu().numpy(), shared["Wl"].cpu().numpy(), tensor, n, R)
             elif tensor is not None:
-                Wk, Wl = (w[:g].cpu().numpy() for w in modes_kl)
+                Wk, Wl = (shared[w][:g].cpu().numpy() for w in ("Wk", "Wl"))
             for j in range(g):
                 if isinstance(tensor, list):
                     modes = [[wa[j].T, wk[j].T, wl[j].T] if X.ndim == 4 else [wb[j].T] if X.ndim == 2 else [wa[j].T, wb[j].T]
@@ -253,21 +238,17 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
     M = Yh.shape[1]
     ref, _, _ = model_factors(pls)
 
-    why: Optional[str] = None
     G = 0
     masked = None
     ctensor = None                                                # (B1, B2) per block of a ctPLS under tensor_resamples_coupled
-    if not device_folds:
-        why = "device folds switched off"
-    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
-        masked, mwhy = masked_models(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
+    route, detail = _route(pls, X, device_folds)
+    why: Optional[str] = detail if route == OFF else None
+    if route in (MASKED, MASKED_COUPLED):       # EngineOptions.masked_folds, masked_tensor_folds (8s), masked_folds_coupled (8j)
+        masked, mwhy = (masked_models if route == MASKED else masked_models_coupled)(pls, X, Y, counts.astype(np.int32), None, tol,
+                                                                                      max_iter, factors=True)
         if masked is None:
-            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {mwhy}"
-    elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
-        masked, mwhy = masked_models_coupled(pls, X, Y, counts.astype(np.int32), None, tol, max_iter, factors=True)
-        if masked is None:
-            why = f"the masked form ({COUPLED_FORM}) declined: {mwhy}"
-    else:
+            why = _masked_declined(detail, mwhy)
+    elif route == PASSES:
         G = min(_groups(X, 1, min(NB, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for X in Xs)   # the LDS of every block's score pass
         if coupled and pls._get_engine().opt.tensor_resamples_coupled and _tensor_dims(Xs, coupled=True) is not None:
             # EngineOptions.tensor_resamples_coupled: the checks of the coupled passes on the I x A x B1 B2 views, then
@@ -335,23 +316,11 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
 
     if masked is not None:
         rep = (masked_coupled_report if coupled else masked_models_report)(masked, refitted, "resamples")
-        pls.bootstrap_report_ = dict(rep, resamples=int(NB), passes=rep["launches"], models_per_pass=-(-NB // rep["launches"]),
-                                     n_iter=n_iters)
-    elif passes:
-        from .kfold import _form_entries
-
-        entries = _form_entries("cmtfpls_kfold_weighted_xcov_*", coupled, "cmtfpls_kfold_epilogue_weighted_f64")
-        form = f"{G} resamples per pass from shared reads of {'every block' if coupled else 'X'} {entries}"
-        if why is not None:
-            form += "; failed passes refitted per resample on the regular engine"
-        x_reads = [2 * R * passes] * len(Xs) if coupled else 2 * R * passes
+        pls.bootstrap_report_ = _masked_run_report(rep, "resamples", NB, "models_per_pass", n_iters)
     else:
-        form, x_reads = "one refit per resample on the regular engine", None
-    if masked is None:
-        rep = {"form": form, "resamples": int(NB), "passes": int(passes), "models_per_pass": int(G) if passes else None,
-               "x_reads": x_reads, "n_iter": n_iters}
-        if why is not None:
-            rep["why"] = why
-        pls.bootstrap_report_ = _with_rank1(rep, tensor, passes)
+        pls.bootstrap_report_ = _passes_report(f"{G} resamples per pass", "cmtfpls_kfold_weighted_xcov_*", "cmtfpls_kfold_epilogue_weighted_f64",
+                                               Xs, coupled, passes, 2 * R * passes, why, "resample",
+                                               "one refit per resample on the regular engine", {"resamples": int(NB)},
+                                               ("models_per_pass", G), n_iters, tensor)
     return {"resamples": idx, **stacks, "se": {k: v[0] for k, v in spread.items()}, "ci": {k: v[1] for k, v in spread.items()},
             "oob_q2y": oob_q2y, "oob_rows": int(rows.sum())}

@@ -23,9 +23,20 @@ A x B1 x B2 cross-covariance inside its workgroup).  The bootstrap's weighted mo
 
 Anything outside the device form refits once per fold on the regular engine (X[train] -> fit -> transform of X[test]).
 
-The permutation test (permutation.py), repeated K-fold (repeated.py) and the bootstrap (bootstrap.py) run the same state with
-more models per pass: _state allocates it (a view per block), _components makes every launch of a pass with the inner and
-epilogue entries of the form, and _device_passes runs the passes and refits whatever they leave.
+The permutation test (permutation.py), repeated K-fold (repeated.py), nested K-fold (nested.py) and the bootstrap (bootstrap.py)
+run the same state with more models per pass, and share every step of a driver with kfold_run, each defined here once:
+  _route            which way the fitted data goes: device folds off, the masked tPLS or coupled form, the device passes, refits only
+                    (a driver's own precedence and option gate are its arguments); _masked_declined words a masked decline
+  _device_pass      one pass: every block's S and mean built by the driver's read (allocation, the "shape outside" wording, the
+                    statistics check of the first pass), then _state (a view per block) and _components, which makes every launch
+                    with the inner and epilogue entries of the form, chosen from _INNER_ENTRIES and _EPILOGUE_ENTRIES; a driver's
+                    run() keeps the Y side of its models and what it reads from the state; _weighted_models is the count side
+                    of the two weighted drivers
+  _device_passes    runs the passes and refits whatever they leave
+  _passes_report    the report of a driver of passes (form from _form_entries, x_reads, passes, its own keys, why, rank1), and
+                    _masked_run_report a masked run's report as such a driver's; _models_report is the skeleton and status table of
+                    masked_models_report and masked_coupled_report
+  _masked_setup     what the three masked routines check and upload before they look at X
 
 Missing values in X (opt-in): a tPLS with EngineOptions.masked_folds refits every fold in a workgroup of cmtfpls_cv_masked_f64
 (masked_predictions) or, count-weighted, of cmtfpls_cv_masked_models_f64 (masked_models); a ctPLS with
@@ -388,6 +399,32 @@ def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: i
     return (_lib.KfoldState * len(views))(*views), shared, own
 
 
+# The entries of _components, one row each: the HipBackend method (cmtfpls_<method>_f64 is the entry it binds and the name a decline
+# gives), and how its arguments are laid out.  Inner entries, by (coupled, form): the method that sizes the workspace and its
+# arguments (st, n, tensor), the arguments before (a, tol, max_iter) from (st, grouped, tensor), and whether (model_fold, groups,
+# Wk, Wl) follow the workspace (the tensor entries serve the plain and the grouped layout: model_fold None, groups 1 is plain).
+_INNER_ENTRIES = {
+    (False, "plain"): ("kfold_inner", "kfold_inner_workspace_bytes", lambda st, n, t: (st[0].A, st[0].B, n), lambda st, g, t: (st[0],), False),
+    (False, "grouped"): ("kfold_inner_grouped", "kfold_inner_workspace_bytes", lambda st, n, t: (st[0].A, st[0].B, n),
+                         lambda st, g, t: (st[0], *g), False),
+    (False, "tensor"): ("kfold_inner_tensor", "kfold_inner_tensor_workspace_bytes", lambda st, n, t: (st[0].A, *t, n),
+                        lambda st, g, t: (st[0], *t), True),
+    (True, "plain"): ("kfold_inner_coupled", "kfold_inner_coupled_workspace_bytes", lambda st, n, t: (st,), lambda st, g, t: (st,), False),
+    (True, "grouped"): ("kfold_inner_coupled_grouped", "kfold_inner_coupled_workspace_bytes", lambda st, n, t: (st,),
+                        lambda st, g, t: (st, *g), False),
+    (True, "tensor"): ("kfold_inner_coupled_tensor", "kfold_inner_coupled_tensor_workspace_bytes", lambda st, n, t: (st, t),
+                       lambda st, g, t: (st, t), True),
+}
+# Epilogue entries, by layout (the first of grouped, splits, weighted that is asked for, else plain): the arguments between the
+# state view and (stage, a, src) from (grouped, splits).
+_EPILOGUE_ENTRIES = {
+    "grouped": ("kfold_epilogue_grouped", lambda g, s: tuple(g)),
+    "splits": ("kfold_epilogue_splits", lambda g, s: (s,)),
+    "weighted": ("kfold_epilogue_weighted", lambda g, s: ()),
+    "plain": ("kfold_epilogue", lambda g, s: ()),
+}
+
+
 def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, coupled: bool, grouped=None, splits: int = 0,
                 weighted: bool = False, tensor=None, tensor_out=None):
     """Every component of the n = st[0].K models of a state: stage 0, then per component the inner loop, one MTTKRP per block (a
@@ -402,45 +439,28 @@ def _components(be, X2s, st, shared, own, R: int, tol: float, max_iter: int, cou
     kfold_inner_coupled_tensor leaves them, the tensor blocks' n x R x B1_b (B2_b) slices one after another in block order.  None, or
     why a kernel declined."""
     nb, n, I = len(st), st[0].K, st[0].I
-    if coupled and tensor is not None:
-        ws = _scratch(be.kfold_inner_coupled_tensor_workspace_bytes(st, tensor), be.device)
-        mf, groups = grouped if grouped else (None, 1)
-        Wk, Wl = tensor_out if tensor_out else (None, None)
-        inner, inner_name = lambda a: be.kfold_inner_coupled_tensor(st, tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), \
-            "kfold_inner_coupled_tensor_f64"
-    elif coupled:
-        ws = _scratch(be.kfold_inner_coupled_workspace_bytes(st), be.device)
-        if grouped:
-            inner, inner_name = lambda a: be.kfold_inner_coupled_grouped(st, *grouped, a, tol, max_iter, ws), "kfold_inner_coupled_grouped_f64"
-        else:
-            inner, inner_name = lambda a: be.kfold_inner_coupled(st, a, tol, max_iter, ws), "kfold_inner_coupled_f64"
-    elif tensor is not None:
-        ws = _scratch(be.kfold_inner_tensor_workspace_bytes(st[0].A, *tensor, n), be.device)
-        mf, groups = grouped if grouped else (None, 1)
-        Wk, Wl = tensor_out if tensor_out else (None, None)
-        inner, inner_name = lambda a: be.kfold_inner_tensor(st[0], *tensor, a, tol, max_iter, ws, mf, groups, Wk, Wl), "kfold_inner_tensor_f64"
-    else:
-        ws = _scratch(be.kfold_inner_workspace_bytes(st[0].A, st[0].B, n), be.device)
-        if grouped:
-            inner, inner_name = lambda a: be.kfold_inner_grouped(st[0], *grouped, a, tol, max_iter, ws), "kfold_inner_grouped_f64"
-        else:
-            inner, inner_name = lambda a: be.kfold_inner(st[0], a, tol, max_iter, ws), "kfold_inner_f64"
-    if grouped:
-        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_grouped(st[b], *grouped, *args), "kfold_epilogue_grouped_f64"
-    elif splits:
-        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_splits(st[b], splits, *args), "kfold_epilogue_splits_f64"
-    elif weighted:
-        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue_weighted(st[b], *args), "kfold_epilogue_weighted_f64"
-    else:
-        epilogue, epilogue_name = lambda b, *args: be.kfold_epilogue(st[b], *args), "kfold_epilogue_f64"
+    inner_method, ws_bytes, ws_args, head, layout = _INNER_ENTRIES[(bool(coupled), "tensor" if tensor is not None else
+                                                                    "grouped" if grouped else "plain")]
+    ws = _scratch(getattr(be, ws_bytes)(*ws_args(st, n, tensor)), be.device)
+    head = head(st, grouped, tensor)
+    tail = (ws, *(grouped if grouped else (None, 1)), *(tensor_out if tensor_out else (None, None))) if layout else (ws,)
+    epilogue_method, extra = _EPILOGUE_ENTRIES["grouped" if grouped else "splits" if splits else "weighted" if weighted else "plain"]
+    extra = extra(grouped, splits)
+
+    def inner(a):
+        return getattr(be, inner_method)(*head, a, tol, max_iter, *tail)
+
+    def epilogue(b, *args):
+        return getattr(be, epilogue_method)(st[b], *extra, *args)
+
     scs = be.empty(nb, I, n)
     sc = be.empty(I, n) if coupled else scs[0]
     rs = be.empty(n * max(v.A * v.B for v in st))
     if epilogue(0, 0, 0, None) is None:
-        return f"shape outside cmtfpls_{epilogue_name}"
+        return f"shape outside cmtfpls_{epilogue_method}_f64"
     for a in range(R):
         if inner(a) is None:
-            return f"shape outside cmtfpls_{inner_name}"
+            return f"shape outside cmtfpls_{inner_method}_f64"
         for b in range(nb):                                                         # X_b,0 [w_1 .. w_n]: one read each
             if be.mttkrp(X2s[b], st[b].A, st[b].B, own[b]["WA"], own[b]["WB"], scs[b]) is None:
                 return f"{f'block {b}: ' if coupled else ''}the models' loadings outside cmtfpls_mttkrp_*"
@@ -465,10 +485,70 @@ def _held_out_predictions(Tout, coef, Qh, nu, ids, K, R, M) -> np.ndarray:
     return pred
 
 
-def _form_entries(build: str, coupled: bool, epilogue: str) -> str:
-    inner = "cmtfpls_kfold_inner_coupled_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64" if coupled else \
-        "cmtfpls_kfold_inner_f64, cmtfpls_mttkrp_*"
+def _form_entries(build: str, coupled: bool, epilogue: str, grouped: bool = False) -> str:
+    """The entries of a device pass as a report's form lists them (grouped: the inner entries of the permutation test's layout)."""
+    g = "_grouped" if grouped else ""
+    inner = f"cmtfpls_kfold_inner_coupled{g}_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64" if coupled else \
+        f"cmtfpls_kfold_inner{g}_f64, cmtfpls_mttkrp_*"
     return f"({build}, {inner}, {epilogue}, cmtfpls_xcov_*)"
+
+
+def _x_reads(reads: int, Xs, coupled: bool):
+    """`x_reads` of a report: the reads of X, a ctPLS one entry per block."""
+    return [reads] * len(Xs) if coupled else reads
+
+
+def _weighted_models(counts_d: torch.Tensor, e0: int, g: int):
+    """(n, C, Cf) of a pass of the weighted drivers (bootstrap.py, nested.py) over models e0 .. e0 + g - 1 of the uploaded counts:
+    their n x I counts as int32 and float64.  n = max(g, 2): a one-model pass runs two copies of its model (the K-fold kernels take
+    at least two models); the caller reads the first g."""
+    C = counts_d[e0:e0 + g] if g > 1 else counts_d[e0:e0 + 1].expand(2, counts_d.shape[1]).contiguous()
+    return max(g, 2), C, C.to(torch.float64)
+
+
+def _device_pass(pls, Xs, blocks, coupled: bool, builder: str, builds, fold_of: torch.Tensor, Yk: torch.Tensor, slots: int, first: bool,
+                 tol: float, max_iter: int, tensor, Ss=None, means=None, mode_loadings: bool = False, **layout):
+    """One device pass of the n = Yk.shape[0] models of a driver: every block's S and mean built, the state (_state, Tout with
+    `slots` slots) and every component (_components with the layout arguments grouped / splits / weighted): (shared, own), or why
+    the device form declined.  blocks: _device_blocks(pls, Xs); tensor: _tensor_dims of the blocks the inner entry is to take.
+    builds: the reads that build S and mean, each a callable (X2, A, B, S, mean) -> the column statistics or None, made on every
+    block in turn; one read builds all models (cmtfpls_<builder>), repeated.py passes one per split, each into its split's slice
+    (`builds` may be a generator: what it does before a yield happens before that read).  S (n x M x P) and mean (n x P) of block b
+    are Ss[b] / means[b] where the driver passes them in (the permutation test's per-fold means), else allocated before the
+    block's first read.  fold_of and Yk as host arrays are uploaded once the builds have passed.  The statistics are checked
+    (_stats_why) after the first read of the first pass (`first`) only.
+    mode_loadings: the tensor inner entry leaves the models' wK and wL in shared["Wk"], shared["Wl"] (the bootstrap's per-mode
+    stacks): n x R x B1 and n x R x B2 of a tPLS, of a ctPLS the tensor blocks' slices one after another."""
+    eng = pls._get_engine()
+    be = eng.be
+    n, I, M = Yk.shape
+    R = pls.n_components
+    built = []
+    for step, build in enumerate(builds):
+        for b, ((X2, A, B), name) in enumerate(zip(blocks, _names(Xs, coupled))):
+            if step == 0:
+                S = Ss[b] if Ss is not None else be.empty(n, M, A * B)
+                built.append((A, B, S, means[b] if means is not None else be.empty(n, A * B)))
+            stats = build(X2, A, B, *built[b][2:])
+            if stats is None:
+                return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_{builder}"
+            if first and step == 0:
+                why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
+                if why is not None:
+                    return why
+    if isinstance(Yk, np.ndarray):                                               # kfold_run's: uploaded once the builds have passed
+        fold_of, Yk = _to_dev(fold_of, be.device, torch.int32), _to_dev(Yk, be.device)
+    st, shared, own = _state(be, fold_of, Yk, built, R, slots)
+    tensor_out = None
+    if mode_loadings and isinstance(tensor, list):
+        tensor_out = (be.zeros(n * R * sum(B1 for B1, B2 in tensor if B2 > 0)), be.zeros(n * R * sum(B2 for _, B2 in tensor if B2 > 0)))
+    elif mode_loadings and tensor is not None:
+        tensor_out = (be.zeros(n, R, tensor[0]), be.zeros(n, R, tensor[1]))
+    if tensor_out is not None:
+        shared["Wk"], shared["Wl"] = tensor_out
+    why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, tensor=tensor, tensor_out=tensor_out,
+                      **layout)
+    return why if why is not None else (shared, own)
 
 
 def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, coupled: bool):
@@ -485,22 +565,13 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
         order, off, ybar, nu, Yk = _fold_y(Yh, ids, K)
         ydev, order_d, off_d, nudev = _to_dev(Yh - ybar, dev), _to_dev(order, dev, torch.int32), _to_dev(off, dev, torch.int32), \
             _to_dev(nu - ybar, dev)
-        X2s, blocks = [], []
-        for (X2, A, B), name in zip(_device_blocks(pls, Xs, dev), _names(Xs, coupled)):
-            S, mean = be.empty(K, M, A * B), be.empty(K, A * B)
-            stats = be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S, mean)
-            if stats is None:
-                return None, f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_xcov"
-            why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
-            if why is not None:
-                return None, why
-            X2s.append(X2)
-            blocks.append((A, B, S, mean))
-        st, shared, own = _state(be, _to_dev(ids, dev, torch.int32), _to_dev(Yk, dev), blocks, R, 1)
         tensor = _tensor_dims(Xs, coupled)
-        why = _components(be, X2s, st, shared, own, R, tol, max_iter, coupled, tensor=tensor)
-        if why is not None:
-            return None, why
+        got = _device_pass(pls, Xs, _device_blocks(pls, Xs, dev), coupled, "kfold_xcov",
+                           [lambda X2, A, B, S, mean: be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S, mean)],
+                           ids, Yk, 1, True, tol, max_iter, tensor)
+        if isinstance(got, str):
+            return None, got
+        shared, _ = got
         status = shared["status"].cpu().numpy()
         if status.any():
             return None, f"non-finite loadings or coefficients in folds {np.flatnonzero(status).tolist()} of the device form"
@@ -512,7 +583,7 @@ def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter
     source = "every block" if coupled else "X"
     report = {"form": f"K folds from shared reads of {source} "
                       + _form_entries("cmtfpls_kfold_xcov_*", coupled, "cmtfpls_kfold_epilogue_f64"),
-              "folds": int(K), "x_reads": [2 * R] * len(Xs) if coupled else 2 * R, "n_iter": n_iter.tolist()}
+              "folds": int(K), "x_reads": _x_reads(2 * R, Xs, coupled), "n_iter": n_iter.tolist()}
     return pred, _with_rank1(report, tensor)
 
 
@@ -572,33 +643,52 @@ def has_missing(X) -> bool:
     return bool(np.isnan(np.asarray(X)).any())
 
 
+def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
+    """What masked_predictions, masked_models and masked_models_coupled check before they look at X, in this order: the backend's
+    kernel (`what` names it in the decline), a sharded model, the order of every block (tensor: _tensor_dims of a tPLS's order-4 X
+    under EngineOptions.masked_tensor_folds, which the order-4 entries take), NaN in Y.  (why, None), or (None, (eng, be, M,
+    upload)): upload(a, I) is the original data in float64 on the device as I x -1."""
+    eng = pls._get_engine()
+    be = eng.be
+    if not hasattr(be, kernel):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no {what} kernel", None
+    if pls._comm is not None:
+        return "sharded model (comm)", None
+    for X, name in zip(Xs, names):
+        if X.ndim not in (2, 3) and tensor is None:
+            return f"{name} of order {X.ndim} (the masked form takes order 2 and 3)", None
+    if has_missing(Y):
+        return "missing values in Y", None
+    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
+    return None, (eng, be, M, lambda a, I: _f64(a, be.device).contiguous().view(I, -1))
+
+
+def _masked_outside(form: str, A: int, B: int, M: int, R: int) -> str:
+    return (f"shape outside {form} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB of LDS): "
+            f"min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+
+
 def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
     """Refits of a tPLS on X with missing values, a workgroup per fold in one launch (cmtfpls_cv_masked_f64), in float64
     on the original data whatever the model's storage type: (pred (R, I, M), report) or (None, why).  Leave-one-out: ids =
     arange(I), K = I.  X of order 4 under EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_f64, the report
     with `rank1` and `launches`."""
-    eng = pls._get_engine()
-    be = eng.be
     R = pls.n_components
     I = ids.shape[0]
-    tensor = _tensor_dims([X]) if eng.opt.masked_tensor_folds else None
-    if not hasattr(be, "cv_masked_tensor" if tensor else "cv_masked"):
-        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked {'order-4 ' if tensor else ''}fold kernel"
-    if pls._comm is not None:
-        return None, "sharded model (comm)"
-    if X.ndim not in (2, 3) and tensor is None:
-        return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
-    if has_missing(Y):
-        return None, "missing values in Y"
+    tensor = _tensor_dims([X]) if pls._get_engine().opt.masked_tensor_folds else None
+    why, ctx = _masked_setup(pls, [X], ["X"], Y, "cv_masked_tensor" if tensor else "cv_masked",
+                             f"masked {'order-4 ' if tensor else ''}fold", tensor)
+    if why is not None:
+        return None, why
+    eng, be, M, upload = ctx
     train = I - np.bincount(ids, minlength=K)
     if train.min() < 2:
         return None, f"fold {int(np.argmin(train))} leaves {int(train.min())} training rows (the masked form needs 2)"
     A, B = _dims(X)
-    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
     with eng.device_ctx():
-        data = (_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M), _to_dev(ids, dev, torch.int32), K)
+        data = (upload(X, I), upload(Y, I), _to_dev(ids, dev, torch.int32), K)
         if tensor:
             out = be.cv_masked_tensor(*data, A, *tensor, R, tol, max_iter)
             if out is None:
@@ -607,8 +697,7 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
         else:
             out = be.cv_masked(*data, A, B, R, tol, max_iter)
             if out is None:
-                return None, (f"shape outside {MASKED_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
-                              f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+                return None, _masked_outside(MASKED_FORM, A, B, M, R)
         pred, n_iter, status, info = (t.cpu().numpy() for t in out[:4])
     if status.any():
         empty, small = np.flatnonzero(status == 1).tolist(), np.flatnonzero(status == 2).tolist()
@@ -635,25 +724,19 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
     coef, Q) -- or (None, why) with masked_predictions' declines.  Models with a status are the caller's to refit.  X of order 4
     under EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_models_f64, `factors` then Wa, Wk, Wl in place
     of Wa, Wb, and out["tensor"] = (B1, B2)."""
-    eng = pls._get_engine()
-    be = eng.be
     R = pls.n_components
     I = counts.shape[1]
-    tensor = _tensor_dims([X]) if eng.opt.masked_tensor_folds else None
-    if not hasattr(be, "cv_masked_tensor_models" if tensor else "cv_masked_models"):
-        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no masked {'order-4 ' if tensor else ''}model kernel"
-    if pls._comm is not None:
-        return None, "sharded model (comm)"
-    if X.ndim not in (2, 3) and tensor is None:
-        return None, f"X of order {X.ndim} (the masked form takes order 2 and 3)"
-    if has_missing(Y):
-        return None, "missing values in Y"
+    tensor = _tensor_dims([X]) if pls._get_engine().opt.masked_tensor_folds else None
+    why, ctx = _masked_setup(pls, [X], ["X"], Y, "cv_masked_tensor_models" if tensor else "cv_masked_models",
+                             f"masked {'order-4 ' if tensor else ''}model", tensor)
+    if why is not None:
+        return None, why
+    eng, be, M, upload = ctx
     A, B = _dims(X)
-    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
     with eng.device_ctx():
-        data = (_f64(X, dev).contiguous().view(I, -1), _f64(Y, dev).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+        data = (upload(X, I), upload(Y, I), _to_dev(counts, dev, torch.int32),
                 None if yrow is None else _to_dev(yrow, dev, torch.int32))
         if tensor:
             out = be.cv_masked_tensor_models(*data, A, *tensor, R, tol, max_iter, factors, max_ws_bytes)
@@ -663,30 +746,39 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
         else:
             out = be.cv_masked_models(*data, A, B, R, tol, max_iter, factors, max_ws_bytes)
             if out is None:
-                return None, (f"shape outside {MODELS_FORM} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB "
-                              f"of LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+                return None, _masked_outside(MODELS_FORM, A, B, M, R)
         return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}, None
+
+
+_STATUS_NAMES = {2: "fewer than 2 training rows", 3: "bad counts or Y rows"}        # status 1: named by the form (no observed entry)
+
+
+def _models_report(out: dict, refitted, what: str, form: str, masked: dict, no_entry: str, rank1: bool = False) -> dict:
+    """The report entries that masked_models_report and masked_coupled_report share: form (with the refit note), models, launches,
+    the form's own counts `masked`, x_reads, and for the models in `refitted` the reason by status in `why` (`no_entry` names
+    status 1)."""
+    status = out["status"]
+    rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
+           "models": int(len(status)), "launches": int(out["launches"]), **masked, "x_reads": None}
+    if rank1:
+        rep["rank1"] = TENSOR_RANK1
+    if len(refitted):
+        names = {1: no_entry, **_STATUS_NAMES}
+        rep["refitted"] = [int(m) for m in refitted]
+        rep["why"] = "; ".join(f"{names[s]} in {what} {np.flatnonzero(status == s).tolist()}" for s in (1, 2, 3) if (status == s).any())
+    return rep
 
 
 def masked_models_report(out: dict, refitted, what: str) -> dict:
     """The report entries of a masked-models run (form, models, launches, masked_models, masked_batches, x_reads); `refitted`
     the models whose status made them refit alone on the regular engine."""
-    status = out["status"]
-    ok = status == 0
-    form = f"a workgroup per model on X with missing values, {len(status)} models in {out['launches']} launch(es) ({MODELS_FORM})"
+    ok = out["status"] == 0
+    form = f"a workgroup per model on X with missing values, {len(ok)} models in {out['launches']} launch(es) ({MODELS_FORM})"
     if "tensor" in out:                                                          # order-4 X (masked_tensor_folds, DESIGN 8s)
         form = form.replace("on X", "on order-4 X").replace(MODELS_FORM, MODELS_TENSOR_FORM)
-    rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
-           "models": int(len(status)), "launches": int(out["launches"]), "masked_models": int(out["info"][ok, 0].sum()),
-           "masked_batches": int(out["info"][ok, 1].sum()), "x_reads": None}
-    if "tensor" in out:
-        rep["rank1"] = TENSOR_RANK1
-    if len(refitted):
-        names = {1: "a training row without an observed entry of X", 2: "fewer than 2 training rows", 3: "bad counts or Y rows"}
-        rep["refitted"] = [int(m) for m in refitted]
-        rep["why"] = "; ".join(f"{names[s]} in {what} {np.flatnonzero(status == s).tolist()}"
-                                     for s in (1, 2, 3) if (status == s).any())
-    return rep
+    return _models_report(out, refitted, what, form, {"masked_models": int(out["info"][ok, 0].sum()),
+                                                      "masked_batches": int(out["info"][ok, 1].sum())},
+                          "a training row without an observed entry of X", rank1="tensor" in out)
 
 
 def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[np.ndarray], tol: float, max_iter: int,
@@ -751,29 +843,20 @@ def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndar
     count 0.  Returns (out, None) -- out the backend's dict on the host (Ypred (n, R, I, M), n_iter, status, info, launches, with
     `factors` Wa, Wb (per block), coef, Q) -- or (None, why) with masked_models' declines.  Models with a status are the caller's to
     refit."""
-    eng = pls._get_engine()
-    be = eng.be
     R = pls.n_components
     I = counts.shape[1]
-    if not hasattr(be, "cv_masked_coupled"):
-        return None, f"the {getattr(be, 'name', type(be).__name__)} backend has no coupled masked model kernel"
-    if pls._comm is not None:
-        return None, "sharded model (comm)"
-    for X, name in zip(Xs, _names(Xs, True)):
-        if X.ndim not in (2, 3):
-            return None, f"{name} of order {X.ndim} (the masked form takes order 2 and 3)"
-    if has_missing(Y):
-        return None, "missing values in Y"
+    why, ctx = _masked_setup(pls, Xs, _names(Xs, True), Y, "cv_masked_coupled", "coupled masked model")
+    if why is not None:
+        return None, why
+    eng, be, M, upload = ctx
     dims = [_dims(X) for X in Xs]
-    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     dev = be.device
 
     with eng.device_ctx():
         out = None
         if len(Xs) <= MAX_BLOCKS:                                                # (the entry declines more blocks itself)
-            out = be.cv_masked_coupled([_f64(X, dev).contiguous().view(I, -1) for X in Xs],
-                                       [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
-                                       _f64(Y, dev).contiguous().view(I, M), _to_dev(counts, dev, torch.int32),
+            out = be.cv_masked_coupled([upload(X, I) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
+                                       upload(Y, I), _to_dev(counts, dev, torch.int32),
                                        None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol, max_iter, factors, max_ws_bytes)
         if out is None:
             return None, (f"shape outside {COUPLED_FORM} (it takes at most {MAX_BLOCKS} blocks, min(J, K) <= 64 in every block, "
@@ -793,20 +876,14 @@ def masked_coupled_report(out: dict, refitted, what: str) -> dict:
     """The report entries of a coupled masked-models run: form, models, launches, masked_blocks / masked_batches (per block: the
     models whose training rows / held-out batch took the masked arithmetic in that block), x_reads; `refitted` (always present)
     the models whose status made them refit alone on the regular engine, with the reason in `why`."""
-    status = out["status"]
-    ok = status == 0
+    ok = out["status"] == 0
     nb = int(out["blocks"])
-    form = (f"a workgroup per model on {nb} coupled blocks with missing values, {len(status)} models in {out['launches']} "
+    form = (f"a workgroup per model on {nb} coupled blocks with missing values, {len(ok)} models in {out['launches']} "
             f"launch(es) ({COUPLED_FORM})")
-    rep = {"form": form + ("; models with a status refitted alone on the regular engine" if len(refitted) else ""),
-           "models": int(len(status)), "launches": int(out["launches"]), "masked_blocks": _block_bits(out["info"][ok, 0], nb),
-           "masked_batches": _block_bits(out["info"][ok, 1], nb), "x_reads": None, "refitted": [int(m) for m in refitted]}
-    if len(refitted):
-        names = {1: "a training row without an observed entry in some block", 2: "fewer than 2 training rows",
-                 3: "bad counts or Y rows"}
-        rep["why"] = "; ".join(f"{names[s]} in {what} {np.flatnonzero(status == s).tolist()}"
-                                     for s in (1, 2, 3) if (status == s).any())
-    return rep
+    rep = _models_report(out, refitted, what, form, {"masked_blocks": _block_bits(out["info"][ok, 0], nb),
+                                                     "masked_batches": _block_bits(out["info"][ok, 1], nb)},
+                         "a training row without an observed entry in some block")
+    return dict(rep, refitted=[int(m) for m in refitted])                        # behaviour: this form lists `refitted` even when empty
 
 
 def masked_predictions_coupled(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
@@ -832,6 +909,62 @@ def masked_predictions_coupled(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, 
     return pred, dict(masked_coupled_report(out, refitted, "folds"), folds=int(K), n_iter=n_iter)
 
 
+# ---- the route of a resampling driver (kfold_run, permutation.py, repeated.py, nested.py, bootstrap.py) -------------------------------
+OFF, MASKED, MASKED_COUPLED, PASSES, REFIT = "off", "masked", "masked coupled", "passes", "refit"
+
+
+def _masked_declined(entry: str, why: str) -> str:
+    """The `why` of a run whose masked form (`entry`, the cmtfpls_cv_masked_* it would have taken) declined."""
+    return f"the masked form ({entry}) declined: {why}"
+
+
+def _route(pls, X, device_folds: bool, models: bool = True, masked: bool = True, coupled_first: bool = False, coupled_gate=None):
+    """Which way a driver takes the fitted data X: (route, detail).  OFF (device_folds is False) and REFIT (no device form for this
+    model): every model refits, detail is the report's `why`.  MASKED (kfold.wants_masked) and MASKED_COUPLED
+    (wants_masked_coupled): the workgroup-per-model refits, detail names their entry for _masked_declined (`models`: the
+    count-weighted entry, else the fold entry).  PASSES: the driver's device passes, which it still checks with _decline_blocks;
+    detail is None.  masked=False: a driver without a masked form (nested.py).  coupled_gate = (on, why): the driver's passes take
+    a ctPLS only when `on` (an EngineOptions switch), else it is REFIT with `why`."""
+    if not device_folds:
+        return OFF, "device folds switched off"
+    asks = ((MASKED, wants_masked, lambda: masked_forms(pls, X)[int(models)]), (MASKED_COUPLED, wants_masked_coupled, lambda: COUPLED_FORM))
+    # behaviour: permutation_test asks the coupled masked form first, kfold_run, repeated_kfold and bootstrap the tPLS one (at most one holds)
+    for route, wants, entry in (asks[::-1] if coupled_first else asks) if masked else ():
+        if wants(pls, X):
+            return route, entry()
+    # (permutation_test had this gate between its two masked tests: the same, a ctPLS is a list, which wants_masked turns away unread)
+    if coupled_gate is not None and isinstance(X, list) and not coupled_gate[0]:
+        return REFIT, coupled_gate[1]
+    return PASSES, None
+
+
+def _passes_report(lead: str, build: str, epilogue: str, Xs, coupled: bool, passes: int, reads: int, why: Optional[str], failed,
+                   refit_form: str, counts: dict, per_pass, n_iter, tensor, grouped: bool = False, scored: str = "", more=None) -> dict:
+    """The report of a driver of _device_passes.  With passes the form is "<lead> from shared reads of X | every block (<the
+    entries: _form_entries(build, coupled, epilogue, grouped)>)<scored>", and with a why and `failed` (what a failed pass refits:
+    "fold", "model", ..) it says that failed passes refitted; without, refit_form.  Then the driver's own `counts`, passes,
+    per_pass = (key, value: None without passes), x_reads (`reads` per block, None without passes), n_iter, `more`, why, and
+    _with_rank1 for the blocks `tensor` the inner entry took."""
+    if passes:
+        form = f"{lead} from shared reads of {'every block' if coupled else 'X'} {_form_entries(build, coupled, epilogue, grouped)}{scored}"
+        if why is not None and failed:
+            form += f"; failed passes refitted per {failed} on the regular engine"
+    else:
+        form = refit_form
+    rep = {"form": form, **counts, "passes": int(passes), per_pass[0]: int(per_pass[1]) if passes else None,
+           "x_reads": _x_reads(reads, Xs, coupled) if passes else None, "n_iter": n_iter, **(more or {})}
+    if why is not None:
+        rep["why"] = why
+    return _with_rank1(rep, tensor, passes)
+
+
+def _masked_run_report(masked: dict, count: str, N: int, per_pass: str, n_iter, **more) -> dict:
+    """A masked run's report (masked_models_report / masked_coupled_report) as the report of a driver of N entries: its launches
+    are the passes, `per_pass` the entries (for "models_per_pass": the models) of one."""
+    per = masked["models"] if per_pass == "models_per_pass" else N
+    return dict(masked, **{count: int(N)}, passes=masked["launches"], **{per_pass: -(-per // masked["launches"])}, n_iter=n_iter, **more)
+
+
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
     """pred (R, *Y.shape): pred[r - 1, i] = prediction for sample i by the model fitted without sample i's fold, with its first
     r components.  `pls` a fitted tPLS or ctPLS.  Sets pls.q2y_report_."""
@@ -842,15 +975,12 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
     ids, K = fold_ids(I, n_splits, folds)
     R = pls.n_components
     pred = None
-    if not device_folds:
-        why = "device folds switched off"
-    elif wants_masked(pls, X):                                                      # EngineOptions.masked_folds / masked_tensor_folds
-        pred, rep = masked_predictions(pls, X, Y, ids, K, tol, max_iter)
-        why = None if pred is not None else f"the masked form ({masked_forms(pls, X)[0]}) declined: {rep}"
-    elif wants_masked_coupled(pls, X):                                              # EngineOptions.masked_folds_coupled
-        pred, rep = masked_predictions_coupled(pls, X, Y, ids, K, tol, max_iter)
-        why = None if pred is not None else f"the masked form ({COUPLED_FORM}) declined: {rep}"
-    else:
+    route, detail = _route(pls, X, device_folds, models=False)
+    why = detail if route == OFF else None
+    if route in (MASKED, MASKED_COUPLED):
+        pred, rep = (masked_predictions if route == MASKED else masked_predictions_coupled)(pls, X, Y, ids, K, tol, max_iter)
+        why = None if pred is not None else _masked_declined(detail, rep)
+    elif route == PASSES:
         inner = ("kfold_inner_coupled", "kfold_combine_scores") if coupled else ("kfold_inner",)
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K, ("kfold_xcov", *inner, "kfold_epilogue", "mttkrp", "xcov"),
                               tensor_ok=True)

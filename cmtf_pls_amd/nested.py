@@ -19,17 +19,20 @@ squared-error sums of the models' scored rows, and the outer models' r-component
 on the device until the last pass.  Per pass only status, n_iter and those sums come back.  The passes run through
 kfold._device_passes: a pass whose status is set refits its own models; anything outside the device form (the NumPy backend,
 device_folds=False, what kfold._decline_blocks declines, missing values in X) refits every model on the regular engine.
+
+The route (kfold._route, without a masked form), the body of a pass (kfold._device_pass over kfold._weighted_models with
+kfold_weighted_xcov as the read) and the report (kfold._passes_report) are the shared ones of kfold.py.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Tuple
 
 import numpy as np
 import torch
 
 from .bootstrap import _ENTRIES, _ENTRIES_COUPLED, MAX_COLUMNS
-from .kfold import (MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_passes, _form_entries, _groups, _host, _names, _rows,
-                    _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids, refit_fold, repeated_fold_ids)
+from .kfold import (MAX_FOLDS, PASSES, _decline_blocks, _device_blocks, _device_pass, _device_passes, _groups, _host, _names, _passes_report,
+                    _route, _rows, _tensor_dims, _to_dev, _training_data, _weighted_models, fold_ids, refit_fold, repeated_fold_ids)
 
 PRESS_FORM = "cmtfpls_press_rows_f64"
 
@@ -121,42 +124,28 @@ def _device_nested(pls, Xs, Y, counts: np.ndarray, ev: np.ndarray, tol: float, m
     """The device form's run(pass, e0, g) of kfold._device_passes: models e0 .. e0 + g - 1 as the models of one weighted state (a
     one-model pass as two copies of its model).  A pass without a status adds its outer models' predictions to pred_d (R, I, M)
     and returns its models' squared-error sums (g, R); scored collects what scored each pass."""
-    eng = pls._get_engine()
-    be = eng.be
+    be = pls._get_engine().be
     R = pls.n_components
     dev = be.device
     I = counts.shape[1]
     Yd = _to_dev(_host(Y).reshape(I, -1).astype(np.float64), dev)
     M = Yd.shape[1]
     blocks = _device_blocks(pls, Xs, dev)
-    names = _names(Xs, coupled)
     counts_d = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int32)).to(dev)  # one upload of the weights and the rows to score
     ev_d = torch.from_numpy(np.ascontiguousarray(ev, dtype=np.int32)).to(dev)
 
     def run(passes, e0, g):
-        n = max(g, 2)
-        C = counts_d[e0:e0 + g] if g > 1 else counts_d[e0:e0 + 1].expand(2, I).contiguous()
-        Cf = C.to(torch.float64)
+        n, C, Cf = _weighted_models(counts_d, e0, g)
         N = Cf.sum(dim=1, keepdim=True)                                               # n x 1: the models' training rows
         nu = (Cf @ Yd) / N                                                            # n x M: their means of Y
         Yk = (Cf.unsqueeze(2) * (Yd.unsqueeze(0) - nu.unsqueeze(1))).contiguous()     # n x I x M: rows with weight 0 are 0
         Yw = torch.cat([Yk.permute(1, 0, 2).reshape(I, n * M), (Cf * (I / N)).t()], dim=1).contiguous()   # the mean: X^T c / N
-        built = []
-        for (X2, A, B), name in zip(blocks, names):                                   # one read of each block
-            S, mean = be.empty(n, M, A * B), be.empty(n, A * B)
-            stats = be.kfold_weighted_xcov(X2, A, B, Yw, n, M, S, mean)
-            if stats is None:
-                return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_weighted_xcov"
-            if passes == 0:
-                why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
-                if why is not None:
-                    return why
-            built.append((A, B, S, mean))
-        st, shared, own = _state(be, C, Yk, built, R, 1)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, weighted=True,
-                          tensor=_tensor_dims(Xs, coupled))
-        if why is not None:
-            return why
+        got = _device_pass(pls, Xs, blocks, coupled, "kfold_weighted_xcov",           # one read of each block
+                           [lambda X2, A, B, S, mean: be.kfold_weighted_xcov(X2, A, B, Yw, n, M, S, mean)],
+                           C, Yk, 1, passes == 0, tol, max_iter, _tensor_dims(Xs, coupled), weighted=True)
+        if isinstance(got, str):
+            return got
+        shared, _ = got
         status = shared["status"][:g].cpu().numpy()
         n_iter = shared["n_iter"][:g].cpu().numpy()
         press = np.zeros((g, R))
@@ -188,11 +177,9 @@ def nested_kfold(pls, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inne
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
 
-    why: Optional[str] = None
     G = 0
-    if not device_folds:
-        why = "device folds switched off"
-    else:
+    route, why = _route(pls, X, device_folds, masked=False)                           # (missing values in X: _decline_blocks says so)
+    if route == PASSES:
         G = min(_groups(Xb, 1, min(n, I, MAX_FOLDS, MAX_COLUMNS // (M + 1))) for Xb in Xs)   # the LDS of every block's score pass
         tidy = G - G % (Ki + 1)                                                       # an outer model and its inner models in one pass,
         if tidy and -(-n // tidy) == -(-n // G):                                      # where that costs no pass
@@ -234,19 +221,10 @@ def nested_kfold(pls, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inne
     chosen = pred[selected[outer] - 1, np.arange(I)]                                  # (I, M)
     q2y = float(1.0 - ((chosen - Yh) ** 2).sum() / den)
 
-    if passes:
-        entries = _form_entries("cmtfpls_kfold_weighted_xcov_*", coupled, "cmtfpls_kfold_epilogue_weighted_f64")
-        by = " and ".join(sorted(set(scored))) if scored else PRESS_FORM
-        form = f"{G} 0/1-weighted models per pass from shared reads of {'every block' if coupled else 'X'} {entries}, scored by {by}"
-        if why is not None:
-            form += "; failed passes refitted per model on the regular engine"
-        x_reads = [2 * R * passes] * len(Xs) if coupled else 2 * R * passes
-    else:
-        form, x_reads = "one refit per model on the regular engine", None
-    rep = {"form": form, "models": int(n), "outer_folds": int(Ko), "inner_folds": int(Ki), "passes": int(passes),
-           "models_per_pass": int(G) if passes else None, "x_reads": x_reads, "n_iter": n_iters}
-    if why is not None:
-        rep["why"] = why
-    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(Xs, coupled), passes)
+    by = " and ".join(sorted(set(scored))) if scored else PRESS_FORM
+    pls.q2y_report_ = _passes_report(f"{G} 0/1-weighted models per pass", "cmtfpls_kfold_weighted_xcov_*", "cmtfpls_kfold_epilogue_weighted_f64",
+                                     Xs, coupled, passes, 2 * R * passes, why, "model", "one refit per model on the regular engine",
+                                     {"models": int(n), "outer_folds": int(Ko), "inner_folds": int(Ki)}, ("models_per_pass", G), n_iters,
+                                     _tensor_dims(Xs, coupled), scored=f", scored by {by}")
     return {"q2y": q2y, "selected": selected.astype(np.int64), "inner_q2y": inner_q2y, "outer_q2y": outer_q2y,
             "predictions": chosen.reshape(tuple(Y.shape)), "outer_folds": outer, "inner_folds": inner}

@@ -26,6 +26,9 @@ With EngineOptions.masked_folds, a tPLS whose X has missing values runs every pe
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators; X of order 4 with EngineOptions.masked_tensor_folds:
 cmtfpls_cv_masked_tensor_models_f64); with EngineOptions.masked_folds_coupled, a ctPLS
 with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
+
+The route (kfold._route: the coupled masked form is asked first, a ctPLS without coupled_permutations refits), the body of a pass
+(kfold._device_pass with kfold_wide_xcov as the read) and the report (kfold._passes_report) are the shared ones of kfold.py.
 """
 from __future__ import annotations
 
@@ -34,9 +37,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes, _groups,
-                    _host, _names, _refit_numerators, _state, _stats_why, _to_dev, _tensor_dims, _training_data, _with_rank1, fold_ids,
-                    masked_fold_numerators, masked_forms, wants_masked, wants_masked_coupled)
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, REFIT, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
+                    _device_passes, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report, _refit_numerators,
+                    _route, _tensor_dims, _to_dev, _training_data, fold_ids, masked_fold_numerators)
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_wide_xcov", "kfold_inner_coupled_grouped", "kfold_combine_scores", "kfold_epilogue_grouped", "mttkrp", "xcov")
@@ -66,11 +69,9 @@ def _device_null(pls, Xs, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: fl
     """The device form's run(pass, p0, g) of kfold._device_passes: permutations p0 .. p0 + g - 1 as K g models, model k g + p
     holding out fold k with Y[pi_p0+p].  Xs: [X] of a tPLS, or the blocks of a ctPLS (coupled: a state view per block, the Y side
     shared)."""
-    eng = pls._get_engine()
-    be = eng.be
+    be = pls._get_engine().be
     R = pls.n_components
     blocks = _device_blocks(pls, Xs, be.device)
-    names = _names(Xs, coupled)
     I = blocks[0][0].shape[0]
     dev = be.device
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
@@ -95,24 +96,14 @@ def _device_null(pls, Xs, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: fl
         nu = (colsum - torch.matmul(onehot, Yp)) / ntr                                # g x K x M: training means
         Yw = (Yp - ybar).permute(1, 0, 2).reshape(I, g * M).contiguous()            # Y': column p M + j
         ydev = (nu - ybar).permute(1, 0, 2).reshape(K, g * M).contiguous()
-        built = []
-        for (X2, A, B), mean, name in zip(blocks, means, names):                       # one read of each block
-            S = be.empty(n, M, A * B)                                                  # = K x (g M) x P: model k g + p
-            stats = be.kfold_wide_xcov(X2, A, B, Yw, order_d, off_d, K, ydev, S, mean)
-            if stats is None:
-                return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_wide_xcov"
-            if passes == 0:
-                why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
-                if why is not None:
-                    return why
-            built.append((A, B, S, mean))
         Yk = torch.where(train, Yp.unsqueeze(0) - nu.permute(1, 0, 2).unsqueeze(2), 0.0).reshape(n, I, M)
         mf = torch.arange(n, dtype=torch.int32, device=dev) // g
-        st, shared, own = _state(be, fold_of, Yk, built, R, g)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, grouped=(mf, g),
-                          tensor=_tensor_dims(Xs, coupled))
-        if why is not None:
-            return why
+        got = _device_pass(pls, Xs, blocks, coupled, "kfold_wide_xcov",                # one read of each block: S = K x (g M) x P, model k g + p
+                           [lambda X2, A, B, S, mean: be.kfold_wide_xcov(X2, A, B, Yw, order_d, off_d, K, ydev, S, mean)],
+                           fold_of, Yk, g, passes == 0, tol, max_iter, _tensor_dims(Xs, coupled), means=means, grouped=(mf, g))
+        if isinstance(got, str):
+            return got
+        shared, _ = got
         num = _device_numerators(shared["Tout"], shared["coef"], shared["Q"], nu, Yp, rows, K, g, R, M)
         n_iter = shared["n_iter"].cpu().numpy().reshape(K, g, R)
         return num.cpu().numpy(), [n_iter[:, p].tolist() for p in range(g)], shared["status"].cpu().numpy()
@@ -132,61 +123,39 @@ def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=Non
     observed = pls.q2y_report_
     den = float((_host(Y).astype(np.float64) ** 2).sum())
 
-    why: Optional[str] = None
+    coupled = isinstance(X, list)
+    Xs = X if coupled else [X]
     G = 0
     masked = None
-    if not device_folds:
-        why = "device folds switched off"
-    elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
-        got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter, coupled=True)
+    # EngineOptions.coupled_permutations: without it a ctPLS refits
+    gate = (coupled and pls._get_engine().opt.coupled_permutations, "coupled model: permutation device form not built")
+    route, detail = _route(pls, X, device_folds, coupled_first=True, coupled_gate=gate)
+    why: Optional[str] = detail if route in (OFF, REFIT) else None
+    if route in (MASKED, MASKED_COUPLED):       # EngineOptions.masked_folds, masked_tensor_folds (8s), masked_folds_coupled (8j)
+        got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter, coupled=route == MASKED_COUPLED)
         if got[0] is None:
-            why = f"the masked form ({COUPLED_FORM}) declined: {got[1]}"
+            why = _masked_declined(detail, got[1])
         else:
             nums, n_iters, masked = got
-    elif isinstance(X, list) and pls._get_engine().opt.coupled_permutations:          # EngineOptions.coupled_permutations
-        G = min(_groups(b, K, NP) for b in X) if K <= MAX_FOLDS else 0                # the LDS of every block's score pass
-        why = _decline_blocks(pls, X, _names(X, True), Y, K * G if G else K, _ENTRIES_COUPLED, tensor_ok=True)
-    elif isinstance(X, list):
-        why = "coupled model: permutation device form not built"
-    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
-        got = masked_fold_numerators(pls, X, Y, np.broadcast_to(ids, (NP, I)), K, perms, tol, max_iter)
-        if got[0] is None:
-            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {got[1]}"
-        else:
-            nums, n_iters, masked = got
-    else:
-        G = _groups(X, K, NP) if K <= MAX_FOLDS else 0
-        why = _decline_blocks(pls, [X], ["X"], Y, K * G if G else K, _ENTRIES, tensor_ok=True)   # the checks with K made with the n models
-    coupled = isinstance(X, list)
+    elif route == PASSES:
+        G = min(_groups(b, K, NP) for b in Xs) if K <= MAX_FOLDS else 0               # the LDS of every block's score pass
+        why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES,
+                              tensor_ok=True)                                         # the checks with K made with the n models
     if masked is None:
         nums, n_iters, passes, why = _device_passes(pls, NP, G, "permutations", why,
-                                                    lambda: _device_null(pls, X if coupled else [X], Y, ids, K, perms, tol, max_iter,
-                                                                         coupled),
+                                                    lambda: _device_null(pls, Xs, Y, ids, K, perms, tol, max_iter, coupled),
                                                     lambda p: _refit_numerators(pls, X, Y, ids, K, perms[p], tol, max_iter))
     null_all = 1.0 - nums / den                                                       # P x R: every component count
     null = null_all if per_component else null_all[:, -1]
     p_value = (1.0 + (null >= q2y).sum(axis=0)) / (NP + 1.0)
     if masked is not None:
-        rep = dict(masked, permutations=int(NP), passes=masked["launches"], models_per_pass=-(-masked["models"] // masked["launches"]),
-                   n_iter=n_iters, observed=observed)
-        pls.q2y_report_ = rep
-        return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}
-    if passes and coupled:
-        form = (f"{K * G} models per pass ({G} permutations x {K} folds) from shared reads of every block (cmtfpls_kfold_wide_xcov_*, "
-                "cmtfpls_kfold_inner_coupled_grouped_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_combine_scores_f64, "
-                "cmtfpls_kfold_epilogue_grouped_f64, cmtfpls_xcov_*)")
-    elif passes:
-        form = (f"{K * G} models per pass ({G} permutations x {K} folds) from shared reads of X (cmtfpls_kfold_wide_xcov_*, "
-                "cmtfpls_kfold_inner_grouped_f64, cmtfpls_mttkrp_*, cmtfpls_kfold_epilogue_grouped_f64, cmtfpls_xcov_*)")
-        if why is not None:
-            form += "; failed passes refitted per fold on the regular engine"
+        pls.q2y_report_ = _masked_run_report(masked, "permutations", NP, "models_per_pass", n_iters, observed=observed)
     else:
-        form = "one refit per fold and permutation on the regular engine"
-    R = pls.n_components
-    x_reads = ([2 * R * passes] * len(X) if coupled else 2 * R * passes) if passes else None
-    rep = {"form": form, "permutations": int(NP), "passes": int(passes), "models_per_pass": int(K * G) if passes else None,
-           "x_reads": x_reads, "n_iter": n_iters, "observed": observed}
-    if why is not None:
-        rep["why"] = why
-    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(X if coupled else [X], coupled), passes)
+        R = pls.n_components
+        # behaviour: the form of a ctPLS does not say that failed passes refitted
+        pls.q2y_report_ = _passes_report(f"{K * G} models per pass ({G} permutations x {K} folds)", "cmtfpls_kfold_wide_xcov_*",
+                                         "cmtfpls_kfold_epilogue_grouped_f64", Xs, coupled, passes, 2 * R * passes, why,
+                                         None if coupled else "fold", "one refit per fold and permutation on the regular engine",
+                                         {"permutations": int(NP)}, ("models_per_pass", K * G), n_iters, _tensor_dims(Xs, coupled),
+                                         grouped=True, more={"observed": observed})
     return {"q2y": q2y, "null": null, "p_value": p_value if per_component else float(p_value), "permutations": perms}

@@ -18,6 +18,9 @@ With EngineOptions.masked_folds, a tPLS whose X has missing values runs every sp
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators; X of order 4 with EngineOptions.masked_tensor_folds:
 cmtfpls_cv_masked_tensor_models_f64); with EngineOptions.masked_folds_coupled, a ctPLS
 with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
+
+The route (kfold._route), the body of a pass (kfold._device_pass: one kfold_xcov read per split, each into its split's slice of S and
+mean, the statistics checked after the first) and the report (kfold._passes_report) are the shared ones of kfold.py.
 """
 from __future__ import annotations
 
@@ -27,10 +30,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (COUPLED_FORM, MAX_FOLDS, _components, _decline_blocks, _device_blocks, _device_numerators, _device_passes,
-                    _fold_means, _form_entries, _groups, _host, _names, _refit_numerators, _state, _stats_why, _to_dev,
-                    _tensor_dims, _training_data, _with_rank1, masked_fold_numerators, masked_forms, repeated_fold_ids, wants_masked,
-                    wants_masked_coupled)
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
+                    _device_passes, _fold_means, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
+                    _refit_numerators, _route, _tensor_dims, _to_dev, _training_data, masked_fold_numerators, repeated_fold_ids)
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
@@ -39,15 +41,13 @@ _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores",
 def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, coupled: bool):
     """The device form's run(pass, g0, g) of kfold._device_passes (a ctPLS: the coupled kernels, one block included): splits
     g0 .. g0 + g - 1 as g K split-major models, each split's S and mean built into its K-model slice of every block's."""
-    eng = pls._get_engine()
-    be = eng.be
+    be = pls._get_engine().be
     R = pls.n_components
     I = ids.shape[1]
     dev = be.device
     Yh = _host(Y).reshape(I, -1).astype(np.float64)
     M = Yh.shape[1]
     blocks = _device_blocks(pls, Xs, dev)
-    names = _names(Xs, coupled)
     Yd = _to_dev(Yh, dev)
     ydev = _to_dev(Yh - Yh.mean(axis=0), dev)                                         # shared by every split
     kk = torch.arange(K, device=dev)
@@ -56,31 +56,28 @@ def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: in
         n = K * g
         fold_of = _to_dev(ids[g0:g0 + g], dev, torch.int32)
         Yk = be.empty(n, I, M)
-        built = [(A, B, be.empty(n, M, A * B), be.empty(n, A * B)) for _, A, B in blocks]
+        Ss, means = zip(*[(be.empty(n, M, A * B), be.empty(n, A * B)) for _, A, B in blocks])   # every split builds into its slice
         nu, rows = [], []
-        for j in range(g):                                                            # split g0 + j: models j K .. j K + K - 1
-            order, off, _, nu_j = _fold_means(Yh, ids[g0 + j], K)                     # kfold._fold_y's bits
-            order_d, off_d, nu_d = _to_dev(order, dev, torch.int32), _to_dev(off, dev, torch.int32), _to_dev(nu_j, dev)
-            nudev = _to_dev(nu_j - Yh.mean(axis=0), dev)
-            sl = slice(j * K, (j + 1) * K)
-            train = (fold_of[j].long().unsqueeze(0) != kk.unsqueeze(1)).unsqueeze(2)                       # K x I x 1
-            Yk[sl] = torch.where(train, Yd.unsqueeze(0) - nu_d.unsqueeze(1), 0.0)
-            for (X2, A, B), (_, _, S, mean), name in zip(blocks, built, names):      # one read of each block per split
-                stats = be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S[sl], mean[sl])
-                if stats is None:
-                    return f"{'' if name == 'X' else name + ': '}shape outside cmtfpls_kfold_xcov"
-                if passes == 0 and j == 0:
-                    why = _stats_why(stats, A * B, I, eng.opt.xcov_raw_max_offset, name)
-                    if why is not None:
-                        return why
-            nu.append(nu_d)
-            order_l = order_d.long()
-            rows.append([order_l[int(off[k]):int(off[k + 1])] for k in range(K)])
-        st, shared, own = _state(be, fold_of, Yk, built, R, g)
-        why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, splits=g,
-                          tensor=_tensor_dims(Xs, coupled))
-        if why is not None:
-            return why
+
+        def builds():                                                                 # split g0 + j: models j K .. j K + K - 1
+            for j in range(g):
+                order, off, _, nu_j = _fold_means(Yh, ids[g0 + j], K)                 # kfold._fold_y's bits
+                order_d, off_d, nu_d = _to_dev(order, dev, torch.int32), _to_dev(off, dev, torch.int32), _to_dev(nu_j, dev)
+                nudev = _to_dev(nu_j - Yh.mean(axis=0), dev)
+                sl = slice(j * K, (j + 1) * K)
+                train = (fold_of[j].long().unsqueeze(0) != kk.unsqueeze(1)).unsqueeze(2)                   # K x I x 1
+                Yk[sl] = torch.where(train, Yd.unsqueeze(0) - nu_d.unsqueeze(1), 0.0)
+                nu.append(nu_d)
+                order_l = order_d.long()
+                rows.append([order_l[int(off[k]):int(off[k + 1])] for k in range(K)])
+                # one read of each block per split, into the split's K-model slice of S and mean
+                yield lambda X2, A, B, S, mean: be.kfold_xcov(X2, A, B, ydev, order_d, off_d, K, nudev, S[sl], mean[sl])
+
+        got = _device_pass(pls, Xs, blocks, coupled, "kfold_xcov", builds(), fold_of, Yk, g, passes == 0, tol, max_iter,
+                           _tensor_dims(Xs, coupled), Ss=Ss, means=means, splits=g)
+        if isinstance(got, str):
+            return got
+        shared, _ = got
         num = torch.cat([_device_numerators(shared["Tout"][j:j + 1], shared["coef"][j * K:(j + 1) * K], shared["Q"][j * K:(j + 1) * K],
                                             nu[j].unsqueeze(0), Yd.unsqueeze(0), rows[j], K, 1, R, M) for j in range(g)])
         n_iter = shared["n_iter"].cpu().numpy().reshape(g, K, R)
@@ -99,24 +96,17 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
     R = pls.n_components
     den = float((_host(Y).astype(np.float64) ** 2).sum())
 
-    why: Optional[str] = None
     G = 0
     masked = None
-    if not device_folds:
-        why = "device folds switched off"
-    elif wants_masked(pls, X):                                    # EngineOptions.masked_folds / masked_tensor_folds (8s)
-        got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter)
+    route, detail = _route(pls, X, device_folds)
+    why: Optional[str] = detail if route == OFF else None
+    if route in (MASKED, MASKED_COUPLED):       # EngineOptions.masked_folds, masked_tensor_folds (8s), masked_folds_coupled (8j)
+        got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter, coupled=route == MASKED_COUPLED)
         if got[0] is None:
-            why = f"the masked form ({masked_forms(pls, X)[1]}) declined: {got[1]}"
+            why = _masked_declined(detail, got[1])
         else:
             nums, n_iters, masked = got
-    elif wants_masked_coupled(pls, X):                                                # EngineOptions.masked_folds_coupled
-        got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter, coupled=True)
-        if got[0] is None:
-            why = f"the masked form ({COUPLED_FORM}) declined: {got[1]}"
-        else:
-            nums, n_iters, masked = got
-    else:
+    elif route == PASSES:
         G = min(_groups(X, K, min(NS, I // K)) for X in Xs) if K <= MAX_FOLDS else 0   # n <= I models, the LDS of every block
         why = _decline_blocks(pls, Xs, _names(Xs, coupled), Y, K * G if G else K, _ENTRIES_COUPLED if coupled else _ENTRIES,
                               tensor_ok=True)
@@ -128,24 +118,12 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
     q_all = 1.0 - nums / den                                                          # S x R: every component count
     q2y = q_all if per_component else q_all[:, -1]
     if masked is not None:
-        pls.q2y_report_ = dict(masked, splits=int(NS), passes=masked["launches"],
-                               splits_per_pass=-(-NS // masked["launches"]), n_iter=n_iters)
-        return dict(summary(q2y), folds=ids)
-    x_reads = None
-    if passes:
-        entries = _form_entries("cmtfpls_kfold_xcov_* per split", coupled, "cmtfpls_kfold_epilogue_splits_f64")
-        form = f"{K * G} models per pass ({G} splits x {K} folds) from shared reads of {'every block' if coupled else 'X'} {entries}"
-        if why is not None:
-            form += "; failed passes refitted per fold on the regular engine"
-        reads = NS + passes * (2 * R - 1)                                            # G + 2R - 1 per pass
-        x_reads = [reads] * len(Xs) if coupled else reads
+        pls.q2y_report_ = _masked_run_report(masked, "splits", NS, "splits_per_pass", n_iters)
     else:
-        form = "one refit per fold and split on the regular engine"
-    rep = {"form": form, "splits": int(NS), "passes": int(passes), "splits_per_pass": int(G) if passes else None,
-           "x_reads": x_reads, "n_iter": n_iters}
-    if why is not None:
-        rep["why"] = why
-    pls.q2y_report_ = _with_rank1(rep, _tensor_dims(Xs, coupled), passes)
+        pls.q2y_report_ = _passes_report(f"{K * G} models per pass ({G} splits x {K} folds)", "cmtfpls_kfold_xcov_* per split",
+                                         "cmtfpls_kfold_epilogue_splits_f64", Xs, coupled, passes, NS + passes * (2 * R - 1), why, "fold",
+                                         "one refit per fold and split on the regular engine", {"splits": int(NS)},
+                                         ("splits_per_pass", G), n_iters, _tensor_dims(Xs, coupled))   # reads: G + 2R - 1 per pass
     return dict(summary(q2y), folds=ids)
 
 

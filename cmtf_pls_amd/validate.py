@@ -23,9 +23,9 @@ the refits.  Which form ran is recorded on the model (``q2y_report_``).
 """
 import numpy as np
 
-from .kfold import (COUPLED_FORM, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
-                    _tensor_dims, _training_data, has_missing, masked_predictions, masked_predictions_coupled, refit_predictions,
-                    wants_masked_coupled, wants_masked_tensor)
+from .kfold import (COUPLED_FORM, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
+                    _masked_declined, _tensor_dims, _training_data, has_missing, masked_predictions, masked_predictions_coupled,
+                    refit_predictions, wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
@@ -90,44 +90,6 @@ def loo_coupled_lds_bytes(dims, M: int, R: int) -> int:
     return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R)
 
 
-def _decline_loo_coupled(pls, Xs, Y):
-    """Why cmtfpls_loo_xcov_coupled_f64 does not take these blocks (its limits in the entry's order, checked before a block is
-    uploaded); None: it does."""
-    be = pls._get_engine().be
-    name = "cmtfpls_loo_xcov_coupled_f64"
-    if not hasattr(be, "loo_ctpls"):
-        return f"the {getattr(be, 'name', type(be).__name__)} backend has no coupled leave-one-out kernel"
-    if pls._comm is not None:
-        return "sharded model (comm)"
-    if len(Xs) > MAX_BLOCKS:
-        return f"{len(Xs)} blocks > {MAX_BLOCKS} ({name})"
-    for b, X in enumerate(Xs):
-        if X.ndim > 3:
-            return f"block {b} of order {X.ndim} > 3 ({name})"
-    for b, X in enumerate(Xs):
-        if has_missing(X):
-            return f"missing values in block {b} (EngineOptions.masked_folds_coupled is off; {name} is the complete-data form)"
-    if has_missing(Y):
-        return "missing values in Y"
-    dims = [_dims(X) for X in Xs]
-    M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
-    R = pls.n_components
-    for b, (A, B) in enumerate(dims):
-        if min(A, B) > MAX_SIDE:
-            return f"block {b}: min(J, K) = {min(A, B)} > {MAX_SIDE} ({name})"
-    if M > LOO_MAX_RESPONSES:
-        return f"M = {M} > {LOO_MAX_RESPONSES} responses ({name})"
-    if R > LOO_MAX_COMPONENTS:
-        return f"R = {R} > {LOO_MAX_COMPONENTS} components ({name})"
-    for b, (A, B) in enumerate(dims):
-        if A * B > LOO_MAX_CELLS:
-            return f"block {b}: J K = {A * B} > {LOO_MAX_CELLS} ({name})"
-    lds = loo_coupled_lds_bytes(dims, M, R)
-    if lds > LOO_COUPLED_LDS_CAP:
-        return f"the fold's vectors need {lds} bytes of LDS > {LOO_COUPLED_LDS_CAP} ({name})"
-    return None
-
-
 def loo_coupled_tensor_lds_bytes(dims, tensor, M: int, R: int) -> int:
     """The LDS of a workgroup of cmtfpls_loo_xcov_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with tensor =
     [(B1, B2), ..] ((0, 0): a block of order 2 or 3), the library's cmtfpls_loo_xcov_coupled_tensor_lds_bytes: loo_coupled_lds_bytes
@@ -142,33 +104,34 @@ def loo_coupled_tensor_lds_bytes(dims, tensor, M: int, R: int) -> int:
     return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R + cp)
 
 
-def _decline_loo_coupled_tensor(pls, Xs, Y):
-    """Why cmtfpls_loo_xcov_coupled_tensor_f64 does not take these blocks, at least one of them of order 4 (its limits in the entry's
-    order, checked before a block is uploaded); None: it does."""
+def _loo_coupled_why(pls, Xs, Y, tensor: bool):
+    """The one list of checks behind _decline_loo_coupled (cmtfpls_loo_xcov_coupled_f64) and, tensor, _decline_loo_coupled_tensor
+    (cmtfpls_loo_xcov_coupled_tensor_f64): the entry's limits in its order, checked before a block is uploaded."""
     be = pls._get_engine().be
-    name = "cmtfpls_loo_xcov_coupled_tensor_f64"
-    if not hasattr(be, "loo_ctpls_tensor"):
-        return f"the {getattr(be, 'name', type(be).__name__)} backend has no order-4 coupled leave-one-out kernel"
+    name = "cmtfpls_loo_xcov_coupled_tensor_f64" if tensor else "cmtfpls_loo_xcov_coupled_f64"
+    if not hasattr(be, "loo_ctpls_tensor" if tensor else "loo_ctpls"):
+        return f"the {getattr(be, 'name', type(be).__name__)} backend has no {'order-4 ' if tensor else ''}coupled leave-one-out kernel"
     if pls._comm is not None:
         return "sharded model (comm)"
-    for b, X in enumerate(Xs):
-        if X.ndim > 4:
-            return f"block {b} of order {X.ndim} > 4 ({name})"
-    if len(Xs) > MAX_BLOCKS:
-        return f"{len(Xs)} blocks > {MAX_BLOCKS} ({name})"
+    top = 4 if tensor else 3
+    count = f"{len(Xs)} blocks > {MAX_BLOCKS} ({name})" if len(Xs) > MAX_BLOCKS else None
+    order = next((f"block {b} of order {X.ndim} > {top} ({name})" for b, X in enumerate(Xs) if X.ndim > top), None)
+    if count or order:                               # behaviour: the tensor entry names a block's order before the block count
+        return (order or count) if tensor else (count or order)
+    note = f"{name} is the complete-data form" if tensor else f"EngineOptions.masked_folds_coupled is off; {name} is the complete-data form"
     for b, X in enumerate(Xs):
         if has_missing(X):
-            return f"missing values in block {b} ({name} is the complete-data form)"
+            return f"missing values in block {b} ({note})"
     if has_missing(Y):
         return "missing values in Y"
     dims = [_dims(X) for X in Xs]
-    tensor = _tensor_dims(Xs, coupled=True)
+    tensors = _tensor_dims(Xs, coupled=True) if tensor else [(0, 0)] * len(Xs)
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
     R = pls.n_components
-    for b, ((A, B), (_, B2)) in enumerate(zip(dims, tensor)):
+    for b, ((A, B), (_, B2)) in enumerate(zip(dims, tensors)):
         if B2 == 0 and min(A, B) > MAX_SIDE:
             return f"block {b}: min(J, K) = {min(A, B)} > {MAX_SIDE} ({name})"
-    for b, ((A, _), (B1, B2)) in enumerate(zip(dims, tensor)):
+    for b, ((A, _), (B1, B2)) in enumerate(zip(dims, tensors)):
         P = A * B1 * B2
         for mode, d in enumerate((A, B1, B2) if B2 > 0 else ()):
             if min(d, P // d) > MAX_SIDE:
@@ -180,10 +143,21 @@ def _decline_loo_coupled_tensor(pls, Xs, Y):
     for b, (A, B) in enumerate(dims):
         if A * B > LOO_MAX_CELLS:
             return f"block {b}: J K = {A * B} > {LOO_MAX_CELLS} ({name})"
-    lds = loo_coupled_tensor_lds_bytes(dims, tensor, M, R)
+    lds = loo_coupled_tensor_lds_bytes(dims, tensors, M, R) if tensor else loo_coupled_lds_bytes(dims, M, R)
     if lds > LOO_COUPLED_LDS_CAP:
         return f"the fold's vectors need {lds} bytes of LDS > {LOO_COUPLED_LDS_CAP} ({name})"
     return None
+
+
+def _decline_loo_coupled(pls, Xs, Y):
+    """Why cmtfpls_loo_xcov_coupled_f64 does not take these blocks (_loo_coupled_why); None: it does."""
+    return _loo_coupled_why(pls, Xs, Y, False)
+
+
+def _decline_loo_coupled_tensor(pls, Xs, Y):
+    """Why cmtfpls_loo_xcov_coupled_tensor_f64 does not take these blocks, at least one of them of order 4 (_loo_coupled_why);
+    None: it does."""
+    return _loo_coupled_why(pls, Xs, Y, True)
 
 
 def _wants_loo_coupled_tensor(pls, Xs) -> bool:
@@ -191,16 +165,34 @@ def _wants_loo_coupled_tensor(pls, Xs) -> bool:
     return bool(pls._get_engine().opt.tensor_resamples_coupled) and any(X.ndim >= 4 for X in Xs)
 
 
+def _upload(a, I: int, dev):
+    """The original data in float64 on the device, as I x -1 (kfold._f64: the same bits as a copy through the host)."""
+    return _f64(a, dev).contiguous().view(I, -1)
+
+
+def _loo_report(form: str, folds: int, n_iter_total, blocks=None, rank1: bool = False, why=None) -> dict:
+    """q2y_report_ of a leave-one-out form (blocks: a ctPLS's; rank1: an order-4 form; why: of the refits)."""
+    rep = {"form": form, **({"rank1": TENSOR_RANK1} if rank1 else {}), "folds": int(folds), **({} if blocks is None else {"blocks": blocks}),
+           "n_iter_total": int(n_iter_total)}
+    return rep if why is None else dict(rep, why=why)
+
+
+def _loo_result(pls, out, entry: str, form: str, Y, blocks=None, rank1: bool = False):
+    """(Y_pred, None) and q2y_report_ from what a workgroup-per-fold entry returned, or (None, why) when it declined the shape."""
+    if out is None:
+        return None, f"{entry} declined the shape"
+    pls.q2y_report_ = _loo_report(form, Y.shape[0], out[1].sum().item(), blocks, rank1)
+    return out[0].cpu().numpy().reshape(tuple(Y.shape)), None
+
+
 def _loo_device_coupled(pls, tol: float, max_iter: int):
     """_loo_device for a fitted ctPLS: (Y_pred, None) from a device form (q2y_report_ set), or (None, why)."""
-    import torch
-
     Xs, Y = _training_data(pls)
     I = Y.shape[0]
     if wants_masked_coupled(pls, Xs):                                     # EngineOptions.masked_folds_coupled: cmtfpls_cv_masked_coupled_f64
         pred, rep = masked_predictions_coupled(pls, Xs, Y, np.arange(I), I, tol, max_iter)
         if pred is None:
-            return None, f"the masked form ({COUPLED_FORM}) declined: {rep}"
+            return None, _masked_declined(COUPLED_FORM, rep)
         pls.q2y_report_ = dict(rep, blocks=len(Xs), n_iter_total=int(np.sum(rep["n_iter"])))
         return pred[-1].reshape(Y.shape), None
     tensor = _wants_loo_coupled_tensor(pls, Xs)                           # EngineOptions.tensor_resamples_coupled (DESIGN 8t)
@@ -210,24 +202,12 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
     eng = pls._get_engine()
     be = eng.be
     with eng.device_ctx():
-        def f64(a):                                                       # the original data in float64, on the device
-            if isinstance(a, torch.Tensor):
-                return a.detach().to(device=be.device, dtype=torch.float64).contiguous().view(I, -1)
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(I, -1), dtype=np.float64)).to(be.device)
-
+        data = ([_upload(X, I, be.device) for X in Xs], _upload(Y, I, be.device), [(X.ndim, *_dims(X)) for X in Xs])
         if tensor:
-            out = be.loo_ctpls_tensor([f64(X) for X in Xs], f64(Y), [(X.ndim, *_dims(X)) for X in Xs], _tensor_dims(Xs, coupled=True),
-                                      pls.n_components, tol, max_iter)
-            if out is None:
-                return None, "cmtfpls_loo_xcov_coupled_tensor_f64 declined the shape"
-            pls.q2y_report_ = {"form": LOO_COUPLED_TENSOR_FORM, "rank1": TENSOR_RANK1, "folds": int(I), "blocks": len(Xs),
-                               "n_iter_total": int(out[1].sum().item())}
-            return out[0].cpu().numpy().reshape(tuple(Y.shape)), None
-        out = be.loo_ctpls([f64(X) for X in Xs], f64(Y), [(X.ndim, *_dims(X)) for X in Xs], pls.n_components, tol, max_iter)
-        if out is None:
-            return None, "cmtfpls_loo_xcov_coupled_f64 declined the shape"
-        pls.q2y_report_ = {"form": LOO_COUPLED_FORM, "folds": int(I), "blocks": len(Xs), "n_iter_total": int(out[1].sum().item())}
-        return out[0].cpu().numpy().reshape(tuple(Y.shape)), None
+            out = be.loo_ctpls_tensor(*data, _tensor_dims(Xs, coupled=True), pls.n_components, tol, max_iter)
+            return _loo_result(pls, out, "cmtfpls_loo_xcov_coupled_tensor_f64", LOO_COUPLED_TENSOR_FORM, Y, len(Xs), rank1=True)
+        out = be.loo_ctpls(*data, pls.n_components, tol, max_iter)
+        return _loo_result(pls, out, "cmtfpls_loo_xcov_coupled_f64", LOO_COUPLED_FORM, Y, len(Xs))
 
 
 def _get_q2y_coupled(pls, device_folds: bool):
@@ -239,11 +219,15 @@ def _get_q2y_coupled(pls, device_folds: bool):
     Y_actual = _host(Y).astype(float)
     if Y_pred is None:
         pred, n_iter = refit_predictions(pls, Xs, Y, np.arange(I), I, 1e-8, 100)
-        pls.q2y_report_ = {"form": LOO_REFIT_FORM, "folds": int(I), "blocks": len(Xs), "n_iter_total": int(np.sum(n_iter)), "why": why}
+        pls.q2y_report_ = _loo_report(LOO_REFIT_FORM, I, np.sum(n_iter), len(Xs), why=why)
         Y_pred = pred[-1].reshape(Y_actual.shape)
     numerator = (Y_pred - Y_actual) ** 2                     # validate.py:35-37
     denominator = Y_actual ** 2
     return 1 - numerator.sum() / denominator.sum()
+
+
+LOO_FORMS = {"lds": "all folds in one launch, a workgroup per fold, vectors in LDS (cmtfpls_loo_tpls_f64)",
+             "xcov": "a workgroup per fold on the fold's cross-covariance (cmtfpls_loo_xcov_f64)"}
 
 
 def _loo_device(pls_tensor, tol: float, max_iter: int):
@@ -253,61 +237,36 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
     X = pls_tensor.original_X
     Y = pls_tensor.original_Y
     eng = pls_tensor._get_engine()
+    I = X.shape[0]
     tensor = wants_masked_tensor(pls_tensor, X)                            # EngineOptions.masked_tensor_folds: cmtfpls_cv_masked_tensor_f64
     if tensor or (eng.opt.masked_folds and X.ndim in (2, 3) and has_missing(X)):   # EngineOptions.masked_folds: cmtfpls_cv_masked_f64
-        I = X.shape[0]
         pred, rep = masked_predictions(pls_tensor, X, Y, np.arange(I), I, tol, max_iter)
         if pred is None:
-            return None, f"the masked form ({MASKED_TENSOR_FORM if tensor else MASKED_FORM}) declined: {rep}"
+            return None, _masked_declined(MASKED_TENSOR_FORM if tensor else MASKED_FORM, rep)
         rep["n_iter_total"] = int(np.sum(rep["n_iter"]))
         pls_tensor.q2y_report_ = rep
         return pred[-1].reshape(Y.shape), None
     be = eng.be
-    if X.ndim == 4 and eng.opt.tensor_folds:                               # EngineOptions.tensor_folds: cmtfpls_loo_xcov_tensor_f64
-        return _loo_device_tensor(pls_tensor, be, X, Y, tol, max_iter)
-    if not hasattr(be, "loo_tpls") or X.ndim not in (2, 3):
+    order4 = X.ndim == 4 and bool(eng.opt.tensor_folds)                    # EngineOptions.tensor_folds: cmtfpls_loo_xcov_tensor_f64
+    if not order4 and (not hasattr(be, "loo_tpls") or X.ndim not in (2, 3)):
         return None, None
-    Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
-    Yh = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-    if np.isnan(Xh).any() or np.isnan(Yh).any():
+    if has_missing(X) or has_missing(Y):             # behaviour: the tPLS forms name no reason for NaN; get_q2y names the limits itself
         return None, None
-    I = Xh.shape[0]
-    A, B = (1, Xh.shape[1]) if Xh.ndim == 2 else (Xh.shape[1], Xh.shape[2])
-    with torch.cuda.device(be.device):
-        Xd = torch.from_numpy(np.ascontiguousarray(Xh.reshape(I, -1), dtype=np.float64)).to(be.device)
-        Yd = torch.from_numpy(np.ascontiguousarray(Yh.reshape(I, -1), dtype=np.float64)).to(be.device)
-        out = be.loo_tpls(Xd, Yd, A, B, pls_tensor.n_components, tol, max_iter)
-        if out is None:
-            return None, None
-        pls_tensor.q2y_report_ = {"form": {"lds": "all folds in one launch, a workgroup per fold, vectors in LDS (cmtfpls_loo_tpls_f64)",
-                                           "xcov": "a workgroup per fold on the fold's cross-covariance (cmtfpls_loo_xcov_f64)"}[out[2]],
-                                  "folds": int(I), "n_iter_total": int(out[1].sum().item())}
-        return out[0].cpu().numpy().reshape(Yh.shape), None
-
-
-def _loo_device_tensor(pls_tensor, be, X, Y, tol: float, max_iter: int):
-    """_loo_device for X of order 4 under EngineOptions.tensor_folds: (Y_pred, None), or (None, why) with the limit that declined;
-    why is None with missing values (get_q2y then names the limits as it always did)."""
-    import torch
-
-    Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
-    Yh = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-    if np.isnan(Xh).any() or np.isnan(Yh).any():
-        return None, None
-    I, A, B1, B2 = (int(d) for d in Xh.shape)
     R = pls_tensor.n_components
-    why = _decline_loo_tensor(be, A, B1, B2, int(Yh.reshape(I, -1).shape[1]), R)
-    if why is not None:
-        return None, why
+    if order4:                                       # (its limits are checked here, before X is uploaded)
+        A, B1, B2 = (int(d) for d in X.shape[1:])
+        why = _decline_loo_tensor(be, A, B1, B2, int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1, R)
+        if why is not None:
+            return None, why
     with torch.cuda.device(be.device):
-        Xd = torch.from_numpy(np.ascontiguousarray(Xh.reshape(I, -1), dtype=np.float64)).to(be.device)
-        Yd = torch.from_numpy(np.ascontiguousarray(Yh.reshape(I, -1), dtype=np.float64)).to(be.device)
-        out = be.loo_tpls_tensor(Xd, Yd, A, B1, B2, R, tol, max_iter)
-        if out is None:
-            return None, "cmtfpls_loo_xcov_tensor_f64 declined the shape"
-        pls_tensor.q2y_report_ = {"form": LOO_TENSOR_FORM, "rank1": TENSOR_RANK1, "folds": int(I),
-                                  "n_iter_total": int(out[1].sum().item())}
-        return out[0].cpu().numpy().reshape(Yh.shape), None
+        Xd, Yd = _upload(X, I, be.device), _upload(Y, I, be.device)
+        if order4:
+            return _loo_result(pls_tensor, be.loo_tpls_tensor(Xd, Yd, A, B1, B2, R, tol, max_iter), "cmtfpls_loo_xcov_tensor_f64",
+                               LOO_TENSOR_FORM, Y, rank1=True)
+        out = be.loo_tpls(Xd, Yd, *_dims(X), R, tol, max_iter)
+        if out is None:                              # behaviour: neither form took the shape; get_q2y names the limits itself
+            return None, None
+        return _loo_result(pls_tensor, out, "", LOO_FORMS[out[2]], Y)
 
 
 def get_q2y(pls_tensor, device_folds: bool = True):
@@ -322,7 +281,9 @@ def get_q2y(pls_tensor, device_folds: bool = True):
     if Y_pred is None:
         why = ("device folds switched off" if not device_folds else why or
                "order > 3, missing values, min(J, K) > 256, M > 128 (or an M x M Gram beyond the LDS) or R > 64: outside both workgroup-per-fold kernels")
-        pls_tensor.q2y_report_ = {"form": "one refit per fold on the regular engine", "folds": int(n), "why": why}
+        pls_tensor.q2y_report_ = {"form": LOO_REFIT_FORM, "folds": int(n), "why": why}
+        # behaviour: this loop is the reference's, and its tPLS is built without the fitted model's graphs, matrix_precision and
+        # options, unlike kfold.refit_fold
         refit = tPLS(pls_tensor.n_components, dtype=pls_tensor._dtype, device=pls_tensor._device,
                      backend=pls_tensor._backend, algorithm=pls_tensor._algorithm)
         Y_pred = np.zeros(Y.shape)
