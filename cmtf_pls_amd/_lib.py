@@ -217,6 +217,10 @@ SIGNATURES = {
     "cmtfpls_cv_masked_coupled_lds_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, c_int, c_int, c_int]),
     "cmtfpls_cv_masked_coupled_f64": (c_int, [ctypes.POINTER(CvCoupledBlock), c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_double,
                                               c_int, c_int, c_int] + [_P] * 8 + [_P, c_size_t, _P]),
+    "cmtfpls_cv_masked_coupled_tensor_workspace_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, _P, c_int, c_int, c_int]),
+    "cmtfpls_cv_masked_coupled_tensor_lds_bytes": (c_size_t, [ctypes.POINTER(CvCoupledBlock), c_int, _P, c_int, c_int, c_int]),
+    "cmtfpls_cv_masked_coupled_tensor_f64": (c_int, [ctypes.POINTER(CvCoupledBlock), c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                                     c_double, c_int, c_int, c_int] + [_P] * 10 + [_P, c_size_t, _P]),
     "cmtfpls_fit_small_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cmtfpls_fit_small_f64": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int] + [_P] * 11 + [_P, c_size_t, _P]),
     "cmtfpls_add_noise_f32": (c_int, [_P, c_int64, c_double, c_uint64, c_uint64, c_double, _P]),

@@ -929,6 +929,45 @@ class HipBackend:
             out["Wa"], out["Wb"] = Wa, Wb
         return out
 
+    def cv_masked_coupled_tensor(self, X2s, dims, tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int,
+                                 tol: float, max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
+        """cv_masked_coupled for a ctPLS with blocks of order 4 (cmtfpls_cv_masked_coupled_tensor_f64): a block I x A x B1 x B2 is
+        given as I x A B1 B2 with dims (4, A, B1 B2) and tensor (B1, B2); a block of order 2 or 3 has tensor (0, 0).  The loading of a
+        tensor block is the rank-1 CP of its contraction inside the model's workgroup.  Returns cv_masked_coupled's dict, with
+        `factors` also Wk, Wl (lists: per block (n, R, B1_b) / (n, R, B2_b), None for a block of order 2 or 3; Wb of a tensor block is
+        wK (x) wL), or None when the shape is outside the form.  Models run in chunks as cv_masked_coupled's."""
+        nb = len(X2s)
+        I = X2s[0].shape[0]
+        M = Y.shape[1]
+        nm = counts.shape[0]
+        assert nb >= 1 and len(dims) == nb and len(tensor) == nb and Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape[0] == I
+        for X2, (_, A, B) in zip(X2s, dims):
+            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
+        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
+        blocks = (_lib.CvCoupledBlock * nb)(*[_lib.CvCoupledBlock(_ptr(X2), int(o), int(A), int(B)) for X2, (o, A, B) in zip(X2s, dims)])
+        pairs = _int_pairs(tensor)
+        sumA, sumB = sum(A for _, A, _ in dims), sum(B for _, _, B in dims)
+        sumK, sumL = sum(B1 for B1, B2 in tensor if B2 > 0), sum(B2 for _, B2 in tensor)
+        shapes = {"Wa": (R * sumA,), "Wb": (R * sumB,), "Wk": (R * sumK,), "Wl": (R * sumL,), "coef": (R, R), "Q": (R, M)}
+        args = (blocks, nb, pairs, _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, M, R, float(tol), int(max_iter))
+        out = self._masked_launch("cv_masked_coupled_tensor", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}),
+                                  shapes, nm, lambda: self.lib.cmtfpls_cv_masked_coupled_tensor_workspace_bytes(blocks, nb, pairs, I, M, R),
+                                  max_ws_bytes, extra=R * I * M * 8)
+        if out is not None and factors:                                              # block b's R x A_b at R * (A_0 + .. + A_(b-1))
+            oa = ob = ok = ol = 0
+            Wa, Wb, Wk, Wl = [], [], [], []
+            for (_, A, B), (B1, B2) in zip(dims, tensor):
+                Wa.append(out["Wa"][:, R * oa:R * (oa + A)].reshape(nm, R, A))
+                Wb.append(out["Wb"][:, R * ob:R * (ob + B)].reshape(nm, R, B))
+                Wk.append(out["Wk"][:, R * ok:R * (ok + B1)].reshape(nm, R, B1) if B2 > 0 else None)
+                Wl.append(out["Wl"][:, R * ol:R * (ol + B2)].reshape(nm, R, B2) if B2 > 0 else None)
+                oa, ob = oa + A, ob + B
+                if B2 > 0:
+                    ok, ol = ok + B1, ol + B2
+            out["Wa"], out["Wb"], out["Wk"], out["Wl"] = Wa, Wb, Wk, Wl
+        return out
+
     # -- K-fold cross-validation (validate.kfold_predictions, kfold.py): every fold from the same reads of X ----------------
     def kfold_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,
                    ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:

@@ -28,7 +28,8 @@ coupled passes with cmtfpls_kfold_inner_coupled_tensor_f64 as the inner entry (D
 block with B = B1 B2 and wB = wK (x) wL), the entry leaves every model's wK and wL of every order-4 block, and a resample's loadings of
 such a block are [wA, wK, wL].  With
 EngineOptions.masked_folds_coupled, a ctPLS with a missing value in some block does the same through cmtfpls_cv_masked_coupled_f64
-(kfold.masked_models_coupled), every block's factors aligned by align_factors.
+(kfold.masked_models_coupled), every block's factors aligned by align_factors; with a block of order 4 and
+EngineOptions.masked_tensor_folds_coupled through cmtfpls_cv_masked_coupled_tensor_f64, such a block's loadings [wA, wK, wL].
 
 The route (kfold._route), the body of a pass (kfold._device_pass over kfold._weighted_models with kfold_weighted_xcov as the read; it
 allocates the per-mode stacks Wk / Wl) and the report (kfold._passes_report, kfold._masked_run_report) are the shared ones of kfold.py.
@@ -285,7 +286,10 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
                 _, n_iters[e] = refit_one(e)
                 refitted.append(e)
                 continue
-            if coupled:
+            if coupled and "tensor" in masked:                                        # an order-4 block: [wA, wK, wL]
+                modes = [[wa[e].T, wk[e].T, wl[e].T] if Xb.ndim == 4 else [wb[e].T] if Xb.ndim == 2 else [wa[e].T, wb[e].T]
+                         for Xb, wa, wb, wk, wl in zip(Xs, masked["Wa"], masked["Wb"], masked["Wk"], masked["Wl"])]
+            elif coupled:
                 modes = [[wb[e].T] if Xb.ndim == 2 else [wa[e].T, wb[e].T] for Xb, wa, wb in zip(Xs, masked["Wa"], masked["Wb"])]
             elif "tensor" in masked:                                                  # order-4 X: wB = wK (x) wL, the modes themselves
                 modes = [[masked["Wa"][e].T, masked["Wk"][e].T, masked["Wl"][e].T]]

@@ -43,7 +43,9 @@ Missing values in X (opt-in): a tPLS with EngineOptions.masked_folds refits ever
 EngineOptions.masked_folds_coupled and a NaN in at least one block refits every model in a workgroup of
 cmtfpls_cv_masked_coupled_f64 (masked_models_coupled, masked_predictions_coupled).  A tPLS whose X has order 4 and a NaN,
 with EngineOptions.masked_tensor_folds: the same two routines through cmtfpls_cv_masked_tensor_f64 and
-cmtfpls_cv_masked_tensor_models_f64, the rank-1 CP of the fold's contraction inside its workgroup.
+cmtfpls_cv_masked_tensor_models_f64, the rank-1 CP of the fold's contraction inside its workgroup.  A ctPLS with a
+block of order 4 and a NaN in some block, with EngineOptions.masked_tensor_folds_coupled: masked_models_coupled through
+cmtfpls_cv_masked_coupled_tensor_f64, the CP of every order-4 block's contraction inside the model's workgroup.
 """
 from __future__ import annotations
 
@@ -829,10 +831,52 @@ def coupled_lds_bytes(dims, I: int, M: int, R: int) -> int:
     return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 256 + Pmax + 2 * nmax * nmax + nmax + kmax + own)
 
 
+# a ctPLS with a block of order 4 among them (EngineOptions.masked_tensor_folds_coupled)
+COUPLED_TENSOR_FORM = "cmtfpls_cv_masked_coupled_tensor_f64"
+COUPLED_TENSOR_THREADS = 512              # the workgroup of cmtfpls_cv_masked_coupled_tensor_f64: the partial rows in its LDS
+
+
+def coupled_tensor_masked_lds_bytes(dims, tensor, I: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with tensor =
+    [(B1, B2), ..] ((0, 0): a block of order 2 or 3), the library's cmtfpls_cv_masked_coupled_tensor_lds_bytes: coupled_lds_bytes
+    with 512 partial rows, the Gram buffers over every matrix block's short side and every unfolding's, the long vector over the
+    matrix blocks alone, then the CP's wK, wL, v and unscaled contraction sized over the tensor blocks and its argmax scratch."""
+    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
+    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
+    Pmax = max(A * B for A, B in dims)
+    nmax = max([min(A, B) for A, B in mats] + [masked_tensor_side(*t) for t in tens])
+    kmax = max([max(A, B) for A, B in mats], default=0)
+    own = sum((R + 1) * (A + B) + I for A, B in dims)
+    cp = (max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens)
+          + COUPLED_TENSOR_THREADS // 64 + COUPLED_TENSOR_THREADS // 128)
+    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + COUPLED_TENSOR_THREADS + Pmax + 2 * nmax * nmax + nmax + kmax + cp + own)
+
+
+def coupled_tensor_masked_workspace_bytes(dims, tensor, I: int, M: int, R: int) -> int:
+    """The workspace of one resident model of cmtfpls_cv_masked_coupled_tensor_f64 (the library's
+    cmtfpls_cv_masked_coupled_tensor_workspace_bytes): per block the working copy, counts and means, then Yf | T, then the CP's
+    Zt | U | yl | vr sized for the largest tensor block."""
+    ptmax = max(A * B for (A, B), (_, B2) in zip(dims, tensor) if B2 > 0)
+    return 8 * (sum((I + 2) * A * B for A, B in dims) + I * M + I * R + 4 * ptmax)
+
+
+def wants_masked_coupled_tensor(pls, X) -> bool:
+    """Whether the coupled masked order-4 form is asked for: a ctPLS (X a list of blocks) with at least one block of order 4,
+    EngineOptions.masked_tensor_folds_coupled and a missing value in at least one block (of any order)."""
+    return (isinstance(X, list) and pls._get_engine().opt.masked_tensor_folds_coupled and any(b.ndim == 4 for b in X)
+            and any(has_missing(b) for b in X))
+
+
 def wants_masked_coupled(pls, X) -> bool:
-    """Whether the coupled masked form is asked for: a ctPLS (X a list of blocks) with EngineOptions.masked_folds_coupled and a
-    missing value in at least one block."""
-    return isinstance(X, list) and pls._get_engine().opt.masked_folds_coupled and any(has_missing(b) for b in X)
+    """Whether a coupled masked form is asked for: a ctPLS (X a list of blocks) with EngineOptions.masked_folds_coupled and a
+    missing value in at least one block, or wants_masked_coupled_tensor."""
+    return isinstance(X, list) and ((pls._get_engine().opt.masked_folds_coupled and any(has_missing(b) for b in X))
+                                    or wants_masked_coupled_tensor(pls, X))
+
+
+def coupled_form(pls, X) -> str:
+    """The entry that masked_models_coupled takes for the blocks X."""
+    return COUPLED_TENSOR_FORM if wants_masked_coupled_tensor(pls, X) else COUPLED_FORM
 
 
 def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol: float, max_iter: int,
@@ -842,29 +886,45 @@ def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndar
     on counts[m, r] copies of row r of every block paired with Y row yrow[m, r] (yrow None: identity) and predicts its rows with
     count 0.  Returns (out, None) -- out the backend's dict on the host (Ypred (n, R, I, M), n_iter, status, info, launches, with
     `factors` Wa, Wb (per block), coef, Q) -- or (None, why) with masked_models' declines.  Models with a status are the caller's to
-    refit."""
+    refit.  With a block of order 4 under EngineOptions.masked_tensor_folds_coupled: cmtfpls_cv_masked_coupled_tensor_f64,
+    `factors` then also Wk, Wl (per block, None for a block of order 2 or 3), and out["tensor"] = [(B1, B2), ..]."""
     R = pls.n_components
     I = counts.shape[1]
-    why, ctx = _masked_setup(pls, Xs, _names(Xs, True), Y, "cv_masked_coupled", "coupled masked model")
+    tensor = _tensor_dims(Xs, coupled=True) if wants_masked_coupled_tensor(pls, Xs) else None
+    why, ctx = _masked_setup(pls, Xs, _names(Xs, True), Y, "cv_masked_coupled_tensor" if tensor else "cv_masked_coupled",
+                             f"coupled masked {'order-4 ' if tensor else ''}model", tensor)
+    if why is None and tensor:
+        why = next((f"block {b} of order {X.ndim} (the masked form takes order 2, 3 and 4)" for b, X in enumerate(Xs)
+                    if X.ndim not in (2, 3, 4)), None)
     if why is not None:
         return None, why
     eng, be, M, upload = ctx
     dims = [_dims(X) for X in Xs]
     dev = be.device
 
+    def to_host(v):
+        return v.cpu().numpy() if isinstance(v, torch.Tensor) else v
+
     with eng.device_ctx():
         out = None
         if len(Xs) <= MAX_BLOCKS:                                                # (the entry declines more blocks itself)
-            out = be.cv_masked_coupled([upload(X, I) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)],
-                                       upload(Y, I), _to_dev(counts, dev, torch.int32),
-                                       None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol, max_iter, factors, max_ws_bytes)
+            data = ([upload(X, I) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)])
+            rest = (upload(Y, I), _to_dev(counts, dev, torch.int32), None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol,
+                    max_iter, factors, max_ws_bytes)
+            out = be.cv_masked_coupled_tensor(*data, tensor, *rest) if tensor else be.cv_masked_coupled(*data, *rest)
+        if out is None and tensor:
+            sides = [masked_tensor_side(A, *t) if t[1] > 0 else min(A, B) for (A, B), t in zip(dims, tensor)]
+            lds = coupled_tensor_masked_lds_bytes(dims, tensor, I, M, R)
+            return None, (f"shape outside {COUPLED_TENSOR_FORM} (it takes at most {MAX_BLOCKS} blocks, min(J, K) <= 64 in every block "
+                          f"of order 2 or 3 and the short side of every unfolding of a block of order 4 <= 64, M <= 64, R <= 16 and its "
+                          f"vectors within {COUPLED_LDS_CAP} bytes of LDS): {len(Xs)} blocks, largest short side = {sides}, M = {M}, "
+                          f"R = {R}, LDS = {lds} bytes")
         if out is None:
             return None, (f"shape outside {COUPLED_FORM} (it takes at most {MAX_BLOCKS} blocks, min(J, K) <= 64 in every block, "
                           f"M <= 64, R <= 16 and its vectors within {COUPLED_LDS_CAP} bytes of LDS): {len(Xs)} blocks, min(J, K) = "
                           f"{[min(A, B) for A, B in dims]}, M = {M}, R = {R}, LDS = {coupled_lds_bytes(dims, I, M, R)} bytes")
-        host = {k: ([t.cpu().numpy() for t in v] if isinstance(v, list) else v.cpu().numpy() if isinstance(v, torch.Tensor) else v)
-                for k, v in out.items()}
-        return dict(host, blocks=len(Xs)), None
+        host = {k: ([to_host(t) for t in v] if isinstance(v, list) else to_host(v)) for k, v in out.items()}
+        return dict(host, blocks=len(Xs), **({"tensor": tensor} if tensor else {})), None
 
 
 def _block_bits(mask: np.ndarray, nb: int):
@@ -880,9 +940,11 @@ def masked_coupled_report(out: dict, refitted, what: str) -> dict:
     nb = int(out["blocks"])
     form = (f"a workgroup per model on {nb} coupled blocks with missing values, {len(ok)} models in {out['launches']} "
             f"launch(es) ({COUPLED_FORM})")
+    if "tensor" in out:                                                          # order-4 blocks (masked_tensor_folds_coupled)
+        form = form.replace("coupled blocks", "coupled blocks, order-4 blocks among them,").replace(COUPLED_FORM, COUPLED_TENSOR_FORM)
     rep = _models_report(out, refitted, what, form, {"masked_blocks": _block_bits(out["info"][ok, 0], nb),
                                                      "masked_batches": _block_bits(out["info"][ok, 1], nb)},
-                         "a training row without an observed entry in some block")
+                         "a training row without an observed entry in some block", rank1="tensor" in out)
     return dict(rep, refitted=[int(m) for m in refitted])                        # behaviour: this form lists `refitted` even when empty
 
 
@@ -927,7 +989,7 @@ def _route(pls, X, device_folds: bool, models: bool = True, masked: bool = True,
     a ctPLS only when `on` (an EngineOptions switch), else it is REFIT with `why`."""
     if not device_folds:
         return OFF, "device folds switched off"
-    asks = ((MASKED, wants_masked, lambda: masked_forms(pls, X)[int(models)]), (MASKED_COUPLED, wants_masked_coupled, lambda: COUPLED_FORM))
+    asks = ((MASKED, wants_masked, lambda: masked_forms(pls, X)[int(models)]), (MASKED_COUPLED, wants_masked_coupled, lambda: coupled_form(pls, X)))
     # behaviour: permutation_test asks the coupled masked form first, kfold_run, repeated_kfold and bootstrap the tPLS one (at most one holds)
     for route, wants, entry in (asks[::-1] if coupled_first else asks) if masked else ():
         if wants(pls, X):

@@ -94,6 +94,13 @@ class EngineOptions:
     # tensor_folds_coupled, tensor_folds and masked_folds_coupled, each of which alone leaves these two routines on their refits
     # (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
     tensor_resamples_coupled: bool = False
+    # cross-validation of a ctPLS with at least one block of order 4 (among blocks of order 2, 3 and 4) AND a missing value in at least
+    # one block, of any order: the masked workgroup-per-model refits of masked_folds_coupled with every order-4 block on its
+    # I x A x B1 B2 view and the rank-1 CP of its contraction inside the model's workgroup (cmtfpls_cv_masked_coupled_tensor_f64,
+    # kfold.masked_models_coupled): leave-one-out and K-fold Q2Y, the permutation test, repeated K-fold and the bootstrap
+    # (per-mode stacks [wA, wK, wL]); opt-in, and separate from masked_folds_coupled, which alone declines such a model to the refits
+    # (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
+    masked_tensor_folds_coupled: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -25,7 +25,8 @@ taken: the inner entry is then kfold_inner_coupled_tensor in the gro
 With EngineOptions.masked_folds, a tPLS whose X has missing values runs every permutation x fold as a workgroup of
 cmtfpls_cv_masked_models_f64 instead (kfold.masked_fold_numerators; X of order 4 with EngineOptions.masked_tensor_folds:
 cmtfpls_cv_masked_tensor_models_f64); with EngineOptions.masked_folds_coupled, a ctPLS
-with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64.
+with a missing value in some block runs them as workgroups of cmtfpls_cv_masked_coupled_f64, and with a block of
+order 4 and EngineOptions.masked_tensor_folds_coupled of cmtfpls_cv_masked_coupled_tensor_f64.
 
 The route (kfold._route: the coupled masked form is asked first, a ctPLS without coupled_permutations refits), the body of a pass
 (kfold._device_pass with kfold_wide_xcov as the read) and the report (kfold._passes_report) are the shared ones of kfold.py.

@@ -11,8 +11,9 @@ missing values takes ``cmtfpls_loo_xcov_tensor_f64`` when ``EngineOptions.tensor
 each fold's cross-covariance inside its workgroup).  A fitted ``ctPLS`` on complete data (at most 8 blocks of order 2 or
 3, min(J, K) <= 256 in every block, M <= 128, R <= 64) takes ``cmtfpls_loo_xcov_coupled_f64``: a workgroup per fold on the
 cross-covariances of all blocks, which share the fold's score; with a NaN in a block and
-``EngineOptions.masked_folds_coupled`` it takes ``cmtfpls_cv_masked_coupled_f64``; anything else refits ``ctPLS`` once per fold and
-says why.  With ``EngineOptions.tensor_resamples_coupled`` a ``ctPLS`` on complete data with a block of order 4 among blocks of
+``EngineOptions.masked_folds_coupled`` it takes ``cmtfpls_cv_masked_coupled_f64``, and with a block of order 4 among them and
+``EngineOptions.masked_tensor_folds_coupled`` ``cmtfpls_cv_masked_coupled_tensor_f64`` (the rank-1 CP of every order-4 block's
+contraction inside the model's workgroup); anything else refits ``ctPLS`` once per fold and says why.  With ``EngineOptions.tensor_resamples_coupled`` a ``ctPLS`` on complete data with a block of order 4 among blocks of
 order 2, 3 and 4 takes ``cmtfpls_loo_xcov_coupled_tensor_f64``: the same workgroup per fold with the rank-1 CP of every order-4 block's
 cross-covariance inside it.  X with missing values
 (order 2 or 3, Y complete) takes ``cmtfpls_cv_masked_f64`` when ``EngineOptions.masked_folds`` is on (a workgroup per fold with
@@ -23,9 +24,9 @@ the refits.  Which form ran is recorded on the model (``q2y_report_``).
 """
 import numpy as np
 
-from .kfold import (COUPLED_FORM, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
-                    _masked_declined, _tensor_dims, _training_data, has_missing, masked_predictions, masked_predictions_coupled,
-                    refit_predictions, wants_masked_coupled, wants_masked_tensor)
+from .kfold import (MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
+                    _masked_declined, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
+                    masked_predictions_coupled, refit_predictions, wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
@@ -189,10 +190,12 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
     """_loo_device for a fitted ctPLS: (Y_pred, None) from a device form (q2y_report_ set), or (None, why)."""
     Xs, Y = _training_data(pls)
     I = Y.shape[0]
-    if wants_masked_coupled(pls, Xs):                                     # EngineOptions.masked_folds_coupled: cmtfpls_cv_masked_coupled_f64
+    # EngineOptions.masked_folds_coupled: cmtfpls_cv_masked_coupled_f64; masked_tensor_folds_coupled with a block of order 4:
+    # cmtfpls_cv_masked_coupled_tensor_f64 (DESIGN 8v)
+    if wants_masked_coupled(pls, Xs):
         pred, rep = masked_predictions_coupled(pls, Xs, Y, np.arange(I), I, tol, max_iter)
         if pred is None:
-            return None, _masked_declined(COUPLED_FORM, rep)
+            return None, _masked_declined(coupled_form(pls, Xs), rep)
         pls.q2y_report_ = dict(rep, blocks=len(Xs), n_iter_total=int(np.sum(rep["n_iter"])))
         return pred[-1].reshape(Y.shape), None
     tensor = _wants_loo_coupled_tensor(pls, Xs)                           # EngineOptions.tensor_resamples_coupled (DESIGN 8t)
@@ -308,7 +311,9 @@ def kfold_predictions(pls_tensor, n_splits: int = 5, folds=None, tol: float = 1e
     With missing values in X a tPLS takes cmtfpls_cv_masked_f64 under EngineOptions.masked_folds, and a ctPLS with a NaN in some
     block takes cmtfpls_cv_masked_coupled_f64 under EngineOptions.masked_folds_coupled (every fold a workgroup, leave-one-out is
     n_splits = I), and a tPLS whose X has order 4 takes cmtfpls_cv_masked_tensor_f64 under
-    EngineOptions.masked_tensor_folds; the permutation test, repeated K-fold and the bootstrap below route the same way.
+    EngineOptions.masked_tensor_folds, and a ctPLS with a block of order 4 and a NaN in some block takes
+    cmtfpls_cv_masked_coupled_tensor_f64 under EngineOptions.masked_tensor_folds_coupled; the permutation test, repeated
+    K-fold and the bootstrap below route the same way.  What still refits by class is nested K-fold of data with missing values.
     Which form ran is recorded on the model (``q2y_report_``)."""
     from .kfold import kfold_run
 
@@ -337,6 +342,8 @@ def permutation_test_q2y(pls_tensor, n_permutations: int = 99, n_splits: int = 5
     per pass, permutation.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes cmtfpls_cv_masked_models_f64 when
     EngineOptions.masked_folds is on: every permutation x fold is a workgroup with the reference's masked arithmetic (DESIGN 8i);
     X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when EngineOptions.masked_tensor_folds is on.
+    A ctPLS with a NaN in some block takes cmtfpls_cv_masked_coupled_f64 under EngineOptions.masked_folds_coupled, with a
+    block of order 4 cmtfpls_cv_masked_coupled_tensor_f64 under EngineOptions.masked_tensor_folds_coupled.
     Anything else refits every fold of every permutation.  Which form ran is recorded on the model (``q2y_report_``)."""
     from .permutation import permutation_test
 
@@ -355,7 +362,9 @@ def get_q2y_repeated_kfold(pls_tensor, n_splits: int = 5, n_repeats: int = 10, f
     per pass and block, repeated.py).  A tPLS whose X has missing values (order 2 or 3, Y complete) takes
     cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every split x fold is a workgroup with the reference's
     masked arithmetic; X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when
-    EngineOptions.masked_tensor_folds is on.  Anything else refits every fold of every split.  Which form ran is recorded on the model
+    EngineOptions.masked_tensor_folds is on.  A ctPLS with a NaN in some block takes cmtfpls_cv_masked_coupled_f64 under
+    EngineOptions.masked_folds_coupled, with a block of order 4 cmtfpls_cv_masked_coupled_tensor_f64 under
+    EngineOptions.masked_tensor_folds_coupled.  Anything else refits every fold of every split.  Which form ran is recorded on the model
     (``q2y_report_``)."""
     from .repeated import repeated_kfold
 
@@ -404,7 +413,10 @@ def bootstrap_factors(pls_tensor, n_resamples: int = 100, resamples=None, random
     cmtfpls_cv_masked_models_f64 when EngineOptions.masked_folds is on: every resample is a count-weighted workgroup with the
     reference's masked arithmetic; X of order 4 with missing values takes cmtfpls_cv_masked_tensor_models_f64 when
     EngineOptions.masked_tensor_folds is on, its per-mode stacks [wA, wK, wL].  A tPLS whose X has order 4 takes the same passes with cmtfpls_kfold_inner_tensor_f64
-    when EngineOptions.tensor_folds is on.  Anything else refits every resample.  Which form ran is recorded on the model
+    when EngineOptions.tensor_folds is on.  A ctPLS with a NaN in some block takes cmtfpls_cv_masked_coupled_f64 under
+    EngineOptions.masked_folds_coupled, with a block of order 4 cmtfpls_cv_masked_coupled_tensor_f64 under
+    EngineOptions.masked_tensor_folds_coupled, such a block's per-mode stacks [wA, wK, wL].  Anything else refits every
+    resample.  Which form ran is recorded on the model
     (``bootstrap_report_``)."""
     from .bootstrap import bootstrap
 

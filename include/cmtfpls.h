@@ -744,7 +744,7 @@ int cmtfpls_cv_masked_tensor_models_f64(const double* X, const double* Y, const 
  * a block's min(A, B) > 64, M > 64, R > 16 or the LDS exceeds 150 KB. */
 typedef struct {
   const double* X;        /* I x A*B row-major, the original block, NaN = missing */
-  int order;              /* 2 (a matrix: A = 1) or 3; 4 (B = B1 B2) for cmtfpls_loo_xcov_coupled_tensor_f64 alone */
+  int order;              /* 2 (a matrix: A = 1) or 3; 4 (B = B1 B2) for cmtfpls_cv_masked_coupled_tensor_f64 alone */
   int A, B;
 } cmtfpls_cv_coupled_block;
 size_t cmtfpls_cv_masked_coupled_workspace_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, int I, int M, int R);
@@ -753,6 +753,32 @@ int cmtfpls_cv_masked_coupled_f64(const cmtfpls_cv_coupled_block* blocks, int nb
                                   const int* yrow, int nm, int I, int M, int R, double tol, int max_iter, int model0, int nmodels,
                                   double* Ypred, double* Wa, double* Wb, double* coef, double* Q, int* n_iter, int* status,
                                   int* info, void* ws, size_t ws_bytes, void* stream);
+/* cmtfpls_cv_masked_coupled_f64 for a coupled model with blocks of order 4 next to blocks of order 2 and 3.  A block I x A x B1 x B2
+ * is given as I x A*B with order 4 and B = B1 B2; dims is a HOST array of 2 nb ints, (B1, B2) for a block of order 4 and (0, 0) for
+ * another (B2 = 1 is still a tensor).  Every step runs on the I x A x B view unchanged; only the loading of a tensor block differs:
+ * the rank-1 CP of its contraction Z (A x B1 x B2, already / c_p * n when the block is masked) inside the workgroup
+ * (parafac(Z, 1, tol, init="svd", normalize_factors=True), as cmtfpls_rank1_tensor_f64 states it), wB = wK (x) wL in C order.  One
+ * 512-thread workgroup per model.  The arguments, outputs, status and info are cmtfpls_cv_masked_coupled_f64's (Wb of a tensor
+ * block receives wK (x) wL), with Wk (nullable, nm x R sumB1; model m's tensor block b is the R x B1_b matrix at m * R * sumB1 +
+ * R * (the B1 of the tensor blocks before b)) and Wl (nullable, nm x R sumB2, likewise), the sums over the tensor blocks only.
+ * ws >= nmodels * cmtfpls_cv_masked_coupled_tensor_workspace_bytes(...): cmtfpls_cv_masked_coupled_workspace_bytes plus 4 Ptmax
+ * doubles (the CP's Zt | U | yl | vr, Ptmax = max A_b B_b over the tensor blocks).
+ * cmtfpls_cv_masked_coupled_tensor_lds_bytes: in doubles 3 I + 3 M + 2 R^2 + R M + 3 R + 512 + Pmax + 2 nmax^2 + nmax + kmax +
+ * max B1 + max B2 + max B1 B2 + max(A, B1, B2) + 12 + sum_b [(R + 1)(A_b + B_b) + I], nmax over min(A_b, B_b) of the matrix blocks
+ * and the shorter side of every unfolding of every tensor block, kmax over max(A_b, B_b) of the matrix blocks alone, the four maxima
+ * over the tensor blocks; 0 for a bad argument or description.
+ * CMTFPLS_EINVAL (before any pointer is read) for what cmtfpls_cv_masked_coupled_f64 calls a bad argument or block, dims == NULL, a
+ * negative dim, B1 * B2 != B, order 4 with B2 = 0, another order with B2 > 0, order > 4, or no block of order 4 (that is
+ * cmtfpls_cv_masked_coupled_f64's call).  CMTFPLS_EUNSUPPORTED when nb > 8, a matrix block's min(A, B) > 64, a tensor block has an
+ * unfolding whose shorter side is > 64, M > 64, R > 16 or the LDS exceeds 150 KB. */
+size_t cmtfpls_cv_masked_coupled_tensor_workspace_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, const int* dims, int I, int M,
+                                                        int R);
+size_t cmtfpls_cv_masked_coupled_tensor_lds_bytes(const cmtfpls_cv_coupled_block* blocks, int nb, const int* dims, int I, int M, int R);
+int cmtfpls_cv_masked_coupled_tensor_f64(const cmtfpls_cv_coupled_block* blocks, int nb, const int* dims, const double* Y,
+                                         const int* counts, const int* yrow, int nm, int I, int M, int R, double tol, int max_iter,
+                                         int model0, int nmodels, double* Ypred, double* Wa, double* Wb, double* Wk, double* Wl,
+                                         double* coef, double* Q, int* n_iter, int* status, int* info, void* ws, size_t ws_bytes,
+                                         void* stream);
 /* ---- K-fold cross-validation with every fold served by the same reads of X (validate.kfold_predictions) ------------------------
  * The folds of a K-fold split share X_0 (the caller's uncentred tensor, never written); a fold differs only in its training rows,
  * their means and its loadings.  Per component: kfold_inner (the inner loop of every fold on its training cross-covariance, a
