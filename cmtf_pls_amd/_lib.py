@@ -70,6 +70,8 @@ SIGNATURES = {
     "cmtfpls_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "cmtfpls_xcov_f32": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
     "cmtfpls_xcov_f64": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    "cmtfpls_xcov_bf16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    "cmtfpls_xcov_f16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
     "cmtfpls_quadform_f64": (c_int, [_P, c_int, _P, _P, _P, _P]),
     "cmtfpls_xcov_iterate_f64": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P, c_size_t, _P]),
     "cmtfpls_s_downdate_f64": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
@@ -89,17 +91,23 @@ SIGNATURES = {
     "cmtfpls_xcov_stats_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "cmtfpls_xcov_stats_f32": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_xcov_stats_f64": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_xcov_stats_bf16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_xcov_stats_f16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_xcov_ssq_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "cmtfpls_xcov_ssq_f32": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_xcov_ssq_f64": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_score_contract_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "cmtfpls_score_contract_f32": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_score_contract_f64": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_score_contract_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_score_contract_f16": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kr_axpy_f64": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P]),
     "cmtfpls_xcov_f32_mixed": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
     "cmtfpls_mttkrp_f32_mixed": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
     "cmtfpls_mttkrp_f32": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
     "cmtfpls_mttkrp_f64": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
+    "cmtfpls_mttkrp_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
+    "cmtfpls_mttkrp_f16": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
     "cmtfpls_score_f32": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P]),
     "cmtfpls_score_f64": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P]),
     "cmtfpls_score_s_f64": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -13,7 +13,9 @@ import torch
 
 from . import _lib
 
-_SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
+_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
+HALF_DTYPES = (torch.bfloat16, torch.float16)                # 16-bit storage: only ever read, converted to f64 on load
+_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp")   # the entries that have _bf16 / _f16 forms
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -106,9 +108,16 @@ class HipBackend:
     def zeros(self, *shape, dtype=torch.float64) -> torch.Tensor:
         return torch.zeros(*shape, dtype=dtype, device=self.device)
 
+    def has_half(self, base: str) -> bool:
+        """Whether entry `base` has a form for 16-bit storage (bfloat16 / float16): the read-only matrix-core passes only."""
+        return base in _HALF_ENTRIES and hasattr(self.lib, f"cmtfpls_{base}_bf16") and hasattr(self.lib, f"cmtfpls_{base}_f16")
+
     def _fn(self, base: str, X: torch.Tensor):
         if X.dtype not in _SUFFIX:
             raise TypeError(f"X must be float32 or float64 on device, got {X.dtype}")
+        if X.dtype in HALF_DTYPES and not self.has_half(base):
+            raise TypeError(f"{base} has no form for {X.dtype} storage (16-bit X is only read by {', '.join(_HALF_ENTRIES)}); "
+                            "use a float32 copy")
         assert X.is_contiguous() and X.device == self.device
         return getattr(self.lib, f"cmtfpls_{base}_{_SUFFIX[X.dtype]}")
 
@@ -231,6 +240,8 @@ class HipBackend:
         f32-stored X).  More than 64 responses: tiles of 64, one pass over X each (inside the C entry)."""
         I, P = X2.shape
         M = Y.shape[1]
+        if X2.dtype in HALF_DTYPES and (mixed or not self.has_half("xcov")):
+            return None
         ws = self._workspace("contract", self.lib.cmtfpls_xcov_workspace_bytes(I, P, M))
         S = out if out is not None else self.empty(M, P)
         fn = self.lib.cmtfpls_xcov_f32_mixed if (mixed and X2.dtype == torch.float32) else self._fn("xcov", X2)
@@ -281,7 +292,7 @@ class HipBackend:
         (S, stats) with stats[:P] the sums and stats[P:] the sums of squares, or None for more than 64 responses."""
         I, P = X2.shape
         M = Y.shape[1]
-        if M > 64 or not X2.is_contiguous():
+        if M > 64 or not X2.is_contiguous() or (X2.dtype in HALF_DTYPES and not self.has_half("xcov_stats")):
             return None
         ws = self._workspace("contract", self.lib.cmtfpls_xcov_stats_workspace_bytes(I, P, M))
         stats = self.empty(2 * P)
@@ -406,6 +417,8 @@ class HipBackend:
         """out (I, R) = X_(0) (WA (.) WB); None when R > 32 or the loadings do not fit LDS."""
         R = WA.shape[1]
         assert WA.is_contiguous() and WB.is_contiguous() and out.stride(1) == 1
+        if X2.dtype in HALF_DTYPES and (mixed or not self.has_half("mttkrp")):
+            return None
         fn = self.lib.cmtfpls_mttkrp_f32_mixed if (mixed and X2.dtype == torch.float32) else self._fn("mttkrp", X2)
         rc = fn(_ptr(X2), X2.shape[0], A, B, _ptr(WA), _ptr(WB), R, _ptr(out), out.stride(0), self._stream())
         return self._form(rc, "mttkrp", out)
@@ -427,7 +440,7 @@ class HipBackend:
         """t = X w - shift - sub_own and Z = X^T c, c = alpha (t + add_other), in one read of X (cmtfpls_score_contract_*); csum[0] =
         sum(c) when given; None when the row fits neither the registers of one workgroup nor those of 16 (the caller then makes the two passes)."""
         I, P = X2.shape
-        if not X2.is_contiguous() or P != A * B:
+        if not X2.is_contiguous() or P != A * B or (X2.dtype in HALF_DTYPES and not self.has_half("score_contract")):
             return None
         for v in (sub_own, add_other):
             assert v is None or (v.is_contiguous() and v.numel() == I and v.dtype == torch.float64)

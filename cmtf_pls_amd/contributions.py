@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _host, _kept_training_blocks, _training_stats
-from .tpls import _as_torch_dtype, to_device_copy
+from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
 
 MAX_CELLS = 1 << 28        # n * P above which cells=True is refused (2 GiB per returned float64 array)
 
@@ -56,6 +56,7 @@ def _mode_sums(first, rest, shape):
     return out
 
 
+@reports_storage_upcast("contributions_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
 def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bool = True) -> dict:
     from .cmtf import ctPLS
 
@@ -73,14 +74,14 @@ def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bo
             if Xs is None:
                 raise ValueError("the model was fitted with copy_X=False, so the training X was not kept: pass X")
             idx = _row_list(rows, int(st.T.shape[0]))
-            Xd = [to_device_copy(x, blk.dtype or torch.float64, dev, copy=False) for x, blk in zip(Xs, st.blocks)]
+            Xd = [to_device_read(x, blk.dtype or torch.float64, dev, pls=pls) for x, blk in zip(Xs, st.blocks)]
             scores, pform, proj_reads = st.T, None, 0
         else:
             Xs = list(X) if coupled else [X]
             if coupled and len(Xs) != pls.Xs_len:
                 raise ValueError(f"Training Xs has {pls.Xs_len} blocks, while the new Xs has {len(Xs)}")
             idx = _row_list(rows, int(Xs[0].shape[0]))
-            Xd = [to_device_copy(x, _as_torch_dtype(pls._dtype, x), dev, copy=False) for x in Xs]
+            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls) for x in Xs]
             scores = pls._project_dev(Xd if coupled else Xd[0])           # transform's projection: shape checks, forms, bits
             pform = "sequential passes on private copies (f32 matrix precision)" if pls._mixed else eng.last_projection["form"]
             proj_reads = _PROJECTION_READS.get(pform)

@@ -48,6 +48,34 @@ struct VecOf {
   using type = Pack<T, N>;
 };
 
+// 16-bit storage of X (bfloat16 / IEEE half): the raw bits, only ever READ and converted to f64 on load.  Both conversions are
+// exact (bf16 is the upper half of an f32 word; f16 -> f32 is the hardware convert), so an element enters the f64 arithmetic
+// with exactly the value the caller stored; NaN stays NaN and Inf stays Inf.
+struct bf16_t { uint16_t b; };
+struct f16_t { uint16_t b; };
+// The one conversion of a stored element of X to the f64 it is computed with.
+template <typename T>
+__device__ __forceinline__ double to_f64(T x) { return (double)x; }
+template <>
+__device__ __forceinline__ double to_f64<bf16_t>(bf16_t x) { return (double)__uint_as_float((uint32_t)x.b << 16); }
+template <>
+__device__ __forceinline__ double to_f64<f16_t>(f16_t x) {
+  _Float16 h;
+  __builtin_memcpy(&h, &x.b, 2);
+  return (double)(float)h;
+}
+// ... with NaN (a missing value) -> 0 when MASKED: on the stored type for f32 / f64, on the converted value for 16 bits.
+template <bool MASKED, typename T>
+__device__ __forceinline__ double to_f64_masked(T x) {
+  if constexpr (sizeof(T) == 2) {
+    const double d = to_f64(x);
+    return (!MASKED || d == d) ? d : 0.0;
+  } else {
+    if (MASKED) x = (x == x) ? x : (T)0;
+    return (double)x;
+  }
+}
+
 // Streaming accesses of X: every element is touched once per sweep, so loads and stores are marked
 // non-temporal.  Measured on cfg-2 (profiles/r01c_tune_sweeps.txt): nt loads take the read sweeps from
 // 5.76 / 5.86 TB/s to 6.42 / 6.53 TB/s (contraction / score); nt stores +2 % on the deflation sweep.

@@ -15,6 +15,7 @@
 //   B operand of MFMA e = W[c0 + 4*kq + e][r = l & 15] = sA[j][r] * sB[k][r]   (B[k = l>>4][j = l&15])
 //   all four MFMAs accumulate into the same D: D[(l>>4) + 4*g][l & 15] = M[i0 + (l>>4) + 4*g][r].
 // One wavefront owns 16 whole rows (no partials, fixed summation order).
+// 16-bit storage (bf16_t / f16_t): this tile form for every shape, the lane's 4 columns as one 8-byte vector, converted by to_f64.
 //
 // Round-2 negative results (kept out of the code): (1) the operand layout makes every load instruction touch
 // 16 rows x 64 B, a pattern that by itself tops out at 6.0 TB/s against 7.0-7.2 TB/s for row-contiguous reads
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(NT) void mttkrp_kernel(const T* __restrict__ X, int
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const bool ok = FAST || (rok && (c + e < P));
-          const double a = ok ? (double)x[s].e[e] : 0.0;
+          const double a = ok ? to_f64(x[s].e[e]) : 0.0;
           int j = w.j, k = w.k + e;
           if (!VEC && k >= B) { j += k / B; k = k % B; }   // scalar path: a 4-column group may straddle a j boundary
           const bool wok = FAST || (c + e < P);
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256) void mttkrp_jk_kernel(const T* __restrict__ X,
         for (int p = 0; p < CH; ++p)
 #pragma unroll
           for (int e = 0; e < V; ++e) {
-            accs[p % NACC] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)buf[p].e[e], breg[(CC < 0 ? 0 : CC) * CH + p][e], accs[p % NACC], 0, 0, 0);
+            accs[p % NACC] = __builtin_amdgcn_mfma_f64_16x16x4f64(to_f64(buf[p].e[e]), breg[(CC < 0 ? 0 : CC) * CH + p][e], accs[p % NACC], 0, 0, 0);
           }
       } else {
         const double* __restrict__ sbc = sB + (size_t)(c * CH * 4 * V + V * kq) * RP + jr;
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(256) void mttkrp_jk_kernel(const T* __restrict__ X,
         for (int p = 0; p < CH; ++p)
 #pragma unroll
           for (int e = 0; e < V; ++e)
-            accs[p % NACC] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)buf[p].e[e], sbc[(size_t)(p * 4 * V + e) * RP], accs[p % NACC], 0, 0, 0);
+            accs[p % NACC] = __builtin_amdgcn_mfma_f64_16x16x4f64(to_f64(buf[p].e[e]), sbc[(size_t)(p * 4 * V + e) * RP], accs[p % NACC], 0, 0, 0);
       }
       if (c == npj - 1) {                                   // end of the j-block: fold WA in, start a fresh accumulator
         const double* __restrict__ sa = sA + (size_t)(jb * 16 + kq) * RP + jr;
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(256) void mttkrp_kj_kernel(const T* __restrict__ X,
         for (int n = 0; n < NL; ++n)
 #pragma unroll
           for (int e = 0; e < V; ++e) {
-            acc[n][e] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)buf[h][n].e[e], wa, acc[n][e], 0, 0, 0);
+            acc[n][e] = __builtin_amdgcn_mfma_f64_16x16x4f64(to_f64(buf[h][n].e[e]), wa, acc[n][e], 0, 0, 0);
           }
       }
       if (c == cpp - 1) {                                 // end of the pass: fold WB in, start fresh accumulators
@@ -409,7 +410,7 @@ __global__ __launch_bounds__(256) void mttkrp_kj4_kernel(const T* __restrict__ X
         for (int n = 0; n < NL; ++n)
 #pragma unroll
           for (int e = 0; e < V; ++e) {
-            const double a = (double)buf[h][n].e[e];
+            const double a = to_f64(buf[h][n].e[e]);
 #pragma unroll
             for (int g = 0; g < NG; ++g) acc[n][e][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, wa[g], acc[n][e][g], 0, 0, 0);
           }
@@ -461,7 +462,7 @@ static int run_mttkrp(const T* X, int64_t I, int A, int B, const double* WA, con
   const size_t lds = (size_t)(A + B) * 16 * rt * sizeof(double);
   if (lds > kMttkrpLdsMax) { set_error("mttkrp: loadings exceed LDS"); return CMTFPLS_EUNSUPPORTED; }
 #ifndef CMTFPLS_MTTKRP_TILE_ONLY
-  {
+  if constexpr (sizeof(T) != 2) {                             // 16-bit storage takes the tile form below for every shape
     // the j-block form (round 3): whole samples per wavefront, WB as the plain B operand (registers or LDS)
     constexpr int V = 16 / (int)sizeof(T);
     const size_t lds1 = (size_t)(A + B) * 16 * sizeof(double);
@@ -585,5 +586,12 @@ int cmtfpls_mttkrp_f32(const float* X, int64_t I, int A, int B, const double* WA
 }
 int cmtfpls_mttkrp_f64(const double* X, int64_t I, int A, int B, const double* WA, const double* WB, int R, double* out, int ldo, void* stream) {
   return run_mttkrp<double>(X, I, A, B, WA, WB, R, out, ldo, (hipStream_t)stream);
+}
+// 16-bit storage (raw bits, converted on load): the tile form, 8-byte loads of 4 columns per lane
+int cmtfpls_mttkrp_bf16(const uint16_t* X, int64_t I, int A, int B, const double* WA, const double* WB, int R, double* out, int ldo, void* stream) {
+  return run_mttkrp<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, A, B, WA, WB, R, out, ldo, (hipStream_t)stream);
+}
+int cmtfpls_mttkrp_f16(const uint16_t* X, int64_t I, int A, int B, const double* WA, const double* WB, int R, double* out, int ldo, void* stream) {
+  return run_mttkrp<f16_t>(reinterpret_cast<const f16_t*>(X), I, A, B, WA, WB, R, out, ldo, (hipStream_t)stream);
 }
 }

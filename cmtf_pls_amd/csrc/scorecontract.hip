@@ -19,6 +19,8 @@
 // rank-one correction X_c^T c = X^T c - (1^T c) mean of an uncentred X needs (a 65536-element sum_kernel launch otherwise).
 // Shapes: B % V == 0, no missing values; rows of at most 1024 * V * 4 (f32) / 1024 * V * 8 (f64) elements = 16384 in this form, up to
 // 16 x 16384 (f32) / 16 x 8192 (f64) elements in the split form further down (round 4: the north-star 256 x 256 row).
+// 16-bit storage (bf16_t / f16_t): V = 8, NV in {1, 2} (16 f64 accumulators per lane as f32 has at NV = 4), rows of 4096..16384
+// elements, B % 8 == 0; the rows form only -- no 16-bit instantiation of the split form.
 #include "common.hpp"
 
 namespace cmtfpls {
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(1024) void score_contract_rows_kernel(const T* __re
     for (int n = 0; n < NV; ++n) {
       double dn = 0.0;
 #pragma unroll
-      for (int e = 0; e < V; ++e) dn = fma((double)buf[n].e[e], wb[KC ? 0 : n][e], dn);
+      for (int e = 0; e < V; ++e) dn = fma(to_f64(buf[n].e[e]), wb[KC ? 0 : n][e], dn);
       d = fma(WL ? wls[j0 * NV + n] : wa[WL ? 0 : n], dn, d);       // (WL: the lane's NV loadings are contiguous in LDS)
     }
     d = wave_sum(d);
@@ -131,10 +133,20 @@ __global__ __launch_bounds__(1024) void score_contract_rows_kernel(const T* __re
 #pragma unroll
         for (int e = 0; e < V; ++e) asm volatile("" : "+v"(buf[n].e[e]));
     }
+    if constexpr (sizeof(T) == 2) {                          // the same for 16-bit storage, on the four words of a vector
+#pragma unroll
+      for (int n = 0; n < NV; ++n) {
+        uint32_t w[4];
+        __builtin_memcpy(w, &buf[n], 16);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(w[k]));
+        __builtin_memcpy(&buf[n], w, 16);
+      }
+    }
 #pragma unroll
     for (int n = 0; n < NV; ++n)
 #pragma unroll
-      for (int e = 0; e < V; ++e) acc[n][e] = fma(ti, (double)buf[n].e[e], acc[n][e]);
+      for (int e = 0; e < V; ++e) acc[n][e] = fma(ti, to_f64(buf[n].e[e]), acc[n][e]);
   };
   const int64_t last = I - 1;
   if (r < I) load(bufA, r);
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(1024) void score_contract_split_kernel(const T* __r
           for (int n = 0; n < NV; ++n) {
             double dn = 0.0;
 #pragma unroll
-            for (int e = 0; e < V; ++e) dn = fma((double)buf[j][n].e[e], wb[KC ? 0 : n][e], dn);
+            for (int e = 0; e < V; ++e) dn = fma(to_f64(buf[j][n].e[e]), wb[KC ? 0 : n][e], dn);
             d = fma(wa[n], dn, d);
           }
           d = wave_sum(d);
@@ -285,7 +297,7 @@ __global__ __launch_bounds__(1024) void score_contract_split_kernel(const T* __r
 #pragma unroll
           for (int n = 0; n < NV; ++n)
 #pragma unroll
-            for (int e = 0; e < V; ++e) acc[n][e] = fma(ti, (double)bc[n].e[e], acc[n][e]);
+            for (int e = 0; e < V; ++e) acc[n][e] = fma(ti, to_f64(bc[n].e[e]), acc[n][e]);
         }
         par ^= 1;
       }
@@ -320,13 +332,18 @@ static int run_score_contract(const T* X, int64_t I, int A, int B, const double*
   const int64_t P = (int64_t)A * B;
   const int64_t stride = (int64_t)1024 * V;
   const int nv = (int)((P + stride - 1) / stride);
-  constexpr int kMaxNV = (V == 4) ? 4 : 8;
+  constexpr int kMaxNV = (V == 8) ? 2 : (V == 4) ? 4 : 8;   // 16 f64 accumulators per lane at 16-bit and f32 storage, 16 at f64
   if ((B % V) != 0 || P < stride / 2 || P >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(X) & 15) != 0) {
     set_error("score_contract: shape outside the row-in-registers form; use score + mode0_contract");
     return CMTFPLS_EUNSUPPORTED;
   }
   const bool kc = (stride % B) == 0;
-  if (nv > kMaxNV) {                                          // the row split over G workgroups
+  if constexpr (sizeof(T) == 2) {
+    if (nv > kMaxNV) {                                        // 16-bit storage has the rows form only
+      set_error("score_contract: 16-bit rows beyond 16384 elements; use mttkrp + xcov");
+      return CMTFPLS_EUNSUPPORTED;
+    }
+  } else if (nv > kMaxNV) {                                   // the row split over G workgroups
     // vectors per lane and slab: 4 (16384 f32 / 8192 f64 elements per workgroup); 2 for f32 rows whose lanes meet different mode-2
     // indices in their vectors (4 sets of wB would spill: 0.62 ms against 0.54 ms of two passes at 8192 x 250 x 200)
     const int NVS = (sizeof(T) == 4 && !kc) ? 2 : 4;
@@ -371,11 +388,13 @@ static int run_score_contract(const T* X, int64_t I, int A, int B, const double*
   } while (0)
   if (nv <= 1) SCL(1);
   else if (nv <= 2) SCL(2);
-  else if (nv <= 4) SCL(4);
-  else if constexpr (kMaxNV >= 8) {
-    if (kc && P == 8 * stride && A <= kScLdsA)
-      hipLaunchKernelGGL((score_contract_rows_kernel<T, 8, true, true>), dim3(grid), dim3(1024), 0, st, X, I, (unsigned)P, B, wA, wB, shift, sub_own, add_other, alpha, t, part, csum_part);
-    else SCL(8);
+  else if constexpr (kMaxNV >= 4) {
+    if (nv <= 4) SCL(4);
+    else if constexpr (kMaxNV >= 8) {
+      if (kc && P == 8 * stride && A <= kScLdsA)
+        hipLaunchKernelGGL((score_contract_rows_kernel<T, 8, true, true>), dim3(grid), dim3(1024), 0, st, X, I, (unsigned)P, B, wA, wB, shift, sub_own, add_other, alpha, t, part, csum_part);
+      else SCL(8);
+    }
   }
 #undef SCL
   launch_reduce_rows(part, grid, P, Z, st);
@@ -401,5 +420,19 @@ int cmtfpls_score_contract_f64(const double* X, int64_t I, int A, int B, const d
                                const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
                                void* ws, size_t ws_bytes, void* stream) {
   return run_score_contract<double>(X, I, A, B, wA, wB, shift, sub_own, add_other, alpha, t, Z, csum, ws, ws_bytes, (hipStream_t)stream);
+}
+// 16-bit storage (raw bits, converted on load): the rows form with 8 elements per 16-byte vector, 1 or 2 vectors per lane --
+// B % 8 == 0 and 4096 <= A * B <= 16384; no split form
+int cmtfpls_score_contract_bf16(const uint16_t* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* shift,
+                                const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
+                                void* ws, size_t ws_bytes, void* stream) {
+  return run_score_contract<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, A, B, wA, wB, shift, sub_own, add_other, alpha, t, Z, csum,
+                                    ws, ws_bytes, (hipStream_t)stream);
+}
+int cmtfpls_score_contract_f16(const uint16_t* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* shift,
+                               const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
+                               void* ws, size_t ws_bytes, void* stream) {
+  return run_score_contract<f16_t>(reinterpret_cast<const f16_t*>(X), I, A, B, wA, wB, shift, sub_own, add_other, alpha, t, Z, csum,
+                                   ws, ws_bytes, (hipStream_t)stream);
 }
 }

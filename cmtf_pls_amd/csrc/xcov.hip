@@ -16,6 +16,8 @@
 //   D tile e, register g: S[16*mt + kq + 4*g][cb + 4*nn + e]  (f64 map: col = l&15, row = (l>>4) + 4*g)
 //   so each lane ends with 4 consecutive columns per (mt, g): 32-byte stores, 512 B per 16 lanes.
 // Rows are split over gridDim.y row blocks -> (row block, M, P) f64 partials, summed in fixed order.
+// 16-bit storage (bf16_t / f16_t, common.hpp): the same mapping, the lane's 4 columns are one 8-byte vector and every element
+// goes through to_f64 (exact) before the MFMA; nothing else in the tile changes.
 #include "common.hpp"
 
 namespace cmtfpls {
@@ -115,9 +117,8 @@ __global__ __launch_bounds__(256) void xcov_kernel(const T* __restrict__ X, int6
       const bool rok = FAST || (r + 4 * s + kq) < r1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        T xv = x[s].e[e];
-        if (MASKED) xv = (xv == xv) ? xv : (T)0;
-        const double b = (FAST || (rok && c + e < P)) ? (double)xv : 0.0;
+        const double xv = to_f64_masked<MASKED>(x[s].e[e]);
+        const double b = (FAST || (rok && c + e < P)) ? xv : 0.0;
         if constexpr (SSQ) {
           const double dv = (FAST || (rok && c + e < P)) ? b - mu[e] : 0.0;
           ssq = fma(dv, dv, ssq);
@@ -318,7 +319,10 @@ static int run_xcov_tile(const T* X, int64_t I, int64_t P, const double* Y, int 
 #define XT1(VC, MTT, FS) hipLaunchKernelGGL((xcov_kernel<T, false, VC, MTT, FS, false, true>), grid, block, 0, st, X, I, P, Y, ldy, M, part, p.rows_per_block, (const double*)nullptr, ssq_part)
 #define XT(VC, FS) do { if (mt == 1) XT1(VC, 1, FS); else if (mt == 2) XT1(VC, 2, FS); else XT1(VC, 4, FS); } while (0)
   if (with_stats)  { if (fast) XT(true, true); else if (vec) XT(true, false); else XT(false, false); }
-  else if (with_ssq) { if (fast) XQ(true, true); else if (vec) XQ(true, false); else XQ(false, false); }
+  else if (with_ssq) {
+    if constexpr (sizeof(T) == 2) { set_error("xcov_ssq: no 16-bit form; xcov_stats gives the norm"); return CMTFPLS_EUNSUPPORTED; }   // (no entry asks for it)
+    else { if (fast) XQ(true, true); else if (vec) XQ(true, false); else XQ(false, false); }
+  }
   else if (masked) { if (fast) XM(true, true, true); else if (vec) XM(true, true, false); else XM(true, false, false); }
   else             { if (fast) XM(false, true, true); else if (vec) XM(false, true, false); else XM(false, false, false); }
 #undef XT
@@ -399,6 +403,15 @@ int cmtfpls_xcov_f64(const double* X, int64_t I, int64_t P, const double* Y, int
                      void* ws, size_t ws_bytes, void* stream) {
   return run_xcov<double>(X, I, P, Y, ldy, M, S, masked, ws, ws_bytes, (hipStream_t)stream);
 }
+// 16-bit storage: the same kernel with the element converted on load (common.hpp: to_f64); X is the raw bits
+int cmtfpls_xcov_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, int masked,
+                      void* ws, size_t ws_bytes, void* stream) {
+  return run_xcov<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, P, Y, ldy, M, S, masked, ws, ws_bytes, (hipStream_t)stream);
+}
+int cmtfpls_xcov_f16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, int masked,
+                     void* ws, size_t ws_bytes, void* stream) {
+  return run_xcov<f16_t>(reinterpret_cast<const f16_t*>(X), I, P, Y, ldy, M, S, masked, ws, ws_bytes, (hipStream_t)stream);
+}
 size_t cmtfpls_xcov_ssq_workspace_bytes(int64_t I, int64_t P, int M) {
   if (I <= 0 || P <= 0 || M <= 0) return 0;
   const XcovPlan p = plan_xcov(I, P);
@@ -431,6 +444,18 @@ int cmtfpls_xcov_stats_f64(const double* X, int64_t I, int64_t P, const double* 
   if (!X || !Y || !S || !stats || I <= 0 || P <= 0 || M <= 0 || ldy < M) { set_error("xcov_stats: bad argument"); return CMTFPLS_EINVAL; }
   if (M > kXcovMaxResponses) { set_error("xcov_stats: more than 64 responses; use colstats + xcov"); return CMTFPLS_EUNSUPPORTED; }
   return run_xcov_tile<double>(X, I, P, Y, ldy, M, S, 0, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, stats);
+}
+int cmtfpls_xcov_stats_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
+                            void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !Y || !S || !stats || I <= 0 || P <= 0 || M <= 0 || ldy < M) { set_error("xcov_stats: bad argument"); return CMTFPLS_EINVAL; }
+  if (M > kXcovMaxResponses) { set_error("xcov_stats: more than 64 responses; use xcov"); return CMTFPLS_EUNSUPPORTED; }
+  return run_xcov_tile<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, P, Y, ldy, M, S, 0, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, stats);
+}
+int cmtfpls_xcov_stats_f16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
+                           void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !Y || !S || !stats || I <= 0 || P <= 0 || M <= 0 || ldy < M) { set_error("xcov_stats: bad argument"); return CMTFPLS_EINVAL; }
+  if (M > kXcovMaxResponses) { set_error("xcov_stats: more than 64 responses; use xcov"); return CMTFPLS_EUNSUPPORTED; }
+  return run_xcov_tile<f16_t>(reinterpret_cast<const f16_t*>(X), I, P, Y, ldy, M, S, 0, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, stats);
 }
 int cmtfpls_xcov_deflate_f32(float* X, int64_t I, int A, int B, const double* Y, int ldy, int M, const double* t, const double* wA,
                              const double* wB, double* S, double* ssq, void* ws, size_t ws_bytes, void* stream) {

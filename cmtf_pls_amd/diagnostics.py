@@ -23,7 +23,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .tpls import _as_torch_dtype, to_device_copy
+from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
 
 # reads of the caller's X that each projection form takes (project_readonly's forms); other forms work on private copies
 _PROJECTION_READS = {
@@ -97,7 +97,7 @@ def _training_stats(pls, eng, st, coupled: bool, device: bool, spe_train: Option
             why = "the training X was not kept (copy_X=False): no training SPE"
         else:
             dev = eng.be.device
-            Xd = [to_device_copy(X, blk.dtype or torch.float64, dev, copy=False) for X, blk in zip(Xs, st.blocks)]
+            Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls) for X, blk in zip(Xs, st.blocks)]
             spe_train = [r[:, 0] for r, _ in eng.residual_rows(st, Xd, T, want_cols=False, device=device)]
             reads = 1
     moments = None if spe_train is None else [_spe_moments(comm, s) for s in spe_train]
@@ -106,6 +106,7 @@ def _training_stats(pls, eng, st, coupled: bool, device: bool, spe_train: Option
     return cache, False, reads
 
 
+@reports_storage_upcast("diagnostics_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
 def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = True) -> dict:
     from .cmtf import ctPLS
 
@@ -127,7 +128,7 @@ def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = 
                 raise ValueError("the model was fitted with copy_X=False, so the training X was not kept: pass X")
             if Y is None:
                 Y = pls.original_Y
-            Xd = [to_device_copy(X, blk.dtype or torch.float64, dev, copy=False) for X, blk in zip(Xs, st.blocks)]
+            Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls) for X, blk in zip(Xs, st.blocks)]
             scores = st.T
             form, proj_reads = "fitted scores + residual pass", 0
         else:
@@ -135,7 +136,7 @@ def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = 
             if coupled and len(Xs) != pls.Xs_len:
                 raise ValueError(f"Training Xs has {pls.Xs_len} blocks, while the new Xs has {len(Xs)}")
             dtypes = [_as_torch_dtype(pls._dtype, x) for x in Xs]
-            Xd = [to_device_copy(x, dt, dev, copy=False) for x, dt in zip(Xs, dtypes)]
+            Xd = [to_device_read(x, dt, dev, pls=pls) for x, dt in zip(Xs, dtypes)]
             scores = pls._project_dev(Xd if coupled else Xd[0])          # transform's projection: shape checks, forms, bits
             pform = "sequential passes on private copies (f32 matrix precision)" if pls._mixed else eng.last_projection["form"]
             form, proj_reads = f"projection ({pform}) + residual pass", _PROJECTION_READS.get(pform)

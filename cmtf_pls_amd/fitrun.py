@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .fitrun_xcov import XcovMixin
-from .state import BlockState, FitState, split_trailing, validate_limits
+from .state import HALF_DTYPES, BlockState, FitState, split_trailing, validate_limits
 
 
 class FitRun(XcovMixin):
@@ -51,6 +51,26 @@ class FitRun(XcovMixin):
         want_raw = (allow_raw and algorithm == "xcov" and eng.opt.xcov_raw and eng.opt.xcov_nowrite
                     and n_components <= 64
                     and all(hasattr(be, f) for f in ("axpy_scalar", "total", "recon_r2", "s_downdate", "deflate_contract_yq", "kr_axpy")))
+        # 16-bit storage (bfloat16 / float16) is only ever READ: such blocks stay as they are on the uncentred cross-covariance path
+        # (statistics and S from backend.xcov_stats, score and down-date from score_contract or mttkrp + xcov) and are replaced by an
+        # exact float32 upcast, a private copy, for everything else -- the same code on the same values as a float32 model
+        self.half_storage = [X.dtype if X.dtype in HALF_DTYPES else None for X in Xs]
+        self.half_fallback: Optional[str] = None
+        self.half_reads: Dict[int, set] = {}                      # block -> the entries that read the 16-bit tensor, noted where taken
+
+        def upcast(why: str) -> None:
+            names = sorted({str(d).replace("torch.", "") for d in self.half_storage if d is not None})
+            for b, d in enumerate(self.half_storage):
+                if d is not None and Xs[b].dtype in HALF_DTYPES:
+                    Xs[b] = Xs[b].to(torch.float32)
+                    owned[b] = True
+            self.half_fallback = f"float32 private copy of the {' / '.join(names)} data: {why}"
+            self.notes.append(self.half_fallback)
+
+        if any(d is not None for d in self.half_storage):
+            why = self._half_declined(want_raw, allow_raw, [tuple(X.shape) for X in Xs], M)
+            if why is not None:
+                upcast(why)
         if not want_raw:
             for b in range(len(Xs)):
                 if not owned[b]:
@@ -78,18 +98,27 @@ class FitRun(XcovMixin):
             if self.blocks is None:                               # a missing / non-finite value after all: the statistics pass proper
                 self._s_prebuilt, self._ssq0_dev = {}, {}
                 self.notes.append("column statistics from the read that builds S declined: a column sum came out non-finite")
+        if self.blocks is None and any(X.dtype in HALF_DTYPES for X in Xs):
+            upcast("missing or non-finite values in X (the statistics read shows them; the masked forms write X)")
         if self.blocks is None:
             self.blocks = [eng._prepare_block(X, self.n_total, defer_centring=want_raw) for X in Xs]
         self.raw = want_raw and not any(blk.has_miss for blk in self.blocks)
+        raw_declined = None                                       # why self.raw was cleared after the statistics, in words
         if self.raw:
             # the uncentred form subtracts mean-sized terms from data-sized results: beyond ~1e4 x the spread it loses digits
             # the centred copy keeps (error ~ 1e-16 * ratio), so such data is centred after all
             ratio = eng._offset_ratio(self.blocks, Xs)
             if not ratio <= eng.opt.xcov_raw_max_offset:
                 self.raw = False
-                self.notes.append(f"uncentred xcov form declined: max|column mean| / spread = {ratio:.3g} > {eng.opt.xcov_raw_max_offset:g}")
+                raw_declined = f"uncentred xcov form declined: max|column mean| / spread = {ratio:.3g} > {eng.opt.xcov_raw_max_offset:g}"
+                self.notes.append(raw_declined)
         if self.raw and not self._ssq_with_s:
             self.raw = all(eng._ssq_uncentred(blk, X) for blk, X in zip(self.blocks, Xs))
+        if not self.raw and any(X.dtype in HALF_DTYPES for X in Xs):
+            upcast(raw_declined or "the uncentred cross-covariance form declined: no read-only norm of the block")
+        for blk, d in zip(self.blocks, self.half_storage):
+            if d is not None:
+                blk.dtype = d                                     # the model's storage type, whichever copy the fit ran on
         if want_raw and not self.raw:                            # missing values (or no read-only norm): the deflating form after all
             for b, blk in enumerate(self.blocks):
                 if not owned[b]:
@@ -225,6 +254,38 @@ class FitRun(XcovMixin):
                         self.corr = be.empty(I)
                         self.csum = be.empty(1)
             assert self._nowrite or not self.raw, "an uncentred X needs the form of the loop that never writes it"
+
+    def _half_declined(self, want_raw: bool, allow_raw: bool, shapes, M: int) -> Optional[str]:
+        """Why a fit with 16-bit blocks cannot run on them in place, known before X is read; None: it can."""
+        eng, be = self.eng, self.eng.be
+        if self.algorithm != "xcov":
+            return 'algorithm="direct" centres and deflates X in place'
+        if not (hasattr(be, "has_half") and all(be.has_half(f) for f in ("xcov", "xcov_stats", "score_contract", "mttkrp"))):
+            return "the backend has no 16-bit entries"
+        if self.R > 64:
+            return "more than 64 components"
+        if M > 64:
+            return "more than 64 responses (the statistics come out of the read that builds S, 64 responses per pass)"
+        if not allow_raw:
+            return "f32 matrix precision"
+        if not (want_raw and eng.opt.xcov_ssq_with_s and eng.opt.xcov_stats_with_s and hasattr(be, "xcov_ssq")):
+            return "the options switch off the uncentred cross-covariance form that never writes X"
+        for shape, d in zip(shapes, self.half_storage):
+            A, B = split_trailing(shape)
+            if d is not None and (A + B) * 16 * 8 > 152 * 1024:
+                return f"a block of trailing extents {A} x {B}: loadings beyond the LDS of the 16-bit score pass (MTTKRP)"
+        return None
+
+    def _half_reads_form(self, b: int) -> str:
+        """How the components read 16-bit block b after the statistics read, from the entries that actually ran on it."""
+        seen = self.half_reads.get(b, set())
+        if "score_contract" in seen:
+            return "one-read (score_contract)"
+        if {"mttkrp", "xcov"} <= seen:
+            return "two-read (mttkrp + xcov)"
+        if "mttkrp" in seen:
+            return "one read (mttkrp: a single component needs no down-date of S)"
+        return "none"
 
     def _blocks_from_one_read(self, Xs: List[torch.Tensor]) -> Optional[List[BlockState]]:
         """tpls.py:61-71 for candidates of the uncentred cross-covariance form: ONE read of every block gives its S = X^T Y_c
@@ -828,6 +889,15 @@ class FitRun(XcovMixin):
                                   "last mode a multiple of 4 / 2)")
         # the rank-1 extraction of order-3 blocks with min(J, K) <= 256: every Gram squaring in one launch, unless the process had to
         # switch that off (a GPU shared with another process)
+        if any(d is not None for d in self.half_storage):
+            # 16-bit storage: read in place (which reads a component takes, per block), or the float32 private copy and why
+            rep["storage"] = [str(d if d is not None else b.dtype).replace("torch.", "") for d, b in zip(self.half_storage, self.blocks)]
+            rep["half_storage"] = {
+                "in_place": self.half_fallback is None,
+                "fallback": self.half_fallback,
+                "reads": [None if d is None or self.half_fallback is not None else self._half_reads_form(b)
+                          for b, d in enumerate(self.half_storage)],
+            }
         rep["rank1_one_launch_chain"] = bool(getattr(eng.be, "rank1_chain_side", 0)) and any(
             len(blk.shape) == 3 and min(blk.A, blk.B) <= int(getattr(eng.be, "rank1_chain_side", 0)) for blk in self.blocks)
         rep["declined"] = list(self.notes)

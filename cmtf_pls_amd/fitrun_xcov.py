@@ -15,8 +15,31 @@ from typing import Optional
 
 import torch
 
+from .state import HALF_DTYPES
+
 
 class XcovMixin:
+    def _score_x0(self, b: int, out: torch.Tensor) -> None:
+        """out = X_{b,0} w_b (tpls.py:97-99 on the never-deflated block).  A 16-bit block has no score sweep: the MTTKRP with the
+        one loading column (the same f64 products, on the matrix cores, X converted on load)."""
+        be, blk, X2 = self.eng.be, self.blocks[b], self.X2[b]
+        if X2.dtype in HALF_DTYPES:
+            self.half_reads.setdefault(b, set()).add("mttkrp")
+            if be.mttkrp(X2, blk.A, blk.B, self.wA[b].view(-1, 1), self.wB[b].view(-1, 1), out.view(-1, 1)) is None:
+                raise RuntimeError("mttkrp refused a shape the 16-bit fit was planned for")
+        else:
+            be.score(X2, blk.A, blk.B, self.wA[b], self.wB[b], None, out)
+
+    def _contract_x0(self, b: int, v: torch.Tensor, out: torch.Tensor) -> None:
+        """out = X_{b,0}^T v (tpls.py:83).  A 16-bit block has no contraction sweep: the cross-covariance build with v as its one response."""
+        be, X2 = self.eng.be, self.X2[b]
+        if X2.dtype in HALF_DTYPES:
+            self.half_reads.setdefault(b, set()).add("xcov")
+            if be.xcov(X2, v.view(-1, 1), False, out=out.view(1, -1)) is None:
+                raise RuntimeError("xcov refused a block the 16-bit fit was planned for")
+        else:
+            be.mode0_contract(X2, v, False, out=out)
+
     def _iterate_xcov(self, it: int) -> Optional[float]:
         """The same iteration with X x_0 u = sum_m q_m S_m and Y^T t = S_(0) kron(wA, wB): only S is
         touched (no X read, no communication: S is already global).  |u_old - u|^2 = dq^T (Y^T Y) dq."""
@@ -314,9 +337,11 @@ class XcovMixin:
                                              sub_own=corr, add_other=others, alpha=1.0 / nb,
                                              csum=self.csum if self.raw else None) is not None
                 if one_read:
+                    if self.X2[b].dtype in HALF_DTYPES:
+                        self.half_reads.setdefault(b, set()).add("score_contract")
                     continue
                 self._one_read = False                                           # shape outside that kernel: two passes from here on
-            be.score(self.X2[b], blk.A, blk.B, self.wA[b], self.wB[b], None, self.Ts[b])       # X_0 w_a
+            self._score_x0(b, self.Ts[b])                                        # X_0 w_a
             if mw is not None:
                 be.axpy_scalar(self.Ts[b], mw)
             if a > 0:
@@ -352,7 +377,7 @@ class XcovMixin:
                 if one_read and b == fused_b:                                    # X_0^T yhat = sum_j b_j (X_0^T t_j): no read of X
                     be.rowdot(self.Rm[:, :k], b_dev, self.vs[b], None)
                 else:
-                    be.mode0_contract(self.X2[b], self.yhat.view(-1), False, out=self.vs[b])   # X_0^T yhat
+                    self._contract_x0(b, self.yhat.view(-1), self.vs[b])           # X_0^T yhat
                     comm.allreduce(self.vs[b])
                     if self.raw:                                                 # uncentred X: X_c^T yhat = X^T yhat - (1^T yhat) mean
                         be.axpy_scalar(self.vs[b], comm.allreduce(be.total(self.yhat.view(-1))), blk.mean)

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _kept_training_blocks
-from .tpls import _as_torch_dtype, to_device_copy
+from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -79,6 +79,7 @@ def _first_empty_row(X: torch.Tensor) -> Optional[int]:
     return None
 
 
+@reports_storage_upcast("imputation_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
 def impute(pls, X=None, device: bool = True):
     from .cmtf import ctPLS
 
@@ -98,7 +99,7 @@ def impute(pls, X=None, device: bool = True):
             if len(Xs) != len(st.blocks):
                 raise ValueError(f"Training Xs has {len(st.blocks)} blocks, while the new Xs has {len(Xs)}")
             dtypes = [_as_torch_dtype(pls._dtype, x) for x in Xs]
-        Xd = [to_device_copy(x, dt, dev, copy=False) for x, dt in zip(Xs, dtypes)]
+        Xd = [to_device_read(x, dt, dev, pls=pls) for x, dt in zip(Xs, dtypes)]
         if training:
             scores, pform, proj_reads = st.T, None, 0
         else:
@@ -133,6 +134,7 @@ def impute(pls, X=None, device: bool = True):
     return out if coupled else out[0]
 
 
+@reports_storage_upcast("q2x_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
 def get_q2x_heldout(pls, fraction: float = 0.1, n_repeats: int = 5, random_state=0, device: bool = True, tol: float = 1e-8,
                     max_iter: int = 100) -> dict:
     from .cmtf import ctPLS
@@ -156,7 +158,7 @@ def get_q2x_heldout(pls, fraction: float = 0.1, n_repeats: int = 5, random_state
     sums = np.empty((n_repeats, nb, R + 2))
     n_iter, forms = [], []
     with eng.device_ctx():
-        Xd = [to_device_copy(X, blk.dtype or torch.float64, dev, copy=False) for X, blk in zip(Xs, st.blocks)]      # read only
+        Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls) for X, blk in zip(Xs, st.blocks)]      # read only
         for g, seed in enumerate(int(s) for s in seeds):
             masked = eng.holdout_copies(Xd, fraction, seed, device=device)
             for b, (m, _) in enumerate(masked):

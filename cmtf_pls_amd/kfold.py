@@ -376,9 +376,9 @@ def _to_dev(a, dev, dt=torch.float64) -> torch.Tensor:
 
 def _device_blocks(pls, Xs, dev):
     """Each block as (X2, A, B): the device tensor of the storage type (the caller's own when it is one: never copied), I x P."""
-    from .tpls import _as_torch_dtype, to_device_copy
+    from .tpls import _as_torch_dtype, to_device_read
 
-    return [(to_device_copy(X, _as_torch_dtype(pls._dtype, X), dev, copy=False).view(X.shape[0], -1), *_dims(X)) for X in Xs]
+    return [(to_device_read(X, _as_torch_dtype(pls._dtype, X), dev, pls=pls).view(X.shape[0], -1), *_dims(X)) for X in Xs]
 
 
 def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: int):
@@ -1027,6 +1027,20 @@ def _masked_run_report(masked: dict, count: str, N: int, per_pass: str, n_iter, 
     return dict(masked, **{count: int(N)}, passes=masked["launches"], **{per_pass: -(-per // masked["launches"])}, n_iter=n_iter, **more)
 
 
+def _reports_upcast(attr: str = "q2y_report_"):
+    """tpls.reports_storage_upcast for the resampling drivers (imported late: tpls imports the engine)."""
+    def deco(fn):
+        import functools
+
+        @functools.wraps(fn)
+        def run(pls, *args, **kw):
+            from .tpls import reports_storage_upcast
+            return reports_storage_upcast(attr, "the fold and resampling kernels have no 16-bit form and read an exact float32 upcast of the rounded data")(fn)(pls, *args, **kw)
+        return run
+    return deco
+
+
+@_reports_upcast()
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
     """pred (R, *Y.shape): pred[r - 1, i] = prediction for sample i by the model fitted without sample i's fold, with its first
     r components.  `pls` a fitted tPLS or ctPLS.  Sets pls.q2y_report_."""

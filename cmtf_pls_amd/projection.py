@@ -13,7 +13,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .state import BlockState, FitState
+from .state import BlockState, FitState, read_dtype
 
 
 class ProjectionMixin:
@@ -113,6 +113,35 @@ class ProjectionMixin:
             rep["why"] = ("shape outside the MTTKRP and the rows-in-registers kernel" if scores is None
                           else "every sample has a missing value; shape outside the rows-in-registers kernel")
             return None
+
+    def project_half(self, state: FitState, Xs: List[torch.Tensor]) -> Tuple[Optional[torch.Tensor], Optional[str]]:
+        """A batch with 16-bit blocks (bfloat16 / float16 storage): (scores, None) from the one-pass MTTKRP on the blocks as they
+        are -- one read, converted on load, nothing copied or written -- else (None, why): no other projection form reads 16-bit
+        rows, so the caller upcasts the batch to float32 (exact) and takes the forms of `project_readonly` / `project`."""
+        with self.device_ctx():
+            be = self.be
+            nb, I = len(state.blocks), Xs[0].shape[0]
+            rep = self.last_projection = {"rows": int(I), "blocks": nb, "form": "sequential passes on private copies", "why": None}
+            if not (hasattr(be, "has_half") and be.has_half("mttkrp")):
+                return None, "the backend has no 16-bit MTTKRP"
+            if any(bool(torch.isnan(blk.mean).any().item()) for blk in state.blocks):
+                return None, "a training column without observations (NaN mean)"
+            frac, ratio = self._projection_probe(state, Xs) if I > 0 else (0.0, 0.0)
+            rep["offset_ratio"] = ratio
+            if not ratio <= self.opt.project_raw_max_offset:
+                return None, (f"max|column mean| / spread = {ratio:.3g} > {self.opt.project_raw_max_offset:g}: the one-pass form on "
+                              "uncentred rows would lose digits")
+            if frac > 0.0:
+                return None, "rows with missing values in the batch"
+            flag = torch.zeros(1, dtype=torch.int32, device=be.device)
+            scores = self._project_one_pass(state, Xs, False, centred=False, nan_flag=flag)
+            if scores is None:
+                return None, "shape outside the one-pass MTTKRP"
+            if int(flag.item()) != 0:
+                return None, "rows with missing or non-finite values in the batch"
+            rep.update(form="one-pass MTTKRP (one read, nothing written)",
+                       storage=[str(X.dtype).replace("torch.", "") for X in Xs])
+            return scores, None
 
     @staticmethod
     def _projection_probe(state: FitState, Xs: List[torch.Tensor]) -> Tuple[float, float]:
@@ -216,7 +245,7 @@ class ProjectionMixin:
         with self.device_ctx():
             T = state.T if rows is None else state.T[rows]
             WA, WB = self._kr_operands(blk, state.n_components)
-            out = be.empty(T.shape[0], blk.A * blk.B, dtype=dtype or blk.dtype or torch.float64)
+            out = be.empty(T.shape[0], blk.A * blk.B, dtype=dtype or read_dtype(blk.dtype) or torch.float64)
             if T.shape[0] == 0 or be.recon(T, WA, WB, blk.mean, out) is None:
                 return None
             return out.view((T.shape[0],) + tuple(blk.shape[1:]))

@@ -4,7 +4,8 @@
 Same constructor, ``fit / predict / transform / X_reconstructed / copy``, Mapping protocol
 (``[0], [1], [2]`` -> X_factors, Y_factors, coef_) and fitted attributes; NumPy in, NumPy out.
 Opt-in extras (defaults reproduce the reference): ``dtype`` (storage type of X on the GPU:
-"float32" | "float64" | None = follow the input), ``algorithm`` ("direct" = the reference's loop,
+"float32" | "float64" | None = follow the input; "bfloat16" | "float16": 16-bit storage that is only ever read --
+``algorithm="xcov"`` fits it in place, everything else runs on an exact float32 upcast), ``algorithm`` ("direct" = the reference's loop,
 "xcov" = the same iteration through the cross-covariance S = X_(0)^T Y, one X read per component),
 ``graphs`` (replay each iteration as a HIP graph), ``matrix_precision`` ("f64" | "f32": the opt-in
 f32-MFMA form of the two matrix-core kernels), ``copy_X`` (False: fit a device-resident X in place),
@@ -17,6 +18,7 @@ pipelined, graph replay, projection form; every declined fast form in words) and
 """
 from __future__ import annotations
 
+import functools
 from collections.abc import Mapping
 from copy import copy
 from typing import Optional
@@ -25,6 +27,7 @@ import numpy as np
 import torch
 
 from .engine import Comm, EngineOptions, NipalsEngine
+from .state import HALF_DTYPES, read_dtype  # noqa: F401  (16-bit storage: read in place or as an exact float32 upcast)
 
 
 def _as_torch_dtype(dtype, like) -> torch.dtype:
@@ -34,7 +37,70 @@ def _as_torch_dtype(dtype, like) -> torch.dtype:
     if isinstance(dtype, torch.dtype):
         return dtype
     name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
-    return {"float32": torch.float32, "f32": torch.float32, "float64": torch.float64, "f64": torch.float64}[name]
+    return {"float32": torch.float32, "f32": torch.float32, "float64": torch.float64, "f64": torch.float64,
+            "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.float16, "f16": torch.float16}[name]
+
+
+def to_device_read(X, dtype: torch.dtype, device, pls=None) -> torch.Tensor:
+    """X on the device as the routines beside fit / transform read it (diagnostics, contributions, importance, imputation, the
+    resampling drivers, R2X_literal): `to_device_copy(X, dtype, device, copy=False)` -- and for a model with 16-bit storage the
+    data ROUNDED to that type, then upcast to float32: exactly the values the model was fitted on, in a type those kernels take.
+    `pls`: the model on whose behalf X is read; the upcast is noted on it for the routine's report (`reports_storage_upcast`)."""
+    Xd = to_device_copy(X, dtype, device, copy=False)
+    if dtype not in HALF_DTYPES:
+        return Xd
+    seen = getattr(pls, "_storage_upcasts", None)
+    if seen is not None:
+        seen.append(str(dtype).replace("torch.", ""))
+    return Xd.to(torch.float32)
+
+
+def reports_storage_upcast(report_attr: str, why: str):
+    """Decorator of a routine `fn(pls, ...)` that leaves its report in `pls.<report_attr>`: when the routine read X of a model with
+    16-bit storage through `to_device_read(..., pls=pls)` -- a full float32 copy -- the report gets
+    "storage_fallback": "float32 private copy of the <type> data: <why>"."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def run(pls, *args, **kw):
+            outer = getattr(pls, "_storage_upcasts", None)
+            pls._storage_upcasts = seen = []
+            try:
+                out = fn(pls, *args, **kw)
+            finally:
+                pls._storage_upcasts = outer
+            rep = getattr(pls, report_attr, None)
+            if seen and isinstance(rep, dict):
+                rep["storage_fallback"] = f"float32 private copy of the {' / '.join(sorted(set(seen)))} data: {why}"
+            if outer is not None:
+                outer.extend(seen)
+            return out
+        return run
+    return deco
+
+
+def _round_once(x64: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """float64 -> bfloat16 / float16 with ONE rounding to nearest even, on any device.  A plain cast goes through float32 and
+    rounds twice (about 1 value in 20000 then differs from the correctly rounded one).  Here the float32 step rounds to ODD
+    (truncate towards zero, set the last bit when anything was lost), which keeps what the final rounding needs to know; the
+    float32 -> 16-bit cast is then a single rounding of the right value (float32 has more than two bits to spare)."""
+    f = x64.to(torch.float32)
+    back = f.to(torch.float64)
+    lost = (back != x64) & torch.isfinite(x64)
+    bits = f.view(torch.int32)
+    bits = torch.where(lost & (back.abs() > x64.abs()), bits - 1, bits)      # sign-magnitude: one less is one step towards zero
+    bits = torch.where(lost, bits | 1, bits)
+    return bits.view(torch.float32).to(dtype)
+
+
+def _half_from_f64(src: torch.Tensor, dtype: torch.dtype, device) -> torch.Tensor:
+    """A float64 tensor (host or device) as a fresh 16-bit device tensor, rounded once, in row blocks of <= 256 MB."""
+    out = torch.empty(src.shape, dtype=dtype, device=device)
+    if src.ndim == 0:
+        return out.copy_(_round_once(src.to(device), dtype))
+    rows = max(1, (256 << 20) // max(src[0].numel() * 8, 1))
+    for r in range(0, src.shape[0], rows):
+        out[r:r + rows].copy_(_round_once(src[r:r + rows].to(device), dtype))
+    return out
 
 
 def to_device_copy(X, dtype: torch.dtype, device, copy: bool = True) -> torch.Tensor:
@@ -48,10 +114,14 @@ def to_device_copy(X, dtype: torch.dtype, device, copy: bool = True) -> torch.Te
     if isinstance(X, torch.Tensor):
         if not copy and X.is_contiguous() and X.dtype == dtype and X.device == torch.device(device):
             return X
+        if dtype in HALF_DTYPES and X.dtype == torch.float64:
+            return _half_from_f64(X.contiguous(), dtype, device)     # one rounding, whatever the container (as NumPy's astype)
         out = X.to(device=device, dtype=dtype, copy=True)
         return out.contiguous()
     Xn = np.ascontiguousarray(X)
     src = torch.from_numpy(Xn)
+    if dtype in HALF_DTYPES and src.dtype == torch.float64:
+        return _half_from_f64(src, dtype, device)                    # the stored data is X.astype(np.float16), not a double rounding
     if src.dtype == dtype or Xn.ndim == 0 or Xn.nbytes < (64 << 20):
         return src.to(device=device, dtype=dtype, copy=True).contiguous()
     out = torch.empty(Xn.shape, dtype=dtype, device=device)
@@ -68,12 +138,26 @@ def _project_blocks(eng: NipalsEngine, state, Xs, dtypes, mixed: bool) -> torch.
     project-and-deflate on private copies, which it centres and deflates in place."""
     dev = eng.be.device
     Xd = [to_device_copy(X, dt, dev, copy=False) for X, dt in zip(Xs, dtypes)]
+    half_why = None
+    if any(xd.dtype in HALF_DTYPES for xd in Xd):
+        # 16-bit batch: the one-pass MTTKRP in place, or everything below on an exact float32 upcast of the batch
+        scores, half_why = (None, "f32 matrix precision") if mixed else eng.project_half(state, Xd)
+        if scores is not None:
+            return scores
+        names = sorted({str(xd.dtype).replace("torch.", "") for xd in Xd if xd.dtype in HALF_DTYPES})
+        half_why = f"float32 private copy of the {' / '.join(names)} data: {half_why}"
+        Xd = [xd.to(torch.float32) if xd.dtype in HALF_DTYPES else xd for xd in Xd]     # (private: not cloned again below)
     if not mixed:
         scores = eng.project_readonly(state, Xd)
+        if half_why is not None:
+            eng.last_projection["storage_fallback"] = half_why
         if scores is not None:
             return scores
     Xd = [xd.clone() if xd is X else xd for xd, X in zip(Xd, Xs)]        # never touch the caller's tensor
-    return eng.project(state, Xd, mixed=mixed)
+    scores = eng.project(state, Xd, mixed=mixed)
+    if half_why is not None:
+        eng.last_projection["storage_fallback"] = half_why
+    return scores
 
 
 class _EstimatorBase(Mapping):
@@ -284,7 +368,7 @@ class tPLS(_EstimatorBase):
         """calcR2X(X - X_mean, factors_to_tensor(X_factors)) of the training X (util.py:7-15 as tpls.py:115-117 calls it)
         in one read of X on the GPU; equals R2X[-1], which the fit obtains from the deflation sweep instead."""
         eng = self._get_engine()
-        Xd = to_device_copy(X, self._state.blocks[0].dtype or torch.float64, eng.be.device, copy=False)
+        Xd = to_device_read(X, self._state.blocks[0].dtype or torch.float64, eng.be.device, pls=self)
         r2 = eng.r2x_literal(self._state, Xd, 0)
         if r2 is None:
             from .util import calcR2X, factors_to_tensor

@@ -146,6 +146,15 @@ int cmtfpls_xcov_f32(const float* X, int64_t I, int64_t P, const double* Y, int 
 int cmtfpls_xcov_f64(const double* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S,
                      int masked, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_quadform_f64(const double* G, int M, const double* q, const double* q_old, double* out, void* stream);
+/* 16-bit storage of X (suffixes _bf16: bfloat16, _f16: IEEE half; X = the raw bits).  A 16-bit X is only ever READ: the element is
+ * converted to f64 on load (both conversions are exact; NaN and Inf stay what they are) and everything after that is the f64
+ * arithmetic of the f32 / f64 entries -- same arguments, workspaces, limits, `masked` semantics and fixed-order partial sums.
+ * Entries: xcov, xcov_stats, score_contract (the rows form only: B % 8 == 0, 4096 <= A * B <= 16384), mttkrp (every shape of
+ * the f32 entry, tile form).  No other entry has a 16-bit form: whatever writes X or has none runs on a float32 copy. */
+int cmtfpls_xcov_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S,
+                      int masked, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_xcov_f16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S,
+                     int masked, void* ws, size_t ws_bytes, void* stream);
 /* xcov_deflate (round 3): the deflation X -= t (x) w (tpls.py:109; NaN stays NaN, values rounded to the storage type) AND the
  * cross-covariance S = Y^T X0 of the DEFLATED block (X0: NaN -> 0) AND ssq[0] = |X0|^2, in one read + write of X.  For blocks with
  * missing values inside the cross-covariance loop: their S cannot be carried across a deflation algebraically, so a component
@@ -168,6 +177,10 @@ size_t cmtfpls_xcov_stats_workspace_bytes(int64_t I, int64_t P, int M);
 int cmtfpls_xcov_stats_f32(const float* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
                            void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_xcov_stats_f64(const double* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
+                           void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_xcov_stats_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
+                            void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_xcov_stats_f16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, double* stats,
                            void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_xcov_ssq_f32(const float* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S, const double* mean,
                          double* ssq, void* ws, size_t ws_bytes, void* stream);
@@ -242,6 +255,12 @@ int cmtfpls_score_contract_f32(const float* X, int64_t I, int A, int B, const do
 int cmtfpls_score_contract_f64(const double* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* shift,
                                const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
                                void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_score_contract_bf16(const uint16_t* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* shift,
+                                const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
+                                void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_score_contract_f16(const uint16_t* X, int64_t I, int A, int B, const double* wA, const double* wB, const double* shift,
+                               const double* sub_own, const double* add_other, double alpha, double* t, double* Z, double* csum,
+                               void* ws, size_t ws_bytes, void* stream);
 /* Opt-in mixed-precision forms of xcov and mttkrp for f32-stored X: v_mfma_f32_16x16x4_f32 (half the
  * matrix cycles of the f64 form, HBM-bound instead of matrix-pipe-bound).  X is exact; the other
  * operand is rounded once to f32; f32 accumulation only inside chains of 64 rows (xcov) / 256 columns
@@ -262,6 +281,10 @@ int cmtfpls_mttkrp_f32_mixed(const float* X, int64_t I, int A, int B, const doub
 int cmtfpls_mttkrp_f32(const float* X, int64_t I, int A, int B, const double* WA, const double* WB, int R,
                        double* out, int ldo, void* stream);
 int cmtfpls_mttkrp_f64(const double* X, int64_t I, int A, int B, const double* WA, const double* WB, int R,
+                       double* out, int ldo, void* stream);
+int cmtfpls_mttkrp_bf16(const uint16_t* X, int64_t I, int A, int B, const double* WA, const double* WB, int R,
+                        double* out, int ldo, void* stream);
+int cmtfpls_mttkrp_f16(const uint16_t* X, int64_t I, int A, int B, const double* WA, const double* WB, int R,
                        double* out, int ldo, void* stream);
 
 /* ---- K3 score contraction: multi_mode_dot(X, [w...], range(1, X.ndim))  tpls.py:97-99 ---------
