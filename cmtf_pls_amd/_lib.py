@@ -172,12 +172,14 @@ SIGNATURES = {
     "cmtfpls_kfold_inner_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cmtfpls_kfold_inner_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_double, c_int, _P, c_size_t, _P]),
     "cmtfpls_kfold_inner_tensor_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cmtfpls_kfold_inner_tensor_lds_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cmtfpls_kfold_inner_tensor_f64": (c_int, [ctypes.POINTER(KfoldState), _P, c_int, c_int, c_int, c_int, c_double, c_int, _P, _P, _P,
                                        c_size_t, _P]),
     "cmtfpls_kfold_epilogue_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, _P, _P]),
     "cmtfpls_kfold_inner_coupled_workspace_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int]),
     "cmtfpls_kfold_inner_coupled_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, c_double, c_int, _P, c_size_t, _P]),
     "cmtfpls_kfold_inner_coupled_tensor_workspace_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int, ctypes.POINTER(c_int)]),
+    "cmtfpls_kfold_inner_coupled_tensor_lds_bytes": (c_size_t, [ctypes.POINTER(KfoldState), c_int, ctypes.POINTER(c_int)]),
     "cmtfpls_kfold_inner_coupled_tensor_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, ctypes.POINTER(c_int), _P, c_int, c_int, c_double,
                                                        c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_combine_scores_f64": (c_int, [_P, c_int, c_int64, _P, _P]),
@@ -197,6 +199,7 @@ SIGNATURES = {
     "cmtfpls_press_rows_f64": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_loo_xcov_tensor_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cmtfpls_loo_xcov_tensor_lds_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cmtfpls_loo_xcov_tensor_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, _P, _P, _P,
                                             c_size_t, _P]),
     "cmtfpls_loo_xcov_coupled_fold_workspace_bytes": (c_size_t, [ctypes.POINTER(LooCoupledBlock), c_int, c_int, c_int, c_int]),
@@ -216,6 +219,7 @@ SIGNATURES = {
     "cmtfpls_cv_masked_models_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int]
                                      + [_P] * 8 + [_P, c_size_t, _P]),
     "cmtfpls_cv_masked_tensor_fold_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cmtfpls_cv_masked_tensor_lds_bytes": (c_size_t, [c_int] * 6),
     "cmtfpls_cv_masked_tensor_f64": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int,
                                              c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_cv_masked_tensor_model_workspace_bytes": (c_size_t, [c_int] * 6),

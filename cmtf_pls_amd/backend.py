@@ -830,6 +830,24 @@ class HipBackend:
                                                self._ws_budget(max_ws_bytes), extra=extra)
         return out if out["launches"] is not None else None
 
+    def _cv_masked_folds(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, tensor, R: int,
+                         tol: float, max_iter: int, max_ws_bytes: Optional[int]):
+        """cv_masked (tensor None) and cv_masked_tensor (tensor = (B1, B2), B = B1 B2): cmtfpls_cv_masked[_tensor]_f64 through
+        _masked_launch.  Returns (Ypred, n_iter, status, info, launches) or None when the entry declines the shape."""
+        name, trail = ("cv_masked_tensor", tuple(tensor)) if tensor else ("cv_masked", (B,))
+        I, P = X2.shape
+        M = Y.shape[1]
+        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
+        assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
+        colsum_x, colcnt_x = self.colstats(X2)
+        colsum_y, _ = self.colstats(Y)
+        args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, *trail, M, R, float(tol),
+                int(max_iter))
+        per_fn = getattr(self.lib, f"cmtfpls_{name}_fold_workspace_bytes")
+        out = self._masked_launch(name, args, self._masked_outputs(K, I, M, R, False, {}), (), K, lambda: per_fn(I, A, *trail, M, R),
+                                  max_ws_bytes)
+        return None if out is None else (out["Ypred"], out["n_iter"], out["status"], out["info"], out["launches"])
+
     def cv_masked(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B: int, R: int, tol: float,
                   max_iter: int, max_ws_bytes: Optional[int] = None
                   ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]:
@@ -838,17 +856,34 @@ class HipBackend:
         whether the fold's training rows / held-out batch took the masked arithmetic), or None when the shape is outside the form.
         fold_of: (I,) int32 fold ids 0..K-1 (leave-one-out: arange(I), K = I).  Folds run in chunks whose workspace fits
         `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
+        out = self._cv_masked_folds(X2, Y, fold_of, K, A, B, None, R, tol, max_iter, max_ws_bytes)
+        return None if out is None else out[:4]
+
+    def cv_masked_tensor(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B1: int, B2: int, R: int,
+                         tol: float, max_iter: int, max_ws_bytes: Optional[int] = None
+                         ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, int]]:
+        """cv_masked for X of order 4 (I x A x B1 x B2 as I x A B1 B2, NaN = missing): the rank-1 CP of each fold's A x B1 x B2
+        contraction inside its workgroup (cmtfpls_cv_masked_tensor_f64).  Returns cv_masked's (Ypred, n_iter, status, info) and the
+        number of launches, or None when the shape is outside the form."""
+        return self._cv_masked_folds(X2, Y, fold_of, K, A, B1 * B2, (B1, B2), R, tol, max_iter, max_ws_bytes)
+
+    def _cv_masked_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int, B: int,
+                          tensor, R: int, tol: float, max_iter: int, factors: bool, max_ws_bytes: Optional[int]) -> Optional[dict]:
+        """cv_masked_models (tensor None) and cv_masked_tensor_models (tensor = (B1, B2), B = B1 B2): cmtfpls_cv_masked[_tensor]_models_f64
+        through _masked_launch, the trailing loadings Wb, or Wk and Wl."""
+        name, trail = ("cv_masked_tensor", tuple(tensor)) if tensor else ("cv_masked", (B,))
         I, P = X2.shape
         M = Y.shape[1]
+        nm = counts.shape[0]
         assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
-        assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
-        colsum_x, colcnt_x = self.colstats(X2)
-        colsum_y, _ = self.colstats(Y)
-        args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B, M, R, float(tol),
-                int(max_iter))
-        out = self._masked_launch("cv_masked", args, self._masked_outputs(K, I, M, R, False, {}), (), K,
-                                  lambda: self.lib.cmtfpls_cv_masked_fold_workspace_bytes(I, A, B, M, R), max_ws_bytes)
-        return None if out is None else (out["Ypred"], out["n_iter"], out["status"], out["info"])
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
+        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
+        trailing = {"Wk": (R, trail[0]), "Wl": (R, trail[1])} if tensor else {"Wb": (R, B)}
+        shapes = {"Wa": (R, A), **trailing, "coef": (R, R), "Q": (R, M)}
+        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, A, *trail, M, R, float(tol), int(max_iter))
+        per_fn = getattr(self.lib, f"cmtfpls_{name}_model_workspace_bytes")
+        return self._masked_launch(name + "_models", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
+                                   lambda: per_fn(I, A, *trail, M, R), max_ws_bytes, extra=R * I * M * 8)
 
     def cv_masked_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int, B: int,
                          R: int, tol: float, max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None
@@ -859,35 +894,7 @@ class HipBackend:
         Ypred (n, R, I, M) (zero where the model trained), n_iter (n, R), status (n), info (n, 2) and with `factors` Wa (n, R, A),
         Wb (n, R, B), coef (n, R, R), Q (n, R, M) -- or None when the shape is outside the form.  Models run in chunks whose
         workspace and Ypred rows fit `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
-        I, P = X2.shape
-        M = Y.shape[1]
-        nm = counts.shape[0]
-        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
-        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
-        shapes = {"Wa": (R, A), "Wb": (R, B), "coef": (R, R), "Q": (R, M)}
-        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, A, B, M, R, float(tol), int(max_iter))
-        return self._masked_launch("cv_masked_models", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
-                                   lambda: self.lib.cmtfpls_cv_masked_model_workspace_bytes(I, A, B, M, R), max_ws_bytes,
-                                   extra=R * I * M * 8)
-
-    def cv_masked_tensor(self, X2: torch.Tensor, Y: torch.Tensor, fold_of: torch.Tensor, K: int, A: int, B1: int, B2: int, R: int,
-                         tol: float, max_iter: int, max_ws_bytes: Optional[int] = None
-                         ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, int]]:
-        """cv_masked for X of order 4 (I x A x B1 x B2 as I x A B1 B2, NaN = missing): the rank-1 CP of each fold's A x B1 x B2
-        contraction inside its workgroup (cmtfpls_cv_masked_tensor_f64).  Returns cv_masked's (Ypred, n_iter, status, info) and the
-        number of launches, or None when the shape is outside the form."""
-        I, P = X2.shape
-        M = Y.shape[1]
-        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
-        assert fold_of.dtype == torch.int32 and fold_of.is_contiguous() and fold_of.numel() == I
-        colsum_x, colcnt_x = self.colstats(X2)
-        colsum_y, _ = self.colstats(Y)
-        args = (_ptr(X2), _ptr(Y), _ptr(fold_of), int(K), _ptr(colsum_x), _ptr(colcnt_x), _ptr(colsum_y), I, A, B1, B2, M, R, float(tol),
-                int(max_iter))
-        out = self._masked_launch("cv_masked_tensor", args, self._masked_outputs(K, I, M, R, False, {}), (), K,
-                                  lambda: self.lib.cmtfpls_cv_masked_tensor_fold_workspace_bytes(I, A, B1, B2, M, R), max_ws_bytes)
-        return None if out is None else (out["Ypred"], out["n_iter"], out["status"], out["info"], out["launches"])
+        return self._cv_masked_models(X2, Y, counts, yrow, A, B, None, R, tol, max_iter, factors, max_ws_bytes)
 
     def cv_masked_tensor_models(self, X2: torch.Tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], A: int,
                                 B1: int, B2: int, R: int, tol: float, max_iter: int, factors: bool = False,
@@ -895,60 +902,14 @@ class HipBackend:
         """cv_masked_models for X of order 4 (I x A x B1 x B2 as I x A B1 B2, NaN = missing; cmtfpls_cv_masked_tensor_models_f64).
         Returns cv_masked_models' dict, with `factors` Wa (n, R, A), Wk (n, R, B1), Wl (n, R, B2), coef and Q, or None when the
         shape is outside the form."""
-        I, P = X2.shape
-        M = Y.shape[1]
-        nm = counts.shape[0]
-        assert X2.dtype == torch.float64 and Y.dtype == torch.float64 and X2.is_contiguous() and Y.is_contiguous() and P == A * B1 * B2
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
-        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
-        shapes = {"Wa": (R, A), "Wk": (R, B1), "Wl": (R, B2), "coef": (R, R), "Q": (R, M)}
-        args = (_ptr(X2), _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, A, B1, B2, M, R, float(tol), int(max_iter))
-        return self._masked_launch("cv_masked_tensor_models", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}),
-                                   shapes, nm, lambda: self.lib.cmtfpls_cv_masked_tensor_model_workspace_bytes(I, A, B1, B2, M, R),
-                                   max_ws_bytes, extra=R * I * M * 8)
+        return self._cv_masked_models(X2, Y, counts, yrow, A, B1 * B2, (B1, B2), R, tol, max_iter, factors, max_ws_bytes)
 
-    def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
-                          max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
-        """Refits of a ctPLS whose blocks X2s (each I x P_b, NaN = missing) have missing values on count-weighted rows, a workgroup
-        per model (cmtfpls_cv_masked_coupled_f64): model m trains on counts[m, r] copies of row r of every block paired with Y row
-        yrow[m, r] and predicts its rows with count 0.  dims: (order, A, B) per block; counts: (n, I) int32; yrow: (n, I) int32 or
-        None (identity).  Returns a dict of device tensors -- Ypred (n, R, I, M) (zero where the model trained), n_iter (n, R),
-        status (n), info (n, 2) (bit masks over the blocks) and with `factors` Wa, Wb (lists: per block (n, R, A_b) / (n, R, B_b)),
-        coef (n, R, R), Q (n, R, M) -- or None when the shape is outside the form.  Models run in chunks whose workspace and Ypred
-        rows fit `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
-        nb = len(X2s)
-        I = X2s[0].shape[0]
-        M = Y.shape[1]
-        nm = counts.shape[0]
-        assert nb >= 1 and len(dims) == nb and Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape[0] == I
-        for X2, (_, A, B) in zip(X2s, dims):
-            assert X2.dtype == torch.float64 and X2.is_contiguous() and tuple(X2.shape) == (I, A * B)
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
-        assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
-        blocks = (_lib.CvCoupledBlock * nb)(*[_lib.CvCoupledBlock(_ptr(X2), int(o), int(A), int(B)) for X2, (o, A, B) in zip(X2s, dims)])
-        sumA, sumB = sum(A for _, A, _ in dims), sum(B for _, _, B in dims)
-        shapes = {"Wa": (R * sumA,), "Wb": (R * sumB,), "coef": (R, R), "Q": (R, M)}
-        args = (blocks, nb, _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, M, R, float(tol), int(max_iter))
-        out = self._masked_launch("cv_masked_coupled", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
-                                  lambda: self.lib.cmtfpls_cv_masked_coupled_workspace_bytes(blocks, nb, I, M, R), max_ws_bytes,
-                                  extra=R * I * M * 8)
-        if out is not None and factors:                                              # block b's R x A_b at R * (A_0 + .. + A_(b-1))
-            oa = ob = 0
-            Wa, Wb = [], []
-            for _, A, B in dims:
-                Wa.append(out["Wa"][:, R * oa:R * (oa + A)].reshape(nm, R, A))
-                Wb.append(out["Wb"][:, R * ob:R * (ob + B)].reshape(nm, R, B))
-                oa, ob = oa + A, ob + B
-            out["Wa"], out["Wb"] = Wa, Wb
-        return out
-
-    def cv_masked_coupled_tensor(self, X2s, dims, tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int,
-                                 tol: float, max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
-        """cv_masked_coupled for a ctPLS with blocks of order 4 (cmtfpls_cv_masked_coupled_tensor_f64): a block I x A x B1 x B2 is
-        given as I x A B1 B2 with dims (4, A, B1 B2) and tensor (B1, B2); a block of order 2 or 3 has tensor (0, 0).  The loading of a
-        tensor block is the rank-1 CP of its contraction inside the model's workgroup.  Returns cv_masked_coupled's dict, with
-        `factors` also Wk, Wl (lists: per block (n, R, B1_b) / (n, R, B2_b), None for a block of order 2 or 3; Wb of a tensor block is
-        wK (x) wL), or None when the shape is outside the form.  Models run in chunks as cv_masked_coupled's."""
+    def _cv_masked_coupled(self, name: str, X2s, dims, tensor, pairs, Y: torch.Tensor, counts: torch.Tensor,
+                           yrow: Optional[torch.Tensor], R: int, tol: float, max_iter: int, factors: bool,
+                           max_ws_bytes: Optional[int]) -> Optional[dict]:
+        """cv_masked_coupled (pairs = (), tensor (0, 0) per block) and cv_masked_coupled_tensor (pairs = (the (B1, B2) int array,)):
+        cmtfpls_<name>_f64 on the blocks' description through _masked_launch, then with `factors` every block's slice of the
+        loadings (Wk, Wl only with pairs)."""
         nb = len(X2s)
         I = X2s[0].shape[0]
         M = Y.shape[1]
@@ -959,27 +920,49 @@ class HipBackend:
         assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nm, I) and nm > 0
         assert yrow is None or (yrow.dtype == torch.int32 and yrow.is_contiguous() and tuple(yrow.shape) == (nm, I))
         blocks = (_lib.CvCoupledBlock * nb)(*[_lib.CvCoupledBlock(_ptr(X2), int(o), int(A), int(B)) for X2, (o, A, B) in zip(X2s, dims)])
-        pairs = _int_pairs(tensor)
         sumA, sumB = sum(A for _, A, _ in dims), sum(B for _, _, B in dims)
         sumK, sumL = sum(B1 for B1, B2 in tensor if B2 > 0), sum(B2 for _, B2 in tensor)
-        shapes = {"Wa": (R * sumA,), "Wb": (R * sumB,), "Wk": (R * sumK,), "Wl": (R * sumL,), "coef": (R, R), "Q": (R, M)}
-        args = (blocks, nb, pairs, _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, M, R, float(tol), int(max_iter))
-        out = self._masked_launch("cv_masked_coupled_tensor", args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}),
-                                  shapes, nm, lambda: self.lib.cmtfpls_cv_masked_coupled_tensor_workspace_bytes(blocks, nb, pairs, I, M, R),
-                                  max_ws_bytes, extra=R * I * M * 8)
-        if out is not None and factors:                                              # block b's R x A_b at R * (A_0 + .. + A_(b-1))
-            oa = ob = ok = ol = 0
-            Wa, Wb, Wk, Wl = [], [], [], []
-            for (_, A, B), (B1, B2) in zip(dims, tensor):
-                Wa.append(out["Wa"][:, R * oa:R * (oa + A)].reshape(nm, R, A))
-                Wb.append(out["Wb"][:, R * ob:R * (ob + B)].reshape(nm, R, B))
-                Wk.append(out["Wk"][:, R * ok:R * (ok + B1)].reshape(nm, R, B1) if B2 > 0 else None)
-                Wl.append(out["Wl"][:, R * ol:R * (ol + B2)].reshape(nm, R, B2) if B2 > 0 else None)
-                oa, ob = oa + A, ob + B
-                if B2 > 0:
-                    ok, ol = ok + B1, ol + B2
-            out["Wa"], out["Wb"], out["Wk"], out["Wl"] = Wa, Wb, Wk, Wl
+        modes = {"Wk": (R * sumK,), "Wl": (R * sumL,)} if pairs else {}
+        shapes = {"Wa": (R * sumA,), "Wb": (R * sumB,), **modes, "coef": (R, R), "Q": (R, M)}
+        args = (blocks, nb, *pairs, _ptr(Y), _ptr(counts), _ptr(yrow), nm, I, M, R, float(tol), int(max_iter))
+        per_fn = getattr(self.lib, f"cmtfpls_{name}_workspace_bytes")
+        out = self._masked_launch(name, args, self._masked_outputs(nm, I, M, R, True, shapes if factors else {}), shapes, nm,
+                                  lambda: per_fn(blocks, nb, *pairs, I, M, R), max_ws_bytes, extra=R * I * M * 8)
+        def per_block(key, widths):                      # block b's R x n_b at R * (n_0 + .. + n_(b-1)); None for a width of 0
+            cut, o = [], 0
+            for n in widths:
+                cut.append(out[key][:, R * o:R * (o + n)].reshape(nm, R, n) if n else None)
+                o += n
+            return cut
+
+        if out is not None and factors:
+            out["Wa"], out["Wb"] = per_block("Wa", [A for _, A, _ in dims]), per_block("Wb", [B for _, _, B in dims])
+            if pairs:                                    # a block of order 2 or 3 has no mode loadings
+                out["Wk"] = per_block("Wk", [B1 if B2 > 0 else 0 for B1, B2 in tensor])
+                out["Wl"] = per_block("Wl", [B2 for _, B2 in tensor])
         return out
+
+    def cv_masked_coupled(self, X2s, dims, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int, tol: float,
+                          max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
+        """Refits of a ctPLS whose blocks X2s (each I x P_b, NaN = missing) have missing values on count-weighted rows, a workgroup
+        per model (cmtfpls_cv_masked_coupled_f64): model m trains on counts[m, r] copies of row r of every block paired with Y row
+        yrow[m, r] and predicts its rows with count 0.  dims: (order, A, B) per block; counts: (n, I) int32; yrow: (n, I) int32 or
+        None (identity).  Returns a dict of device tensors -- Ypred (n, R, I, M) (zero where the model trained), n_iter (n, R),
+        status (n), info (n, 2) (bit masks over the blocks) and with `factors` Wa, Wb (lists: per block (n, R, A_b) / (n, R, B_b)),
+        coef (n, R, R), Q (n, R, M) -- or None when the shape is outside the form.  Models run in chunks whose workspace and Ypred
+        rows fit `max_ws_bytes` (default 4 GiB); the workspace is allocated per call and released with it."""
+        return self._cv_masked_coupled("cv_masked_coupled", X2s, dims, [(0, 0)] * len(X2s), (), Y, counts, yrow, R, tol, max_iter,
+                                       factors, max_ws_bytes)
+
+    def cv_masked_coupled_tensor(self, X2s, dims, tensor, Y: torch.Tensor, counts: torch.Tensor, yrow: Optional[torch.Tensor], R: int,
+                                 tol: float, max_iter: int, factors: bool = False, max_ws_bytes: Optional[int] = None) -> Optional[dict]:
+        """cv_masked_coupled for a ctPLS with blocks of order 4 (cmtfpls_cv_masked_coupled_tensor_f64): a block I x A x B1 x B2 is
+        given as I x A B1 B2 with dims (4, A, B1 B2) and tensor (B1, B2); a block of order 2 or 3 has tensor (0, 0).  The loading of a
+        tensor block is the rank-1 CP of its contraction inside the model's workgroup.  Returns cv_masked_coupled's dict, with
+        `factors` also Wk, Wl (lists: per block (n, R, B1_b) / (n, R, B2_b), None for a block of order 2 or 3; Wb of a tensor block is
+        wK (x) wL), or None when the shape is outside the form.  Models run in chunks as cv_masked_coupled's."""
+        return self._cv_masked_coupled("cv_masked_coupled_tensor", X2s, dims, tensor, (_int_pairs(tensor),), Y, counts, yrow, R, tol,
+                                       max_iter, factors, max_ws_bytes)
 
     # -- K-fold cross-validation (validate.kfold_predictions, kfold.py): every fold from the same reads of X ----------------
     def kfold_xcov(self, X2: torch.Tensor, A: int, B: int, Y: torch.Tensor, order: torch.Tensor, fold_off: torch.Tensor, K: int,

@@ -372,6 +372,11 @@ size_t cmtfpls_cv_masked_tensor_model_workspace_bytes(int I, int A, int B1, int 
   return cv_masked_tensor_workspace_bytes(I, A, B1, B2, M, R);
 }
 
+size_t cmtfpls_cv_masked_tensor_lds_bytes(int I, int A, int B1, int B2, int M, int R) {
+  if (I <= 1 || A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0) return 0;
+  return cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R);
+}
+
 int cmtfpls_cv_masked_tensor_f64(const double* X, const double* Y, const int* fold_of, int K, const double* colsum_x,
                                  const double* colcnt_x, const double* colsum_y, int I, int A, int B1, int B2, int M, int R, double tol,
                                  int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, int* status, int* info, void* ws,

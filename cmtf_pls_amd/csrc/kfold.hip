@@ -1137,6 +1137,11 @@ size_t cmtfpls_kfold_inner_tensor_workspace_bytes(int A, int B1, int B2, int K) 
   return (size_t)K * (size_t)kf_inner_tensor_ws_per_fold(A, B1, B2) * sizeof(double);
 }
 
+size_t cmtfpls_kfold_inner_tensor_lds_bytes(int A, int B1, int B2, int M) {
+  if (A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0) return 0;
+  return kf_inner_tensor_lds_bytes(A, B1, B2, M);
+}
+
 int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int B1, int B2, int a, double tol,
                                    int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, void* stream) {
   if (!kf_state_ok(st) || B1 <= 0 || B2 <= 0 || (int64_t)B1 * B2 != st->B || a < 0 || a >= st->R || max_iter <= 0 || groups < 1 ||
@@ -1210,6 +1215,13 @@ size_t cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(const cmtfpls_kfold_st
   for (int b = 0; b < nb; ++b)
     if (blocks[b].A <= 0 || blocks[b].B <= 0 || (int64_t)blocks[b].A * blocks[b].B > (int64_t)1 << 24) return 0;
   return (size_t)blocks[0].K * (size_t)kf_coupled_tensor_ws_per_fold(kf_coupled_tensor_dims(blocks, nb, dims)) * sizeof(double);
+}
+
+size_t cmtfpls_kfold_inner_coupled_tensor_lds_bytes(const cmtfpls_kfold_state* blocks, int nb, const int* dims) {
+  if (!kf_coupled_tensor_dims_ok(blocks, nb, dims) || blocks[0].M <= 0) return 0;
+  for (int b = 0; b < nb; ++b)
+    if (blocks[b].A <= 0 || blocks[b].B <= 0) return 0;
+  return kf_coupled_tensor_lds_bytes(kf_coupled_tensor_dims(blocks, nb, dims), blocks[0].M);
 }
 
 int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, int nb, const int* dims, const int* model_fold, int groups,

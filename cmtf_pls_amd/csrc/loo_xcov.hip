@@ -230,6 +230,11 @@ size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2
   return ((size_t)I * P + (size_t)I * M + (size_t)I * R + (size_t)M * P + 6 * P + 2 * n * n + 2 * (size_t)I + (size_t)R * ((size_t)A + B)) * sizeof(double);
 }
 
+size_t cmtfpls_loo_xcov_tensor_lds_bytes(int A, int B1, int B2, int M, int R) {
+  if (A <= 0 || B1 <= 0 || B2 <= 0 || M <= 0 || R <= 0) return 0;
+  return lx_tensor_lds_bytes(A, B1, B2, M, R);
+}
+
 int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A, int B, int M,
                          int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred, int* n_iter, void* ws,
                          size_t ws_bytes, void* stream) {

@@ -56,7 +56,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .backend import _scratch
+from .backend import _int_pairs, _scratch
 
 MAX_FOLDS, MAX_RESPONSES, MAX_COMPONENTS, MAX_SIDE = 32, 64, 64, 256
 MAX_BLOCKS = 8                    # blocks of a coupled model (cmtfpls_kfold_inner_coupled_f64)
@@ -195,6 +195,58 @@ def _tensor_dims(Xs, coupled: bool = False):
     return (int(Xs[0].shape[2]), int(Xs[0].shape[3])) if len(Xs) == 1 and Xs[0].ndim == 4 else None
 
 
+# ---- LDS and workspace sizes are the library's alone (include/cmtfpls.h): host arithmetic on a description of the blocks, asked
+# before an upload with block pointers of NULL.  dims = [(A, B), ..]; tensor = [(B1, B2), ..], (0, 0) for a block of order 2 or 3.
+def _size_blocks(block, dims, tensor=None):
+    """The blocks as an array of `block` (_lib.LooCoupledBlock or _lib.CvCoupledBlock) for a size function of the library: order 4
+    where tensor has (B1, B2), else 2 (A = 1) or 3."""
+    orders = [4 if B2 > 0 else 2 if A == 1 else 3 for (A, _), (_, B2) in zip(dims, tensor or [(0, 0)] * len(dims))]
+    return (block * len(dims))(*[block(order=o, A=int(A), B=int(B)) for o, (A, B) in zip(orders, dims)])
+
+
+def _size_states(dims, M: int):
+    """The blocks as an array of _lib.KfoldState for cmtfpls_kfold_inner_coupled_tensor_lds_bytes, which reads A, B and M alone."""
+    return (_lib.KfoldState * len(dims))(*[_lib.KfoldState(A=int(A), B=int(B), M=int(M)) for A, B in dims])
+
+
+def coupled_tensor_lds_bytes(dims, tensor, M: int) -> int:
+    """The LDS of a workgroup of cmtfpls_kfold_inner_coupled_tensor_f64, from the library."""
+    return _lib.load().cmtfpls_kfold_inner_coupled_tensor_lds_bytes(_size_states(dims, M), len(dims), _int_pairs(tensor))
+
+
+def masked_tensor_lds_bytes(I: int, A: int, B1: int, B2: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of the masked order-4 entries, from the library."""
+    return _lib.load().cmtfpls_cv_masked_tensor_lds_bytes(I, A, B1, B2, M, R)
+
+
+def coupled_lds_bytes(dims, I: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_f64, from the library."""
+    return _lib.load().cmtfpls_cv_masked_coupled_lds_bytes(_size_blocks(_lib.CvCoupledBlock, dims), len(dims), I, M, R)
+
+
+def _coupled_tensor_masked(what: str, dims, tensor, I: int, M: int, R: int) -> int:
+    fn = getattr(_lib.load(), f"cmtfpls_cv_masked_coupled_tensor_{what}_bytes")
+    return fn(_size_blocks(_lib.CvCoupledBlock, dims, tensor), len(dims), _int_pairs(tensor), I, M, R)
+
+
+def coupled_tensor_masked_lds_bytes(dims, tensor, I: int, M: int, R: int) -> int:
+    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_tensor_f64, from the library."""
+    return _coupled_tensor_masked("lds", dims, tensor, I, M, R)
+
+
+def coupled_tensor_masked_workspace_bytes(dims, tensor, I: int, M: int, R: int) -> int:
+    """The workspace of one resident model of cmtfpls_cv_masked_coupled_tensor_f64, from the library (what a caller sizes
+    `max_ws_bytes` by)."""
+    return _coupled_tensor_masked("workspace", dims, tensor, I, M, R)
+
+
+def masked_tensor_side(A: int, B1: int, B2: int) -> int:
+    """The largest short side of the three unfoldings of an A x B1 x B2 tensor: the number the masked entries hold against their
+    side limit, which the decline texts print next to it (the limits stay on this side)."""
+    P = A * B1 * B2
+    return max(min(d, P // d) for d in (A, B1, B2))
+
+
 def _decline_tensor(be, A: int, B1: int, B2: int, M: int) -> Optional[str]:
     """Why cmtfpls_kfold_inner_tensor_f64 does not take an A x B1 x B2 cross-covariance (its limits, checked here before a read)."""
     if not hasattr(be, "kfold_inner_tensor"):
@@ -203,24 +255,10 @@ def _decline_tensor(be, A: int, B1: int, B2: int, M: int) -> Optional[str]:
     for mode, d in enumerate((A, B1, B2)):
         if min(d, P // d) > MAX_SIDE:
             return f"mode-{mode} unfolding: min({d}, {P // d}) = {min(d, P // d)} > {MAX_SIDE}"
-    nmax = max(min(d, P // d) for d in (A, B1, B2))
-    lds = 8 * (A + 2 * B1 * B2 + 3 * M + M * M + nmax + B1 + B2 + max(A, B1, B2) + 1024)
+    lds = _lib.load().cmtfpls_kfold_inner_tensor_lds_bytes(A, B1, B2, M)
     if lds > TENSOR_LDS_CAP:
         return f"the fold's vectors need {lds} bytes of LDS > {TENSOR_LDS_CAP} (cmtfpls_kfold_inner_tensor_f64)"
     return None
-
-
-def coupled_tensor_lds_bytes(dims, tensor, M: int) -> int:
-    """The LDS of a workgroup of cmtfpls_kfold_inner_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with
-    tensor = [(B1, B2), ..] ((0, 0): a matrix block), the library's kf_coupled_tensor_lds_bytes: the coupled kernel's vectors (the
-    Gram seed over every matrix block's short side and every unfolding's, the long vector over the matrix blocks alone), then the
-    CP's wK, wL, v, unscaled contraction and 1024 partials, sized over the tensor blocks."""
-    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
-    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
-    nmax = max([min(A, B) for A, B in mats] + [min(d, A * B1 * B2 // d) for A, B1, B2 in tens for d in (A, B1, B2)])
-    kmax = max([max(A, B) for A, B in mats], default=0)
-    cp = max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens) + 1024
-    return 8 * (max(A for A, _ in dims) + max(B for _, B in dims) + 3 * M + M * M + nmax + kmax + cp)
 
 
 def _decline_coupled_tensor(be, dims, tensor, M: int) -> Optional[str]:
@@ -595,22 +633,6 @@ MODELS_TENSOR_FORM = "cmtfpls_cv_masked_tensor_models_f64"
 MASKED_LDS_CAP = 150 * 1024
 
 
-def masked_tensor_side(A: int, B1: int, B2: int) -> int:
-    """The largest short side of the three unfoldings of an A x B1 x B2 contraction: the Gram matrices of the CP's seeds."""
-    P = A * B1 * B2
-    return max(min(d, P // d) for d in (A, B1, B2))
-
-
-def masked_tensor_lds_bytes(I: int, A: int, B1: int, B2: int, M: int, R: int) -> int:
-    """The LDS of a workgroup of the masked order-4 entries (the library's cv_masked_tensor_lds_bytes): the order-3 form's vectors
-    on the A x B1 B2 view with the Gram seed over the unfoldings' short sides and 512 partials (a 512-thread workgroup), then the CP's wK, wL, v, unscaled
-    contraction and argmax scratch."""
-    B, n = B1 * B2, masked_tensor_side(A, B1, B2)
-    P = A * B
-    return 8 * (2 * I + P + A + B + 2 * M + 2 * n * n + n + M + R * R + R * (A + B) + R * M + R * R + 3 * R + 512 + 2 * I
-                + B1 + B2 + B + max(A, B1, B2) + 12)
-
-
 def wants_masked_tensor(pls, X) -> bool:
     """Whether the masked order-4 form is asked for: a tPLS whose X has order 4 and holds a NaN, with
     EngineOptions.masked_tensor_folds."""
@@ -666,8 +688,8 @@ def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
 
 
 def _masked_outside(form: str, A: int, B: int, M: int, R: int) -> str:
-    return (f"shape outside {form} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within 150 KB of LDS): "
-            f"min(J, K) = {min(A, B)}, M = {M}, R = {R}")
+    return (f"shape outside {form} (it takes min(J, K) <= 64, M <= 64, R <= 16 and its vectors within {MASKED_LDS_CAP // 1024} KB of "
+            f"LDS): min(J, K) = {min(A, B)}, M = {M}, R = {R}")
 
 
 def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: int):
@@ -820,44 +842,8 @@ def masked_fold_numerators(pls, X, Y, ids: np.ndarray, K: int, yrows: Optional[n
 COUPLED_FORM = "cmtfpls_cv_masked_coupled_f64"
 COUPLED_LDS_CAP = 150 * 1024
 
-
-def coupled_lds_bytes(dims, I: int, M: int, R: int) -> int:
-    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_f64 for blocks of trailing shape dims = [(A, B), ..] (the library's
-    cmtfpls_cv_masked_coupled_lds_bytes): the per-block scratch is shared, sized for the largest block."""
-    Pmax = max(A * B for A, B in dims)
-    nmax = max(min(A, B) for A, B in dims)
-    kmax = max(max(A, B) for A, B in dims)
-    own = sum((R + 1) * (A + B) + I for A, B in dims)
-    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 256 + Pmax + 2 * nmax * nmax + nmax + kmax + own)
-
-
 # a ctPLS with a block of order 4 among them (EngineOptions.masked_tensor_folds_coupled, DESIGN 8v)
 COUPLED_TENSOR_FORM = "cmtfpls_cv_masked_coupled_tensor_f64"
-COUPLED_TENSOR_THREADS = 512              # the workgroup of cmtfpls_cv_masked_coupled_tensor_f64: the partial rows in its LDS
-
-
-def coupled_tensor_masked_lds_bytes(dims, tensor, I: int, M: int, R: int) -> int:
-    """The LDS of a workgroup of cmtfpls_cv_masked_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with tensor =
-    [(B1, B2), ..] ((0, 0): a block of order 2 or 3), the library's cmtfpls_cv_masked_coupled_tensor_lds_bytes: coupled_lds_bytes
-    with 512 partial rows, the Gram buffers over every matrix block's short side and every unfolding's, the long vector over the
-    matrix blocks alone, then the CP's wK, wL, v and unscaled contraction sized over the tensor blocks and its argmax scratch."""
-    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
-    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
-    Pmax = max(A * B for A, B in dims)
-    nmax = max([min(A, B) for A, B in mats] + [masked_tensor_side(*t) for t in tens])
-    kmax = max([max(A, B) for A, B in mats], default=0)
-    own = sum((R + 1) * (A + B) + I for A, B in dims)
-    cp = (max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens)
-          + COUPLED_TENSOR_THREADS // 64 + COUPLED_TENSOR_THREADS // 128)
-    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + COUPLED_TENSOR_THREADS + Pmax + 2 * nmax * nmax + nmax + kmax + cp + own)
-
-
-def coupled_tensor_masked_workspace_bytes(dims, tensor, I: int, M: int, R: int) -> int:
-    """The workspace of one resident model of cmtfpls_cv_masked_coupled_tensor_f64 (the library's
-    cmtfpls_cv_masked_coupled_tensor_workspace_bytes): per block the working copy, counts and means, then Yf | T, then the CP's
-    Zt | U | yl | vr sized for the largest tensor block."""
-    ptmax = max(A * B for (A, B), (_, B2) in zip(dims, tensor) if B2 > 0)
-    return 8 * (sum((I + 2) * A * B for A, B in dims) + I * M + I * R + 4 * ptmax)
 
 
 def wants_masked_coupled_tensor(pls, X) -> bool:

@@ -24,8 +24,10 @@ the refits.  Which form ran is recorded on the model (``q2y_report_``).
 """
 import numpy as np
 
+from . import _lib
+from .backend import _int_pairs
 from .kfold import (MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
-                    _masked_declined, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
+                    _masked_declined, _size_blocks, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
                     masked_predictions_coupled, refit_predictions, wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
@@ -36,16 +38,6 @@ LOO_COUPLED_TENSOR_FORM = ("a workgroup per fold on the cross-covariances of the
 LOO_REFIT_FORM = "one refit per fold on the regular engine"
 LOO_MAX_RESPONSES, LOO_MAX_COMPONENTS, LOO_MAX_CELLS = 128, 64, 1 << 24
 LOO_COUPLED_LDS_CAP = 150 * 1024
-LOO_COUPLED_TENSOR_THREADS = 512          # the workgroup of cmtfpls_loo_xcov_coupled_tensor_f64: the CP's partial sums in its LDS
-
-
-def loo_tensor_lds_bytes(A: int, B1: int, B2: int, M: int, R: int) -> int:
-    """The LDS of a workgroup of cmtfpls_loo_xcov_tensor_f64 (the library's lx_tensor_lds_bytes): wA, wB, q, qn, tq, my, G_y, the Gram
-    seed over the unfoldings' short sides, the CP's wK, wL, v, unscaled contraction and 1024 partials, then coef (R x R), Q (R x M)
-    and the normal equations (R x R + 3 R)."""
-    P = A * B1 * B2
-    nmax = max(min(d, P // d) for d in (A, B1, B2))
-    return 8 * (A + 2 * B1 * B2 + 4 * M + M * M + nmax + B1 + B2 + max(A, B1, B2) + 1024 + 2 * R * R + R * M + 3 * R)
 
 
 def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
@@ -62,7 +54,7 @@ def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
         return f"R = {R} > {LOO_MAX_COMPONENTS} components (cmtfpls_loo_xcov_tensor_f64)"
     if P > LOO_MAX_CELLS:
         return f"A B1 B2 = {P} > {LOO_MAX_CELLS} (cmtfpls_loo_xcov_tensor_f64)"
-    lds = loo_tensor_lds_bytes(A, B1, B2, M, R)
+    lds = _lib.load().cmtfpls_loo_xcov_tensor_lds_bytes(A, B1, B2, M, R)
     if lds > TENSOR_LDS_CAP:
         return f"the fold's vectors need {lds} bytes of LDS > {TENSOR_LDS_CAP} (cmtfpls_loo_xcov_tensor_f64)"
     return None
@@ -80,29 +72,6 @@ def _is_coupled(pls) -> bool:
     from .cmtf import ctPLS
 
     return isinstance(pls, ctPLS)
-
-
-def loo_coupled_lds_bytes(dims, M: int, R: int) -> int:
-    """The LDS of a workgroup of cmtfpls_loo_xcov_coupled_f64 for blocks of trailing shape dims = [(A, B), ..] (the library's
-    cmtfpls_loo_xcov_coupled_lds_bytes): every block's wA and wB, q, qn, tq, my, G_y, the extraction's xs and ys sized for the
-    largest block, then coef (R x R), Q (R x M) and the normal equations (R x R + 3 R)."""
-    nmax = max(min(A, B) for A, B in dims)
-    kmax = max(max(A, B) for A, B in dims)
-    return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R)
-
-
-def loo_coupled_tensor_lds_bytes(dims, tensor, M: int, R: int) -> int:
-    """The LDS of a workgroup of cmtfpls_loo_xcov_coupled_tensor_f64 for blocks of trailing shape dims = [(A, B), ..] with tensor =
-    [(B1, B2), ..] ((0, 0): a block of order 2 or 3), the library's cmtfpls_loo_xcov_coupled_tensor_lds_bytes: loo_coupled_lds_bytes
-    with the Gram seed over every order-2/3 block's short side and every unfolding's and the long vector over the order-2/3 blocks
-    alone, then the CP's wK, wL, v, unscaled contraction and the workgroup's 512 partials, sized over the tensor blocks."""
-    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
-    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
-    nmax = max([min(A, B) for A, B in mats] + [min(d, A * B1 * B2 // d) for A, B1, B2 in tens for d in (A, B1, B2)])
-    kmax = max([max(A, B) for A, B in mats], default=0)
-    cp = (max(B1 for _, B1, _ in tens) + max(B2 for _, _, B2 in tens) + max(B1 * B2 for _, B1, B2 in tens) + max(max(t) for t in tens)
-          + LOO_COUPLED_TENSOR_THREADS)
-    return 8 * (sum(A + B for A, B in dims) + 4 * M + M * M + nmax + kmax + 2 * R * R + R * M + 3 * R + cp)
 
 
 def _loo_coupled_why(pls, Xs, Y, tensor: bool):
@@ -144,7 +113,9 @@ def _loo_coupled_why(pls, Xs, Y, tensor: bool):
     for b, (A, B) in enumerate(dims):
         if A * B > LOO_MAX_CELLS:
             return f"block {b}: J K = {A * B} > {LOO_MAX_CELLS} ({name})"
-    lds = loo_coupled_tensor_lds_bytes(dims, tensors, M, R) if tensor else loo_coupled_lds_bytes(dims, M, R)
+    blocks, lib = _size_blocks(_lib.LooCoupledBlock, dims, tensors), _lib.load()
+    lds = (lib.cmtfpls_loo_xcov_coupled_tensor_lds_bytes(blocks, len(dims), _int_pairs(tensors), Y.shape[0], M, R) if tensor
+           else lib.cmtfpls_loo_xcov_coupled_lds_bytes(blocks, len(dims), Y.shape[0], M, R))
     if lds > LOO_COUPLED_LDS_CAP:
         return f"the fold's vectors need {lds} bytes of LDS > {LOO_COUPLED_LDS_CAP} ({name})"
     return None

@@ -612,8 +612,12 @@ int cmtfpls_loo_xcov_f64(const double* X, const double* Y, const double* colsum_
  * sides (wA, wB, q, qn, tq, my, G_y, the Gram seed, then the CP's wK, wL, v, unscaled contraction and 1024 row-group partials, then
  * coef, Q, the normal equations); CMTFPLS_EWORKSPACE below nfolds * cmtfpls_loo_xcov_tensor_fold_workspace_bytes(...): per fold
  * (I P + I M + I R + M P + 6 P + 2 n^2 + 2 I + R (A + B)) doubles, P = A B (cmtfpls_loo_xcov_f64's with the CP's three length-P
- * scratch vectors). */
+ * scratch vectors).
+ * cmtfpls_loo_xcov_tensor_lds_bytes (host only): the LDS of a workgroup as the launch sizes it, in doubles A + 2 B1 B2 + 4 M + M^2 + n +
+ * B1 + B2 + max(A, B1, B2) + 1024 + 2 R^2 + R M + 3 R with the n above.  0 for a size <= 0 alone: a shape past a limit of the entry
+ * (a short side, M, R, the cells, the 150 KB) still gets its byte count. */
 size_t cmtfpls_loo_xcov_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R);
+size_t cmtfpls_loo_xcov_tensor_lds_bytes(int A, int B1, int B2, int M, int R);
 int cmtfpls_loo_xcov_tensor_f64(const double* X, const double* Y, const double* colsum_x, const double* colsum_y, int I, int A,
                                 int B1, int B2, int M, int R, double tol, int max_iter, int fold0, int nfolds, double* Ypred,
                                 int* n_iter, void* ws, size_t ws_bytes, void* stream);
@@ -722,7 +726,10 @@ int cmtfpls_cv_masked_models_f64(const double* X, const double* Y, const int* co
  * LDS of a workgroup, in doubles, with n the largest of min(A, B1 B2), min(B1, A B2), min(B2, A B1): 4 I + P + A + 2 B + 3 M +
  * 2 n^2 + n + 2 R^2 + R (A + B) + R M + 3 R + 512 + B1 + B2 + max(A, B1, B2) + 12.
  * CMTFPLS_EUNSUPPORTED (checked before the workspace and before any pointer is read) when that n > 64, M > 64, R > 16, the LDS
- * exceeds 150 KB, or, in the fold form, K > I. */
+ * exceeds 150 KB, or, in the fold form, K > I.
+ * cmtfpls_cv_masked_tensor_lds_bytes (host only) returns that LDS in bytes, as the launch of either entry sizes it; 0 for I <= 1 or
+ * another size <= 0 alone: a shape past a limit of the entries still gets its byte count. */
+size_t cmtfpls_cv_masked_tensor_lds_bytes(int I, int A, int B1, int B2, int M, int R);
 /* reference: tpls.py:73-113, 122-143 (fit and predict of one fold), missingvals.py:7-38 */
 size_t cmtfpls_cv_masked_tensor_fold_workspace_bytes(int I, int A, int B1, int B2, int M, int R);
 /* reference: validate.py:24-33 (one refit per fold) over tpls.py:73-143 */
@@ -859,8 +866,13 @@ int cmtfpls_kfold_inner_f64(const cmtfpls_kfold_state* st, int a, double tol, in
  * else it writes is what cmtfpls_kfold_inner_f64 writes.  Limits, checked before the launch (CMTFPLS_EUNSUPPORTED): those of
  * kfold_inner, the shorter side of each of the three unfoldings of A x B1 x B2 <= 256, and the fold's vectors
  * (A + 2 B1 B2 + B1 + B2 + max dim + 3 M + M^2 + 1280 doubles at most) within 150 KB of LDS.
- * ws >= cmtfpls_kfold_inner_tensor_workspace_bytes(A, B1, B2, K). */
+ * ws >= cmtfpls_kfold_inner_tensor_workspace_bytes(A, B1, B2, K).
+ * cmtfpls_kfold_inner_tensor_lds_bytes (host only): the LDS of a workgroup as the launch sizes it, in doubles A + 2 B1 B2 + 3 M + M^2 +
+ * n + B1 + B2 + max(A, B1, B2) + 1024 with n the largest of min(A, B1 B2), min(B1, A B2), min(B2, A B1) (wA, wB, q, qn, tq, G_y, the
+ * Gram seed, then the CP's wK, wL, v, unscaled contraction and 1024 row-group partials).  0 for a size <= 0 alone: a shape past a
+ * limit of the entry still gets its byte count. */
 size_t cmtfpls_kfold_inner_tensor_workspace_bytes(int A, int B1, int B2, int K);
+size_t cmtfpls_kfold_inner_tensor_lds_bytes(int A, int B1, int B2, int M);
 int cmtfpls_kfold_inner_tensor_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int B1, int B2, int a, double tol,
                                    int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes, void* stream);
 /* kfold_epilogue: stage 0 = the partial Gy of every fold (before component 0; `in` unused); stage 1 = component a's epilogue from
@@ -895,8 +907,13 @@ int cmtfpls_kfold_inner_coupled_f64(const cmtfpls_kfold_state* blocks, int nb, i
  * limits of kfold_inner_coupled, a tensor block with the shorter side of one of its three unfoldings > 256, and the blocks' vectors
  * (max A + max B + 3 M + M^2 + n + k + max B1 + max B2 + max B1 B2 + max dim + 1024 doubles: n the largest short side over every
  * matrix block and every unfolding, k the largest long side of a matrix block, the other maxima over the tensor blocks) beyond
- * 150 KB of LDS.  ws >= cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(blocks, nb, dims) (0 for bad dims). */
+ * 150 KB of LDS.  ws >= cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(blocks, nb, dims) (0 for bad dims).
+ * cmtfpls_kfold_inner_coupled_tensor_lds_bytes (host only) returns those doubles in bytes, as the launch sizes them.  It reads A and B
+ * of every view and M of the first and no buffer, so the views' pointers may be null and their other fields unset.  0 for nb outside
+ * 1..8, dims that do not multiply to B, or A, B or M <= 0 alone: blocks past a limit of the entry still get their byte count.  With
+ * one block of order 4 it is cmtfpls_kfold_inner_tensor_lds_bytes of that block. */
 size_t cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(const cmtfpls_kfold_state* blocks, int nb, const int* dims);
+size_t cmtfpls_kfold_inner_coupled_tensor_lds_bytes(const cmtfpls_kfold_state* blocks, int nb, const int* dims);
 int cmtfpls_kfold_inner_coupled_tensor_f64(const cmtfpls_kfold_state* blocks, int nb, const int* dims, const int* model_fold, int groups,
                                            int a, double tol, int max_iter, double* Wk, double* Wl, void* ws, size_t ws_bytes,
                                            void* stream);

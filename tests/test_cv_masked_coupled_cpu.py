@@ -195,7 +195,7 @@ def _probe(lib, dims, I, M, R, nm=3, orders=None):
 
 
 def test_c_entry_limits(lib):
-    from cmtf_pls_amd.kfold import MAX_BLOCKS, coupled_lds_bytes
+    from cmtf_pls_amd.kfold import MAX_BLOCKS
     assert MAX_BLOCKS == 8
     assert _probe(lib, [(64, 64), (1, 7)], 40, 2, 2) == 2              # min(A, B) = 64
     assert _probe(lib, [(6, 5), (65, 65)], 8, 2, 1) == 4
@@ -209,7 +209,7 @@ def test_c_entry_limits(lib):
     assert _probe(lib, [(6, 5), (1, 7)], 40, 2, 2, orders=[4, 2]) == 4  # an order-4 block
     dims = [(1, 3000), (6, 5)]
     I = 2
-    while coupled_lds_bytes(dims, I + 1, 2, 1) <= LDS_CAP:
+    while lib.cmtfpls_cv_masked_coupled_lds_bytes(_blocks(dims)[0], 2, I + 1, 2, 1) <= LDS_CAP:
         I += 1
     assert _probe(lib, dims, I, 2, 1) == 2                             # the LDS at its cap
     assert _probe(lib, dims, I + 1, 2, 1) == 4
@@ -221,8 +221,14 @@ def test_c_entry_limits(lib):
     assert lib.cmtfpls_cv_masked_coupled_workspace_bytes(arr, 9, 40, 3, 2) == 0
 
 
+def _carve_up(dims, I, M, R):
+    """The LDS of a workgroup as include/cmtfpls.h states it (doubles): the per-block scratch is shared, sized for the largest block."""
+    Pmax, nmax, kmax = max(A * B for A, B in dims), max(min(d) for d in dims), max(max(d) for d in dims)
+    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 256 + Pmax + 2 * nmax * nmax + nmax + kmax
+                + sum((R + 1) * (A + B) + I for A, B in dims))
+
+
 def test_host_lds_formula_is_the_librarys(lib):
-    from cmtf_pls_amd.kfold import coupled_lds_bytes
     rng = np.random.default_rng(0)
     seen = set()
     for _ in range(300):
@@ -231,7 +237,7 @@ def test_host_lds_formula_is_the_librarys(lib):
                 for _ in range(nb)]
         I, M, R = int(rng.integers(2, 1500)), int(rng.integers(1, 65)), int(rng.integers(1, 17))
         arr, _ = _blocks(dims)
-        want = coupled_lds_bytes(dims, I, M, R)
+        want = _carve_up(dims, I, M, R)
         assert lib.cmtfpls_cv_masked_coupled_lds_bytes(arr, nb, I, M, R) == want
         fits = all(min(d) <= 64 for d in dims) and want <= LDS_CAP
         assert _probe(lib, dims, I, M, R) == (2 if fits else 4), (dims, I, M, R)
@@ -240,5 +246,5 @@ def test_host_lds_formula_is_the_librarys(lib):
     # one block: the formula of cmtfpls_cv_masked_models_f64 (tests/test_cv_masked_models_cpu.py)
     I, A, B, M, R = 40, 6, 5, 3, 2
     n, k, P = min(A, B), max(A, B), A * B
-    assert coupled_lds_bytes([(A, B)], I, M, R) == 8 * (2 * I + P + A + B + 2 * M + 2 * n * n + n + k + M + R * R + R * (A + B) +
-                                                         R * M + R * R + 3 * R + 256 + 2 * I)
+    assert lib.cmtfpls_cv_masked_coupled_lds_bytes(_blocks([(A, B)])[0], 1, I, M, R) == 8 * (2 * I + P + A + B + 2 * M + 2 * n * n + n + k + M + R * R + R * (A + B) +
+        R * M + R * R + 3 * R + 256 + 2 * I)

@@ -11,8 +11,7 @@ import pytest
 import oracle as O
 from cmtf_pls_amd import ctPLS
 from cmtf_pls_amd.engine import EngineOptions
-from cmtf_pls_amd.kfold import (COUPLED_FORM, COUPLED_TENSOR_FORM, MAX_BLOCKS, coupled_tensor_masked_lds_bytes,
-                                coupled_tensor_masked_workspace_bytes, masked_tensor_side, wants_masked_coupled)
+from cmtf_pls_amd.kfold import COUPLED_FORM, COUPLED_TENSOR_FORM, MAX_BLOCKS, wants_masked_coupled
 from cmtf_pls_amd.validate import bootstrap_factors, get_q2y, get_q2y_repeated_kfold, kfold_predictions, permutation_test_q2y
 from coupled_masked_order4_ref import coupled_masked_order4_fit
 from numpy_backend import NumpyBackend
@@ -202,6 +201,31 @@ def _probe(lib, trailing, I, M, R, nm=3, orders=None, pairs=None, no_dims=False)
                                                     None, None, None, None, p, None, None, 0, None)
 
 
+def _short_side(A, B1, B2):
+    """The largest short side of the three unfoldings of an A x B1 x B2 contraction."""
+    return max(min(d, A * B1 * B2 // d) for d in (A, B1, B2))
+
+
+def _carve_up(dims, pairs, I, M, R):
+    """The LDS of a workgroup as include/cmtfpls.h states it (doubles), dims = [(A, B), ..], pairs = [(B1, B2), ..] ((0, 0): a matrix
+    block): nmax over the matrix blocks' short sides and every unfolding's, kmax over the matrix blocks alone, the CP's four maxima
+    over the tensor blocks, then its argmax scratch (12)."""
+    mats = [(A, B) for (A, B), (_, B2) in zip(dims, pairs) if B2 == 0]
+    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, pairs) if B2 > 0]
+    nmax = max([min(A, B) for A, B in mats] + [_short_side(*t) for t in tens])
+    kmax = max([max(A, B) for A, B in mats], default=0)
+    cp = max(t[1] for t in tens) + max(t[2] for t in tens) + max(t[1] * t[2] for t in tens) + max(max(t) for t in tens) + 12
+    return 8 * (3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 512 + max(A * B for A, B in dims) + 2 * nmax * nmax + nmax + kmax + cp
+                + sum((R + 1) * (A + B) + I for A, B in dims))
+
+
+def _workspace(dims, pairs, I, M, R):
+    """The workspace of one resident model as include/cmtfpls.h states it: per block the working copy, counts and means, then
+    Yf | T, then the CP's Zt | U | yl | vr sized for the largest tensor block."""
+    ptmax = max(A * B for (A, B), (_, B2) in zip(dims, pairs) if B2 > 0)
+    return 8 * (sum((I + 2) * A * B for A, B in dims) + I * M + I * R + 4 * ptmax)
+
+
 def test_c_entry_bad_arguments(lib):
     ok = [(3, 2, 2), (5,)]
     assert _probe(lib, ok, 40, 2, 2) == EWORKSPACE                                      # accepted
@@ -226,7 +250,7 @@ def test_c_entry_bad_arguments(lib):
 
 def test_c_entry_limits(lib):
     assert MAX_BLOCKS == 8
-    assert masked_tensor_side(64, 8, 8) == 64 and masked_tensor_side(65, 13, 5) == 65
+    assert _short_side(64, 8, 8) == 64 and _short_side(65, 13, 5) == 65
     assert _probe(lib, [(64, 8, 8), (7,)], 12, 2, 2) == EWORKSPACE                      # the largest short side = 64: mode 0
     assert _probe(lib, [(32, 64, 2), (7,)], 12, 2, 1) == EWORKSPACE                     # ... mode 1
     assert _probe(lib, [(32, 2, 64), (7,)], 12, 2, 1) == EWORKSPACE                     # ... mode 2
@@ -242,11 +266,11 @@ def test_c_entry_limits(lib):
     assert _probe(lib, [(3, 2, 2)] + [(3, 2)] * 7, 40, 2, 2) == EWORKSPACE              # nb = 8 with one tensor block
     assert _probe(lib, [(3, 2, 2)] + [(3, 2)] * 8, 40, 2, 2) == EUNSUPPORTED
     trailing = [(4000,), (3, 2, 2)]
-    _, _, dims, pairs = _blocks(trailing)
+    arr, _, _, pairs = _blocks(trailing)
     I = 2
-    while coupled_tensor_masked_lds_bytes(dims, pairs, I + 1, 2, 1) <= LDS_CAP:
+    while lib.cmtfpls_cv_masked_coupled_tensor_lds_bytes(arr, 2, _ints(pairs), I + 1, 2, 1) <= LDS_CAP:
         I += 1
-    assert _probe(lib, trailing, I, 2, 1) == EWORKSPACE                                 # the LDS at its cap (the mirrored formula)
+    assert _probe(lib, trailing, I, 2, 1) == EWORKSPACE                                 # the LDS at its cap (the library's own count)
     assert _probe(lib, trailing, I + 1, 2, 1) == EUNSUPPORTED
     assert _probe(lib, [(1, 1, 1 << 30)], 40, 2, 1) == EUNSUPPORTED                     # short sides of 1, and nothing that fits
 
@@ -271,19 +295,21 @@ def test_host_lds_and_workspace_formulas_are_the_librarys(lib):
         trailing = [trailing[i] for i in order]
         I, M, R = int(rng.integers(2, 1500)), int(rng.integers(1, 65)), int(rng.integers(1, 17))
         arr, _, dims, pairs = _blocks(trailing)
-        want = coupled_tensor_masked_lds_bytes(dims, pairs, I, M, R)
+        want = _carve_up(dims, pairs, I, M, R)
         assert lib.cmtfpls_cv_masked_coupled_tensor_lds_bytes(arr, nb, _ints(pairs), I, M, R) == want, (trailing, I, M, R)
         assert lib.cmtfpls_cv_masked_coupled_tensor_workspace_bytes(arr, nb, _ints(pairs), I, M, R) == \
-            coupled_tensor_masked_workspace_bytes(dims, pairs, I, M, R), (trailing, I, M, R)
-        sides = [masked_tensor_side(*t) if len(t) == 3 else min(A, B) for t, (A, B) in zip(trailing, dims)]
+            _workspace(dims, pairs, I, M, R), (trailing, I, M, R)
+        sides = [_short_side(*t) if len(t) == 3 else min(A, B) for t, (A, B) in zip(trailing, dims)]
         fits = max(sides) <= 64 and want <= LDS_CAP
         assert _probe(lib, trailing, I, M, R) == (EWORKSPACE if fits else EUNSUPPORTED), (trailing, I, M, R)
         seen.add(fits)
     assert seen == {True, False}
     # one tensor block next to nothing: the order-3 coupled formula at 512 partials, ys gone, plus the CP's vectors and argmax scratch
     I, (A, B1, B2), M, R = 40, (6, 5, 4), 3, 2
-    B, n = B1 * B2, masked_tensor_side(A, B1, B2)
-    assert coupled_tensor_masked_lds_bytes([(A, B)], [(B1, B2)], I, M, R) == 8 * (
+    B, n = B1 * B2, _short_side(A, B1, B2)
+    arr, _, _, pairs = _blocks([(A, B1, B2)])
+    assert lib.cmtfpls_cv_masked_coupled_tensor_lds_bytes(arr, 1, _ints(pairs), I, M, R) == 8 * (
         3 * I + 3 * M + 2 * R * R + R * M + 3 * R + 512 + A * B + 2 * n * n + n + (B1 + B2 + B + max(A, B1, B2) + 12) + (R + 1) * (A + B) + I)
-    assert coupled_tensor_masked_workspace_bytes([(A, B), (1, 7)], [(B1, B2), (0, 0)], I, M, R) == 8 * (
+    arr, _, _, pairs = _blocks([(A, B1, B2), (7,)])
+    assert lib.cmtfpls_cv_masked_coupled_tensor_workspace_bytes(arr, 2, _ints(pairs), I, M, R) == 8 * (
         (I + 2) * 120 + (I + 2) * 7 + I * M + I * R + 4 * 120)

@@ -10,7 +10,7 @@ import pytest
 import oracle as O
 from cmtf_pls_amd import tPLS
 from cmtf_pls_amd.engine import EngineOptions
-from cmtf_pls_amd.kfold import MASKED_TENSOR_FORM, fold_ids, masked_tensor_lds_bytes, masked_tensor_side
+from cmtf_pls_amd.kfold import MASKED_TENSOR_FORM, fold_ids
 from cmtf_pls_amd.validate import get_q2y, kfold_predictions, loo_predictions
 from numpy_backend import NumpyBackend
 
@@ -92,9 +92,47 @@ def _probe_models(lib, I, A, B1, B2, M, R):
                                                    None, p, None, None, 0, None)
 
 
+def _short_side(A, B1, B2):
+    """The largest short side of the three unfoldings of an A x B1 x B2 contraction."""
+    return max(min(d, A * B1 * B2 // d) for d in (A, B1, B2))
+
+
+def _carve_up(I, A, B1, B2, M, R):
+    """The LDS of a workgroup of the two entries as include/cmtfpls.h states it (doubles)."""
+    B, n = B1 * B2, _short_side(A, B1, B2)
+    return 8 * (4 * I + A * B + A + 2 * B + 3 * M + 2 * n * n + n + 2 * R * R + R * (A + B) + R * M + 3 * R + 512 + B1 + B2
+                + max(A, B1, B2) + 12)
+
+
+# a cube, the Gram buffers from the B1 unfolding (16, not 3), M = 1, a mode of size 1, every limit reached, then one shape past each
+# (a short side of 65, M = 65, R = 17): the byte count is not gated by them
+LDS_SHAPES = [(12, 5, 5, 5, 2, 2), (12, 3, 16, 16, 1, 1), (40, 6, 5, 4, 1, 3), (9, 6, 1, 5, 2, 3), (12, 64, 8, 8, 64, 16), (8, 65, 13, 5, 2, 1),
+              (8, 33, 65, 2, 2, 1), (40, 6, 5, 4, 65, 2), (40, 6, 5, 4, 2, 17), (2, 1, 1, 7, 1, 1)]
+
+
+@pytest.mark.parametrize("shape", LDS_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_exported_lds_bytes_is_the_carve_up(lib, shape):
+    assert lib.cmtfpls_cv_masked_tensor_lds_bytes(*shape) == _carve_up(*shape)
+
+
+def test_exported_lds_bytes_over_the_cap_and_malformed(lib):
+    lds_bytes = lib.cmtfpls_cv_masked_tensor_lds_bytes
+    assert lds_bytes(12, 3, 16, 16, 1, 1) == 8 * (48 + 768 + 3 + 512 + 3 + 512 + 16 + 2 + 259 + 1 + 3 + 512 + 16 + 16 + 16 + 12)   # n: 16, not 3
+    I = (LDS_CAP - _carve_up(0, 64, 8, 8, 2, 1)) // 32                     # the last I within the cap: a row costs 4 doubles
+    assert _carve_up(I, 64, 8, 8, 2, 1) <= LDS_CAP < _carve_up(I + 1, 64, 8, 8, 2, 1)
+    assert lds_bytes(I + 1, 64, 8, 8, 2, 1) == _carve_up(I + 1, 64, 8, 8, 2, 1) and _probe(lib, I + 1, 64, 8, 8, 2, 1, 2) == 4
+    assert lds_bytes(I, 64, 8, 8, 2, 1) == _carve_up(I, 64, 8, 8, 2, 1) and _probe(lib, I, 64, 8, 8, 2, 1, 2) == 2
+    for bad in range(6):
+        for v in (0, -1):
+            args = [12, 6, 5, 4, 2, 3]
+            args[bad] = v
+            assert lds_bytes(*args) == 0, args
+    assert lds_bytes(1, 6, 5, 4, 2, 3) == 0                                # I = 1: no training row left
+
+
 def test_c_entry_limits(lib):
     for probe in (lambda I, A, B1, B2, M, R: _probe(lib, I, A, B1, B2, M, R, 2), lambda *s: _probe_models(lib, *s)):
-        assert masked_tensor_side(64, 8, 8) == 64 and masked_tensor_side(65, 13, 5) == 65
+        assert _short_side(64, 8, 8) == 64 and _short_side(65, 13, 5) == 65
         assert probe(12, 64, 8, 8, 2, 2) == 2                    # the largest short side = 64: mode 0
         assert probe(12, 32, 64, 2, 2, 1) == 2                   # ... mode 1
         assert probe(12, 32, 2, 64, 2, 1) == 2                   # ... mode 2
@@ -106,9 +144,9 @@ def test_c_entry_limits(lib):
         assert probe(40, 6, 5, 4, 2, 16) == 2                    # R = 16
         assert probe(40, 6, 5, 4, 2, 17) == 4
         I = 2
-        while masked_tensor_lds_bytes(I + 1, 64, 8, 8, 2, 1) <= LDS_CAP:
+        while lib.cmtfpls_cv_masked_tensor_lds_bytes(I + 1, 64, 8, 8, 2, 1) <= LDS_CAP:
             I += 1
-        assert probe(I, 64, 8, 8, 2, 1) == 2                     # the LDS at its cap (the mirrored formula)
+        assert probe(I, 64, 8, 8, 2, 1) == 2                     # the LDS at its cap (the library's own count)
         assert probe(I + 1, 64, 8, 8, 2, 1) == 4
         assert probe(40, 1, 1, 1 << 30, 2, 1) == 4               # short sides of 1, and nothing that fits
     assert _probe(lib, 40, 6, 5, 4, 2, 2, 40) == 2               # K = I (leave-one-out)

@@ -33,10 +33,11 @@ def test_every_status_text_and_size_is_the_recorded_one(result):
     for got, exp in zip(result["calls"], want["calls"]):
         assert got == exp
     assert result["sizes"] == want["sizes"]
+    assert result["lds_sizes"] == want["lds_sizes"]
 
 
 def test_the_table_names_every_entry_in_scope(probe, result):
     in_scope = {name for name in _lib.SIGNATURES if name.startswith(probe.PREFIXES) and not name.startswith(probe.OUT_OF_SCOPE)}
-    assert len(in_scope) == 32
+    assert len(in_scope) == 36
     assert in_scope - probe.named(result) == set()
     assert probe.named(result) <= set(_lib.SIGNATURES)

@@ -4,9 +4,11 @@ folds, the LDS formula of the entry, and the wording of kfold._decline_blocks fo
 from types import SimpleNamespace
 
 import numpy as np
+import pytest
 
 import oracle as O
-from cmtf_pls_amd import kfold
+from cmtf_pls_amd import _lib, kfold
+from cmtf_pls_amd.backend import _int_pairs
 from cmtf_pls_amd.options import EngineOptions
 from kfold_coupled_order4_ref import coupled_data, coupled_inner_loop
 from kfold_order4_ref import inner_loop, planted
@@ -93,12 +95,60 @@ def test_tensor_dims_per_block():
     assert [kfold._dims(X) for X in Xs] == [(6, 20), (1, 7), (3, 2)]
 
 
+def _lds_bytes(dims, tensor, m, nb=None):
+    """cmtfpls_kfold_inner_coupled_tensor_lds_bytes of blocks dims = [(A, B), ..], tensor = [(B1, B2), ..], on states with null buffers."""
+    states = kfold._size_states(dims, m)
+    return _lib.load().cmtfpls_kfold_inner_coupled_tensor_lds_bytes(states, len(dims) if nb is None else nb, _int_pairs(tensor))
+
+
+def _carve_up(dims, tensor, m):
+    """The LDS of the kernel as include/cmtfpls.h lists it (doubles): wA, wB, q, qn, tq, G_y, xs, ys, then the CP's wK, wL, v, tmp, part."""
+    mats = [(A, B) for (A, B), (_, B2) in zip(dims, tensor) if B2 == 0]
+    tens = [(A, B1, B2) for (A, _), (B1, B2) in zip(dims, tensor) if B2 > 0]
+    xs = max([min(A, B) for A, B in mats] + [min(d, A * B1 * B2 // d) for A, B1, B2 in tens for d in (A, B1, B2)])
+    ys = max([max(A, B) for A, B in mats], default=0)
+    cp = [max((t[i] for t in tens), default=0) for i in (1, 2)] + [max((B1 * B2 for _, B1, B2 in tens), default=0),
+                                                                    max((max(t) for t in tens), default=0), 1024]
+    return 8 * (max(A for A, _ in dims) + max(B for _, B in dims) + 3 * m + m * m + xs + ys + sum(cp))
+
+
 def test_lds_formula_of_the_coupled_tensor_entry():
     # one block of order 4: the formula of cmtfpls_kfold_inner_tensor_f64 (A, 2 B, 3 M, M^2, nmax, B1, B2, max dim, part)
-    assert kfold.coupled_tensor_lds_bytes([(6, 20)], [(5, 4)], 3) == 8 * (6 + 2 * 20 + 9 + 9 + 6 + 5 + 4 + 6 + 1024)
+    assert _lds_bytes([(6, 20)], [(5, 4)], 3) == 8 * (6 + 2 * 20 + 9 + 9 + 6 + 5 + 4 + 6 + 1024)
     # tensor + order 2 + order 3: amax 5, bmax 21, n = max(5, 7, 3 | 1 | 4) = 7, k = max(9, 6) = 9 over the matrix blocks alone
-    got = kfold.coupled_tensor_lds_bytes([(5, 21), (1, 9), (6, 4)], [(7, 3), (0, 0), (0, 0)], 3)
+    got = _lds_bytes([(5, 21), (1, 9), (6, 4)], [(7, 3), (0, 0), (0, 0)], 3)
     assert got == 8 * (6 + 21 + 9 + 9 + 7 + 9 + 7 + 3 + 21 + 7 + 1024)
+
+
+# a cube, the Gram seed from the B1 unfolding (16, not 3), M = 1, tensor blocks next to matrix blocks, 8 blocks, then blocks past a
+# limit of the entry (a short side of 257 in an unfolding and in a matrix block, M = 65, more than 2^24 cells) and the two sides of
+# the 150 KB cap ((1, 9000) next to 2 x 90 x 90 is 218 984 bytes: far past it): the byte count is not gated by them
+LDS_BLOCKS = [([(5, 25)], [(5, 5)], 2), ([(3, 256)], [(16, 16)], 1), ([(6, 20), (1, 7)], [(5, 4), (0, 0)], 1),
+              ([(5, 21), (1, 9), (6, 4)], [(7, 3), (0, 0), (0, 0)], 3), ([(3, 2)] * 7 + [(2, 6)], [(0, 0)] * 7 + [(3, 2)], 2),
+              ([(17, 257 * 16), (1, 7)], [(257, 16), (0, 0)], 2), ([(257, 300), (6, 20)], [(0, 0), (5, 4)], 2),
+              ([(6, 20), (1, 7)], [(5, 4), (0, 0)], 65), ([(257, 256 * 256)], [(256, 256)], 2), ([(1, 9000), (2, 8100)], [(0, 0), (90, 90)], 3),
+              ([(1, 4540)], [(1, 4540)], 2), ([(1, 4541)], [(1, 4541)], 2)]
+
+
+@pytest.mark.parametrize("dims, tensor, m", LDS_BLOCKS, ids=lambda v: str(v).replace(" ", ""))
+def test_exported_lds_bytes_is_the_carve_up(dims, tensor, m):
+    assert _lds_bytes(dims, tensor, m) == _carve_up(dims, tensor, m)
+    if len(dims) == 1:                          # one block of order 4: the order-4 entry's own function
+        assert _lds_bytes(dims, tensor, m) == _lib.load().cmtfpls_kfold_inner_tensor_lds_bytes(dims[0][0], *tensor[0], m)
+
+
+def test_exported_lds_bytes_over_the_cap_and_malformed():
+    assert _lds_bytes([(1, 4541)], [(1, 4541)], 2) - 32 == _lds_bytes([(1, 4540)], [(1, 4540)], 2) == 150 * 1024 - 24
+    good = ([(6, 20), (1, 7)], [(5, 4), (0, 0)])
+    assert _lds_bytes(*good, 3) > 0
+    assert _lds_bytes(*good, 0) == 0 and _lds_bytes(*good, 3, nb=0) == 0
+    assert _lds_bytes([(3, 2)] * 9, [(0, 0)] * 8 + [(2, 1)], 3) == 0                                       # nb = 9
+    assert _lds_bytes([(6, 20), (1, 7)], [(5, 5), (0, 0)], 3) == 0                                         # B1 B2 != B
+    assert _lds_bytes([(6, 20), (1, 7)], [(5, 4), (7, 0)], 3) == 0 and _lds_bytes([(6, 20), (1, 7)], [(-5, -4), (0, 0)], 3) == 0
+    assert _lds_bytes([(0, 20), (1, 7)], [(5, 4), (0, 0)], 3) == 0 and _lds_bytes([(6, 20), (1, 0)], [(5, 4), (0, 0)], 3) == 0
+    lib = _lib.load()
+    assert lib.cmtfpls_kfold_inner_coupled_tensor_lds_bytes(None, 1, _int_pairs([(5, 4)])) == 0
+    assert lib.cmtfpls_kfold_inner_coupled_tensor_lds_bytes(kfold._size_states([(6, 20)], 3), 1, None) == 0
 
 
 def test_decline_wording_for_coupled_blocks_of_order4():

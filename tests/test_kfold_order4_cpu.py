@@ -104,3 +104,35 @@ def test_decline_wording_for_order4_blocks():
     blocks = [np.zeros((48, 6, 5)), np.zeros((48, 6, 5, 4))]                         # a ctPLS block of order 4 keeps refitting
     assert kfold._decline_blocks(_stub_model(), blocks, ["block 0", "block 1"], np.zeros((48, 3)), 4, _COUPLED, tensor_ok=True) \
         == "block 1 of order 4 (the device form takes order 2 and 3)"
+
+
+def _carve_up(A, B1, B2, M):
+    """The LDS of cmtfpls_kfold_inner_tensor_f64 as include/cmtfpls.h lists it, vector by vector (doubles)."""
+    B, P = B1 * B2, A * B1 * B2
+    vectors = {"wA": A, "wB": B, "q": M, "qn": M, "tq": M, "Gy": M * M, "xs": max(min(d, P // d) for d in (A, B1, B2)),
+               "wK": B1, "wL": B2, "v": B, "tmp": max(A, B1, B2), "part": 1024}
+    return 8 * sum(vectors.values())
+
+
+# a cube, the Gram seed from the B1 unfolding (16, not 3), M = 1, a mode of size 1, then one shape past each limit of the entry (a
+# short side of 257, M = 65, more than 2^24 cells) and the two sides of the 150 KB cap: the byte count is not gated by them
+LDS_SHAPES = [(5, 5, 5, 2), (3, 16, 16, 1), (6, 5, 4, 1), (6, 1, 5, 3), (257, 272, 1, 2), (17, 257, 16, 2), (6, 5, 4, 65), (257, 256, 256, 2),
+              (4, 200, 50, 3), (1, 1, 4540, 2), (1, 1, 4541, 2)]
+
+
+@pytest.mark.parametrize("shape", LDS_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_exported_lds_bytes_is_the_carve_up(shape):
+    from cmtf_pls_amd import _lib
+    assert _lib.load().cmtfpls_kfold_inner_tensor_lds_bytes(*shape) == _carve_up(*shape)
+
+
+def test_exported_lds_bytes_over_the_cap_and_malformed():
+    from cmtf_pls_amd import _lib
+    lds_bytes = _lib.load().cmtfpls_kfold_inner_tensor_lds_bytes
+    assert lds_bytes(3, 16, 16, 1) == 8 * (3 + 2 * 256 + 3 + 1 + 16 + 16 + 16 + 16 + 1024)                # xs: 16, not 3
+    assert lds_bytes(1, 1, 4541, 2) - 32 == lds_bytes(1, 1, 4540, 2) == 150 * 1024 - 24                  # wB, v, tmp and wL grow
+    for bad in range(4):
+        for v in (0, -1):
+            args = [6, 5, 4, 2]
+            args[bad] = v
+            assert lds_bytes(*args) == 0, args

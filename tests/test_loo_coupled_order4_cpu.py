@@ -135,12 +135,18 @@ def test_the_order23_entry_still_declines_order4(lib):
     assert rc == EUNSUPPORTED and "order > 3" in msg
 
 
-# ---- validate's mirror and its texts ---------------------------------------------------------------------------------------------
-def test_validate_lds_bytes_equals_the_mirror():
+# ---- what validate asks the library, and its texts --------------------------------------------------------------------------------
+def test_validate_lds_bytes_equals_the_mirror(lib):
+    """The description validate._loo_coupled_why builds from its dims / tensor lists (null pointers, the order from the lists) gets the
+    restatement's byte count from the library."""
+    from cmtf_pls_amd import _lib
     from cmtf_pls_amd import validate as V
     for I, dims, M, R in SHAPES:
-        assert V.loo_coupled_tensor_lds_bytes([T.split(d) for d in dims], [T.pair(d) for d in dims], M, R) == T.form(I, dims, M, R)[0]["lds_bytes"]
-    assert V.LOO_COUPLED_TENSOR_THREADS == T.THREADS and NAME in V.LOO_COUPLED_TENSOR_FORM
+        ab, pairs = [T.split(d) for d in dims], [T.pair(d) for d in dims]
+        blocks = V._size_blocks(_lib.LooCoupledBlock, ab, pairs)
+        assert [b.order for b in blocks] == [len(d) + 1 for d in dims]
+        assert lib.cmtfpls_loo_xcov_coupled_tensor_lds_bytes(blocks, len(dims), V._int_pairs(pairs), I, M, R) == T.form(I, dims, M, R)[0]["lds_bytes"]
+    assert NAME in V.LOO_COUPLED_TENSOR_FORM
 
 
 class _Shape:

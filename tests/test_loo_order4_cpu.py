@@ -4,13 +4,20 @@ leave-one-out helper, and the Kronecker identities that let the bootstrap align 
 from types import SimpleNamespace
 
 import numpy as np
+import pytest
 
 import oracle as O
+from cmtf_pls_amd import _lib
 from cmtf_pls_amd import validate as V
 from cmtf_pls_amd.bootstrap import align_factors
 from loo_order4_ref import loo_case, planted_xy
 
 ENTRY = "cmtfpls_loo_xcov_tensor_f64"
+
+
+@pytest.fixture(scope="module")
+def lds_bytes():
+    return _lib.load().cmtfpls_loo_xcov_tensor_lds_bytes
 
 
 def _be(tensor=True):
@@ -30,7 +37,7 @@ def test_decline_wording():
     assert d(_be(), 17, 16, 257, 2, 2) == "mode-2 unfolding: min(257, 272) = 257 > 256"
     assert d(_be(), 6, 5, 4, 129, 2) == f"M = 129 > 128 responses ({ENTRY})"
     assert d(_be(), 6, 5, 4, 2, 65) == f"R = 65 > 64 components ({ENTRY})"
-    lds = V.loo_tensor_lds_bytes(4, 200, 50, 2, 2)
+    lds = _carve_up(4, 200, 50, 2, 2)
     assert lds > 150 * 1024 and d(_be(), 4, 200, 50, 2, 2) == f"the fold's vectors need {lds} bytes of LDS > 153600 ({ENTRY})"
     assert d(_be(), 6, 1, 5, 2, 3) is None and d(_be(), 6, 5, 1, 2, 3) is None       # a mode of size 1 is a tensor, not a decline
 
@@ -45,11 +52,31 @@ def _carve_up(A, B1, B2, M, R):
     return 8 * sum(vectors.values())
 
 
-def test_lds_formula_is_the_documented_carve_up():
-    assert V.loo_tensor_lds_bytes(6, 5, 4, 2, 3) == _carve_up(6, 5, 4, 2, 3) == 8 * (6 + 20 + 8 + 4 + 6 + 5 + 4 + 20 + 6 + 1024 + 9 + 6 + 9 + 9)
-    assert V.loo_tensor_lds_bytes(40, 3, 2, 128, 64) == _carve_up(40, 3, 2, 128, 64)
+def test_lds_formula_is_the_documented_carve_up(lds_bytes):
+    assert lds_bytes(6, 5, 4, 2, 3) == _carve_up(6, 5, 4, 2, 3) == 8 * (6 + 20 + 8 + 4 + 6 + 5 + 4 + 20 + 6 + 1024 + 9 + 6 + 9 + 9)
+    assert lds_bytes(40, 3, 2, 128, 64) == _carve_up(40, 3, 2, 128, 64)
     # the Gram seed is sized by the largest short side of the three unfoldings, not by min(A, B1 B2)
-    assert V.loo_tensor_lds_bytes(3, 16, 16, 1, 1) == 8 * (3 + 2 * 256 + 4 + 1 + 16 + 16 + 16 + 16 + 1024 + 2 + 1 + 3)   # xs: 16, not 3
+    assert lds_bytes(3, 16, 16, 1, 1) == 8 * (3 + 2 * 256 + 4 + 1 + 16 + 16 + 16 + 16 + 1024 + 2 + 1 + 3)   # xs: 16, not 3
+
+
+# a cube, the Gram seed from the B1 unfolding, M = 1, the cap's two sides, then one shape past each limit of the entry (a short side
+# of 257, M = 129, R = 65, more than 2^24 cells, just over 150 KB): the byte count is not gated by them
+LDS_SHAPES = [(5, 5, 5, 2, 2), (3, 16, 16, 1, 1), (6, 5, 4, 1, 3), (6, 1, 5, 2, 3), (141, 16, 16, 128, 10), (257, 272, 1, 2, 2),
+              (17, 257, 16, 2, 2), (6, 5, 4, 129, 2), (6, 5, 4, 2, 65), (257, 256, 256, 2, 2), (1, 1, 4535, 2, 2), (1, 1, 4536, 2, 2)]
+
+
+@pytest.mark.parametrize("shape", LDS_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_exported_lds_bytes_is_the_carve_up(lds_bytes, shape):
+    assert lds_bytes(*shape) == _carve_up(*shape)
+
+
+def test_exported_lds_bytes_over_the_cap_and_malformed(lds_bytes):
+    assert lds_bytes(1, 1, 4536, 2, 2) - 32 == lds_bytes(1, 1, 4535, 2, 2) == 150 * 1024 - 24          # wB, v, tmp and wL grow
+    for bad in range(5):
+        for v in (0, -1):
+            args = [6, 5, 4, 2, 3]
+            args[bad] = v
+            assert lds_bytes(*args) == 0, args
 
 
 def test_oracle_leave_one_out_helper():

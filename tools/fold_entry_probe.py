@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the host side of the fold entries answers, on a fixed table of calls: (status, cmtfpls_last_error()) of every call and the
-value of every workspace-size export, as JSON.  No GPU: every call of the table is refused by a check of the entry's host code,
+value of every workspace-size and LDS-size export, as JSON.  No GPU: every call of the table is refused by a check of the entry's host code,
 before a data pointer is read or a kernel launched (the pointers are stand-ins); the tool stops at the first call that is not.
 The entries: the four of csrc/cv_masked.hip, the two of csrc/loo_xcov.hip and, of csrc/kfold.hip, the six inner entries, the four
 epilogue entries and the wide and weighted cross-covariance builds.  The table reaches every `return CMTFPLS_E*` of those entries
@@ -334,8 +334,9 @@ def table(lib):
     return rows
 
 
-def sizes(lib):
-    """[(export, printable arguments, value)] on about ten shapes each, some of which the export answers with 0."""
+def sizes(lib, lds=False):
+    """[(export, printable arguments, value)] on about ten shapes each, some of which the export answers with 0: of the workspace-size
+    exports, or (lds) of the LDS-size exports."""
     out = []
 
     def plain(sym, shapes):
@@ -354,9 +355,9 @@ def sizes(lib):
         plain(sym, six)
     plain("cmtfpls_kfold_inner_workspace_bytes", [(6, 5, 4), (1, 9, 2), (128, 128, 5), (256, 4096, 32), (300, 300, 32), (1, 1, 1), (4096, 4096, 8),
                                                   (0, 5, 4), (6, 0, 4), (6, 5, 0), (-1, 5, 4)])
-    plain("cmtfpls_kfold_inner_tensor_workspace_bytes", [(6, 4, 2, 4), (3, 4, 2, 2), (6, 1, 5, 5), (2, 9, 3, 32), (64, 64, 64, 8), (8, 257, 33, 4),
-                                                         (256, 256, 256, 32), (256, 256, 257, 4), (0, 4, 2, 4), (6, 0, 2, 4), (6, 4, 0, 4),
-                                                         (6, 4, 2, 0)])
+    tensor4 = [(6, 4, 2, 4), (3, 4, 2, 2), (6, 1, 5, 5), (2, 9, 3, 32), (64, 64, 64, 8), (8, 257, 33, 4), (256, 256, 256, 32),
+               (256, 256, 257, 4), (0, 4, 2, 4), (6, 0, 2, 4), (6, 4, 0, 4), (6, 4, 2, 0)]
+    plain("cmtfpls_kfold_inner_tensor_workspace_bytes", tensor4)
     four = [(4096, 30, 40, 4), (40, 30, 3, 4), (65536, 16384, 16, 5), (65536, 16384, 1024, 32), (1 << 20, 64, 8, 2), (100, 1, 1, 1),
             (8192, 1 << 24, 16, 5), (0, 30, 40, 4), (4096, 0, 40, 4), (4096, 30, 0, 4), (4096, 30, 40, 0)]
     plain("cmtfpls_kfold_wide_xcov_workspace_bytes", four)
@@ -377,6 +378,17 @@ def sizes(lib):
     for bl, ds in tblocks:
         out.append(("cmtfpls_kfold_inner_coupled_tensor_workspace_bytes", [[list(b) for b in bl], [list(d) for d in ds]],
                     lib.cmtfpls_kfold_inner_coupled_tensor_workspace_bytes(views(*[state(*b) for b in bl]), len(bl), pairs(*ds))))
+    if not lds:
+        return out
+    # the LDS-size exports, a list of their own (the record of the workspace sizes is older): the same shapes, the last of tensor4's
+    # four read as M; a shape past a limit of its entry keeps its byte count
+    out = []
+    plain("cmtfpls_cv_masked_tensor_lds_bytes", six)
+    plain("cmtfpls_loo_xcov_tensor_lds_bytes", [s[1:] for s in six])
+    plain("cmtfpls_kfold_inner_tensor_lds_bytes", tensor4)
+    for bl, ds in tblocks:
+        out.append(("cmtfpls_kfold_inner_coupled_tensor_lds_bytes", [[list(b) for b in bl], [list(d) for d in ds]],
+                    lib.cmtfpls_kfold_inner_coupled_tensor_lds_bytes(views(*[state(*b) for b in bl]), len(bl), pairs(*ds))))
     return out
 
 
@@ -390,12 +402,13 @@ def probe(lib):
         assert rc in (1, 2, 4), f"{label}: status {rc} ({msg}) -- every call of the table must be refused on the host"
         calls.append({"call": label, "status": rc, "error": msg})
     assert len({c["call"] for c in calls}) == len(calls)
-    return {"calls": calls, "sizes": [{"export": s, "args": a, "bytes": v} for s, a, v in sizes(lib)]}
+    return {"calls": calls, "sizes": [{"export": s, "args": a, "bytes": v} for s, a, v in sizes(lib)],
+            "lds_sizes": [{"export": s, "args": a, "bytes": v} for s, a, v in sizes(lib, lds=True)]}
 
 
 def named(result):
     """The SIGNATURES names the table reaches."""
-    return {"cmtfpls_" + c["call"].split(":")[0] for c in result["calls"]} | {s["export"] for s in result["sizes"]}
+    return {"cmtfpls_" + c["call"].split(":")[0] for c in result["calls"]} | {s["export"] for s in result["sizes"] + result["lds_sizes"]}
 
 
 if __name__ == "__main__":
@@ -405,4 +418,4 @@ if __name__ == "__main__":
     with open(sys.argv[1], "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
-    print(f"{len(res['calls'])} calls, {len(res['sizes'])} sizes -> {sys.argv[1]}; library {_lib.LIB_PATH}")
+    print(f"{len(res['calls'])} calls, {len(res['sizes'])} + {len(res['lds_sizes'])} sizes -> {sys.argv[1]}; library {_lib.LIB_PATH}")
