@@ -167,6 +167,8 @@ SIGNATURES = {
     "cmtfpls_kfold_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "cmtfpls_kfold_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_xcov_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_xcov_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_xcov_f16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_row_tiles": (c_int, [c_int64]),
     "cmtfpls_kfold_part_stride": (c_int, []),
     "cmtfpls_kfold_inner_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -186,6 +188,8 @@ SIGNATURES = {
     "cmtfpls_kfold_wide_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "cmtfpls_kfold_wide_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_wide_xcov_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_wide_xcov_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_wide_xcov_f16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_inner_grouped_f64": (c_int, [ctypes.POINTER(KfoldState), _P, c_int, c_int, c_double, c_int, _P, c_size_t, _P]),
     "cmtfpls_kfold_inner_coupled_grouped_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, _P, c_int, c_int, c_double, c_int, _P, c_size_t,
                                                         _P]),
@@ -194,6 +198,8 @@ SIGNATURES = {
     "cmtfpls_kfold_weighted_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "cmtfpls_kfold_weighted_xcov_f32": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_weighted_xcov_f64": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_weighted_xcov_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_kfold_weighted_xcov_f16": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_kfold_epilogue_weighted_f64": (c_int, [ctypes.POINTER(KfoldState), c_int, c_int, _P, _P]),
     "cmtfpls_press_rows_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "cmtfpls_press_rows_f64": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),

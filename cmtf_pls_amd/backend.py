@@ -15,7 +15,8 @@ from . import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
 HALF_DTYPES = (torch.bfloat16, torch.float16)                # 16-bit storage: only ever read, converted to f64 on load
-_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp")   # the entries that have _bf16 / _f16 forms
+# the entries that have _bf16 / _f16 forms: the fit's and the projection's passes, and the S builds of the resampling drivers
+_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp", "kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov")
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -109,7 +110,7 @@ class HipBackend:
         return torch.zeros(*shape, dtype=dtype, device=self.device)
 
     def has_half(self, base: str) -> bool:
-        """Whether entry `base` has a form for 16-bit storage (bfloat16 / float16): the read-only matrix-core passes only."""
+        """Whether entry `base` has a form for 16-bit storage (bfloat16 / float16): the read-only passes over X only."""
         return base in _HALF_ENTRIES and hasattr(self.lib, f"cmtfpls_{base}_bf16") and hasattr(self.lib, f"cmtfpls_{base}_f16")
 
     def _fn(self, base: str, X: torch.Tensor):
@@ -969,9 +970,12 @@ class HipBackend:
                    ydev: torch.Tensor, S: torch.Tensor, mean: torch.Tensor) -> Optional[torch.Tensor]:
         """Every fold's training cross-covariance S[k] (K x M x P) and training means (K x P) from ONE read of the uncentred X2
         (cmtfpls_kfold_xcov_*); returns the column sums / sums of squares of all rows (2 P), or None when the shape is outside
-        the device form.  The partial-sum workspace is local to the call."""
+        the device form (a 16-bit X2 on a library without the 16-bit entries included).  The partial-sum workspace is local to
+        the call."""
         I, P = X2.shape
         M = Y.shape[1]
+        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_xcov"):
+            return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and order.dtype == torch.int32 and fold_off.dtype == torch.int32 and P == A * B
         ws = _scratch(self.lib.cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K), self.device)
         stats = self.empty(2 * P)
@@ -1056,6 +1060,8 @@ class HipBackend:
         squares of all rows (2 P); None when the shape is outside the device form.  The partial-sum workspace is local to the call."""
         I, P = X2.shape
         W = Y.shape[1]
+        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_wide_xcov"):
+            return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and ydev.is_contiguous() and S.is_contiguous() and P == A * B
         assert order.dtype == torch.int32 and fold_off.dtype == torch.int32 and S.numel() == K * W * P and mean.numel() == K * P
         ws = _scratch(self.lib.cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K), self.device)
@@ -1105,6 +1111,8 @@ class HipBackend:
         the column sums / sums of squares of all rows (2 P), or None when the shape is outside the device form.  The partial-sum
         workspace is local to the call."""
         I, P = X2.shape
+        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_weighted_xcov"):
+            return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape == (I, n * (M + 1)) and P == A * B
         assert S.is_contiguous() and S.numel() == n * M * P and mean.is_contiguous() and mean.numel() == n * P
         ws = _scratch(self.lib.cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M), self.device)

@@ -13,7 +13,8 @@
 //                   fold; stage 2: the down-date of S_k from r = X_c^T t
 //   (contraction)   X_0^T [t_1 * train_1 .. t_K * train_K] through cmtfpls_xcov_*                    ONE read of X
 // 2R reads of X for all K folds; nothing is written to X and no copy of it is made.  Arithmetic: float64 (an f32 X is widened
-// on load).  No workgroup waits on another.  Coupled models (ctPLS): the same steps per block with the score shared, see the
+// on load; 16-bit storage, bf16_t / f16_t of common.hpp, likewise: every stored element goes through to_f64, which is exact, so the
+// _bf16 / _f16 builds of S return the bits of the _f32 build on the upcast values).  No workgroup waits on another.  Coupled models (ctPLS): the same steps per block with the score shared, see the
 // section "coupled models" below.
 #include "fold_loop.hpp"
 #include "fold_regress.hpp"
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kKfCols) void kfold_partials_kernel(const T* __rest
 #pragma unroll
     for (int u = 0; u < 4; ++u) i4[u] = order[r + u];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) x[u] = (double)X[(int64_t)i4[u] * P + c];
+    for (int u = 0; u < 4; ++u) x[u] = to_f64(X[(int64_t)i4[u] * P + c]);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const double* y = Y + (int64_t)i4[u] * M;
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(kKfCols) void kfold_partials_kernel(const T* __rest
   }
   for (; r < hi; ++r) {
     const int i = order[r];
-    const double xv = (double)X[(int64_t)i * P + c];
+    const double xv = to_f64(X[(int64_t)i * P + c]);
     const double* y = Y + (int64_t)i * M;
 #pragma unroll
     for (int j = 0; j < MT; ++j)
@@ -833,7 +834,7 @@ __global__ __launch_bounds__(kKfWideCols) void kfold_wide_kernel(const T* __rest
       const bool rok = r + 4 * s + kq < hi;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const double b = (rok && cok[e]) ? (double)x[s].e[e] : 0.0;
+        const double b = (rok && cok[e]) ? to_f64(x[s].e[e]) : 0.0;
         cs[e] += b;
         cq[e] = fma(b, b, cq[e]);
 #pragma unroll
@@ -872,7 +873,8 @@ template <typename T, int MT>
 static void kf_wide_launch(dim3 g, hipStream_t st, const T* X, int64_t P, const double* Y, int W, const int* order, const int* off,
                            int nyb, int nch, double* part) {
   // VEC reads X + i P + c as a Pack<T, 4>: every row start is aligned only when P % 4 == 0 and X itself is (a view into a larger
-  // buffer need not be)
+  // buffer need not be).  16-bit storage: the lane's 4 columns are one 8-byte load, so the base must be 8-byte aligned; a base that
+  // is only 2-byte aligned takes the scalar path, whose indices are clamped into the row
   if (P % 4 == 0 && reinterpret_cast<uintptr_t>(X) % sizeof(Pack<T, 4>) == 0)
     hipLaunchKernelGGL((kfold_wide_kernel<T, MT, true>), g, dim3(kKfWideCols), 0, st, X, P, Y, W, order, off, nyb, nch, part);
   else
@@ -1113,6 +1115,18 @@ int cmtfpls_kfold_xcov_f64(const double* X, int64_t I, int A, int B, const doubl
   return run_kfold_xcov<double>(X, I, A, B, Y, M, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int cmtfpls_kfold_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                            const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_xcov<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, A, B, Y, M, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes,
+                                (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_xcov<f16_t>(reinterpret_cast<const f16_t*>(X), I, A, B, Y, M, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
 int cmtfpls_kfold_row_tiles(int64_t I) { return I > 0 ? kf_tiles(I) : 0; }
 
 int cmtfpls_kfold_part_stride(void) { return 2 * kKfMaxR + 1 + kKfMaxM; }
@@ -1279,6 +1293,18 @@ int cmtfpls_kfold_wide_xcov_f64(const double* X, int64_t I, int A, int B, const 
   return run_kfold_wide<double>(X, I, A, B, Y, W, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int cmtfpls_kfold_wide_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                 int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_wide<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, A, B, Y, W, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes,
+                                (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_wide_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_wide<f16_t>(reinterpret_cast<const f16_t*>(X), I, A, B, Y, W, order, fold_off, K, ydev, S, mean, stats, ws, ws_bytes,
+                               (hipStream_t)stream);
+}
+
 int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int a, double tol, int max_iter,
                                     void* ws, size_t ws_bytes, void* stream) {
   int rc = kf_grouped_check(st, model_fold, groups, a, "kfold_inner_grouped: bad argument");
@@ -1339,6 +1365,16 @@ int cmtfpls_kfold_weighted_xcov_f32(const float* X, int64_t I, int A, int B, con
 int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
                                     double* stats, void* ws, size_t ws_bytes, void* stream) {
   return run_kfold_weighted<double>(X, I, A, B, Y, n, M, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_weighted_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                     double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_weighted<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, A, B, Y, n, M, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int cmtfpls_kfold_weighted_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream) {
+  return run_kfold_weighted<f16_t>(reinterpret_cast<const f16_t*>(X), I, A, B, Y, n, M, S, mean, stats, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int cmtfpls_kfold_epilogue_weighted_f64(const cmtfpls_kfold_state* st, int stage, int a, const double* in, void* stream) {

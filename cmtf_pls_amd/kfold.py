@@ -412,11 +412,57 @@ def _to_dev(a, dev, dt=torch.float64) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
 
 
-def _device_blocks(pls, Xs, dev):
-    """Each block as (X2, A, B): the device tensor of the storage type (the caller's own when it is one: never copied), I x P."""
-    from .tpls import _as_torch_dtype, to_device_read
+# the five entries through which the device passes read X: the three builders of S and the mean, the score pass, the contraction
+HALF_READS = ("kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov", "mttkrp", "xcov")
 
-    return [(to_device_read(X, _as_torch_dtype(pls._dtype, X), dev, pls=pls).view(X.shape[0], -1), *_dims(X)) for X in Xs]
+
+# why the routes without 16-bit kernels copy 16-bit storage (the report's storage_fallback under EngineOptions.half_folds)
+HALF_MASKED_WHY = "the masked routes (cmtfpls_cv_masked_*) have no 16-bit form and read a float64 upload of the data"
+HALF_LOO_WHY = "leave-one-out (cmtfpls_loo_*) takes float64 X and reads a float64 upload of the data"
+
+
+def _half_in_place(pls) -> Optional[str]:
+    """None when the device passes read 16-bit storage in place (EngineOptions.half_folds and a backend with the _bf16 / _f16 form
+    of every entry of HALF_READS); else why they read a float32 upcast, None again while the option is off (the general reason
+    of _reports_upcast then stands)."""
+    eng = pls._get_engine()
+    if not getattr(eng.opt, "half_folds", False):
+        return None
+    be = eng.be
+    missing = [e for e in HALF_READS if not (hasattr(be, "has_half") and be.has_half(e))]
+    if missing:
+        return (f"EngineOptions.half_folds: the {getattr(be, 'name', type(be).__name__)} backend has no 16-bit form of "
+                + ", ".join(f"cmtfpls_{e}_*" for e in missing))
+    return None
+
+
+def _note_half_copy(pls, X, why: str) -> None:
+    """Under EngineOptions.half_folds, note that a route without 16-bit kernels (leave-one-out, the masked routes) read a private
+    copy of block X of a model with 16-bit storage (the report's storage_fallback); with the option off nothing is noted."""
+    from .tpls import HALF_DTYPES, _as_torch_dtype, note_storage_upcast
+
+    dtype = _as_torch_dtype(pls._dtype, X)
+    if dtype in HALF_DTYPES and getattr(pls._get_engine().opt, "half_folds", False):
+        note_storage_upcast(pls, dtype, why)
+
+
+def _device_blocks(pls, Xs, dev):
+    """Each block as (X2, A, B): the device tensor of the storage type (the caller's own when it is one: never copied), I x P.
+    16-bit storage: an exact float32 upcast of the rounded data, noted for the report -- or, under EngineOptions.half_folds on a
+    backend with the 16-bit entries (_half_in_place), the 16-bit tensor itself: the caller's own, or the once-rounded upload."""
+    from .tpls import HALF_DTYPES, _as_torch_dtype, to_device_copy, to_device_read
+
+    why = _half_in_place(pls)
+    in_place = why is None and bool(getattr(pls._get_engine().opt, "half_folds", False))
+    blocks = []
+    for X in Xs:
+        dtype = _as_torch_dtype(pls._dtype, X)
+        if in_place and dtype in HALF_DTYPES:
+            X2 = to_device_copy(X, dtype, dev, copy=False)                           # (_device_pass notes the entries that read it)
+        else:
+            X2 = to_device_read(X, dtype, dev, pls=pls, why=why)
+        blocks.append((X2.view(X.shape[0], -1), *_dims(X)))
+    return blocks
 
 
 def _state(be, fold_of: torch.Tensor, Yk: torch.Tensor, blocks, R: int, slots: int):
@@ -588,7 +634,15 @@ def _device_pass(pls, Xs, blocks, coupled: bool, builder: str, builds, fold_of: 
         shared["Wk"], shared["Wl"] = tensor_out
     why = _components(be, [X2 for X2, _, _ in blocks], st, shared, own, R, tol, max_iter, coupled, tensor=tensor, tensor_out=tensor_out,
                       **layout)
-    return why if why is not None else (shared, own)
+    if why is not None:
+        return why
+    from .tpls import HALF_DTYPES, note_storage_in_place
+
+    for X2, _, _ in blocks:                                                      # EngineOptions.half_folds: 16-bit blocks read in place
+        if X2.dtype in HALF_DTYPES:
+            suffix = "bf16" if X2.dtype == torch.bfloat16 else "f16"
+            note_storage_in_place(pls, X2.dtype, [f"cmtfpls_{e}_{suffix}" for e in (builder, "mttkrp", *(("xcov",) if R > 1 else ()))])
+    return shared, own
 
 
 def device_predictions(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: int, coupled: bool):
@@ -671,7 +725,8 @@ def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
     """What masked_predictions, masked_models and masked_models_coupled check before they look at X, in this order: the backend's
     kernel (`what` names it in the decline), a sharded model, the order of every block (tensor: _tensor_dims of a tPLS's order-4 X
     under EngineOptions.masked_tensor_folds, which the order-4 entries take), NaN in Y.  (why, None), or (None, (eng, be, M,
-    upload)): upload(a, I) is the original data in float64 on the device as I x -1."""
+    upload)): upload(a, I) is the original data in float64 on the device as I x -1; upload(X, I, True) for a block of X, which notes
+    the copy of 16-bit storage under EngineOptions.half_folds (_note_half_copy)."""
     eng = pls._get_engine()
     be = eng.be
     if not hasattr(be, kernel):
@@ -684,7 +739,13 @@ def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
     if has_missing(Y):
         return "missing values in Y", None
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
-    return None, (eng, be, M, lambda a, I: _f64(a, be.device).contiguous().view(I, -1))
+
+    def upload(a, I, block=False):
+        if block:
+            _note_half_copy(pls, a, HALF_MASKED_WHY)
+        return _f64(a, be.device).contiguous().view(I, -1)
+
+    return None, (eng, be, M, upload)
 
 
 def _masked_outside(form: str, A: int, B: int, M: int, R: int) -> str:
@@ -712,7 +773,7 @@ def masked_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter:
     dev = be.device
 
     with eng.device_ctx():
-        data = (upload(X, I), upload(Y, I), _to_dev(ids, dev, torch.int32), K)
+        data = (upload(X, I, True), upload(Y, I), _to_dev(ids, dev, torch.int32), K)
         if tensor:
             out = be.cv_masked_tensor(*data, A, *tensor, R, tol, max_iter)
             if out is None:
@@ -760,7 +821,7 @@ def masked_models(pls, X, Y, counts: np.ndarray, yrow: Optional[np.ndarray], tol
     dev = be.device
 
     with eng.device_ctx():
-        data = (upload(X, I), upload(Y, I), _to_dev(counts, dev, torch.int32),
+        data = (upload(X, I, True), upload(Y, I), _to_dev(counts, dev, torch.int32),
                 None if yrow is None else _to_dev(yrow, dev, torch.int32))
         if tensor:
             out = be.cv_masked_tensor_models(*data, A, *tensor, R, tol, max_iter, factors, max_ws_bytes)
@@ -894,7 +955,7 @@ def masked_models_coupled(pls, Xs, Y, counts: np.ndarray, yrow: Optional[np.ndar
     with eng.device_ctx():
         out = None
         if len(Xs) <= MAX_BLOCKS:                                                # (the entry declines more blocks itself)
-            data = ([upload(X, I) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)])
+            data = ([upload(X, I, True) for X in Xs], [(X.ndim, A, B) for X, (A, B) in zip(Xs, dims)])
             rest = (upload(Y, I), _to_dev(counts, dev, torch.int32), None if yrow is None else _to_dev(yrow, dev, torch.int32), R, tol,
                     max_iter, factors, max_ws_bytes)
             out = be.cv_masked_coupled_tensor(*data, tensor, *rest) if tensor else be.cv_masked_coupled(*data, *rest)

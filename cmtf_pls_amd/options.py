@@ -101,6 +101,15 @@ class EngineOptions:
     # (per-mode stacks [wA, wK, wL]); opt-in, and separate from masked_folds_coupled, which alone declines such a model to the refits
     # (report: q2y_report_ / bootstrap_report_ with "rank1", a decline names its reason)
     masked_tensor_folds_coupled: bool = False
+    # cross-validation and the bootstrap of a model with 16-bit storage (dtype="bfloat16" / "float16") on the 16-bit tensor itself:
+    # the complete-data device passes of K-fold, the permutation test, repeated and nested K-fold and bootstrap_factors (tPLS and
+    # ctPLS, order-4 blocks under tensor_folds / tensor_folds_coupled / tensor_resamples_coupled included) read X through
+    # cmtfpls_kfold_xcov_* / kfold_wide_xcov_* / kfold_weighted_xcov_*, cmtfpls_mttkrp_* and cmtfpls_xcov_* in their _bf16 / _f16
+    # forms -- a caller's 16-bit device tensor is never copied -- instead of an exact float32 upcast of twice its size (DESIGN 8w,
+    # "Resampling"); the float32 model's arithmetic in another f64 summation order, so not bit-identical to the upcast route.
+    # Leave-one-out, the masked routes and a backend without the entries still upcast; opt-in (report: q2y_report_ /
+    # bootstrap_report_ with "half_storage", else "storage_fallback" with the reason)
+    half_folds: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

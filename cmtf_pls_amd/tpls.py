@@ -41,38 +41,61 @@ def _as_torch_dtype(dtype, like) -> torch.dtype:
             "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.float16, "f16": torch.float16}[name]
 
 
-def to_device_read(X, dtype: torch.dtype, device, pls=None) -> torch.Tensor:
-    """X on the device as the routines beside fit / transform read it (diagnostics, contributions, importance, imputation, the
-    resampling drivers, R2X_literal): `to_device_copy(X, dtype, device, copy=False)` -- and for a model with 16-bit storage the
-    data ROUNDED to that type, then upcast to float32: exactly the values the model was fitted on, in a type those kernels take.
-    `pls`: the model on whose behalf X is read; the upcast is noted on it for the routine's report (`reports_storage_upcast`)."""
-    Xd = to_device_copy(X, dtype, device, copy=False)
-    if dtype not in HALF_DTYPES:
-        return Xd
+def note_storage_upcast(pls, dtype: torch.dtype, why: Optional[str] = None) -> None:
+    """Note on `pls` that a routine read a private upcast of its 16-bit data (`reports_storage_upcast` writes the report); `why`: this
+    read's own reason, which then replaces the routine's general one."""
     seen = getattr(pls, "_storage_upcasts", None)
     if seen is not None:
         seen.append(str(dtype).replace("torch.", ""))
+        if why is not None and why not in pls._storage_upcast_whys:
+            pls._storage_upcast_whys.append(why)
+
+
+def note_storage_in_place(pls, dtype: torch.dtype, entries) -> None:
+    """Note on `pls` that a routine's device passes read the 16-bit tensor itself through `entries` (EngineOptions.half_folds)."""
+    here = getattr(pls, "_storage_in_place", None)
+    if here is not None:
+        here.append((str(dtype).replace("torch.", ""), tuple(entries)))
+
+
+def to_device_read(X, dtype: torch.dtype, device, pls=None, why: Optional[str] = None) -> torch.Tensor:
+    """X on the device as the routines beside fit / transform read it (diagnostics, contributions, importance, imputation, the
+    resampling drivers, R2X_literal): `to_device_copy(X, dtype, device, copy=False)` -- and for a model with 16-bit storage the
+    data ROUNDED to that type, then upcast to float32: exactly the values the model was fitted on, in a type those kernels take.
+    `pls`: the model on whose behalf X is read; the upcast is noted on it for the routine's report (`reports_storage_upcast`),
+    with this read's own reason `why` where it has one."""
+    Xd = to_device_copy(X, dtype, device, copy=False)
+    if dtype not in HALF_DTYPES:
+        return Xd
+    note_storage_upcast(pls, dtype, why)
     return Xd.to(torch.float32)
 
 
 def reports_storage_upcast(report_attr: str, why: str):
     """Decorator of a routine `fn(pls, ...)` that leaves its report in `pls.<report_attr>`: when the routine read X of a model with
     16-bit storage through `to_device_read(..., pls=pls)` -- a full float32 copy -- the report gets
-    "storage_fallback": "float32 private copy of the <type> data: <why>"."""
+    "storage_fallback": "float32 private copy of the <type> data: <why>" (the reads' own reasons where they gave any).  When its
+    device passes read the 16-bit tensor itself instead (`note_storage_in_place`, EngineOptions.half_folds) and the report shows
+    reads of X, it gets "half_storage": {"in_place": True, "dtype": <type>, "entries": [...]} and no "storage_fallback"."""
     def deco(fn):
         @functools.wraps(fn)
         def run(pls, *args, **kw):
-            outer = getattr(pls, "_storage_upcasts", None)
-            pls._storage_upcasts = seen = []
+            outer = [getattr(pls, a, None) for a in ("_storage_upcasts", "_storage_upcast_whys", "_storage_in_place")]
+            pls._storage_upcasts, pls._storage_upcast_whys, pls._storage_in_place = seen, whys, here = [], [], []
             try:
                 out = fn(pls, *args, **kw)
             finally:
-                pls._storage_upcasts = outer
+                pls._storage_upcasts, pls._storage_upcast_whys, pls._storage_in_place = outer
             rep = getattr(pls, report_attr, None)
             if seen and isinstance(rep, dict):
-                rep["storage_fallback"] = f"float32 private copy of the {' / '.join(sorted(set(seen)))} data: {why}"
-            if outer is not None:
-                outer.extend(seen)
+                rep["storage_fallback"] = f"float32 private copy of the {' / '.join(sorted(set(seen)))} data: {'; '.join(whys) or why}"
+            elif here and isinstance(rep, dict) and rep.get("x_reads") is not None:
+                rep["half_storage"] = {"in_place": True, "dtype": " / ".join(sorted({d for d, _ in here})),
+                                       "entries": sorted({e for _, es in here for e in es})}
+            if outer[0] is not None:
+                outer[0].extend(seen)
+                outer[1].extend(w for w in whys if w not in outer[1])
+                outer[2].extend(here)
             return out
         return run
     return deco

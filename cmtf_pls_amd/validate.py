@@ -26,8 +26,8 @@ import numpy as np
 
 from . import _lib
 from .backend import _int_pairs
-from .kfold import (MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
-                    _masked_declined, _size_blocks, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
+from .kfold import (HALF_LOO_WHY, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
+                    _masked_declined, _note_half_copy, _reports_upcast, _size_blocks, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
                     masked_predictions_coupled, refit_predictions, wants_masked_coupled, wants_masked_tensor)
 from .tpls import tPLS
 
@@ -60,6 +60,7 @@ def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
     return None
 
 
+@_reports_upcast()
 def loo_predictions(pls_tensor, tol: float = 1e-8, max_iter: int = 100):
     """Y_pred[i] = prediction for sample i by the model refitted without it (validate.py:24-33), all folds in one
     launch; None when the device form does not apply (see get_q2y).  `pls_tensor` is a fitted tPLS or ctPLS."""
@@ -176,6 +177,8 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
     eng = pls._get_engine()
     be = eng.be
     with eng.device_ctx():
+        for X in Xs:
+            _note_half_copy(pls, X, HALF_LOO_WHY)                            # 16-bit storage under EngineOptions.half_folds
         data = ([_upload(X, I, be.device) for X in Xs], _upload(Y, I, be.device), [(X.ndim, *_dims(X)) for X in Xs])
         if tensor:
             out = be.loo_ctpls_tensor(*data, _tensor_dims(Xs, coupled=True), pls.n_components, tol, max_iter)
@@ -233,6 +236,7 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         if why is not None:
             return None, why
     with torch.cuda.device(be.device):
+        _note_half_copy(pls_tensor, X, HALF_LOO_WHY)                         # 16-bit storage under EngineOptions.half_folds
         Xd, Yd = _upload(X, I, be.device), _upload(Y, I, be.device)
         if order4:
             return _loo_result(pls_tensor, be.loo_tpls_tensor(Xd, Yd, A, B1, B2, R, tol, max_iter), "cmtfpls_loo_xcov_tensor_f64",
@@ -243,6 +247,7 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         return _loo_result(pls_tensor, out, "", LOO_FORMS[out[2]], Y)
 
 
+@_reports_upcast()
 def get_q2y(pls_tensor, device_folds: bool = True):
     if _is_coupled(pls_tensor):
         return _get_q2y_coupled(pls_tensor, device_folds)

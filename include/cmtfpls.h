@@ -854,6 +854,13 @@ int cmtfpls_kfold_xcov_f32(const float* X, int64_t I, int A, int B, const double
                            const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kfold_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
                            const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X (the raw bits, only ever read): every argument, workspace size, limit and status is that of _f32, and S, mean and stats
+ * are the bits _f32 returns on the upcast values (each element is converted to f64 on load, exactly; the sums run in _f32's order).
+ * NaN and Inf reach stats.  The same holds for the _bf16 / _f16 forms of kfold_wide_xcov and kfold_weighted_xcov below. */
+int cmtfpls_kfold_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                            const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int M, const int* order, const int* fold_off, int K,
+                           const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
 /* kfold_inner: component a's inner loop (tpls.py:78-107 on S, as cmtfpls_loo_xcov_f64) for every fold, a 1024-thread workgroup per
  * fold: writes WA / WB (columns k), Q[k, a], n_iter[k, a].  ws >= cmtfpls_kfold_inner_workspace_bytes(A, B, K). */
 size_t cmtfpls_kfold_inner_workspace_bytes(int A, int B, int K);
@@ -937,6 +944,11 @@ int cmtfpls_kfold_wide_xcov_f32(const float* X, int64_t I, int A, int B, const d
                                 int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kfold_wide_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
                                 int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X: as cmtfpls_kfold_xcov_bf16.  A lane's 4 columns are one 8-byte load when A * B % 4 == 0 and X is 8-byte aligned. */
+int cmtfpls_kfold_wide_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                 int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_wide_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int W, const int* order, const int* fold_off,
+                                int K, const double* ydev, double* S, double* mean, double* stats, void* ws, size_t ws_bytes, void* stream);
 /* kfold_inner_grouped / kfold_epilogue_grouped: cmtfpls_kfold_inner_f64 / cmtfpls_kfold_epilogue_f64 for st->K = n models in
  * `groups` groups (n % groups == 0), model m holding out fold model_fold[m] (device, n entries, < n / groups). */
 int cmtfpls_kfold_inner_grouped_f64(const cmtfpls_kfold_state* st, const int* model_fold, int groups, int a, double tol, int max_iter,
@@ -985,6 +997,11 @@ size_t cmtfpls_kfold_weighted_xcov_workspace_bytes(int64_t I, int64_t P, int n, 
 int cmtfpls_kfold_weighted_xcov_f32(const float* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
                                     double* stats, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kfold_weighted_xcov_f64(const double* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                    double* stats, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X: as cmtfpls_kfold_xcov_bf16. */
+int cmtfpls_kfold_weighted_xcov_bf16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
+                                     double* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_kfold_weighted_xcov_f16(const uint16_t* X, int64_t I, int A, int B, const double* Y, int n, int M, double* S, double* mean,
                                     double* stats, void* ws, size_t ws_bytes, void* stream);
 /* kfold_epilogue_weighted: cmtfpls_kfold_epilogue_f64 for st->K = n weighted models (2 <= n <= I): stage 0 builds the Gram
  * sum_i c_i y_i y_i^T of each model's Yk (rows with c = 0 must be 0); stage 1 weights every training-row sum by c, writes

@@ -18,10 +18,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cmtf_pls_amd import _lib  # noqa: E402
 
 # the entries and exports of this table start with one of these; OUT_OF_SCOPE: those that do but live in files with one entry or
-# one checked launch of their own (cv_masked_coupled.hip, loo_xcov_coupled.hip)
+# one checked launch of their own (cv_masked_coupled.hip, loo_xcov_coupled.hip), and the _bf16 / _f16 forms of the wide and weighted
+# builds: they did not exist in the build the table was recorded from, and they are run_kfold_wide / run_kfold_weighted -- the host
+# checks this table probes through the _f32 / _f64 entries -- instantiated for another storage type (their statuses are held to the
+# _f32 entry's on the device, tests/test_gpu_half_fold_kernels.py)
 PREFIXES = ("cmtfpls_cv_masked_", "cmtfpls_loo_xcov_", "cmtfpls_kfold_inner", "cmtfpls_kfold_epilogue", "cmtfpls_kfold_wide_xcov",
             "cmtfpls_kfold_weighted_xcov")
-OUT_OF_SCOPE = ("cmtfpls_cv_masked_coupled_", "cmtfpls_loo_xcov_coupled_")
+OUT_OF_SCOPE = ("cmtfpls_cv_masked_coupled_", "cmtfpls_loo_xcov_coupled_", "cmtfpls_kfold_wide_xcov_bf16", "cmtfpls_kfold_wide_xcov_f16",
+                "cmtfpls_kfold_weighted_xcov_bf16", "cmtfpls_kfold_weighted_xcov_f16")
 
 _BUF = ctypes.create_string_buffer(64)
 P = ctypes.addressof(_BUF)                 # the stand-in for every pointer that a check only compares with NULL
