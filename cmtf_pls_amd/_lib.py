@@ -142,14 +142,22 @@ SIGNATURES = {
     "cmtfpls_recon_r2_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "cmtfpls_recon_r2_f32": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_recon_r2_f64": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_recon_r2_bf16": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_recon_r2_f16": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_resid_rows_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "cmtfpls_resid_rows_f32": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_resid_rows_f64": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_resid_rows_bf16": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_resid_rows_f16": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_contrib_rows_f32": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "cmtfpls_contrib_rows_f64": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "cmtfpls_contrib_rows_bf16": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "cmtfpls_contrib_rows_f16": (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "cmtfpls_selectivity_cols_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "cmtfpls_selectivity_cols_f32": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_selectivity_cols_f64": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_selectivity_cols_bf16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cmtfpls_selectivity_cols_f16": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cmtfpls_holdout_mask_workspace_bytes": (c_size_t, [c_int64]),
     "cmtfpls_holdout_mask_f32": (c_int, [_P, _P, c_int64, c_double, c_uint64, c_uint32, c_uint64, _P, _P, c_size_t, _P]),
     "cmtfpls_holdout_mask_f64": (c_int, [_P, _P, c_int64, c_double, c_uint64, c_uint32, c_uint64, _P, _P, c_size_t, _P]),

@@ -15,8 +15,10 @@ from . import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
 HALF_DTYPES = (torch.bfloat16, torch.float16)                # 16-bit storage: only ever read, converted to f64 on load
-# the entries that have _bf16 / _f16 forms: the fit's and the projection's passes, and the S builds of the resampling drivers
-_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp", "kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov")
+# the entries that have _bf16 / _f16 forms: the fit's and the projection's passes, the S builds of the resampling drivers and the
+# read-only diagnostics passes
+_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp", "kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov",
+                 "recon_r2", "resid_rows", "contrib_rows", "selectivity_cols")
 
 
 def _ptr(t: Optional[torch.Tensor]):

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _host, _kept_training_blocks, _training_stats
-from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
+from .tpls import _as_torch_dtype, note_half_fallbacks, reports_storage_upcast, to_device_read
 
 MAX_CELLS = 1 << 28        # n * P above which cells=True is refused (2 GiB per returned float64 array)
 
@@ -74,14 +74,14 @@ def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bo
             if Xs is None:
                 raise ValueError("the model was fitted with copy_X=False, so the training X was not kept: pass X")
             idx = _row_list(rows, int(st.T.shape[0]))
-            Xd = [to_device_read(x, blk.dtype or torch.float64, dev, pls=pls) for x, blk in zip(Xs, st.blocks)]
+            Xd = [to_device_read(x, blk.dtype or torch.float64, dev, pls=pls, entry="contrib_rows") for x, blk in zip(Xs, st.blocks)]
             scores, pform, proj_reads = st.T, None, 0
         else:
             Xs = list(X) if coupled else [X]
             if coupled and len(Xs) != pls.Xs_len:
                 raise ValueError(f"Training Xs has {pls.Xs_len} blocks, while the new Xs has {len(Xs)}")
             idx = _row_list(rows, int(Xs[0].shape[0]))
-            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls) for x in Xs]
+            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls, entry="contrib_rows") for x in Xs]
             scores = pls._project_dev(Xd if coupled else Xd[0])           # transform's projection: shape checks, forms, bits
             pform = "sequential passes on private copies (f32 matrix precision)" if pls._mixed else eng.last_projection["form"]
             proj_reads = _PROJECTION_READS.get(pform)
@@ -105,6 +105,7 @@ def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bo
         H = eng.t2_direction_solve(st, Gd) / nb
         res = eng.contribution_rows(st, Xd, T, H, ridx, device=device)
         forms = list(eng.last_contribution)
+        note_half_fallbacks(pls, Xd, forms)
         spe, spe_mode, t2_mode, spe_cells, t2_cells = [], [], [], [], []
         for blk, X_b, (speA, speB, t2A, t2B) in zip(st.blocks, Xd, res):
             spe_mode.append(_mode_sums(speA, speB, blk.shape))

@@ -64,6 +64,15 @@ __device__ __forceinline__ double to_f64<f16_t>(f16_t x) {
   __builtin_memcpy(&h, &x.b, 2);
   return (double)(float)h;
 }
+// Columns a thread of the read-only diagnostics passes (recon_r2, resid_rows, contrib_rows) owns on the vector path.  They keep
+// RC x V doubles of loading products in registers, so 16-bit storage takes V = 4 as ONE 8-byte load (the mapping of xcov.hip and
+// mttkrp.hip), not the 8 of a 16-byte vector (256 VGPRs of loadings at RC = 16).  That is f32's thread-to-column mapping: every
+// sum runs in the f32 entry's order, and the result has its bits on the upcast values.
+template <typename T>
+struct DiagVec {
+  static constexpr int N = sizeof(T) == 2 ? 4 : VecOf<T>::N;
+  static constexpr uintptr_t kAlignMask = N * sizeof(T) - 1;      // of X: 16 bytes for f32 / f64, 8 for 16 bits
+};
 // ... with NaN (a missing value) -> 0 when MASKED: on the stored type for f32 / f64, on the converted value for 16 bits.
 template <bool MASKED, typename T>
 __device__ __forceinline__ double to_f64_masked(T x) {
@@ -86,6 +95,7 @@ template <> struct NtRaw<32> { using type = nt_d4; };
 template <> struct NtRaw<16> { using type = nt_f4; };
 template <> struct NtRaw<8> { using type = double; };
 template <> struct NtRaw<4> { using type = float; };
+template <> struct NtRaw<2> { using type = uint16_t; };    // one 16-bit element (the one-element paths of the diagnostics passes)
 
 template <typename VT>
 __device__ __forceinline__ VT ld_stream(const VT* p) {

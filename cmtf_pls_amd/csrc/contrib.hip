@@ -5,7 +5,8 @@
 // in ONE read of the uncentred X, nothing of the size of X written.  A workgroup owns whole rows (G of them), so both mode sums
 // close inside it: no partials in global memory, no second kernel, no atomics, the same bits on every call.
 //
-// Layout.  A thread keeps V consecutive k (one 16-byte vector; V = 1 on the one-element path) for the whole row, so their R
+// Layout.  A thread keeps V consecutive k (one 16-byte vector, for 16-bit storage 4 k in one 8-byte vector as f32: DiagVec; V = 1
+// on the one-element path) for the whole row, so their R
 // loadings WB[k.., :] stay in registers over every j and every row of the group, and walks j in steps of JP = 256 / LK, LK = the
 // lanes along k (a power of two <= 64, so a j slice never leaves a wavefront).  The row's t and h are folded into the A side once
 // per row, TH[j][r] = (t_r WA[j, r], h_r WA[j, r]) in LDS, read as a broadcast: per cell rec and dir are 2 R multiply-adds
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(kSweepThreads) void contrib_rows_kernel(const T* __
                                                                     int G, int lgLK, double* __restrict__ speA, double* __restrict__ speB,
                                                                     double* __restrict__ t2A, double* __restrict__ t2B) {
   extern __shared__ double lds[];
-  constexpr int V = VEC ? VecOf<T>::N : 1;
+  constexpr int V = VEC ? DiagVec<T>::N : 1;
   constexpr int U = kContribUnroll;
   using VT = Pack<T, V>;
   const int tid = threadIdx.x;
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(kSweepThreads) void contrib_rows_kernel(const T* __
             double se = 0.0, sd = 0.0;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-              const double xc = (double)xs[u].e[e] - mu[u][e];
+              const double xc = to_f64(xs[u].e[e]) - mu[u][e];
               const bool fin = jlive && klive && isfinite(xc);   // the np.isfinite mask of calcR2X (util.py:7-15)
               const double ev = fin ? xc - rec[e] : 0.0;         // a NaN score row stays NaN
               const double dv = fin ? xc * dir[e] : 0.0;
@@ -251,9 +252,10 @@ static int run_contrib_rows(const T* X, int64_t I, const double* Tm, int ldt, co
     return CMTFPLS_EINVAL;
   }
   if (R > kContribMaxR) { set_error("contrib_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
-  const bool vec = (B % VecOf<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(mean) & 15) == 0;
+  const bool vec = (B % DiagVec<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & DiagVec<T>::kAlignMask) == 0 &&
+                   (reinterpret_cast<uintptr_t>(mean) & 15) == 0;
   ContribPlan p;
-  if (!contrib_plan(n, R, A, B, vec, VecOf<T>::N, speA != nullptr, &p)) {
+  if (!contrib_plan(n, R, A, B, vec, DiagVec<T>::N, speA != nullptr, &p)) {
     set_error("contrib_rows: the first mode's loadings and accumulators (2 A (R + 1) doubles) do not fit the LDS");
     return CMTFPLS_EUNSUPPORTED;
   }
@@ -287,5 +289,19 @@ int cmtfpls_contrib_rows_f64(const double* X, int64_t I, const double* T, int ld
                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
                              double* t2A, double* t2B, void* stream) {
   return run_contrib_rows<double>(X, I, T, ldt, H, ldh, R, WA, WB, A, B, mean, rows, n, speA, speB, t2A, t2B, (hipStream_t)stream);
+}
+// 16-bit X, read in place: 4 k per thread as one 8-byte load, so LK, JP, G and the LDS size are those of the f32 call and the
+// outputs have its bits on the upcast values
+int cmtfpls_contrib_rows_bf16(const uint16_t* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                              double* t2A, double* t2B, void* stream) {
+  return run_contrib_rows<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, T, ldt, H, ldh, R, WA, WB, A, B, mean, rows, n, speA, speB, t2A, t2B,
+                                  (hipStream_t)stream);
+}
+int cmtfpls_contrib_rows_f16(const uint16_t* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                             const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                             double* t2A, double* t2B, void* stream) {
+  return run_contrib_rows<f16_t>(reinterpret_cast<const f16_t*>(X), I, T, ldt, H, ldh, R, WA, WB, A, B, mean, rows, n, speA, speB, t2A, t2B,
+                                 (hipStream_t)stream);
 }
 }

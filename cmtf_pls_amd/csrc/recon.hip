@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kSweepThreads) void recon_r2_kernel(const T* __rest
                                                                 const double* __restrict__ mean, int64_t I, int64_t P, int rows_per_block,
                                                                 double* __restrict__ part) {
   __shared__ double red[16];
-  constexpr int V = VEC ? VecOf<T>::N : 1;
+  constexpr int V = VEC ? DiagVec<T>::N : 1;
   using VT = Pack<T, V>;
   const int64_t c = ((int64_t)blockIdx.x * kSweepThreads + threadIdx.x) * V;
   const bool live = c < P;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kSweepThreads) void recon_r2_kernel(const T* __rest
       }
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        const double xc = (double)x.e[e] - mu[e];
+        const double xc = to_f64(x.e[e]) - mu[e];
         const bool fin = isfinite(xc);                      // np.isfinite(X) mask of util.py:11-13
         const double d = fin ? acc[e] - xc : 0.0;
         res = fma(d, d, res);
@@ -154,8 +154,8 @@ static int run_recon_r2(const T* X, const double* Tm, int64_t I, int ldt, int R,
                         const double* mean, double* out, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!X || !Tm || !WA || !WB || !out || I <= 0 || R <= 0 || A <= 0 || B <= 0 || ldt < R) { set_error("recon_r2: bad argument"); return CMTFPLS_EINVAL; }
   if (R > kReconMaxR) { set_error("recon_r2: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
-  const bool vec = (B % VecOf<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  const int V = vec ? VecOf<T>::N : 1;
+  const bool vec = (B % DiagVec<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & DiagVec<T>::kAlignMask) == 0;
+  const int V = vec ? DiagVec<T>::N : 1;
   const int64_t P = (int64_t)A * B;
   int col_tiles, row_blocks;
   int64_t rpb;
@@ -204,5 +204,14 @@ int cmtfpls_recon_r2_f32(const float* X, const double* T, int64_t I, int ldt, in
 int cmtfpls_recon_r2_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
                          const double* mean, double* out, void* ws, size_t ws_bytes, void* stream) {
   return run_recon_r2<double>(X, T, I, ldt, R, WA, WB, A, B, mean, out, ws, ws_bytes, (hipStream_t)stream);
+}
+// 16-bit X, read in place: 4 columns per thread as one 8-byte load, f32's mapping and so its bits on the upcast values
+int cmtfpls_recon_r2_bf16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
+                          const double* mean, double* out, void* ws, size_t ws_bytes, void* stream) {
+  return run_recon_r2<bf16_t>(reinterpret_cast<const bf16_t*>(X), T, I, ldt, R, WA, WB, A, B, mean, out, ws, ws_bytes, (hipStream_t)stream);
+}
+int cmtfpls_recon_r2_f16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
+                         const double* mean, double* out, void* ws, size_t ws_bytes, void* stream) {
+  return run_recon_r2<f16_t>(reinterpret_cast<const f16_t*>(X), T, I, ldt, R, WA, WB, A, B, mean, out, ws, ws_bytes, (hipStream_t)stream);
 }
 }

@@ -2,7 +2,7 @@
 //   e[i, c] = x - xhat,  x = X[i, c] - mean[c],  xhat = sum_r T[i, r] WA[c / B, r] WB[c % B, r]
 //   rows[i] = (sum_c e^2, sum_c x^2, #finite x)      cols[c] = (sum_i e^2, sum_i x^2)       (entries with x not finite skipped)
 // in ONE read of the uncentred X, the reconstruction never materialised.  Same thread layout as recon_r2_kernel (recon.hip):
-// column tiles x row blocks, a thread owns V consecutive columns and keeps their R loading products in registers across the
+// column tiles x row blocks, a thread owns V consecutive columns (16-bit storage: 4, one 8-byte load, f32's mapping: DiagVec) and keeps their R loading products in registers across the
 // rows of its row block.  The column sums stay in the thread's registers; a row sum is a wavefront total (DPP within the
 // 16-lane rows, four lane reads across them), parked in the lane numbered after the row and combined over the four
 // wavefronts every 64 rows through LDS into one partial per (column tile, row).  Two small fixed-order reduces close the
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kSweepThreads) void resid_rows_kernel(const T* __re
                                                                   const double* __restrict__ mean, int64_t I, int64_t P, int rows_per_block,
                                                                   double* __restrict__ rpart, double* __restrict__ cpart) {
   __shared__ double red[3][kResidWaves][kWave];
-  constexpr int V = VEC ? VecOf<T>::N : 1;
+  constexpr int V = VEC ? DiagVec<T>::N : 1;
   using VT = Pack<T, V>;
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int64_t c = ((int64_t)blockIdx.x * kSweepThreads + threadIdx.x) * V;
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kSweepThreads) void resid_rows_kernel(const T* __re
         int cnt = 0;
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-          const double xc = (double)xs[u].e[e] - mu[e];
+          const double xc = to_f64(xs[u].e[e]) - mu[e];
           const bool fin = use && live && isfinite(xc);  // np.isfinite mask of calcR2X (util.py:7-15)
           const double d = fin ? xc - acc[e] : 0.0;      // a NaN score row stays NaN
           const double xo = fin ? xc : 0.0;
@@ -154,8 +154,8 @@ static int run_resid_rows(const T* X, const double* Tm, int64_t I, int ldt, int 
                           const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!X || !Tm || !WA || !WB || !rows || I <= 0 || R <= 0 || A <= 0 || B <= 0 || ldt < R) { set_error("resid_rows: bad argument"); return CMTFPLS_EINVAL; }
   if (R > kResidMaxR) { set_error("resid_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
-  const bool vec = (B % VecOf<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  const int V = vec ? VecOf<T>::N : 1;
+  const bool vec = (B % DiagVec<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & DiagVec<T>::kAlignMask) == 0;
+  const int V = vec ? DiagVec<T>::N : 1;
   const int64_t P = (int64_t)A * B;
   int col_tiles, row_blocks;
   int64_t rpb;
@@ -197,5 +197,14 @@ int cmtfpls_resid_rows_f32(const float* X, const double* T, int64_t I, int ldt, 
 int cmtfpls_resid_rows_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
                            const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream) {
   return run_resid_rows<double>(X, T, I, ldt, R, WA, WB, A, B, mean, rows, cols, ws, ws_bytes, (hipStream_t)stream);
+}
+// 16-bit X, read in place: 4 columns per thread as one 8-byte load, f32's mapping and so its bits on the upcast values
+int cmtfpls_resid_rows_bf16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
+                            const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream) {
+  return run_resid_rows<bf16_t>(reinterpret_cast<const bf16_t*>(X), T, I, ldt, R, WA, WB, A, B, mean, rows, cols, ws, ws_bytes, (hipStream_t)stream);
+}
+int cmtfpls_resid_rows_f16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
+                           const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream) {
+  return run_resid_rows<f16_t>(reinterpret_cast<const f16_t*>(X), T, I, ldt, R, WA, WB, A, B, mean, rows, cols, ws, ws_bytes, (hipStream_t)stream);
 }
 }

@@ -26,6 +26,8 @@ constexpr int kSelMaxMasked = 32;                        // masked: two accumula
 // FAST: every tile is interior (P % 256 == 0, M % 16 == 0, every row block a whole number of 32-row trips): no clamps, no selects
 // on the row / column / response index (the mask o of the masked form stays).  One response tile of f32 X in vector loads without a mask (M <= 16,
 // the flagship shape) is held to 3 waves per SIMD, xcov_kernel's residency there: the allocator otherwise lands 3 registers above it.
+// The 16-bit instances take no hint: their X stages are half the registers, and the compiler's report puts that instance at
+// 96 + 32 (bf16) / 88 + 32 (f16) registers = 4 waves per SIMD on its own, every other vector instance at or above f32's residency.
 template <typename T, bool MASKED, bool VEC, int MT, bool FAST>
 __global__ __launch_bounds__(256, (MT == 1 && !MASKED && VEC && sizeof(T) == 4) ? 3 : 1) void selectivity_kernel(const T* __restrict__ X, int64_t I, int64_t P,
                                                          const double* __restrict__ Tau, int ldtau, int M,
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256, (MT == 1 && !MASKED && VEC && sizeof(T) == 4) 
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const double dv = (double)x[s].e[e] - mu[e];
+        const double dv = to_f64(x[s].e[e]) - mu[e];
         bool o = FAST || (rok && c + e < P);
         if (MASKED) o = o && __builtin_isfinite(dv);
         const double b = o ? dv : 0.0;
@@ -223,6 +225,15 @@ int cmtfpls_selectivity_cols_f32(const float* X, int64_t I, int64_t P, const dou
 int cmtfpls_selectivity_cols_f64(const double* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
                                  int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream) {
   return run_selectivity<double>(X, I, P, Tau, ldtau, M, mean, masked, a, d, s, n, ws, ws_bytes, (hipStream_t)stream);
+}
+// 16-bit X, read in place: the lane's 4 columns are one 8-byte load, every MFMA operand the f32 entry's on the upcast values
+int cmtfpls_selectivity_cols_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                  int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream) {
+  return run_selectivity<bf16_t>(reinterpret_cast<const bf16_t*>(X), I, P, Tau, ldtau, M, mean, masked, a, d, s, n, ws, ws_bytes, (hipStream_t)stream);
+}
+int cmtfpls_selectivity_cols_f16(const uint16_t* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                 int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream) {
+  return run_selectivity<f16_t>(reinterpret_cast<const f16_t*>(X), I, P, Tau, ldtau, M, mean, masked, a, d, s, n, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _host, _kept_training_blocks
-from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
+from .tpls import _as_torch_dtype, note_half_fallbacks, reports_storage_upcast, to_device_read
 
 _ONE_PASS = "one-pass MTTKRP (one read, nothing written)"
 
@@ -82,14 +82,14 @@ def selectivity_ratio(pls, X=None, level: float = 0.95, cells: bool = True, devi
             Xs = _kept_training_blocks(pls, coupled)
             if Xs is None:
                 raise ValueError("the model was fitted with copy_X=False, so the training X was not kept: pass X")
-            Xd = [to_device_read(x, blk.dtype or torch.float64, dev, pls=pls) for x, blk in zip(Xs, st.blocks)]
+            Xd = [to_device_read(x, blk.dtype or torch.float64, dev, pls=pls, entry="selectivity_cols") for x, blk in zip(Xs, st.blocks)]
             scores, pform, proj_reads = st.T, None, 0
             masked = [bool(blk.has_miss) for blk in st.blocks]
         else:
             Xs = list(X) if coupled else [X]
             if coupled and len(Xs) != pls.Xs_len:
                 raise ValueError(f"Training Xs has {pls.Xs_len} blocks, while the new Xs has {len(Xs)}")
-            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls) for x in Xs]
+            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls, entry="selectivity_cols") for x in Xs]
             scores = pls._project_dev(Xd if coupled else Xd[0])           # transform's projection: shape checks, forms, bits
             pform = "sequential passes on private copies (f32 matrix precision)" if pls._mixed else eng.last_projection["form"]
             proj_reads = _PROJECTION_READS.get(pform)
@@ -101,6 +101,7 @@ def selectivity_ratio(pls, X=None, level: float = 0.95, cells: bool = True, devi
         M = int(Tau.shape[1])
         res = eng.selectivity_cols(st, Xd, Tau, device=device, masked=masked)
         forms = list(eng.last_selectivity)
+        note_half_fallbacks(pls, Xd, forms)
         # one all-reduce: [rows, sum_i tau^2 (M), then per block a, (d), s, n]
         head = torch.cat([Tau.new_tensor([float(Tau.shape[0])]), (Tau * Tau).sum(dim=0)])
         parts = [head] + [t.reshape(-1) for a, d, s, n in res for t in (a, d, s, n) if t is not None]

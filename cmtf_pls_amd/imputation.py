@@ -99,7 +99,7 @@ def impute(pls, X=None, device: bool = True):
             if len(Xs) != len(st.blocks):
                 raise ValueError(f"Training Xs has {len(st.blocks)} blocks, while the new Xs has {len(Xs)}")
             dtypes = [_as_torch_dtype(pls._dtype, x) for x in Xs]
-        Xd = [to_device_read(x, dt, dev, pls=pls) for x, dt in zip(Xs, dtypes)]
+        Xd = [to_device_read(x, dt, dev, pls=pls, entry="impute") for x, dt in zip(Xs, dtypes)]
         if training:
             scores, pform, proj_reads = st.T, None, 0
         else:
@@ -158,7 +158,7 @@ def get_q2x_heldout(pls, fraction: float = 0.1, n_repeats: int = 5, random_state
     sums = np.empty((n_repeats, nb, R + 2))
     n_iter, forms = [], []
     with eng.device_ctx():
-        Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls) for X, blk in zip(Xs, st.blocks)]      # read only
+        Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls, entry="q2x_heldout") for X, blk in zip(Xs, st.blocks)]      # read only
         for g, seed in enumerate(int(s) for s in seeds):
             masked = eng.holdout_copies(Xd, fraction, seed, device=device)
             for b, (m, _) in enumerate(masked):

@@ -110,6 +110,15 @@ class EngineOptions:
     # Leave-one-out, the masked routes and a backend without the entries still upcast; opt-in (report: q2y_report_ /
     # bootstrap_report_ with "half_storage", else "storage_fallback" with the reason)
     half_folds: bool = False
+    # the read-only diagnostics of a model with 16-bit storage on the 16-bit tensor itself: sample_diagnostics (its training-statistics
+    # pass included), sample_contributions, selectivity_ratio, R2X_literal and the engine's one-read norm (tPLS and ctPLS, blocks of
+    # order >= 4 on their I x A x B view) read the training tensor, or a new X that already is a device tensor of the storage type,
+    # through cmtfpls_resid_rows_* / contrib_rows_* / selectivity_cols_* / recon_r2_* in their _bf16 / _f16 forms -- never copied --
+    # instead of an exact float32 upcast of twice its size ("Diagnostics"); the f32 entry's thread-to-column mapping, so
+    # every result has the bits of the upcast route.  A block whose kernel declines the shape (R > 16, the LDS bound of
+    # contrib_rows), impute, get_q2x_heldout and a backend without the entries still upcast; opt-in (report: diagnostics_report_ /
+    # contributions_report_ / importance_report_ / r2x_literal_report_ with "half_storage", else "storage_fallback" with the reason)
+    half_diagnostics: bool = False
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -13,7 +13,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .state import BlockState, FitState, read_dtype
+from .state import HALF_DTYPES, BlockState, FitState, read_dtype
 
 
 class ProjectionMixin:
@@ -266,6 +266,12 @@ class ProjectionMixin:
             res, ssq = self.comm.allreduce(out).cpu().tolist()
             return 1.0 - res / ssq
 
+    @staticmethod
+    def _fallback_block(X2: torch.Tensor) -> torch.Tensor:
+        """The block as the torch fallbacks read it: a 16-bit block (read in place under EngineOptions.half_diagnostics, its kernel
+        declined) as an exact float32 upcast of that block; anything else as it is."""
+        return X2.to(torch.float32) if X2.dtype in HALF_DTYPES else X2
+
     def residual_rows(self, state: FitState, Xs: List[torch.Tensor], T: torch.Tensor, want_cols: bool = True,
                       device: bool = True) -> List[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
         """Per block, for the rows Xs[b] (device, storage type, UNCENTRED, read only) with scores T (I x R):
@@ -291,7 +297,7 @@ class ProjectionMixin:
                     if res is None:
                         why = f"R = {R} > 16: outside cmtfpls_resid_rows"
                 if res is None:
-                    res = self._residual_rows_torch(X2, T, WA, WB, blk.mean, want_cols)
+                    res = self._residual_rows_torch(self._fallback_block(X2), T, WA, WB, blk.mean, want_cols)
                 out.append(res)
                 forms.append({"form": "torch fallback" if why else "residual pass (cmtfpls_resid_rows)", "why": why})
         self.last_residual = forms
@@ -343,7 +349,7 @@ class ProjectionMixin:
                 if why is None and I > 0:
                     res = be.selectivity_cols(X2, Tau, blk.mean, msk)
                 else:
-                    res = self._selectivity_cols_torch(X2, Tau, blk.mean, msk)
+                    res = self._selectivity_cols_torch(self._fallback_block(X2), Tau, blk.mean, msk)
                 out.append(res)
                 forms.append({"form": "torch fallback" if why else "selectivity pass (cmtfpls_selectivity_cols)", "why": why,
                               "masked": msk})
@@ -537,7 +543,7 @@ class ProjectionMixin:
                         why = (f"R = {R} > 16: outside cmtfpls_contrib_rows" if R > 16 else
                                f"first mode of {blk.A} slices x R = {R}: 2 A (R + 1) doubles beyond the LDS of cmtfpls_contrib_rows")
                 if res is None:
-                    res = self._contribution_rows_torch(X2, T, H, WA, WB, blk.mean, rows)
+                    res = self._contribution_rows_torch(self._fallback_block(X2), T, H, WA, WB, blk.mean, rows)
                 out.append(res)
                 forms.append({"form": "torch fallback" if why else "contribution pass (cmtfpls_contrib_rows)", "why": why})
         self.last_contribution = forms

@@ -52,30 +52,71 @@ def note_storage_upcast(pls, dtype: torch.dtype, why: Optional[str] = None) -> N
 
 
 def note_storage_in_place(pls, dtype: torch.dtype, entries) -> None:
-    """Note on `pls` that a routine's device passes read the 16-bit tensor itself through `entries` (EngineOptions.half_folds)."""
+    """Note on `pls` that a routine's device passes read the 16-bit tensor itself through `entries` (EngineOptions.half_folds /
+    half_diagnostics)."""
     here = getattr(pls, "_storage_in_place", None)
     if here is not None:
         here.append((str(dtype).replace("torch.", ""), tuple(entries)))
 
 
-def to_device_read(X, dtype: torch.dtype, device, pls=None, why: Optional[str] = None) -> torch.Tensor:
+# the routines that copy 16-bit storage whatever EngineOptions.half_diagnostics says, and why (the report's storage_fallback)
+HALF_DIAGNOSTICS_UPCASTS = {
+    "impute": "impute returns a float32 tensor of X's size either way, so reading the 16-bit tensor in place would save nothing",
+    "q2x_heldout": "get_q2x_heldout refits masked copies of X, and the refit writes them",
+}
+
+
+def _half_diagnostics_read(pls, entry: str):
+    """How a diagnostics routine reads 16-bit storage under EngineOptions.half_diagnostics: (True, None) = the tensor itself through
+    the _bf16 / _f16 form of cmtfpls_<entry>; (False, why) = a float32 upcast for that reason; (False, None) while the option is off
+    (the routine's general reason then stands, and every bit and report text is that of a model without the option)."""
+    eng = pls._get_engine()
+    if not getattr(eng.opt, "half_diagnostics", False):
+        return False, None
+    if entry in HALF_DIAGNOSTICS_UPCASTS:
+        return False, "EngineOptions.half_diagnostics: " + HALF_DIAGNOSTICS_UPCASTS[entry]
+    be = eng.be
+    if not (hasattr(be, "has_half") and be.has_half(entry)):
+        return False, (f"EngineOptions.half_diagnostics: the {getattr(be, 'name', type(be).__name__)} backend has no 16-bit form of "
+                       f"cmtfpls_{entry}_*")
+    return True, None
+
+
+def to_device_read(X, dtype: torch.dtype, device, pls=None, why: Optional[str] = None, entry: Optional[str] = None) -> torch.Tensor:
     """X on the device as the routines beside fit / transform read it (diagnostics, contributions, importance, imputation, the
     resampling drivers, R2X_literal): `to_device_copy(X, dtype, device, copy=False)` -- and for a model with 16-bit storage the
     data ROUNDED to that type, then upcast to float32: exactly the values the model was fitted on, in a type those kernels take.
     `pls`: the model on whose behalf X is read; the upcast is noted on it for the routine's report (`reports_storage_upcast`),
-    with this read's own reason `why` where it has one."""
+    with this read's own reason `why` where it has one.
+    `entry`: the kernel (or, for impute / get_q2x_heldout, the routine) that reads X.  Under EngineOptions.half_diagnostics on a
+    backend with its 16-bit form the 16-bit tensor itself comes back -- the caller's own device tensor, or the once-rounded upload
+    -- and the entry is noted for the report's "half_storage"; every other case under the option upcasts with its own reason."""
     Xd = to_device_copy(X, dtype, device, copy=False)
     if dtype not in HALF_DTYPES:
         return Xd
+    if entry is not None and pls is not None and why is None:
+        in_place, why = _half_diagnostics_read(pls, entry)
+        if in_place:
+            note_storage_in_place(pls, dtype, [f"cmtfpls_{entry}_{'bf16' if dtype == torch.bfloat16 else 'f16'}"])
+            return Xd
     note_storage_upcast(pls, dtype, why)
     return Xd.to(torch.float32)
+
+
+def note_half_fallbacks(pls, Xd, forms) -> None:
+    """After a diagnostics pass over the blocks Xd whose per-block `forms` the engine recorded: a 16-bit block read in place whose
+    kernel declined the shape (or was switched off) went through the torch fallback on an exact float32 upcast of that block
+    (ProjectionMixin._fallback_block); noted with the pass's own reason, so that the report says storage_fallback."""
+    for X, f in zip(Xd, forms):
+        if X.dtype in HALF_DTYPES and f.get("why"):
+            note_storage_upcast(pls, X.dtype, f["why"])
 
 
 def reports_storage_upcast(report_attr: str, why: str):
     """Decorator of a routine `fn(pls, ...)` that leaves its report in `pls.<report_attr>`: when the routine read X of a model with
     16-bit storage through `to_device_read(..., pls=pls)` -- a full float32 copy -- the report gets
     "storage_fallback": "float32 private copy of the <type> data: <why>" (the reads' own reasons where they gave any).  When its
-    device passes read the 16-bit tensor itself instead (`note_storage_in_place`, EngineOptions.half_folds) and the report shows
+    device passes read the 16-bit tensor itself instead (`note_storage_in_place`, EngineOptions.half_folds / half_diagnostics) and the report shows
     reads of X, it gets "half_storage": {"in_place": True, "dtype": <type>, "entries": [...]} and no "storage_fallback"."""
     def deco(fn):
         @functools.wraps(fn)
@@ -387,16 +428,28 @@ class tPLS(_EstimatorBase):
             return X_scores, self._y_scores(scores, Y)
         return X_scores
 
+    @reports_storage_upcast("r2x_literal_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
     def R2X_literal(self, X):
         """calcR2X(X - X_mean, factors_to_tensor(X_factors)) of the training X (util.py:7-15 as tpls.py:115-117 calls it)
-        in one read of X on the GPU; equals R2X[-1], which the fit obtains from the deflation sweep instead."""
+        in one read of X on the GPU; equals R2X[-1], which the fit obtains from the deflation sweep instead.
+        `r2x_literal_report_`: the form that ran and, for 16-bit storage, how X was read."""
         eng = self._get_engine()
-        Xd = to_device_read(X, self._state.blocks[0].dtype or torch.float64, eng.be.device, pls=self)
+        Xd = to_device_read(X, self._state.blocks[0].dtype or torch.float64, eng.be.device, pls=self, entry="recon_r2")
         r2 = eng.r2x_literal(self._state, Xd, 0)
+        why = None
         if r2 is None:
             from .util import calcR2X, factors_to_tensor
-            Xh = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+            R = self._state.n_components
+            why = f"R = {R} > 16: outside cmtfpls_recon_r2" if hasattr(eng.be, "recon_r2") else "backend has no recon_r2 kernel"
+            if Xd.dtype in HALF_DTYPES:                                       # read in place so far: the host formula takes an upcast
+                note_storage_upcast(self, Xd.dtype, why)
+                Xh = Xd.to(torch.float32).cpu().numpy()
+            elif isinstance(X, torch.Tensor):                                 # (NumPy has no bfloat16)
+                Xh = (X.to(torch.float32) if X.dtype in HALF_DTYPES else X).cpu().numpy()
+            else:
+                Xh = np.asarray(X)
             r2 = calcR2X(Xh - self.X_mean, factors_to_tensor(self.X_factors))
+        self.r2x_literal_report_ = {"form": "host formula (calcR2X)" if why else "one read (cmtfpls_recon_r2)", "why": why, "x_reads": [1]}
         return r2
 
     def X_reconstructed(self, rows=None, device: bool = False):

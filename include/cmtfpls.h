@@ -150,7 +150,9 @@ int cmtfpls_quadform_f64(const double* G, int M, const double* q, const double* 
  * converted to f64 on load (both conversions are exact; NaN and Inf stay what they are) and everything after that is the f64
  * arithmetic of the f32 / f64 entries -- same arguments, workspaces, limits, `masked` semantics and fixed-order partial sums.
  * Entries: xcov, xcov_stats, score_contract (the rows form only: B % 8 == 0, 4096 <= A * B <= 16384), mttkrp (every shape of
- * the f32 entry, tile form).  No other entry has a 16-bit form: whatever writes X or has none runs on a float32 copy. */
+ * the f32 entry, tile form), the S builds of the fold entries (kfold_xcov, kfold_wide_xcov, kfold_weighted_xcov) and the read-only
+ * diagnostics passes (recon_r2, resid_rows, contrib_rows, selectivity_cols).  No other entry has a 16-bit form: whatever writes X
+ * or has none runs on a float32 copy. */
 int cmtfpls_xcov_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S,
                       int masked, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_xcov_f16(const uint16_t* X, int64_t I, int64_t P, const double* Y, int ldy, int M, double* S,
@@ -486,6 +488,13 @@ int cmtfpls_recon_r2_f32(const float* X, const double* T, int64_t I, int ldt, in
                          int A, int B, const double* mean, double* out, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_recon_r2_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
                          int A, int B, const double* mean, double* out, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X: as cmtfpls_recon_r2_f32 on the upcast values, bit for bit (X = the raw bits, only ever read; NaN and Inf are skipped as
+ * in f32).  A thread's 4 columns are one 8-byte load when B % 4 == 0 and X is 8-byte aligned: f32's thread-to-column mapping, so
+ * every sum runs in its order.  The same holds for the _bf16 / _f16 forms of resid_rows, contrib_rows and selectivity_cols below. */
+int cmtfpls_recon_r2_bf16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                          int A, int B, const double* mean, double* out, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_recon_r2_f16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                         int A, int B, const double* mean, double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* resid_rows: the residual of recon_r2 kept per sample and per variable (validate.sample_diagnostics), in ONE read of the
  * uncentred X (I x A*B, storage type, any alignment), the reconstruction never materialised.  With x = X[i,c] - mean[c]
@@ -499,6 +508,11 @@ size_t cmtfpls_resid_rows_workspace_bytes(int64_t I, int64_t P);
 int cmtfpls_resid_rows_f32(const float* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
                            int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_resid_rows_f64(const double* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                           int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X: as cmtfpls_resid_rows_f32 on the upcast values, bit for bit (see cmtfpls_recon_r2_bf16). */
+int cmtfpls_resid_rows_bf16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
+                            int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_resid_rows_f16(const uint16_t* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB,
                            int A, int B, const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream);
 
 /* contrib_rows: per-mode contributions of a sample to its Q residual (SPE) and its Hotelling T^2 (validate.sample_contributions), in
@@ -514,6 +528,14 @@ int cmtfpls_contrib_rows_f32(const float* X, int64_t I, const double* T, int ldt
                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
                              double* t2A, double* t2B, void* stream);
 int cmtfpls_contrib_rows_f64(const double* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                             const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                             double* t2A, double* t2B, void* stream);
+/* 16-bit X: as cmtfpls_contrib_rows_f32 on the upcast values, bit for bit (see cmtfpls_recon_r2_bf16): the same lanes along k, rows per
+ * workgroup, LDS size and limits (the vector path also needs mean 16-byte aligned, as in f32). */
+int cmtfpls_contrib_rows_bf16(const uint16_t* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
+                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
+                              double* t2A, double* t2B, void* stream);
+int cmtfpls_contrib_rows_f16(const uint16_t* X, int64_t I, const double* T, int ldt, const double* H, int ldh, int R, const double* WA,
                              const double* WB, int A, int B, const double* mean, const int64_t* rows, int64_t n, double* speA, double* speB,
                              double* t2A, double* t2B, void* stream);
 
@@ -532,6 +554,12 @@ size_t cmtfpls_selectivity_cols_workspace_bytes(int64_t I, int64_t P, int M);
 int cmtfpls_selectivity_cols_f32(const float* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
                                  int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_selectivity_cols_f64(const double* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                 int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
+/* 16-bit X: as cmtfpls_selectivity_cols_f32 on the upcast values, bit for bit (see cmtfpls_recon_r2_bf16).  The lane's 4 columns are one
+ * 8-byte load when P % 4 == 0 and X is 8-byte aligned.  An f16 Inf (a value beyond 65504 when quantised) is masked as a NaN is. */
+int cmtfpls_selectivity_cols_bf16(const uint16_t* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
+                                  int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_selectivity_cols_f16(const uint16_t* X, int64_t I, int64_t P, const double* Tau, int ldtau, int M, const double* mean,
                                  int masked, double* a, double* d, double* s, double* n, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- imputation and entry-wise validation of the X model: validate.impute / validate.get_q2x_heldout (no reference counterpart;
