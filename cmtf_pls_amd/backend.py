@@ -12,13 +12,10 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .storage import HALF_DTYPES, HALF_ENTRIES, SUFFIX, entry_name
 
-_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
-HALF_DTYPES = (torch.bfloat16, torch.float16)                # 16-bit storage: only ever read, converted to f64 on load
-# the entries that have _bf16 / _f16 forms: the fit's and the projection's passes, the S builds of the resampling drivers and the
-# read-only diagnostics passes
-_HALF_ENTRIES = ("xcov", "xcov_stats", "score_contract", "mttkrp", "kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov",
-                 "recon_r2", "resid_rows", "contrib_rows", "selectivity_cols")
+# the entries that have _bf16 / _f16 forms, each once: 16-bit X is only ever read, converted to f64 on load
+_HALF_ENTRIES = tuple(dict.fromkeys(e for group in HALF_ENTRIES.values() for e in group))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -113,16 +110,26 @@ class HipBackend:
 
     def has_half(self, base: str) -> bool:
         """Whether entry `base` has a form for 16-bit storage (bfloat16 / float16): the read-only passes over X only."""
-        return base in _HALF_ENTRIES and hasattr(self.lib, f"cmtfpls_{base}_bf16") and hasattr(self.lib, f"cmtfpls_{base}_f16")
+        return base in _HALF_ENTRIES and all(hasattr(self.lib, entry_name(base, d)) for d in HALF_DTYPES)
+
+    def _read_fn(self, base: str, X: torch.Tensor, mixed: bool = False):
+        """The entry `base` for this X (`mixed`: its f32-MFMA form for f32-stored X); None when X is 16-bit and the entry has no such
+        form, or `mixed` is asked: the caller declines, and 16-bit X is read through a float32 copy."""
+        if X.dtype not in SUFFIX:
+            raise TypeError(f"X must be float32 or float64 on device, got {X.dtype}")
+        if X.dtype in HALF_DTYPES and (mixed or not self.has_half(base)):
+            return None
+        if mixed and X.dtype == torch.float32:
+            return getattr(self.lib, f"cmtfpls_{base}_f32_mixed")
+        assert X.is_contiguous() and X.device == self.device
+        return getattr(self.lib, entry_name(base, X.dtype))
 
     def _fn(self, base: str, X: torch.Tensor):
-        if X.dtype not in _SUFFIX:
-            raise TypeError(f"X must be float32 or float64 on device, got {X.dtype}")
-        if X.dtype in HALF_DTYPES and not self.has_half(base):
+        fn = self._read_fn(base, X)
+        if fn is None:
             raise TypeError(f"{base} has no form for {X.dtype} storage (16-bit X is only read by {', '.join(_HALF_ENTRIES)}); "
                             "use a float32 copy")
-        assert X.is_contiguous() and X.device == self.device
-        return getattr(self.lib, f"cmtfpls_{base}_{_SUFFIX[X.dtype]}")
+        return fn
 
     def _close_partials(self, part: torch.Tensor) -> torch.Tensor:
         out = self.empty(1)
@@ -243,11 +250,11 @@ class HipBackend:
         f32-stored X).  More than 64 responses: tiles of 64, one pass over X each (inside the C entry)."""
         I, P = X2.shape
         M = Y.shape[1]
-        if X2.dtype in HALF_DTYPES and (mixed or not self.has_half("xcov")):
+        fn = self._read_fn("xcov", X2, mixed)
+        if fn is None:
             return None
         ws = self._workspace("contract", self.lib.cmtfpls_xcov_workspace_bytes(I, P, M))
         S = out if out is not None else self.empty(M, P)
-        fn = self.lib.cmtfpls_xcov_f32_mixed if (mixed and X2.dtype == torch.float32) else self._fn("xcov", X2)
         _lib.check(fn(_ptr(X2), I, P, _ptr(Y), Y.stride(0), M, _ptr(S), int(masked), _ptr(ws), ws.numel(), self._stream()), "xcov")
         return S
 
@@ -295,11 +302,12 @@ class HipBackend:
         (S, stats) with stats[:P] the sums and stats[P:] the sums of squares, or None for more than 64 responses."""
         I, P = X2.shape
         M = Y.shape[1]
-        if M > 64 or not X2.is_contiguous() or (X2.dtype in HALF_DTYPES and not self.has_half("xcov_stats")):
+        fn = self._read_fn("xcov_stats", X2) if M <= 64 and X2.is_contiguous() else None
+        if fn is None:
             return None
         ws = self._workspace("contract", self.lib.cmtfpls_xcov_stats_workspace_bytes(I, P, M))
         stats = self.empty(2 * P)
-        rc = self._fn("xcov_stats", X2)(_ptr(X2), I, P, _ptr(Y), Y.stride(0), M, _ptr(out), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+        rc = fn(_ptr(X2), I, P, _ptr(Y), Y.stride(0), M, _ptr(out), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
         return self._form(rc, "xcov_stats", (out, stats))
 
     def status_snapshot(self, status: torch.Tensor, slot: int, slots: Optional[dict] = None):
@@ -420,9 +428,9 @@ class HipBackend:
         """out (I, R) = X_(0) (WA (.) WB); None when R > 32 or the loadings do not fit LDS."""
         R = WA.shape[1]
         assert WA.is_contiguous() and WB.is_contiguous() and out.stride(1) == 1
-        if X2.dtype in HALF_DTYPES and (mixed or not self.has_half("mttkrp")):
+        fn = self._read_fn("mttkrp", X2, mixed)
+        if fn is None:
             return None
-        fn = self.lib.cmtfpls_mttkrp_f32_mixed if (mixed and X2.dtype == torch.float32) else self._fn("mttkrp", X2)
         rc = fn(_ptr(X2), X2.shape[0], A, B, _ptr(WA), _ptr(WB), R, _ptr(out), out.stride(0), self._stream())
         return self._form(rc, "mttkrp", out)
 
@@ -443,13 +451,14 @@ class HipBackend:
         """t = X w - shift - sub_own and Z = X^T c, c = alpha (t + add_other), in one read of X (cmtfpls_score_contract_*); csum[0] =
         sum(c) when given; None when the row fits neither the registers of one workgroup nor those of 16 (the caller then makes the two passes)."""
         I, P = X2.shape
-        if not X2.is_contiguous() or P != A * B or (X2.dtype in HALF_DTYPES and not self.has_half("score_contract")):
+        fn = self._read_fn("score_contract", X2) if X2.is_contiguous() and P == A * B else None
+        if fn is None:
             return None
         for v in (sub_own, add_other):
             assert v is None or (v.is_contiguous() and v.numel() == I and v.dtype == torch.float64)
         nbytes = self.lib.cmtfpls_score_contract_workspace_bytes(I, P)
         ws = self._workspace("score_contract", max(nbytes, 256))
-        rc = self._fn("score_contract", X2)(_ptr(X2), I, A, B, _ptr(wA), _ptr(wB), _ptr(shift), _ptr(sub_own), _ptr(add_other), float(alpha),
+        rc = fn(_ptr(X2), I, A, B, _ptr(wA), _ptr(wB), _ptr(shift), _ptr(sub_own), _ptr(add_other), float(alpha),
                                             _ptr(t), _ptr(Z), _ptr(csum), _ptr(ws), ws.numel(), self._stream())
         return self._form(rc, "score_contract", Z)
 
@@ -976,12 +985,13 @@ class HipBackend:
         the call."""
         I, P = X2.shape
         M = Y.shape[1]
-        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_xcov"):
+        fn = self._read_fn("kfold_xcov", X2)
+        if fn is None:
             return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and order.dtype == torch.int32 and fold_off.dtype == torch.int32 and P == A * B
         ws = _scratch(self.lib.cmtfpls_kfold_xcov_workspace_bytes(I, P, M, K), self.device)
         stats = self.empty(2 * P)
-        rc = self._fn("kfold_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), M, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S), _ptr(mean),
+        rc = fn(_ptr(X2), I, A, B, _ptr(Y), M, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S), _ptr(mean),
                                         _ptr(stats), _ptr(ws), ws.numel(), self._stream())
         return self._form(rc, "kfold_xcov", stats)
 
@@ -1062,13 +1072,14 @@ class HipBackend:
         squares of all rows (2 P); None when the shape is outside the device form.  The partial-sum workspace is local to the call."""
         I, P = X2.shape
         W = Y.shape[1]
-        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_wide_xcov"):
+        fn = self._read_fn("kfold_wide_xcov", X2)
+        if fn is None:
             return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and ydev.is_contiguous() and S.is_contiguous() and P == A * B
         assert order.dtype == torch.int32 and fold_off.dtype == torch.int32 and S.numel() == K * W * P and mean.numel() == K * P
         ws = _scratch(self.lib.cmtfpls_kfold_wide_xcov_workspace_bytes(I, P, W, K), self.device)
         stats = self.empty(2 * P)
-        rc = self._fn("kfold_wide_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), W, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S),
+        rc = fn(_ptr(X2), I, A, B, _ptr(Y), W, _ptr(order), _ptr(fold_off), K, _ptr(ydev), _ptr(S),
                                              _ptr(mean), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
         return self._form(rc, "kfold_wide_xcov", stats)
 
@@ -1113,13 +1124,14 @@ class HipBackend:
         the column sums / sums of squares of all rows (2 P), or None when the shape is outside the device form.  The partial-sum
         workspace is local to the call."""
         I, P = X2.shape
-        if X2.dtype in HALF_DTYPES and not self.has_half("kfold_weighted_xcov"):
+        fn = self._read_fn("kfold_weighted_xcov", X2)
+        if fn is None:
             return None
         assert Y.dtype == torch.float64 and Y.is_contiguous() and Y.shape == (I, n * (M + 1)) and P == A * B
         assert S.is_contiguous() and S.numel() == n * M * P and mean.is_contiguous() and mean.numel() == n * P
         ws = _scratch(self.lib.cmtfpls_kfold_weighted_xcov_workspace_bytes(I, P, n, M), self.device)
         stats = self.empty(2 * P)
-        rc = self._fn("kfold_weighted_xcov", X2)(_ptr(X2), I, A, B, _ptr(Y), n, M, _ptr(S), _ptr(mean), _ptr(stats), _ptr(ws),
+        rc = fn(_ptr(X2), I, A, B, _ptr(Y), n, M, _ptr(S), _ptr(mean), _ptr(stats), _ptr(ws),
                                                  ws.numel(), self._stream())
         return self._form(rc, "kfold_weighted_xcov", stats)
 

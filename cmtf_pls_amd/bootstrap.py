@@ -41,10 +41,11 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _decline_coupled_tensor, _device_blocks, _reports_upcast, _device_pass,
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_pass,
                     _device_passes, _dims, _from_scores, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
                     _route, _tensor_dims, _to_dev, _training_data, _weighted_models, masked_coupled_report, masked_models,
                     masked_models_coupled, masked_models_report)
+from .storage import FOLDS_WHY, reports_storage
 
 _ENTRIES = ("kfold_weighted_xcov", "kfold_inner", "kfold_epilogue_weighted", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_weighted_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_weighted", "mttkrp", "xcov")
@@ -223,7 +224,7 @@ def _spread(stack, level: float):
     return stack.std(axis=0, ddof=1), np.percentile(stack, [q, 100.0 - q], axis=0)
 
 
-@_reports_upcast("bootstrap_report_")
+@reports_storage("bootstrap_report_", FOLDS_WHY)
 def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level: float = 0.95, device_folds: bool = True,
               tol: float = 1e-8, max_iter: int = 100) -> dict:
     if not (0.0 < float(level) < 1.0):

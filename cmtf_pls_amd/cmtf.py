@@ -12,7 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .tpls import _EstimatorBase, _as_torch_dtype, _project_blocks, to_device_copy
+from .storage import _as_torch_dtype, to_device_copy
+from .tpls import _EstimatorBase, _project_blocks
 
 
 class ctPLS(_EstimatorBase):

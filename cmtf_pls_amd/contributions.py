@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _host, _kept_training_blocks, _training_stats
-from .tpls import _as_torch_dtype, note_half_fallbacks, reports_storage_upcast, to_device_read
+from .storage import _as_torch_dtype, notes_of, reports_storage, to_device_read
 
 MAX_CELLS = 1 << 28        # n * P above which cells=True is refused (2 GiB per returned float64 array)
 
@@ -56,7 +56,7 @@ def _mode_sums(first, rest, shape):
     return out
 
 
-@reports_storage_upcast("contributions_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+@reports_storage("contributions_report_")
 def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bool = True) -> dict:
     from .cmtf import ctPLS
 
@@ -105,7 +105,7 @@ def sample_contributions(pls, X=None, rows=None, cells: bool = False, device: bo
         H = eng.t2_direction_solve(st, Gd) / nb
         res = eng.contribution_rows(st, Xd, T, H, ridx, device=device)
         forms = list(eng.last_contribution)
-        note_half_fallbacks(pls, Xd, forms)
+        notes_of(pls).declined(Xd, forms)
         spe, spe_mode, t2_mode, spe_cells, t2_cells = [], [], [], [], []
         for blk, X_b, (speA, speB, t2A, t2B) in zip(st.blocks, Xd, res):
             spe_mode.append(_mode_sums(speA, speB, blk.shape))

@@ -23,7 +23,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .tpls import _as_torch_dtype, note_half_fallbacks, reports_storage_upcast, to_device_read
+from .storage import _as_torch_dtype, notes_of, reports_storage, to_device_read
 
 # reads of the caller's X that each projection form takes (project_readonly's forms); other forms work on private copies
 _PROJECTION_READS = {
@@ -99,7 +99,7 @@ def _training_stats(pls, eng, st, coupled: bool, device: bool, spe_train: Option
             dev = eng.be.device
             Xd = [to_device_read(X, blk.dtype or torch.float64, dev, pls=pls, entry="resid_rows") for X, blk in zip(Xs, st.blocks)]
             spe_train = [r[:, 0] for r, _ in eng.residual_rows(st, Xd, T, want_cols=False, device=device)]
-            note_half_fallbacks(pls, Xd, eng.last_residual)
+            notes_of(pls).declined(Xd, eng.last_residual)
             reads = 1
     moments = None if spe_train is None else [_spe_moments(comm, s) for s in spe_train]
     cache = {"state": st, "I": I, "tbar": tbar, "S_pinv": S_pinv, "moments": moments, "why": why}
@@ -107,7 +107,7 @@ def _training_stats(pls, eng, st, coupled: bool, device: bool, spe_train: Option
     return cache, False, reads
 
 
-@reports_storage_upcast("diagnostics_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+@reports_storage("diagnostics_report_")
 def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = True) -> dict:
     from .cmtf import ctPLS
 
@@ -136,8 +136,7 @@ def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = 
             Xs = list(X) if coupled else [X]
             if coupled and len(Xs) != pls.Xs_len:
                 raise ValueError(f"Training Xs has {pls.Xs_len} blocks, while the new Xs has {len(Xs)}")
-            dtypes = [_as_torch_dtype(pls._dtype, x) for x in Xs]
-            Xd = [to_device_read(x, dt, dev, pls=pls, entry="resid_rows") for x, dt in zip(Xs, dtypes)]
+            Xd = [to_device_read(x, _as_torch_dtype(pls._dtype, x), dev, pls=pls, entry="resid_rows") for x in Xs]
             scores = pls._project_dev(Xd if coupled else Xd[0])          # transform's projection: shape checks, forms, bits
             pform = "sequential passes on private copies (f32 matrix precision)" if pls._mixed else eng.last_projection["form"]
             form, proj_reads = f"projection ({pform}) + residual pass", _PROJECTION_READS.get(pform)
@@ -145,7 +144,7 @@ def sample_diagnostics(pls, X=None, Y=None, level: float = 0.95, device: bool = 
             scores = scores.contiguous()
         res = eng.residual_rows(st, Xd, scores, want_cols=True, device=device)
         resid_forms = list(eng.last_residual)
-        note_half_fallbacks(pls, Xd, resid_forms)
+        notes_of(pls).declined(Xd, resid_forms)
         stats, cached, train_reads = _training_stats(pls, eng, st, coupled, device,
                                                      [r[:, 0] for r, _ in res] if training else None)
         fallback = [f["why"] for f in resid_forms if f["why"]]

@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from .fitrun_xcov import XcovMixin
-from .state import HALF_DTYPES, BlockState, FitState, split_trailing, validate_limits
+from .state import BlockState, FitState, split_trailing, validate_limits
+from .storage import HALF_DTYPES, HALF_ENTRIES, dtype_name, fallback_text, half_route
 
 
 class FitRun(XcovMixin):
@@ -51,20 +52,18 @@ class FitRun(XcovMixin):
         want_raw = (allow_raw and algorithm == "xcov" and eng.opt.xcov_raw and eng.opt.xcov_nowrite
                     and n_components <= 64
                     and all(hasattr(be, f) for f in ("axpy_scalar", "total", "recon_r2", "s_downdate", "deflate_contract_yq", "kr_axpy")))
-        # 16-bit storage (bfloat16 / float16) is only ever READ: such blocks stay as they are on the uncentred cross-covariance path
-        # (statistics and S from backend.xcov_stats, score and down-date from score_contract or mttkrp + xcov) and are replaced by an
-        # exact float32 upcast, a private copy, for everything else -- the same code on the same values as a float32 model
+        # 16-bit blocks (storage.py) stay as they are on the uncentred cross-covariance path, which only reads X (HALF_ENTRIES["fit"]),
+        # and are replaced by an exact float32 upcast, a private copy, for everything else: the code and values of a float32 model
         self.half_storage = [X.dtype if X.dtype in HALF_DTYPES else None for X in Xs]
         self.half_fallback: Optional[str] = None
         self.half_reads: Dict[int, set] = {}                      # block -> the entries that read the 16-bit tensor, noted where taken
 
         def upcast(why: str) -> None:
-            names = sorted({str(d).replace("torch.", "") for d in self.half_storage if d is not None})
             for b, d in enumerate(self.half_storage):
                 if d is not None and Xs[b].dtype in HALF_DTYPES:
                     Xs[b] = Xs[b].to(torch.float32)
                     owned[b] = True
-            self.half_fallback = f"float32 private copy of the {' / '.join(names)} data: {why}"
+            self.half_fallback = fallback_text([dtype_name(d) for d in self.half_storage if d is not None], why)
             self.notes.append(self.half_fallback)
 
         if any(d is not None for d in self.half_storage):
@@ -260,7 +259,7 @@ class FitRun(XcovMixin):
         eng, be = self.eng, self.eng.be
         if self.algorithm != "xcov":
             return 'algorithm="direct" centres and deflates X in place'
-        if not (hasattr(be, "has_half") and all(be.has_half(f) for f in ("xcov", "xcov_stats", "score_contract", "mttkrp"))):
+        if not half_route(eng, None, HALF_ENTRIES["fit"])[0]:
             return "the backend has no 16-bit entries"
         if self.R > 64:
             return "more than 64 components"
@@ -834,7 +833,7 @@ class FitRun(XcovMixin):
         eng, comm, nb = self.eng, self.eng.comm, len(self.blocks)
         rep: Dict[str, object] = {
             "form": "regular", "algorithm_requested": self.algorithm_requested, "algorithm": self.algorithm,
-            "shapes": [tuple(b.shape) for b in self.blocks], "storage": [str(b.dtype).replace("torch.", "") for b in self.blocks],
+            "shapes": [tuple(b.shape) for b in self.blocks], "storage": [dtype_name(b.dtype) for b in self.blocks],
             "missing": [bool(b.has_miss) for b in self.blocks], "responses": self.M,
             "sharded": bool(comm.sharded), "world": int(comm.world),
             "graphs": bool(self.use_graphs and self._graphs), "graph_error": self._graph_error,
@@ -891,7 +890,6 @@ class FitRun(XcovMixin):
         # switch that off (a GPU shared with another process)
         if any(d is not None for d in self.half_storage):
             # 16-bit storage: read in place (which reads a component takes, per block), or the float32 private copy and why
-            rep["storage"] = [str(d if d is not None else b.dtype).replace("torch.", "") for d, b in zip(self.half_storage, self.blocks)]
             rep["half_storage"] = {
                 "in_place": self.half_fallback is None,
                 "fallback": self.half_fallback,

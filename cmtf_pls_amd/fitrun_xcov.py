@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from .state import HALF_DTYPES
+from .storage import HALF_DTYPES
 
 
 class XcovMixin:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _host, _kept_training_blocks
-from .tpls import _as_torch_dtype, note_half_fallbacks, reports_storage_upcast, to_device_read
+from .storage import _as_torch_dtype, notes_of, reports_storage, to_device_read
 
 _ONE_PASS = "one-pass MTTKRP (one read, nothing written)"
 
@@ -64,7 +64,7 @@ def _mode_ratios(explained: np.ndarray, residual: np.ndarray, shape) -> list:
     return out
 
 
-@reports_storage_upcast("importance_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+@reports_storage("importance_report_")
 def selectivity_ratio(pls, X=None, level: float = 0.95, cells: bool = True, device: bool = True) -> dict:
     from .cmtf import ctPLS
 
@@ -101,7 +101,7 @@ def selectivity_ratio(pls, X=None, level: float = 0.95, cells: bool = True, devi
         M = int(Tau.shape[1])
         res = eng.selectivity_cols(st, Xd, Tau, device=device, masked=masked)
         forms = list(eng.last_selectivity)
-        note_half_fallbacks(pls, Xd, forms)
+        notes_of(pls).declined(Xd, forms)
         # one all-reduce: [rows, sum_i tau^2 (M), then per block a, (d), s, n]
         head = torch.cat([Tau.new_tensor([float(Tau.shape[0])]), (Tau * Tau).sum(dim=0)])
         parts = [head] + [t.reshape(-1) for a, d, s, n in res for t in (a, d, s, n) if t is not None]

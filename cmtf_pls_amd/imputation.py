@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .diagnostics import _PROJECTION_READS, _kept_training_blocks
-from .tpls import _as_torch_dtype, reports_storage_upcast, to_device_read
+from .storage import _as_torch_dtype, reports_storage, to_device_read
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -79,7 +79,7 @@ def _first_empty_row(X: torch.Tensor) -> Optional[int]:
     return None
 
 
-@reports_storage_upcast("imputation_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+@reports_storage("imputation_report_")
 def impute(pls, X=None, device: bool = True):
     from .cmtf import ctPLS
 
@@ -134,7 +134,7 @@ def impute(pls, X=None, device: bool = True):
     return out if coupled else out[0]
 
 
-@reports_storage_upcast("q2x_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+@reports_storage("q2x_report_")
 def get_q2x_heldout(pls, fraction: float = 0.1, n_repeats: int = 5, random_state=0, device: bool = True, tol: float = 1e-8,
                     max_iter: int = 100) -> dict:
     from .cmtf import ctPLS

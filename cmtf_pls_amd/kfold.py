@@ -57,6 +57,9 @@ import torch
 
 from . import _lib
 from .backend import _int_pairs, _scratch
+from .cmtf import ctPLS
+from .storage import FOLDS_WHY, HALF_ENTRIES, _as_torch_dtype, half_route, notes_of, reports_storage, to_device_copy, to_device_read
+from .tpls import tPLS
 
 MAX_FOLDS, MAX_RESPONSES, MAX_COMPONENTS, MAX_SIDE = 32, 64, 64, 256
 MAX_BLOCKS = 8                    # blocks of a coupled model (cmtfpls_kfold_inner_coupled_f64)
@@ -155,9 +158,6 @@ def refit_predictions(pls, X, Y, ids: np.ndarray, K: int, tol: float, max_iter: 
 def refit_fold(pls, X, Y, test: np.ndarray, tol: float, max_iter: int):
     """One literal refit on the rows outside the boolean mask `test` (refit_predictions' per-fold step): (the predictions
     (R, n_test, M) of the rows in `test` with the first r = 1..R components, n_iter)."""
-    from .cmtf import ctPLS
-    from .tpls import tPLS
-
     coupled = isinstance(X, list)
     R = pls.n_components
     if coupled:
@@ -413,54 +413,21 @@ def _to_dev(a, dev, dt=torch.float64) -> torch.Tensor:
 
 
 # the five entries through which the device passes read X: the three builders of S and the mean, the score pass, the contraction
-HALF_READS = ("kfold_xcov", "kfold_wide_xcov", "kfold_weighted_xcov", "mttkrp", "xcov")
-
-
+HALF_READS = HALF_ENTRIES["folds"]
 # why the routes without 16-bit kernels copy 16-bit storage (the report's storage_fallback under EngineOptions.half_folds)
 HALF_MASKED_WHY = "the masked routes (cmtfpls_cv_masked_*) have no 16-bit form and read a float64 upload of the data"
 HALF_LOO_WHY = "leave-one-out (cmtfpls_loo_*) takes float64 X and reads a float64 upload of the data"
 
 
-def _half_in_place(pls) -> Optional[str]:
-    """None when the device passes read 16-bit storage in place (EngineOptions.half_folds and a backend with the _bf16 / _f16 form
-    of every entry of HALF_READS); else why they read a float32 upcast, None again while the option is off (the general reason
-    of _reports_upcast then stands)."""
-    eng = pls._get_engine()
-    if not getattr(eng.opt, "half_folds", False):
-        return None
-    be = eng.be
-    missing = [e for e in HALF_READS if not (hasattr(be, "has_half") and be.has_half(e))]
-    if missing:
-        return (f"EngineOptions.half_folds: the {getattr(be, 'name', type(be).__name__)} backend has no 16-bit form of "
-                + ", ".join(f"cmtfpls_{e}_*" for e in missing))
-    return None
-
-
-def _note_half_copy(pls, X, why: str) -> None:
-    """Under EngineOptions.half_folds, note that a route without 16-bit kernels (leave-one-out, the masked routes) read a private
-    copy of block X of a model with 16-bit storage (the report's storage_fallback); with the option off nothing is noted."""
-    from .tpls import HALF_DTYPES, _as_torch_dtype, note_storage_upcast
-
-    dtype = _as_torch_dtype(pls._dtype, X)
-    if dtype in HALF_DTYPES and getattr(pls._get_engine().opt, "half_folds", False):
-        note_storage_upcast(pls, dtype, why)
-
-
 def _device_blocks(pls, Xs, dev):
     """Each block as (X2, A, B): the device tensor of the storage type (the caller's own when it is one: never copied), I x P.
     16-bit storage: an exact float32 upcast of the rounded data, noted for the report -- or, under EngineOptions.half_folds on a
-    backend with the 16-bit entries (_half_in_place), the 16-bit tensor itself: the caller's own, or the once-rounded upload."""
-    from .tpls import HALF_DTYPES, _as_torch_dtype, to_device_copy, to_device_read
-
-    why = _half_in_place(pls)
-    in_place = why is None and bool(getattr(pls._get_engine().opt, "half_folds", False))
+    backend with the 16-bit form of every entry of HALF_READS, the 16-bit tensor itself: the caller's own, or the once-rounded upload."""
+    in_place, why = half_route(pls, "half_folds", HALF_READS)
     blocks = []
     for X in Xs:
-        dtype = _as_torch_dtype(pls._dtype, X)
-        if in_place and dtype in HALF_DTYPES:
-            X2 = to_device_copy(X, dtype, dev, copy=False)                           # (_device_pass notes the entries that read it)
-        else:
-            X2 = to_device_read(X, dtype, dev, pls=pls, why=why)
+        dtype = _as_torch_dtype(pls._dtype, X)                                       # in place: _device_pass notes the entries that read it
+        X2 = to_device_copy(X, dtype, dev, copy=False) if in_place else to_device_read(X, dtype, dev, pls=pls, why=why)
         blocks.append((X2.view(X.shape[0], -1), *_dims(X)))
     return blocks
 
@@ -636,12 +603,8 @@ def _device_pass(pls, Xs, blocks, coupled: bool, builder: str, builds, fold_of: 
                       **layout)
     if why is not None:
         return why
-    from .tpls import HALF_DTYPES, note_storage_in_place
-
     for X2, _, _ in blocks:                                                      # EngineOptions.half_folds: 16-bit blocks read in place
-        if X2.dtype in HALF_DTYPES:
-            suffix = "bf16" if X2.dtype == torch.bfloat16 else "f16"
-            note_storage_in_place(pls, X2.dtype, [f"cmtfpls_{e}_{suffix}" for e in (builder, "mttkrp", *(("xcov",) if R > 1 else ()))])
+        notes_of(pls).in_place(X2.dtype, (builder, "mttkrp", *(("xcov",) if R > 1 else ())))
     return shared, own
 
 
@@ -714,6 +677,14 @@ def _f64(a, dev):
     return a.detach().to(device=dev, dtype=torch.float64) if isinstance(a, torch.Tensor) else _to_dev(np.asarray(a, np.float64), dev)
 
 
+def _upload(pls, a, I: int, dev, why: Optional[str] = None) -> torch.Tensor:
+    """The original data in float64 on the device, as I x -1 (the same bits as a copy through the host).  `why`: `a` is a block of X,
+    read by a route without 16-bit kernels: under EngineOptions.half_folds the copy of 16-bit storage is noted with that reason."""
+    if why is not None and half_route(pls, "half_folds", ())[0]:
+        notes_of(pls).upcast(_as_torch_dtype(pls._dtype, a), why)
+    return _f64(a, dev).contiguous().view(I, -1)
+
+
 def has_missing(X) -> bool:
     """Whether X (a host array or a device tensor) holds a NaN."""
     if isinstance(X, torch.Tensor):
@@ -725,8 +696,7 @@ def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
     """What masked_predictions, masked_models and masked_models_coupled check before they look at X, in this order: the backend's
     kernel (`what` names it in the decline), a sharded model, the order of every block (tensor: _tensor_dims of a tPLS's order-4 X
     under EngineOptions.masked_tensor_folds, which the order-4 entries take), NaN in Y.  (why, None), or (None, (eng, be, M,
-    upload)): upload(a, I) is the original data in float64 on the device as I x -1; upload(X, I, True) for a block of X, which notes
-    the copy of 16-bit storage under EngineOptions.half_folds (_note_half_copy)."""
+    upload)): upload(a, I) is _upload on the backend's device; upload(X, I, True) for a block of X (HALF_MASKED_WHY)."""
     eng = pls._get_engine()
     be = eng.be
     if not hasattr(be, kernel):
@@ -741,9 +711,7 @@ def _masked_setup(pls, Xs, names, Y, kernel: str, what: str, tensor=None):
     M = int(np.prod(Y.shape[1:])) if Y.ndim > 1 else 1
 
     def upload(a, I, block=False):
-        if block:
-            _note_half_copy(pls, a, HALF_MASKED_WHY)
-        return _f64(a, be.device).contiguous().view(I, -1)
+        return _upload(pls, a, I, be.device, HALF_MASKED_WHY if block else None)
 
     return None, (eng, be, M, upload)
 
@@ -1074,20 +1042,7 @@ def _masked_run_report(masked: dict, count: str, N: int, per_pass: str, n_iter, 
     return dict(masked, **{count: int(N)}, passes=masked["launches"], **{per_pass: -(-per // masked["launches"])}, n_iter=n_iter, **more)
 
 
-def _reports_upcast(attr: str = "q2y_report_"):
-    """tpls.reports_storage_upcast for the resampling drivers (imported late: tpls imports the engine)."""
-    def deco(fn):
-        import functools
-
-        @functools.wraps(fn)
-        def run(pls, *args, **kw):
-            from .tpls import reports_storage_upcast
-            return reports_storage_upcast(attr, "the fold and resampling kernels have no 16-bit form and read an exact float32 upcast of the rounded data")(fn)(pls, *args, **kw)
-        return run
-    return deco
-
-
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: int = 100, device_folds: bool = True) -> np.ndarray:
     """pred (R, *Y.shape): pred[r - 1, i] = prediction for sample i by the model fitted without sample i's fold, with its first
     r components.  `pls` a fitted tPLS or ctPLS.  Sets pls.q2y_report_."""

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .tpls import to_device_copy
+from .storage import to_device_copy
 
 _BACKENDS = {}
 

@@ -31,8 +31,9 @@ import numpy as np
 import torch
 
 from .bootstrap import _ENTRIES, _ENTRIES_COUPLED, MAX_COLUMNS
-from .kfold import (MAX_FOLDS, PASSES, _decline_blocks, _device_blocks, _reports_upcast, _device_pass, _device_passes, _groups, _host, _names, _passes_report,
+from .kfold import (MAX_FOLDS, PASSES, _decline_blocks, _device_blocks, _device_pass, _device_passes, _groups, _host, _names, _passes_report,
                     _route, _rows, _tensor_dims, _to_dev, _training_data, _weighted_models, fold_ids, refit_fold, repeated_fold_ids)
+from .storage import FOLDS_WHY, reports_storage
 
 PRESS_FORM = "cmtfpls_press_rows_f64"
 
@@ -164,7 +165,7 @@ def _take_y(Y, sel: np.ndarray):
     return Y[torch.from_numpy(sel).to(Y.device)] if isinstance(Y, torch.Tensor) else Y[sel]
 
 
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def nested_kfold(pls, n_outer: int = 5, n_inner: int = 5, outer_folds=None, inner_folds=None, random_state=0,
                  device_folds: bool = True, tol: float = 1e-8, max_iter: int = 100) -> dict:
     X, Y = _training_data(pls)

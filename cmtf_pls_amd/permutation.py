@@ -38,9 +38,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, REFIT, _decline_blocks, _device_blocks, _reports_upcast, _device_numerators, _device_pass,
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, REFIT, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
                     _device_passes, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report, _refit_numerators,
                     _route, _tensor_dims, _to_dev, _training_data, fold_ids, masked_fold_numerators)
+from .storage import FOLDS_WHY, reports_storage
 
 _ENTRIES = ("kfold_wide_xcov", "kfold_inner_grouped", "kfold_epilogue_grouped", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_wide_xcov", "kfold_inner_coupled_grouped", "kfold_combine_scores", "kfold_epilogue_grouped", "mttkrp", "xcov")
@@ -111,7 +112,7 @@ def _device_null(pls, Xs, Y, ids: np.ndarray, K: int, perms: np.ndarray, tol: fl
     return run
 
 
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def permutation_test(pls, n_permutations: int = 99, n_splits: int = 5, folds=None, permutations=None, random_state=0,
                      per_component: bool = False, device_folds: bool = True, tol: float = 1e-8, max_iter: int = 100) -> dict:
     from .validate import get_q2y_kfold

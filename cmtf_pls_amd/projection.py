@@ -13,7 +13,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .state import HALF_DTYPES, BlockState, FitState, read_dtype
+from .state import BlockState, FitState
+from .storage import HALF_DTYPES, HALF_ENTRIES, dtype_name, half_route, read_dtype
 
 
 class ProjectionMixin:
@@ -122,7 +123,7 @@ class ProjectionMixin:
             be = self.be
             nb, I = len(state.blocks), Xs[0].shape[0]
             rep = self.last_projection = {"rows": int(I), "blocks": nb, "form": "sequential passes on private copies", "why": None}
-            if not (hasattr(be, "has_half") and be.has_half("mttkrp")):
+            if not half_route(self, None, HALF_ENTRIES["projection"])[0]:
                 return None, "the backend has no 16-bit MTTKRP"
             if any(bool(torch.isnan(blk.mean).any().item()) for blk in state.blocks):
                 return None, "a training column without observations (NaN mean)"
@@ -140,7 +141,7 @@ class ProjectionMixin:
             if int(flag.item()) != 0:
                 return None, "rows with missing or non-finite values in the batch"
             rep.update(form="one-pass MTTKRP (one read, nothing written)",
-                       storage=[str(X.dtype).replace("torch.", "") for X in Xs])
+                       storage=[dtype_name(X.dtype) for X in Xs])
             return scores, None
 
     @staticmethod

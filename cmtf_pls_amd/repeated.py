@@ -31,9 +31,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _device_blocks, _reports_upcast, _device_numerators, _device_pass,
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
                     _device_passes, _fold_means, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
                     _refit_numerators, _route, _tensor_dims, _to_dev, _training_data, masked_fold_numerators, repeated_fold_ids)
+from .storage import FOLDS_WHY, reports_storage
 
 _ENTRIES = ("kfold_xcov", "kfold_inner", "kfold_epilogue_splits", "mttkrp", "xcov")
 _ENTRIES_COUPLED = ("kfold_xcov", "kfold_inner_coupled", "kfold_combine_scores", "kfold_epilogue_splits", "mttkrp", "xcov")
@@ -86,7 +87,7 @@ def _device_splits(pls, Xs, Y, ids: np.ndarray, K: int, tol: float, max_iter: in
     return run
 
 
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, random_state=0, per_component: bool = False,
                    device_folds: bool = True, tol: float = 1e-8, max_iter: int = 100) -> dict:
     X, Y = _training_data(pls)

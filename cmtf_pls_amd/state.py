@@ -12,16 +12,6 @@ import numpy as np
 import torch
 
 
-# 16-bit storage of X (chosen explicitly with dtype=, never by dtype=None): X is only ever READ in that type -- the cross-covariance
-# fit and the one-pass projection convert on load; every step that would write X or has no 16-bit form runs on an exact float32 upcast.
-HALF_DTYPES = (torch.bfloat16, torch.float16)
-
-
-def read_dtype(dtype):
-    """The type the routines without a 16-bit form read a model's X in: float32 for 16-bit storage (an exact upcast)."""
-    return torch.float32 if dtype in HALF_DTYPES else dtype
-
-
 def split_trailing(shape: Sequence[int]):
     """(A, B) with A*B = prod(shape[1:]): wA spans the first trailing mode, wB the rest."""
     trailing = list(shape[1:])

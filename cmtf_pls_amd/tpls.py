@@ -18,7 +18,6 @@ pipelined, graph replay, projection form; every declined fast form in words) and
 """
 from __future__ import annotations
 
-import functools
 from collections.abc import Mapping
 from copy import copy
 from typing import Optional
@@ -27,172 +26,7 @@ import numpy as np
 import torch
 
 from .engine import Comm, EngineOptions, NipalsEngine
-from .state import HALF_DTYPES, read_dtype  # noqa: F401  (16-bit storage: read in place or as an exact float32 upcast)
-
-
-def _as_torch_dtype(dtype, like) -> torch.dtype:
-    """Storage type of X on the GPU: explicit, or float32 only when the input already is float32."""
-    if dtype is None:
-        return torch.float32 if like.dtype in (np.float32, torch.float32) else torch.float64
-    if isinstance(dtype, torch.dtype):
-        return dtype
-    name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
-    return {"float32": torch.float32, "f32": torch.float32, "float64": torch.float64, "f64": torch.float64,
-            "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.float16, "f16": torch.float16}[name]
-
-
-def note_storage_upcast(pls, dtype: torch.dtype, why: Optional[str] = None) -> None:
-    """Note on `pls` that a routine read a private upcast of its 16-bit data (`reports_storage_upcast` writes the report); `why`: this
-    read's own reason, which then replaces the routine's general one."""
-    seen = getattr(pls, "_storage_upcasts", None)
-    if seen is not None:
-        seen.append(str(dtype).replace("torch.", ""))
-        if why is not None and why not in pls._storage_upcast_whys:
-            pls._storage_upcast_whys.append(why)
-
-
-def note_storage_in_place(pls, dtype: torch.dtype, entries) -> None:
-    """Note on `pls` that a routine's device passes read the 16-bit tensor itself through `entries` (EngineOptions.half_folds /
-    half_diagnostics)."""
-    here = getattr(pls, "_storage_in_place", None)
-    if here is not None:
-        here.append((str(dtype).replace("torch.", ""), tuple(entries)))
-
-
-# the routines that copy 16-bit storage whatever EngineOptions.half_diagnostics says, and why (the report's storage_fallback)
-HALF_DIAGNOSTICS_UPCASTS = {
-    "impute": "impute returns a float32 tensor of X's size either way, so reading the 16-bit tensor in place would save nothing",
-    "q2x_heldout": "get_q2x_heldout refits masked copies of X, and the refit writes them",
-}
-
-
-def _half_diagnostics_read(pls, entry: str):
-    """How a diagnostics routine reads 16-bit storage under EngineOptions.half_diagnostics: (True, None) = the tensor itself through
-    the _bf16 / _f16 form of cmtfpls_<entry>; (False, why) = a float32 upcast for that reason; (False, None) while the option is off
-    (the routine's general reason then stands, and every bit and report text is that of a model without the option)."""
-    eng = pls._get_engine()
-    if not getattr(eng.opt, "half_diagnostics", False):
-        return False, None
-    if entry in HALF_DIAGNOSTICS_UPCASTS:
-        return False, "EngineOptions.half_diagnostics: " + HALF_DIAGNOSTICS_UPCASTS[entry]
-    be = eng.be
-    if not (hasattr(be, "has_half") and be.has_half(entry)):
-        return False, (f"EngineOptions.half_diagnostics: the {getattr(be, 'name', type(be).__name__)} backend has no 16-bit form of "
-                       f"cmtfpls_{entry}_*")
-    return True, None
-
-
-def to_device_read(X, dtype: torch.dtype, device, pls=None, why: Optional[str] = None, entry: Optional[str] = None) -> torch.Tensor:
-    """X on the device as the routines beside fit / transform read it (diagnostics, contributions, importance, imputation, the
-    resampling drivers, R2X_literal): `to_device_copy(X, dtype, device, copy=False)` -- and for a model with 16-bit storage the
-    data ROUNDED to that type, then upcast to float32: exactly the values the model was fitted on, in a type those kernels take.
-    `pls`: the model on whose behalf X is read; the upcast is noted on it for the routine's report (`reports_storage_upcast`),
-    with this read's own reason `why` where it has one.
-    `entry`: the kernel (or, for impute / get_q2x_heldout, the routine) that reads X.  Under EngineOptions.half_diagnostics on a
-    backend with its 16-bit form the 16-bit tensor itself comes back -- the caller's own device tensor, or the once-rounded upload
-    -- and the entry is noted for the report's "half_storage"; every other case under the option upcasts with its own reason."""
-    Xd = to_device_copy(X, dtype, device, copy=False)
-    if dtype not in HALF_DTYPES:
-        return Xd
-    if entry is not None and pls is not None and why is None:
-        in_place, why = _half_diagnostics_read(pls, entry)
-        if in_place:
-            note_storage_in_place(pls, dtype, [f"cmtfpls_{entry}_{'bf16' if dtype == torch.bfloat16 else 'f16'}"])
-            return Xd
-    note_storage_upcast(pls, dtype, why)
-    return Xd.to(torch.float32)
-
-
-def note_half_fallbacks(pls, Xd, forms) -> None:
-    """After a diagnostics pass over the blocks Xd whose per-block `forms` the engine recorded: a 16-bit block read in place whose
-    kernel declined the shape (or was switched off) went through the torch fallback on an exact float32 upcast of that block
-    (ProjectionMixin._fallback_block); noted with the pass's own reason, so that the report says storage_fallback."""
-    for X, f in zip(Xd, forms):
-        if X.dtype in HALF_DTYPES and f.get("why"):
-            note_storage_upcast(pls, X.dtype, f["why"])
-
-
-def reports_storage_upcast(report_attr: str, why: str):
-    """Decorator of a routine `fn(pls, ...)` that leaves its report in `pls.<report_attr>`: when the routine read X of a model with
-    16-bit storage through `to_device_read(..., pls=pls)` -- a full float32 copy -- the report gets
-    "storage_fallback": "float32 private copy of the <type> data: <why>" (the reads' own reasons where they gave any).  When its
-    device passes read the 16-bit tensor itself instead (`note_storage_in_place`, EngineOptions.half_folds / half_diagnostics) and the report shows
-    reads of X, it gets "half_storage": {"in_place": True, "dtype": <type>, "entries": [...]} and no "storage_fallback"."""
-    def deco(fn):
-        @functools.wraps(fn)
-        def run(pls, *args, **kw):
-            outer = [getattr(pls, a, None) for a in ("_storage_upcasts", "_storage_upcast_whys", "_storage_in_place")]
-            pls._storage_upcasts, pls._storage_upcast_whys, pls._storage_in_place = seen, whys, here = [], [], []
-            try:
-                out = fn(pls, *args, **kw)
-            finally:
-                pls._storage_upcasts, pls._storage_upcast_whys, pls._storage_in_place = outer
-            rep = getattr(pls, report_attr, None)
-            if seen and isinstance(rep, dict):
-                rep["storage_fallback"] = f"float32 private copy of the {' / '.join(sorted(set(seen)))} data: {'; '.join(whys) or why}"
-            elif here and isinstance(rep, dict) and rep.get("x_reads") is not None:
-                rep["half_storage"] = {"in_place": True, "dtype": " / ".join(sorted({d for d, _ in here})),
-                                       "entries": sorted({e for _, es in here for e in es})}
-            if outer[0] is not None:
-                outer[0].extend(seen)
-                outer[1].extend(w for w in whys if w not in outer[1])
-                outer[2].extend(here)
-            return out
-        return run
-    return deco
-
-
-def _round_once(x64: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """float64 -> bfloat16 / float16 with ONE rounding to nearest even, on any device.  A plain cast goes through float32 and
-    rounds twice (about 1 value in 20000 then differs from the correctly rounded one).  Here the float32 step rounds to ODD
-    (truncate towards zero, set the last bit when anything was lost), which keeps what the final rounding needs to know; the
-    float32 -> 16-bit cast is then a single rounding of the right value (float32 has more than two bits to spare)."""
-    f = x64.to(torch.float32)
-    back = f.to(torch.float64)
-    lost = (back != x64) & torch.isfinite(x64)
-    bits = f.view(torch.int32)
-    bits = torch.where(lost & (back.abs() > x64.abs()), bits - 1, bits)      # sign-magnitude: one less is one step towards zero
-    bits = torch.where(lost, bits | 1, bits)
-    return bits.view(torch.float32).to(dtype)
-
-
-def _half_from_f64(src: torch.Tensor, dtype: torch.dtype, device) -> torch.Tensor:
-    """A float64 tensor (host or device) as a fresh 16-bit device tensor, rounded once, in row blocks of <= 256 MB."""
-    out = torch.empty(src.shape, dtype=dtype, device=device)
-    if src.ndim == 0:
-        return out.copy_(_round_once(src.to(device), dtype))
-    rows = max(1, (256 << 20) // max(src[0].numel() * 8, 1))
-    for r in range(0, src.shape[0], rows):
-        out[r:r + rows].copy_(_round_once(src[r:r + rows].to(device), dtype))
-    return out
-
-
-def to_device_copy(X, dtype: torch.dtype, device, copy: bool = True) -> torch.Tensor:
-    """A fresh contiguous device tensor of X (inputs are never modified, tpls.py:74,128,151).
-    copy=False (opt-in ``copy_X=False``): a device tensor that already has the right type is used in
-    place and is centred / deflated by the fit.
-
-    A large HOST array of another type than the storage type (the common case: float64 NumPy input, float32
-    storage) is shipped in row blocks in ITS OWN type and cast on the device: casting 8.6 GB on the host first costs
-    ~0.75 s at 65536 x 128 x 128, the extra PCIe bytes ~0.08 s (profiles/r02aa_pcie_inclusive.txt)."""
-    if isinstance(X, torch.Tensor):
-        if not copy and X.is_contiguous() and X.dtype == dtype and X.device == torch.device(device):
-            return X
-        if dtype in HALF_DTYPES and X.dtype == torch.float64:
-            return _half_from_f64(X.contiguous(), dtype, device)     # one rounding, whatever the container (as NumPy's astype)
-        out = X.to(device=device, dtype=dtype, copy=True)
-        return out.contiguous()
-    Xn = np.ascontiguousarray(X)
-    src = torch.from_numpy(Xn)
-    if dtype in HALF_DTYPES and src.dtype == torch.float64:
-        return _half_from_f64(src, dtype, device)                    # the stored data is X.astype(np.float16), not a double rounding
-    if src.dtype == dtype or Xn.ndim == 0 or Xn.nbytes < (64 << 20):
-        return src.to(device=device, dtype=dtype, copy=True).contiguous()
-    out = torch.empty(Xn.shape, dtype=dtype, device=device)
-    rows = max(1, (256 << 20) // max(Xn[0].nbytes, 1))           # ~256 MB of the source type per block
-    for r in range(0, Xn.shape[0], rows):
-        out[r:r + rows].copy_(src[r:r + rows].to(device))        # H2D in the source type, cast by the device copy
-    return out
+from .storage import HALF_DTYPES, _as_torch_dtype, dtype_name, fallback_text, notes_of, read_dtype, reports_storage, to_device_copy, to_device_read
 
 
 def _project_blocks(eng: NipalsEngine, state, Xs, dtypes, mixed: bool) -> torch.Tensor:
@@ -208,17 +42,12 @@ def _project_blocks(eng: NipalsEngine, state, Xs, dtypes, mixed: bool) -> torch.
         scores, half_why = (None, "f32 matrix precision") if mixed else eng.project_half(state, Xd)
         if scores is not None:
             return scores
-        names = sorted({str(xd.dtype).replace("torch.", "") for xd in Xd if xd.dtype in HALF_DTYPES})
-        half_why = f"float32 private copy of the {' / '.join(names)} data: {half_why}"
+        half_why = fallback_text([dtype_name(xd.dtype) for xd in Xd if xd.dtype in HALF_DTYPES], half_why)
         Xd = [xd.to(torch.float32) if xd.dtype in HALF_DTYPES else xd for xd in Xd]     # (private: not cloned again below)
-    if not mixed:
-        scores = eng.project_readonly(state, Xd)
-        if half_why is not None:
-            eng.last_projection["storage_fallback"] = half_why
-        if scores is not None:
-            return scores
-    Xd = [xd.clone() if xd is X else xd for xd, X in zip(Xd, Xs)]        # never touch the caller's tensor
-    scores = eng.project(state, Xd, mixed=mixed)
+    scores = None if mixed else eng.project_readonly(state, Xd)
+    if scores is None:
+        Xd = [xd.clone() if xd is X else xd for xd, X in zip(Xd, Xs)]    # never touch the caller's tensor
+        scores = eng.project(state, Xd, mixed=mixed)
     if half_why is not None:
         eng.last_projection["storage_fallback"] = half_why
     return scores
@@ -428,7 +257,7 @@ class tPLS(_EstimatorBase):
             return X_scores, self._y_scores(scores, Y)
         return X_scores
 
-    @reports_storage_upcast("r2x_literal_report_", "the kernels of this routine have no 16-bit form and read an exact float32 upcast of the rounded data")
+    @reports_storage("r2x_literal_report_")
     def R2X_literal(self, X):
         """calcR2X(X - X_mean, factors_to_tensor(X_factors)) of the training X (util.py:7-15 as tpls.py:115-117 calls it)
         in one read of X on the GPU; equals R2X[-1], which the fit obtains from the deflation sweep instead.
@@ -441,13 +270,9 @@ class tPLS(_EstimatorBase):
             from .util import calcR2X, factors_to_tensor
             R = self._state.n_components
             why = f"R = {R} > 16: outside cmtfpls_recon_r2" if hasattr(eng.be, "recon_r2") else "backend has no recon_r2 kernel"
-            if Xd.dtype in HALF_DTYPES:                                       # read in place so far: the host formula takes an upcast
-                note_storage_upcast(self, Xd.dtype, why)
-                Xh = Xd.to(torch.float32).cpu().numpy()
-            elif isinstance(X, torch.Tensor):                                 # (NumPy has no bfloat16)
-                Xh = (X.to(torch.float32) if X.dtype in HALF_DTYPES else X).cpu().numpy()
-            else:
-                Xh = np.asarray(X)
+            notes_of(self).upcast(Xd.dtype, why)                              # 16-bit Xd, read in place so far: the host formula takes an upcast
+            src = Xd if Xd.dtype in HALF_DTYPES else X                        # (NumPy has no bfloat16)
+            Xh = src.to(read_dtype(src.dtype)).cpu().numpy() if isinstance(src, torch.Tensor) else np.asarray(src)
             r2 = calcR2X(Xh - self.X_mean, factors_to_tensor(self.X_factors))
         self.r2x_literal_report_ = {"form": "host formula (calcR2X)" if why else "one read (cmtfpls_recon_r2)", "why": why, "x_reads": [1]}
         return r2

@@ -26,9 +26,10 @@ import numpy as np
 
 from . import _lib
 from .backend import _int_pairs
-from .kfold import (HALF_LOO_WHY, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _f64, _host,
-                    _masked_declined, _note_half_copy, _reports_upcast, _size_blocks, _tensor_dims, _training_data, coupled_form, has_missing, masked_predictions,
+from .kfold import (HALF_LOO_WHY, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
+                    _masked_declined, _size_blocks, _tensor_dims, _training_data, _upload, coupled_form, has_missing, masked_predictions,
                     masked_predictions_coupled, refit_predictions, wants_masked_coupled, wants_masked_tensor)
+from .storage import FOLDS_WHY, reports_storage
 from .tpls import tPLS
 
 LOO_TENSOR_FORM = "a workgroup per fold on the fold's cross-covariance, order-4 X (cmtfpls_loo_xcov_tensor_f64)"
@@ -60,7 +61,7 @@ def _decline_loo_tensor(be, A: int, B1: int, B2: int, M: int, R: int):
     return None
 
 
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def loo_predictions(pls_tensor, tol: float = 1e-8, max_iter: int = 100):
     """Y_pred[i] = prediction for sample i by the model refitted without it (validate.py:24-33), all folds in one
     launch; None when the device form does not apply (see get_q2y).  `pls_tensor` is a fitted tPLS or ctPLS."""
@@ -138,11 +139,6 @@ def _wants_loo_coupled_tensor(pls, Xs) -> bool:
     return bool(pls._get_engine().opt.tensor_resamples_coupled) and any(X.ndim >= 4 for X in Xs)
 
 
-def _upload(a, I: int, dev):
-    """The original data in float64 on the device, as I x -1 (kfold._f64: the same bits as a copy through the host)."""
-    return _f64(a, dev).contiguous().view(I, -1)
-
-
 def _loo_report(form: str, folds: int, n_iter_total, blocks=None, rank1: bool = False, why=None) -> dict:
     """q2y_report_ of a leave-one-out form (blocks: a ctPLS's; rank1: an order-4 form; why: of the refits)."""
     rep = {"form": form, **({"rank1": TENSOR_RANK1} if rank1 else {}), "folds": int(folds), **({} if blocks is None else {"blocks": blocks}),
@@ -177,9 +173,7 @@ def _loo_device_coupled(pls, tol: float, max_iter: int):
     eng = pls._get_engine()
     be = eng.be
     with eng.device_ctx():
-        for X in Xs:
-            _note_half_copy(pls, X, HALF_LOO_WHY)                            # 16-bit storage under EngineOptions.half_folds
-        data = ([_upload(X, I, be.device) for X in Xs], _upload(Y, I, be.device), [(X.ndim, *_dims(X)) for X in Xs])
+        data = ([_upload(pls, X, I, be.device, HALF_LOO_WHY) for X in Xs], _upload(pls, Y, I, be.device), [(X.ndim, *_dims(X)) for X in Xs])
         if tensor:
             out = be.loo_ctpls_tensor(*data, _tensor_dims(Xs, coupled=True), pls.n_components, tol, max_iter)
             return _loo_result(pls, out, "cmtfpls_loo_xcov_coupled_tensor_f64", LOO_COUPLED_TENSOR_FORM, Y, len(Xs), rank1=True)
@@ -236,8 +230,7 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         if why is not None:
             return None, why
     with torch.cuda.device(be.device):
-        _note_half_copy(pls_tensor, X, HALF_LOO_WHY)                         # 16-bit storage under EngineOptions.half_folds
-        Xd, Yd = _upload(X, I, be.device), _upload(Y, I, be.device)
+        Xd, Yd = _upload(pls_tensor, X, I, be.device, HALF_LOO_WHY), _upload(pls_tensor, Y, I, be.device)
         if order4:
             return _loo_result(pls_tensor, be.loo_tpls_tensor(Xd, Yd, A, B1, B2, R, tol, max_iter), "cmtfpls_loo_xcov_tensor_f64",
                                LOO_TENSOR_FORM, Y, rank1=True)
@@ -247,7 +240,7 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
         return _loo_result(pls_tensor, out, "", LOO_FORMS[out[2]], Y)
 
 
-@_reports_upcast()
+@reports_storage("q2y_report_", FOLDS_WHY)
 def get_q2y(pls_tensor, device_folds: bool = True):
     if _is_coupled(pls_tensor):
         return _get_q2y_coupled(pls_tensor, device_folds)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import half_storage_ref as HS
-from cmtf_pls_amd import _lib, backend, tpls
+from cmtf_pls_amd import _lib, backend, storage, tpls
 from cmtf_pls_amd import validate as V
 from cmtf_pls_amd.engine import EngineOptions
 
@@ -91,7 +91,7 @@ class _Engine:
 class _Model:
     def __init__(self, opt, be):
         self._engine = _Engine(opt, be)
-        self._storage_upcasts, self._storage_upcast_whys, self._storage_in_place = [], [], []
+        self._storage = storage.StorageNotes()
 
     def _get_engine(self):
         return self._engine
@@ -106,7 +106,7 @@ def test_the_read_follows_the_option_the_entry_and_the_backend(kind):
     off = _Model(EngineOptions(), _Backend())
     X = tpls.to_device_read(q, dt, "cpu", pls=off, entry="resid_rows")
     assert X.dtype == torch.float32 and np.array_equal(X.double().numpy(), up)
-    assert off._storage_upcasts == [name] and off._storage_upcast_whys == [] and off._storage_in_place == []      # the general reason
+    assert off._storage.upcasts == [name] and off._storage.whys == [] and off._storage.reads == []      # the general reason
 
     on = _Model(EngineOptions(half_diagnostics=True), _Backend())
     for entry in BASES:
@@ -114,29 +114,29 @@ def test_the_read_follows_the_option_the_entry_and_the_backend(kind):
         assert X.dtype == dt and X.data_ptr() == q.data_ptr()                                  # the caller's own tensor
     host = tpls.to_device_read(x64, dt, "cpu", pls=on, entry="resid_rows")                     # a float64 array: rounded once
     assert host.dtype == dt and torch.equal(host.view(torch.int16), q.view(torch.int16))
-    assert on._storage_upcasts == []
-    assert on._storage_in_place == [(name, (f"cmtfpls_{e}_{kind}",)) for e in BASES + ("resid_rows",)]
+    assert on._storage.upcasts == []
+    assert on._storage.reads == [(name, (f"cmtfpls_{e}_{kind}",)) for e in BASES + ("resid_rows",)]
 
     for entry, word in (("impute", "impute returns a float32 tensor"), ("q2x_heldout", "the refit writes")):
         m = _Model(EngineOptions(half_diagnostics=True), _Backend())
         assert tpls.to_device_read(q, dt, "cpu", pls=m, entry=entry).dtype == torch.float32
-        assert m._storage_upcasts == [name] and word in m._storage_upcast_whys[0] and m._storage_in_place == []
+        assert m._storage.upcasts == [name] and word in m._storage.whys[0] and m._storage.reads == []
 
     lacking = _Model(EngineOptions(half_diagnostics=True), _Backend(missing=("contrib_rows",)))
     assert tpls.to_device_read(q, dt, "cpu", pls=lacking, entry="contrib_rows").dtype == torch.float32
-    assert "cmtfpls_contrib_rows_*" in lacking._storage_upcast_whys[0] and "stand-in" in lacking._storage_upcast_whys[0]
+    assert "cmtfpls_contrib_rows_*" in lacking._storage.whys[0] and "stand-in" in lacking._storage.whys[0]
     assert tpls.to_device_read(q, dt, "cpu", pls=lacking, entry="resid_rows").dtype == dt
 
     # a read without an entry (the resampling drivers), and float32 storage, are what they were
     plain = _Model(EngineOptions(half_diagnostics=True), _Backend())
-    assert tpls.to_device_read(q, dt, "cpu", pls=plain).dtype == torch.float32 and plain._storage_upcast_whys == []
+    assert tpls.to_device_read(q, dt, "cpu", pls=plain).dtype == torch.float32 and plain._storage.whys == []
     x32 = torch.randn(5, 3)
     assert tpls.to_device_read(x32, torch.float32, "cpu", pls=plain, entry="resid_rows").data_ptr() == x32.data_ptr()
-    assert plain._storage_in_place == []
+    assert plain._storage.reads == []
 
     # a block whose kernel declined after an in-place read: noted as an upcast with the pass's own reason
-    tpls.note_half_fallbacks(on, [q, x32], [{"form": "torch fallback", "why": "R = 17 > 16: outside cmtfpls_resid_rows"}, {"form": "f", "why": "x"}])
-    assert on._storage_upcasts == [name] and on._storage_upcast_whys == ["R = 17 > 16: outside cmtfpls_resid_rows"]
+    storage.notes_of(on).declined([q, x32], [{"form": "torch fallback", "why": "R = 17 > 16: outside cmtfpls_resid_rows"}, {"form": "f", "why": "x"}])
+    assert on._storage.upcasts == [name] and on._storage.whys == ["R = 17 > 16: outside cmtfpls_resid_rows"]
 
 
 def _same(a, b):

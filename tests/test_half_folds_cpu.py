@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import half_storage_ref as HS
-from cmtf_pls_amd import _lib, backend, kfold
+from cmtf_pls_amd import _lib, backend, kfold, storage
 from cmtf_pls_amd.engine import EngineOptions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,12 +74,12 @@ class _Engine:
 
 
 class _Model:
-    """A model as kfold._device_blocks sees it: the storage type, the engine, and the notes that reports_storage_upcast collects."""
+    """A model as kfold._device_blocks sees it: the storage type, the engine, and the notes that storage.reports_storage collects."""
 
     def __init__(self, dtype, opt, be):
         self._dtype = dtype
         self._engine = _Engine(opt, be)
-        self._storage_upcasts, self._storage_upcast_whys, self._storage_in_place = [], [], []
+        self._storage = storage.StorageNotes()
 
     def _get_engine(self):
         return self._engine
@@ -97,24 +97,24 @@ def test_blocks_follow_the_option_and_the_backend(kind):
     blocks = kfold._device_blocks(off, [q, mat16], "cpu")
     assert [b[0].dtype for b in blocks] == [torch.float32] * 2 and [tuple(b[0].shape) for b in blocks] == [(12, 12), (12, 5)]
     assert np.array_equal(blocks[0][0].double().numpy().reshape(up.shape), up)              # the exact upcast
-    assert off._storage_upcasts == [name, name] and off._storage_upcast_whys == []          # noted, with the general reason
+    assert off._storage.upcasts == [name, name] and off._storage.whys == []          # noted, with the general reason
 
     on = _Model(name, EngineOptions(half_folds=True), _Backend())
     blocks = kfold._device_blocks(on, [q, mat16], "cpu")
     assert [b[0].dtype for b in blocks] == [HS.TORCH[kind]] * 2
     assert blocks[0][0].data_ptr() == q.data_ptr() and blocks[1][0].data_ptr() == mat16.data_ptr()     # the caller's own
     assert [b[1:] for b in blocks] == [(4, 3), (1, 5)]
-    assert on._storage_upcasts == []
+    assert on._storage.upcasts == []
     host = kfold._device_blocks(on, [x64], "cpu")[0][0]                                     # a float64 array: the once-rounded upload
     assert host.dtype == HS.TORCH[kind] and torch.equal(host.view(torch.int16), q.view(12, -1).view(torch.int16))
-    assert on._storage_upcasts == []
+    assert on._storage.upcasts == []
 
     lacking = _Model(name, EngineOptions(half_folds=True), _Backend(missing=("kfold_wide_xcov",)))
     blocks = kfold._device_blocks(lacking, [q], "cpu")
     assert blocks[0][0].dtype == torch.float32 and blocks[0][0].data_ptr() != q.data_ptr()
-    assert lacking._storage_upcasts == [name]
-    assert len(lacking._storage_upcast_whys) == 1 and "cmtfpls_kfold_wide_xcov_*" in lacking._storage_upcast_whys[0]
-    assert "stand-in" in lacking._storage_upcast_whys[0]
+    assert lacking._storage.upcasts == [name]
+    assert len(lacking._storage.whys) == 1 and "cmtfpls_kfold_wide_xcov_*" in lacking._storage.whys[0]
+    assert "stand-in" in lacking._storage.whys[0]
 
 
 def test_float32_storage_is_untouched_by_the_option():
@@ -122,19 +122,17 @@ def test_float32_storage_is_untouched_by_the_option():
     m = _Model("float32", EngineOptions(half_folds=True), _Backend())
     (X2, A, B), = kfold._device_blocks(m, [x], "cpu")
     assert X2.dtype == torch.float32 and X2.data_ptr() == x.data_ptr() and (A, B) == (4, 2)
-    assert m._storage_upcasts == [] and m._storage_in_place == []
+    assert m._storage.upcasts == [] and m._storage.reads == []
 
 
 def test_report_keys_of_the_decorator():
-    """reports_storage_upcast: in-place notes give half_storage only when the report shows reads of X; an upcast wins, with the
+    """storage.reports_storage: in-place notes give half_storage only when the report shows reads of X; an upcast wins, with the
     reads' own reasons."""
-    from cmtf_pls_amd.tpls import note_storage_in_place, note_storage_upcast, reports_storage_upcast
-
     class M:
         pass
 
     def run(notes, x_reads):
-        @reports_storage_upcast("rep_", "general reason")
+        @storage.reports_storage("rep_", "general reason")
         def fn(pls):
             for n in notes:
                 n(pls)
@@ -143,13 +141,13 @@ def test_report_keys_of_the_decorator():
         fn(m)
         return m.rep_
 
-    inplace = lambda p: note_storage_in_place(p, torch.bfloat16, ["cmtfpls_kfold_xcov_bf16", "cmtfpls_mttkrp_bf16"])   # noqa: E731
+    inplace = lambda p: storage.notes_of(p).in_place(torch.bfloat16, ["kfold_xcov", "mttkrp"])   # noqa: E731
     rep = run([inplace, inplace], 6)
     assert rep["half_storage"] == {"in_place": True, "dtype": "bfloat16", "entries": ["cmtfpls_kfold_xcov_bf16", "cmtfpls_mttkrp_bf16"]}
     assert "storage_fallback" not in rep
     assert "half_storage" not in run([inplace], None) and "storage_fallback" not in run([inplace], None)     # every model refitted
-    rep = run([lambda p: note_storage_upcast(p, torch.float16)], 6)
+    rep = run([lambda p: storage.notes_of(p).upcast(torch.float16)], 6)
     assert rep["storage_fallback"] == "float32 private copy of the float16 data: general reason" and "half_storage" not in rep
-    rep = run([lambda p: note_storage_upcast(p, torch.float16, "its own reason")], 6)
+    rep = run([lambda p: storage.notes_of(p).upcast(torch.float16, "its own reason")], 6)
     assert rep["storage_fallback"] == "float32 private copy of the float16 data: its own reason"
     assert run([], 6) == {"form": "f", "x_reads": 6}
