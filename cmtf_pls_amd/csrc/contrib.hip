@@ -16,23 +16,13 @@
 //                            owner lane adds into the row's LDS accumulator -- the same lane for every chunk of k.
 // B beyond LK V columns is walked in chunks (chunk outermost: the loadings are reloaded once per chunk and row group).  A matrix
 // block (A = 1) has no j: all 256 threads lie along k, nothing is reduced, and the A outputs are skipped.
-#include "common.hpp"
+#include "model_cols.hpp"                        // the component cap (here: of WB held in registers), its dispatch and dpp_mov
 
 namespace cmtfpls {
 
-constexpr int kContribMaxR = 16;                 // components of WB held in registers
 constexpr int kContribUnroll = 4;                // j steps whose loads are issued together
 constexpr int kContribMaxRows = 8;               // rows of a workgroup (their A-side accumulators share the LDS)
 constexpr size_t kContribLdsMax = 160 * 1024;    // TH (2 A R) + accumulators (2 G A) + slab (512 V) doubles must fit
-
-// the value of another lane of the same 16-lane row, by a DPP control word (as resid.hip); needs every lane of the row active
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
 
 // total over the aligned group of 2^lg lanes (lg uniform, <= 6); every lane of the group ends with the same bits
 __device__ __forceinline__ double slice_total(double v, int lg) {
@@ -251,7 +241,7 @@ static int run_contrib_rows(const T* X, int64_t I, const double* Tm, int ldt, co
     set_error("contrib_rows: bad argument");
     return CMTFPLS_EINVAL;
   }
-  if (R > kContribMaxR) { set_error("contrib_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
+  if (R > kModelMaxR) { set_error("contrib_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
   const bool vec = (B % DiagVec<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & DiagVec<T>::kAlignMask) == 0 &&
                    (reinterpret_cast<uintptr_t>(mean) & 15) == 0;
   ContribPlan p;
@@ -260,18 +250,13 @@ static int run_contrib_rows(const T* X, int64_t I, const double* Tm, int ldt, co
     return CMTFPLS_EUNSUPPORTED;
   }
   const dim3 grid((unsigned)((n + p.G - 1) / p.G)), block(kSweepThreads);
-#define CRK(RCC, VV)                                                                                                              \
-  do {                                                                                                                            \
-    if (p.lds + 1024 > 64 * 1024)                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(contrib_rows_kernel<T, RCC, VV>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)p.lds);                                                                                      \
-    hipLaunchKernelGGL((contrib_rows_kernel<T, RCC, VV>), grid, block, p.lds, st, X, I, Tm, ldt, Hm, ldh, R, WA, WB, A, B, mean, rows, n, \
-                       p.G, p.lgLK, speA, speB, t2A, t2B);                                                                        \
-  } while (0)
-#define CRV(VV) do { if (R <= 4) CRK(4, VV); else if (R <= 8) CRK(8, VV); else if (R <= 12) CRK(12, VV); else CRK(16, VV); } while (0)
-  if (vec) CRV(true); else CRV(false);
-#undef CRV
-#undef CRK
+  dispatch_model(R, vec, [&](auto rcb, auto vb) {
+    auto kernel = contrib_rows_kernel<T, decltype(rcb)::value, decltype(vb)::value>;
+    if (p.lds + 1024 > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipLaunchKernelGGL(kernel, grid, block, p.lds, st, X, I, Tm, ldt, Hm, ldh, R, WA, WB, A, B, mean, rows, n, p.G, p.lgLK, speA, speB, t2A,
+                       t2B);
+  });
   return check_launch("contrib_rows");
 }
 

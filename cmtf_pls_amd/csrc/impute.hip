@@ -9,15 +9,14 @@
 // The hold-out rule: element e of a block (C order) is held out iff
 //   unit_open(philox4x32_10(counter = (offset + e) / 4, stream, key = seed).v[(offset + e) % 4]) < fraction,
 // stream = 2 + block index (streams 0 and 1 belong to add_noise, synth.hip), offset = global index of the block's first element.
-// heldout_resid and impute use the thread layout of recon_r2_kernel (recon.hip): a thread owns V consecutive columns (16 bytes),
-// keeps their R loading products in registers and walks the rows of its row block; the score row is workgroup-uniform.
+// heldout_resid and impute use the column-tile layout of model_cols.hpp with V = 16 bytes of the storage type (VecOf, not DiagVec:
+// the mask and the stores are defined on 16-byte vectors, and neither entry reads 16-bit X).
 // Every sum is two-stage in a fixed order (per-workgroup partials, then reduce_rows_kernel): the same bits on every call.
-#include "common.hpp"
+#include "model_cols.hpp"
 #include "philox.hpp"
 
 namespace cmtfpls {
 
-constexpr int kImputeMaxR = 16;          // components per pass (register budget), as recon_r2
 constexpr int kMaskMaxBlocks = 4096;     // workgroups of holdout_mask (grid stride beyond): its partial rows
 
 void launch_reduce_rows(const double* part, int nrows, int64_t P, double* out, hipStream_t st);
@@ -115,25 +114,9 @@ static int run_holdout_mask(const T* X, T* out, int64_t n, double fraction, uint
   return check_launch("holdout_mask");
 }
 
-// (b), (c): the (column tile, row block) grid of recon_r2 ---------------------------------------------------------------------
-static void impute_plan(int64_t I, int64_t P, int V, int* col_tiles, int* row_blocks, int64_t* rpb) {
-  *col_tiles = (int)(((P + V - 1) / V + kSweepThreads - 1) / kSweepThreads);
-  if (*col_tiles < 1) *col_tiles = 1;
-  const int64_t want = (2048 + *col_tiles - 1) / *col_tiles;
-  *rpb = (I + want - 1) / want;
-  if (*rpb < 8) *rpb = 8;
-  *row_blocks = (int)((I + *rpb - 1) / *rpb);
-}
-
+// (b), (c): the (column tile, row block) grid of model_cols.hpp -----------------------------------------------------------------
 static size_t impute_most_blocks(int64_t I, int64_t P) {
-  size_t most = 0;
-  for (int V = 1; V <= 4; V *= 2) {
-    int ct, rb;
-    int64_t rpb;
-    impute_plan(I, P, V, &ct, &rb, &rpb);
-    if ((size_t)ct * rb > most) most = (size_t)ct * rb;
-  }
-  return most;
+  return most_over_vector_widths(I, P, [](const ColTilePlan& pl) { return (size_t)pl.col_tiles * pl.row_blocks; });
 }
 
 // part[blk][0 .. R-1] = sum (x - xhat_r)^2, [R] = sum (x - mean)^2, [R + 1] = count, over the held-out finite entries of the
@@ -151,17 +134,11 @@ __global__ __launch_bounds__(kSweepThreads) void heldout_resid_kernel(const T* _
   const bool live = c < P;
   const int64_t i0 = (int64_t)blockIdx.y * rows_per_block;
   const int64_t i1 = (i0 + rows_per_block < I) ? i0 + rows_per_block : I;
-  double w[RC][V], mu[V], res[RC];
-  const int64_t cs = live ? c : 0;
-  const int j = (int)(cs / B), k = (int)(cs % B);          // B % V == 0 in the vector form: one j for the whole vector
+  double mu[V];
+  const ModelCols<RC, V> m(live ? c : 0, B, R, WA, WB, mean, mu);
+  double res[RC];
 #pragma unroll
-  for (int r = 0; r < RC; ++r) {
-    res[r] = 0.0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) w[r][e] = (r < R) ? WA[(int64_t)j * R + r] * WB[(int64_t)(k + e) * R + r] : 0.0;
-  }
-#pragma unroll
-  for (int e = 0; e < V; ++e) mu[e] = mean ? mean[cs + e] : 0.0;
+  for (int r = 0; r < RC; ++r) res[r] = 0.0;
   double base = 0.0, cnt = 0.0;
   if (live) {
     for (int64_t i = i0; i < i1; ++i) {
@@ -182,10 +159,9 @@ __global__ __launch_bounds__(kSweepThreads) void heldout_resid_kernel(const T* _
       }
 #pragma unroll
       for (int r = 0; r < RC; ++r) {
-        const double tr = (r < R) ? trow[r] : 0.0;          // uniform across the workgroup
+        m.add(r, (r < R) ? trow[r] : 0.0, acc);             // one component, then the prefix model's residual
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-          acc[e] = fma(tr, w[r][e], acc[e]);
           const double d = use[e] ? xv[e] - acc[e] : 0.0;
           res[r] = fma(d, d, res[r]);
         }
@@ -217,22 +193,19 @@ static int run_heldout_resid(const T* X, int64_t I, int A, int B, const double* 
     set_error("heldout_resid: bad argument");
     return CMTFPLS_EINVAL;
   }
-  if (R > kImputeMaxR) { set_error("heldout_resid: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
+  if (R > kModelMaxR) { set_error("heldout_resid: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
   const bool vec = (B % VecOf<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
   const int V = vec ? VecOf<T>::N : 1;
   const int64_t P = (int64_t)A * B;
-  int col_tiles, row_blocks;
-  int64_t rpb;
-  impute_plan(I, P, V, &col_tiles, &row_blocks, &rpb);
-  const size_t nblk = (size_t)col_tiles * row_blocks;
+  const ColTilePlan pl = col_tile_plan(I, P, V);
+  const size_t nblk = (size_t)pl.col_tiles * pl.row_blocks;
   if (!ws || ws_bytes < nblk * (R + 2) * sizeof(double)) { set_error("heldout_resid: workspace too small"); return CMTFPLS_EWORKSPACE; }
   double* part = static_cast<double*>(ws);
-  const dim3 grid(col_tiles, row_blocks), block(kSweepThreads);
-#define HK(RCC, VV) hipLaunchKernelGGL((heldout_resid_kernel<T, RCC, VV>), grid, block, 0, st, X, Tm, ldt, R, WA, WB, B, mean, I, P, (int)rpb, \
-                                       fraction, seed, stream, offset, part)
-  if (vec) { if (R <= 4) HK(4, true); else if (R <= 8) HK(8, true); else if (R <= 12) HK(12, true); else HK(16, true); }
-  else     { if (R <= 4) HK(4, false); else if (R <= 8) HK(8, false); else if (R <= 12) HK(12, false); else HK(16, false); }
-#undef HK
+  const dim3 grid(pl.col_tiles, pl.row_blocks), block(kSweepThreads);
+  dispatch_model(R, vec, [&](auto rcb, auto vb) {
+    hipLaunchKernelGGL((heldout_resid_kernel<T, decltype(rcb)::value, decltype(vb)::value>), grid, block, 0, st, X, Tm, ldt, R, WA, WB, B,
+                       mean, I, P, (int)pl.rpb, fraction, seed, stream, offset, part);
+  });
   launch_reduce_rows(part, (int)nblk, R + 2, out, st);
   return check_launch("heldout_resid");
 }
@@ -250,15 +223,8 @@ __global__ __launch_bounds__(kSweepThreads) void impute_kernel(const T* X, T* ou
   const bool live = c < P;
   const int64_t i0 = (int64_t)blockIdx.y * rows_per_block;
   const int64_t i1 = (i0 + rows_per_block < I) ? i0 + rows_per_block : I;
-  double w[RC][V], mu[V];
-  const int64_t cs = live ? c : 0;
-  const int j = (int)(cs / B), k = (int)(cs % B);
-#pragma unroll
-  for (int r = 0; r < RC; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) w[r][e] = (r < R) ? WA[(int64_t)j * R + r] * WB[(int64_t)(k + e) * R + r] : 0.0;
-#pragma unroll
-  for (int e = 0; e < V; ++e) mu[e] = mean ? mean[cs + e] : 0.0;
+  double mu[V];
+  const ModelCols<RC, V> m(live ? c : 0, B, R, WA, WB, mean, mu);
   double cnt = 0.0;
   if (live) {
     for (int64_t i = i0; i < i1; ++i) {
@@ -271,12 +237,7 @@ __global__ __launch_bounds__(kSweepThreads) void impute_kernel(const T* X, T* ou
         double acc[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = mu[e];
-#pragma unroll
-        for (int r = 0; r < RC; ++r) {
-          const double tr = (r < R) ? trow[r] : 0.0;
-#pragma unroll
-          for (int e = 0; e < V; ++e) acc[e] = fma(tr, w[r][e], acc[e]);
-        }
+        m.add_all(trow, R, acc);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           const bool fin = isfinite(x.e[e]);
@@ -295,25 +256,24 @@ template <typename T>
 static int run_impute(const T* X, T* out, int64_t I, int A, int B, const double* Tm, int ldt, int R, const double* WA, const double* WB,
                       const double* mean, double* count, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!X || !out || !Tm || !WA || !WB || !count || I <= 0 || R <= 0 || A <= 0 || B <= 0 || ldt < R) { set_error("impute: bad argument"); return CMTFPLS_EINVAL; }
-  if (R > kImputeMaxR) { set_error("impute: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
+  if (R > kModelMaxR) { set_error("impute: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
   const bool inplace = static_cast<const void*>(X) == static_cast<const void*>(out);
   if (!inplace && ranges_overlap(X, out, I * (int64_t)A * B)) { set_error("impute: out overlaps X without being X"); return CMTFPLS_EINVAL; }
   const bool vec = (B % VecOf<T>::N) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
   const int V = vec ? VecOf<T>::N : 1;
   const int64_t P = (int64_t)A * B;
-  int col_tiles, row_blocks;
-  int64_t rpb;
-  impute_plan(I, P, V, &col_tiles, &row_blocks, &rpb);
-  const size_t nblk = (size_t)col_tiles * row_blocks;
+  const ColTilePlan pl = col_tile_plan(I, P, V);
+  const size_t nblk = (size_t)pl.col_tiles * pl.row_blocks;
   if (!ws || ws_bytes < nblk * sizeof(double)) { set_error("impute: workspace too small"); return CMTFPLS_EWORKSPACE; }
   double* part = static_cast<double*>(ws);
-  const dim3 grid(col_tiles, row_blocks), block(kSweepThreads);
-#define IK(RCC, VV, IP) hipLaunchKernelGGL((impute_kernel<T, RCC, VV, IP>), grid, block, 0, st, X, out, Tm, ldt, R, WA, WB, B, mean, I, P, (int)rpb, part)
-#define IKR(VV, IP) do { if (R <= 4) IK(4, VV, IP); else if (R <= 8) IK(8, VV, IP); else if (R <= 12) IK(12, VV, IP); else IK(16, VV, IP); } while (0)
-  if (vec) { if (inplace) IKR(true, true); else IKR(true, false); }
-  else     { if (inplace) IKR(false, true); else IKR(false, false); }
-#undef IKR
-#undef IK
+  const dim3 grid(pl.col_tiles, pl.row_blocks), block(kSweepThreads);
+  dispatch_model(R, vec, [&](auto rcb, auto vb) {
+    constexpr int RC = decltype(rcb)::value;
+    constexpr bool VEC = decltype(vb)::value;
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, X, out, Tm, ldt, R, WA, WB, B, mean, I, P, (int)pl.rpb, part); };
+    if (inplace) launch(impute_kernel<T, RC, VEC, true>);
+    else         launch(impute_kernel<T, RC, VEC, false>);
+  });
   launch_reduce_rows(part, (int)nblk, 1, count, st);
   return check_launch("impute");
 }

@@ -1,29 +1,21 @@
 // Per-row and per-column residual sums of the model reconstruction, for the sample diagnostics (validate.sample_diagnostics):
 //   e[i, c] = x - xhat,  x = X[i, c] - mean[c],  xhat = sum_r T[i, r] WA[c / B, r] WB[c % B, r]
 //   rows[i] = (sum_c e^2, sum_c x^2, #finite x)      cols[c] = (sum_i e^2, sum_i x^2)       (entries with x not finite skipped)
-// in ONE read of the uncentred X, the reconstruction never materialised.  Same thread layout as recon_r2_kernel (recon.hip):
-// column tiles x row blocks, a thread owns V consecutive columns (16-bit storage: 4, one 8-byte load, f32's mapping: DiagVec) and keeps their R loading products in registers across the
-// rows of its row block.  The column sums stay in the thread's registers; a row sum is a wavefront total (DPP within the
+// in ONE read of the uncentred X, the reconstruction never materialised.  The column-tile layout of model_cols.hpp; V is DiagVec's
+// (16-bit storage: 4 columns, one 8-byte load, f32's mapping).  The thread's loading products and their fma loop are ModelCols'
+// written out in the kernel: through the struct the f64 vector forms without column sums took more registers (R <= 8: 82 for 75,
+// R <= 12: 102 for 91) and each lost a wave per SIMD.  The column sums stay in the thread's registers; a row sum is a wavefront total (DPP within the
 // 16-lane rows, four lane reads across them), parked in the lane numbered after the row and combined over the four
 // wavefronts every 64 rows through LDS into one partial per (column tile, row).  Two small fixed-order reduces close the
 // partials: no atomics, no waiting between workgroups, the same bits on every call.
-#include "common.hpp"
+#include "model_cols.hpp"
 
 namespace cmtfpls {
 
-constexpr int kResidMaxR = 16;       // components held in registers (as recon_r2)
 constexpr int kResidWaves = kSweepThreads / kWave;
 constexpr int kResidUnroll = 4;     // rows whose loads are issued together (divides 64)
 
 void launch_reduce_rows(const double* part, int nrows, int64_t P, double* out, hipStream_t st);
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
 
 __device__ __forceinline__ double lane_read(double v, int lane) {
   const long long b = __double_as_longlong(v);
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(kSweepThreads) void resid_rows_kernel(const T* __re
   const int64_t cs = live ? c : 0;                       // dead lanes read column 0 and add nothing: every lane joins the row totals
   const int64_t i0 = (int64_t)blockIdx.y * rows_per_block;
   const int64_t i1 = (i0 + rows_per_block < I) ? i0 + rows_per_block : I;
-  double w[RC][V], mu[V];
+  double w[RC][V], mu[V];                                // ModelCols, written out (see the head of the file)
   const int j = (int)(cs / B), k = (int)(cs % B);        // B % V == 0: one j for the whole vector
 #pragma unroll
   for (int r = 0; r < RC; ++r)
@@ -133,46 +125,32 @@ __global__ __launch_bounds__(kSweepThreads) void resid_rows_kernel(const T* __re
   }
 }
 
-static void resid_plan(int64_t I, int64_t P, int V, int* col_tiles, int* row_blocks, int64_t* rpb) {
-  *col_tiles = (int)(((P + V - 1) / V + kSweepThreads - 1) / kSweepThreads);
-  if (*col_tiles < 1) *col_tiles = 1;
-  const int64_t want = (2048 + *col_tiles - 1) / *col_tiles;      // ~2048 workgroups, as recon_r2
-  *rpb = (I + want - 1) / want;
-  if (*rpb < 8) *rpb = 8;
-  *row_blocks = (int)((I + *rpb - 1) / *rpb);
-}
-
-static size_t resid_ws(int64_t I, int64_t P, int V) {
-  int ct, rb;
-  int64_t rpb;
-  resid_plan(I, P, V, &ct, &rb, &rpb);
-  return ((size_t)ct * I * 3 + (size_t)rb * P * 2) * sizeof(double);
+static size_t resid_ws(int64_t I, int64_t P, const ColTilePlan& pl) {
+  return ((size_t)pl.col_tiles * I * 3 + (size_t)pl.row_blocks * P * 2) * sizeof(double);
 }
 
 template <typename T>
 static int run_resid_rows(const T* X, const double* Tm, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
                           const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!X || !Tm || !WA || !WB || !rows || I <= 0 || R <= 0 || A <= 0 || B <= 0 || ldt < R) { set_error("resid_rows: bad argument"); return CMTFPLS_EINVAL; }
-  if (R > kResidMaxR) { set_error("resid_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
+  if (R > kModelMaxR) { set_error("resid_rows: more than 16 components"); return CMTFPLS_EUNSUPPORTED; }
   const bool vec = (B % DiagVec<T>::N) == 0 && (reinterpret_cast<uintptr_t>(X) & DiagVec<T>::kAlignMask) == 0;
   const int V = vec ? DiagVec<T>::N : 1;
   const int64_t P = (int64_t)A * B;
-  int col_tiles, row_blocks;
-  int64_t rpb;
-  resid_plan(I, P, V, &col_tiles, &row_blocks, &rpb);
-  if (!ws || ws_bytes < resid_ws(I, P, V)) { set_error("resid_rows: workspace too small"); return CMTFPLS_EWORKSPACE; }
+  const ColTilePlan pl = col_tile_plan(I, P, V);
+  if (!ws || ws_bytes < resid_ws(I, P, pl)) { set_error("resid_rows: workspace too small"); return CMTFPLS_EWORKSPACE; }
   double* rpart = static_cast<double*>(ws);
-  double* cpart = rpart + (size_t)col_tiles * I * 3;
-  const dim3 grid(col_tiles, row_blocks), block(kSweepThreads);
-#define RRK(RCC, VV, CC) hipLaunchKernelGGL((resid_rows_kernel<T, RCC, VV, CC>), grid, block, 0, st, X, Tm, ldt, R, WA, WB, B, mean, I, P, \
-                                            (int)rpb, rpart, cpart)
-#define RRV(VV, CC) do { if (R <= 4) RRK(4, VV, CC); else if (R <= 8) RRK(8, VV, CC); else if (R <= 12) RRK(12, VV, CC); else RRK(16, VV, CC); } while (0)
-  if (cols) { if (vec) RRV(true, true); else RRV(false, true); }
-  else      { if (vec) RRV(true, false); else RRV(false, false); }
-#undef RRV
-#undef RRK
-  launch_reduce_rows(rpart, col_tiles, I * 3, rows, st);
-  if (cols) launch_reduce_rows(cpart, row_blocks, P * 2, cols, st);
+  double* cpart = rpart + (size_t)pl.col_tiles * I * 3;
+  const dim3 grid(pl.col_tiles, pl.row_blocks), block(kSweepThreads);
+  dispatch_model(R, vec, [&](auto rcb, auto vb) {
+    constexpr int RC = decltype(rcb)::value;
+    constexpr bool VEC = decltype(vb)::value;
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, X, Tm, ldt, R, WA, WB, B, mean, I, P, (int)pl.rpb, rpart, cpart); };
+    if (cols) launch(resid_rows_kernel<T, RC, VEC, true>);
+    else      launch(resid_rows_kernel<T, RC, VEC, false>);
+  });
+  launch_reduce_rows(rpart, pl.col_tiles, I * 3, rows, st);
+  if (cols) launch_reduce_rows(cpart, pl.row_blocks, P * 2, cols, st);
   return check_launch("resid_rows");
 }
 
@@ -183,12 +161,7 @@ using namespace cmtfpls;
 extern "C" {
 size_t cmtfpls_resid_rows_workspace_bytes(int64_t I, int64_t P) {
   if (I <= 0 || P <= 0) return 0;
-  size_t most = 0;
-  for (int V = 1; V <= 4; V *= 2) {
-    const size_t nb = resid_ws(I, P, V);
-    if (nb > most) most = nb;
-  }
-  return most;
+  return most_over_vector_widths(I, P, [&](const ColTilePlan& pl) { return resid_ws(I, P, pl); });
 }
 int cmtfpls_resid_rows_f32(const float* X, const double* T, int64_t I, int ldt, int R, const double* WA, const double* WB, int A, int B,
                            const double* mean, double* rows, double* cols, void* ws, size_t ws_bytes, void* stream) {

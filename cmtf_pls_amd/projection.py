@@ -280,39 +280,61 @@ class ProjectionMixin:
         None), x = X - mean over the finite entries (the calcR2X mask, util.py:7-15), e = x - T W_b^T.  One read of every
         block through cmtfpls_resid_rows_*; where the backend declines (R > 16, no such kernel, device=False) the same sums
         from torch ops on row blocks of <= 256 MB.  `last_residual` records, per block, the form that ran and why."""
-        be = self.be
+        out, self.last_residual = self._stream_blocks(
+            state, Xs, "resid_rows", "residual pass (cmtfpls_resid_rows)", device,
+            kernel=lambda blk, X2, WA, WB, b: self.be.resid_rows(X2, T, WA, WB, blk.mean, want_cols),
+            fallback=lambda blk, X2, WA, WB, b: self._residual_rows_torch(X2, T, WA, WB, blk.mean, want_cols),
+            declined=lambda blk: f"R = {state.n_components} > 16: outside cmtfpls_resid_rows")
+        return out
+
+    def _stream_blocks(self, state: FitState, Xs: List[torch.Tensor], entry: str, form: str, device: bool, kernel, fallback,
+                       declined=None, as_stored: bool = False, operands: bool = True, rows: Optional[int] = None):
+        """The per-block loop of the streaming passes: (results, per-block {"form", "why"} records).  Block b as X2 (I, P) goes to
+        `kernel(blk, X2, WA, WB, b)`, the backend's `entry`, unless `_streaming_form` rules it out or there is no row (`rows`, default
+        I); a None from it is recorded as `declined(blk)`.  What the kernel did not do, `fallback(blk, X2, WA, WB, b)` does in torch ops.
+        as_stored: the pass depends on the block's element order (the hold-out rule, a write in place), so the block must be
+        contiguous (`view` raises otherwise), the operands are made contiguous and the fallback reads the stored block; otherwise any
+        strides go (`reshape`) and the fallback reads `_fallback_block`.  operands False: a pass without loadings (WA = WB = None)."""
         R = state.n_components
         out, forms = [], []
         with self.device_ctx():
-            for blk, X in zip(state.blocks, Xs):
+            for b, (blk, X) in enumerate(zip(state.blocks, Xs)):
                 I = X.shape[0]
-                X2 = X.reshape(I, -1)
-                WA, WB = self._kr_operands(blk, R)
-                res, why = None, None
-                if not device:
-                    why = "device pass switched off"
-                elif not hasattr(be, "resid_rows"):
-                    why = "backend has no resid_rows kernel"
-                elif I > 0:
-                    res = be.resid_rows(X2, T, WA, WB, blk.mean, want_cols)
-                    if res is None:
-                        why = f"R = {R} > 16: outside cmtfpls_resid_rows"
+                X2 = X.view(I, -1) if as_stored else X.reshape(I, -1)
+                WA, WB = self._kr_operands(blk, R) if operands else (None, None)
+                if as_stored:
+                    WA, WB = WA.contiguous(), WB.contiguous()
+                why = self._streaming_form(entry, device)
+                res = None
+                if why is None and (I if rows is None else rows) > 0:
+                    res = kernel(blk, X2, WA, WB, b)
+                    if res is None and declined is not None:
+                        why = declined(blk)
                 if res is None:
-                    res = self._residual_rows_torch(self._fallback_block(X2), T, WA, WB, blk.mean, want_cols)
+                    res = fallback(blk, X2 if as_stored else self._fallback_block(X2), WA, WB, b)
                 out.append(res)
-                forms.append({"form": "torch fallback" if why else "residual pass (cmtfpls_resid_rows)", "why": why})
-        self.last_residual = forms
-        return out
+                forms.append({"form": "torch fallback" if why else form, "why": why})
+        return out, forms
 
     @staticmethod
-    def _residual_rows_torch(X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+    def _kr_dense(WA: torch.Tensor, WB: torch.Tensor, P: int) -> torch.Tensor:
+        """W (P, R) of `_kr_operands`, materialised: for the torch fallbacks."""
+        return (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+
+    @staticmethod
+    def _row_step(P: int) -> int:
+        """Rows of a fallback's row block: <= 256 MB of float64."""
+        return max(1, (256 << 20) // max(P * 8, 1))
+
+    @classmethod
+    def _residual_rows_torch(cls, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
                              want_cols: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         I, P = X2.shape
         dev = T.device
-        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        W = cls._kr_dense(WA, WB, P)
         rows = torch.empty(I, 3, dtype=torch.float64, device=dev)
         cols = torch.zeros(P, 2, dtype=torch.float64, device=dev) if want_cols else None
-        step = max(1, (256 << 20) // max(P * 8, 1))
+        step = cls._row_step(P)
         for r0 in range(0, I, step):
             x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
             if mean is not None:
@@ -337,35 +359,26 @@ class ProjectionMixin:
         the rows of block b complete: o = 1, d is None (it is sum_i tau^2 for every column) and a missing value shows as a NaN.
         One read of every block through cmtfpls_selectivity_cols_*; where the backend has no such kernel, and for device=False,
         the same sums from torch ops on row blocks of <= 256 MB.  `last_selectivity` records, per block, the form and why."""
-        be = self.be
-        out, forms = [], []
         flags = [bool(blk.has_miss) for blk in state.blocks] if masked is None else [bool(f) for f in masked]
         with self.device_ctx():
             if Tau.stride(1) != 1:
                 Tau = Tau.contiguous()
-            for blk, X, msk in zip(state.blocks, Xs, flags):
-                I = X.shape[0]
-                X2 = X.reshape(I, -1)
-                why = self._streaming_form("selectivity_cols", device)
-                if why is None and I > 0:
-                    res = be.selectivity_cols(X2, Tau, blk.mean, msk)
-                else:
-                    res = self._selectivity_cols_torch(self._fallback_block(X2), Tau, blk.mean, msk)
-                out.append(res)
-                forms.append({"form": "torch fallback" if why else "selectivity pass (cmtfpls_selectivity_cols)", "why": why,
-                              "masked": msk})
-        self.last_selectivity = forms
+            out, forms = self._stream_blocks(
+                state, Xs, "selectivity_cols", "selectivity pass (cmtfpls_selectivity_cols)", device, operands=False,
+                kernel=lambda blk, X2, WA, WB, b: self.be.selectivity_cols(X2, Tau, blk.mean, flags[b]),
+                fallback=lambda blk, X2, WA, WB, b: self._selectivity_cols_torch(X2, Tau, blk.mean, flags[b]))
+        self.last_selectivity = [dict(f, masked=msk) for f, msk in zip(forms, flags)]
         return out
 
-    @staticmethod
-    def _selectivity_cols_torch(X2: torch.Tensor, Tau: torch.Tensor, mean: Optional[torch.Tensor], masked: bool):
+    @classmethod
+    def _selectivity_cols_torch(cls, X2: torch.Tensor, Tau: torch.Tensor, mean: Optional[torch.Tensor], masked: bool):
         I, P = X2.shape
         M = Tau.shape[1]
         dev = Tau.device
         a = torch.zeros(M, P, dtype=torch.float64, device=dev)
         d = torch.zeros(M, P, dtype=torch.float64, device=dev) if masked else None
         s, n = (torch.zeros(P, dtype=torch.float64, device=dev) for _ in range(2))
-        step = max(1, (256 << 20) // max(P * 8, 1))
+        step = cls._row_step(P)
         for r0 in range(0, I, step):
             x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
             tau = Tau[r0:r0 + step]
@@ -399,36 +412,27 @@ class ProjectionMixin:
         cmtfpls_impute_* (in place: only the vectors that held a gap are written); where the backend declines (R > 16, no such
         kernel, device=False) the same from torch ops on row blocks of <= 256 MB.  `last_imputation` records, per block, the form
         that ran and why."""
-        be = self.be
-        R = state.n_components
-        out, forms = [], []
         flags = [bool(inplace)] * len(Xs) if isinstance(inplace, bool) else [bool(f) for f in inplace]
-        with self.device_ctx():
-            for blk, X, own in zip(state.blocks, Xs, flags):
-                I = X.shape[0]
-                X2 = X.view(I, -1)
-                WA, WB = (w.contiguous() for w in self._kr_operands(blk, R))
-                dst = X2 if own else torch.empty_like(X2)
-                why = self._streaming_form("impute", device)
-                count = None
-                if why is None and I > 0:
-                    count = be.impute(X2, dst, T, WA, WB, blk.mean)
-                    if count is None:
-                        why = f"R = {R} > 16: outside cmtfpls_impute"
-                if count is None:
-                    count = self._impute_rows_torch(X2, dst, T, WA, WB, blk.mean)
-                out.append((dst.view(X.shape), int(round(float(count.item())))))
-                forms.append({"form": "torch fallback" if why else "imputation pass (cmtfpls_impute)", "why": why})
-        self.last_imputation = forms
-        return out
 
-    @staticmethod
-    def _impute_rows_torch(X2: torch.Tensor, dst: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+        def complete(step, blk, X2, WA, WB, b):            # a declining kernel has not touched dst
+            dst = X2 if flags[b] else torch.empty_like(X2)
+            count = step(X2, dst, T, WA, WB, blk.mean)
+            return None if count is None else (dst, count)
+
+        done, self.last_imputation = self._stream_blocks(
+            state, Xs, "impute", "imputation pass (cmtfpls_impute)", device, as_stored=True,
+            kernel=lambda *block: complete(self.be.impute, *block),
+            fallback=lambda *block: complete(self._impute_rows_torch, *block),
+            declined=lambda blk: f"R = {state.n_components} > 16: outside cmtfpls_impute")
+        return [(dst.view(X.shape), int(round(float(count.item())))) for X, (dst, count) in zip(Xs, done)]
+
+    @classmethod
+    def _impute_rows_torch(cls, X2: torch.Tensor, dst: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
                            mean: Optional[torch.Tensor]) -> torch.Tensor:
         I, P = X2.shape
-        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        W = cls._kr_dense(WA, WB, P)
         count = torch.zeros(1, dtype=torch.float64, device=T.device)
-        step = max(1, (256 << 20) // max(P * 8, 1))
+        step = cls._row_step(P)
         for r0 in range(0, I, step):
             x = X2[r0:r0 + step]
             gap = ~torch.isfinite(x)
@@ -471,39 +475,27 @@ class ProjectionMixin:
         One read of every block through cmtfpls_heldout_resid_*, no mask tensor; where the backend declines (R > 16, no such
         kernel, device=False) the same sums from torch ops on row blocks of <= 256 MB with the mask of the host restatement.
         `last_heldout` records, per block, the form that ran and why."""
-        be = self.be
-        R = state.n_components
-        out, forms = [], []
-        with self.device_ctx():
-            for b, (blk, X) in enumerate(zip(state.blocks, Xs)):
-                I = X.shape[0]
-                X2 = X.view(I, -1)
-                off = int(offsets[b]) if offsets is not None else 0
-                WA, WB = (w.contiguous() for w in self._kr_operands(blk, R))
-                why = self._streaming_form("heldout_resid", device)
-                res = None
-                if why is None and I > 0:
-                    res = be.heldout_resid(X2, T, WA, WB, blk.mean, fraction, seed, 2 + b, off)
-                    if res is None:
-                        why = f"R = {R} > 16: outside cmtfpls_heldout_resid"
-                if res is None:
-                    res = self._heldout_sums_torch(X2, T, WA, WB, blk.mean, fraction, seed, 2 + b, off)
-                out.append(res)
-                forms.append({"form": "torch fallback" if why else "held-out residual pass (cmtfpls_heldout_resid)", "why": why})
-        self.last_heldout = forms
+        def sums(step, blk, X2, WA, WB, b):
+            return step(X2, T, WA, WB, blk.mean, fraction, seed, 2 + b, int(offsets[b]) if offsets is not None else 0)
+
+        out, self.last_heldout = self._stream_blocks(
+            state, Xs, "heldout_resid", "held-out residual pass (cmtfpls_heldout_resid)", device, as_stored=True,
+            kernel=lambda *block: sums(self.be.heldout_resid, *block),
+            fallback=lambda *block: sums(self._heldout_sums_torch, *block),
+            declined=lambda blk: f"R = {state.n_components} > 16: outside cmtfpls_heldout_resid")
         return out
 
-    @staticmethod
-    def _heldout_sums_torch(X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
+    @classmethod
+    def _heldout_sums_torch(cls, X2: torch.Tensor, T: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor, mean: Optional[torch.Tensor],
                             fraction: float, seed: int, stream: int, offset: int) -> torch.Tensor:
         from .imputation import holdout_mask_host
 
         I, P = X2.shape
         R = T.shape[1]
         dev = T.device
-        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        W = cls._kr_dense(WA, WB, P)
         out = torch.zeros(R + 2, dtype=torch.float64, device=dev)
-        step = max(1, (256 << 20) // max(P * 8, 1))
+        step = cls._row_step(P)
         for r0 in range(0, I, step):
             x = X2[r0:r0 + step].to(device=dev, dtype=torch.float64)
             held = torch.from_numpy(holdout_mask_host(offset + r0 * P, x.numel(), seed, stream, fraction)).to(dev).view(x.shape)
@@ -526,37 +518,21 @@ class ProjectionMixin:
         None: row i); only those rows of Xs[b] (device, storage type, UNCENTRED, read only) are read, once, through
         cmtfpls_contrib_rows_*.  Where the backend declines (R > 16, loadings beyond the LDS, no such kernel, device=False) the same
         sums from torch ops on row blocks of <= 256 MB.  `last_contribution` records, per block, the form that ran and why."""
-        be = self.be
         R = state.n_components
-        out, forms = [], []
-        with self.device_ctx():
-            for blk, X in zip(state.blocks, Xs):
-                X2 = X.reshape(X.shape[0], -1)
-                WA, WB = self._kr_operands(blk, R)
-                res, why = None, None
-                if not device:
-                    why = "device pass switched off"
-                elif not hasattr(be, "contrib_rows"):
-                    why = "backend has no contrib_rows kernel"
-                elif T.shape[0] > 0:
-                    res = be.contrib_rows(X2, T, H, WA.contiguous(), WB.contiguous(), blk.mean, rows)
-                    if res is None:
-                        why = (f"R = {R} > 16: outside cmtfpls_contrib_rows" if R > 16 else
-                               f"first mode of {blk.A} slices x R = {R}: 2 A (R + 1) doubles beyond the LDS of cmtfpls_contrib_rows")
-                if res is None:
-                    res = self._contribution_rows_torch(self._fallback_block(X2), T, H, WA, WB, blk.mean, rows)
-                out.append(res)
-                forms.append({"form": "torch fallback" if why else "contribution pass (cmtfpls_contrib_rows)", "why": why})
-        self.last_contribution = forms
+        out, self.last_contribution = self._stream_blocks(
+            state, Xs, "contrib_rows", "contribution pass (cmtfpls_contrib_rows)", device, rows=T.shape[0],
+            kernel=lambda blk, X2, WA, WB, b: self.be.contrib_rows(X2, T, H, WA.contiguous(), WB.contiguous(), blk.mean, rows),
+            fallback=lambda blk, X2, WA, WB, b: self._contribution_rows_torch(X2, T, H, WA, WB, blk.mean, rows),
+            declined=lambda blk: (f"R = {R} > 16: outside cmtfpls_contrib_rows" if R > 16 else
+                                  f"first mode of {blk.A} slices x R = {R}: 2 A (R + 1) doubles beyond the LDS of cmtfpls_contrib_rows"))
         return out
 
-    @staticmethod
-    def contribution_cells(X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
+    @classmethod
+    def contribution_cells(cls, X2: torch.Tensor, T: torch.Tensor, H: torch.Tensor, WA: torch.Tensor, WB: torch.Tensor,
                            mean: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """(e, d), both (n, P) float64: the signed residual and the T^2 contribution of every cell of the rows X2 (0 where
         x = X2 - mean is not finite), W materialised.  For a handful of rows; the callers bound n * P."""
-        P = X2.shape[1]
-        W = (WA[:, None, :] * WB[None, :, :]).reshape(P, -1)
+        W = cls._kr_dense(WA, WB, X2.shape[1])
         x = X2.to(device=T.device, dtype=torch.float64)
         if mean is not None:
             x = x - mean
@@ -573,7 +549,7 @@ class ProjectionMixin:
         dev = T.device
         speB, t2B = (torch.empty(n, B, dtype=torch.float64, device=dev) for _ in range(2))
         speA, t2A = (torch.empty(n, A, dtype=torch.float64, device=dev) for _ in range(2)) if A > 1 else (None, None)
-        step = max(1, (256 << 20) // max(P * 8, 1))
+        step = cls._row_step(P)
         for r0 in range(0, n, step):
             sl = slice(r0, r0 + step)
             e, d = cls.contribution_cells(X2[sl] if rows is None else X2.index_select(0, rows[sl].to(X2.device)), T[sl], H[sl], WA, WB, mean)

@@ -389,12 +389,13 @@ def test_predict_with_513_responses_falls_back_to_the_host(api, monkeypatch):
 
 # ---- E. recon ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [F32, F64])
-@pytest.mark.parametrize("R", [16, 17, 32, 33])
+@pytest.mark.parametrize("R", [5, 9, 13, 16, 17, 32, 33])
 @pytest.mark.parametrize("form", ["vector", "B % V", "misaligned", "one row"])
 def test_recon_matches_float64(be, dtype, R, form):
     """Xhat = T (WA (.) WB)^T + mean in the storage type: one pass for R <= 16, then accumulate passes of 16.  f32 rounds the
     partial sum to f32 between passes, so its bound is passes x 2^-24 x (|mean| + sum_r |t_r w_r|) per element; f64 1e-14
-    of the same magnitude."""
+    of the same magnitude.  R = 5, 9, 13 are the first of the 8, 12 and 16 component instances (17 and 33 end in the one of 4):
+    a bracket chosen one too low drops a component."""
     A, B = (6, 9) if form == "B % V" else (6, 64)
     I = 1 if form == "one row" else 37
     rng = np.random.default_rng(R)
