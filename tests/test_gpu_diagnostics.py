@@ -41,15 +41,39 @@ def _operands(I, A, B, R, dtype, seed, offset=0, nan_frac=0.0):
     return X2, T, WA, WB, mean
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("I,A,B,R,offset,nan", [
+RESID_KERNEL_CASES = [
     (1, 3, 8, 1, 0, 0.0),                  # one row
     (5000, 4, 12, 10, 0, 0.1),             # many row blocks, missing values
     (300, 5, 7, 16, 0, 0.0),               # B % 4 != 0: one element per thread
     (257, 6, 8, 10, 1, 0.05),              # a view one element into its storage: misaligned base
     (64, 1, 1030, 10, 0, 0.0),             # a matrix block, columns past a whole tile
     (3000, 8, 160, 10, 0, 0.02),           # two column tiles, the second part dead lanes
-])
+    # the shapes of tests/test_gpu_workspace_contract.py, each at R = 1, 5 and 16: B % 4 != 0 with 65 row blocks and a short last
+    # one; the vector form, also misaligned; P = 1320: five column tiles and a partial one
+    (517, 7, 9, 1, 0, 0.1), (517, 7, 9, 5, 0, 0.1), (517, 7, 9, 16, 0, 0.1),
+    (517, 12, 20, 1, 0, 0.1), (517, 12, 20, 5, 0, 0.1), (517, 12, 20, 16, 0, 0.1),
+    (517, 12, 20, 1, 1, 0.1), (517, 12, 20, 5, 1, 0.1), (517, 12, 20, 16, 1, 0.1),
+    (2100, 33, 40, 1, 0, 0.1), (2100, 33, 40, 5, 0, 0.1), (2100, 33, 40, 16, 0, 0.1),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("I,A,B,R,offset,nan", RESID_KERNEL_CASES)
+def test_recon_r2_kernel_against_formula(dtype, I, A, B, R, offset, nan):
+    """cmtfpls_recon_r2_*: calcR2X's two sums are the column sums of resid_rows' first two columns (sums of non-negative terms)."""
+    be = HipBackend()
+    X2, T, WA, WB, mean = _operands(I, A, B, R, dtype, seed=I + R, offset=offset, nan_frac=nan)
+    before = X2.clone()
+    got = be.recon_r2(X2, T, WA, WB, mean)
+    want_r, _ = _formula(X2, T, WA, WB, mean)
+    torch.testing.assert_close(got, want_r[:, :2].sum(0), rtol=1e-11, atol=1e-9)
+    assert torch.equal(got, be.recon_r2(X2, T, WA, WB, mean))                             # deterministic: the same bits
+    bits = torch.int32 if dtype == torch.float32 else torch.int64
+    assert torch.equal(X2.view(bits), before.view(bits))                                   # read only
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("I,A,B,R,offset,nan", RESID_KERNEL_CASES)
 def test_resid_rows_kernel_against_formula(dtype, I, A, B, R, offset, nan):
     be = HipBackend()
     X2, T, WA, WB, mean = _operands(I, A, B, R, dtype, seed=I + R, offset=offset, nan_frac=nan)

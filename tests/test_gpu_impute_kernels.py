@@ -19,7 +19,15 @@ SHAPES = [
     ("two_column_tiles", 19, 40, 32, (40, 32), 0),
     ("matrix_many_row_blocks", 20003, 1, 8, (8,), 0),
     ("order4_kronecker", 21, 4, 24, (4, 3, 8), 0),
+    # the shapes of tests/test_gpu_workspace_contract.py: scalar and vector rows over several row blocks with a short last one
+    ("scalar_row_blocks", 517, 7, 9, (7, 9), 0),
+    ("vector_row_blocks", 517, 12, 20, (12, 20), 0),
+    ("vector_row_blocks_misaligned_base", 517, 12, 20, (12, 20), 1),
 ]
+# P = 1320: five column tiles and a partial one.  Run at R = 1, 5, 16 with one fraction and offset (the NumPy restatement of the
+# hold-out sums takes seconds at this size)
+TILED_SHAPES = [("column_tiles_and_a_partial_one", 2100, 33, 40, (33, 40), 0)]
+FLAT_SIZES = [3, 1021, 300001]             # holdout_mask on a flat tensor: below one vector, a tail of one, many workgroups
 RS = [1, 4, 5, 12, 16]
 FRACTIONS = [0.1, 0.5]
 OFFSETS = [0, 4099]
@@ -165,6 +173,47 @@ def test_impute(be, shape, dt):
         count3 = be.impute(Xi, Xi, Td, WAd, WBd, md)
         assert np.array_equal(_bits(Xi, dt), _bits(out, dt)) and torch.equal(count3, count) and _guards_intact(ibuf, shift, X.size)
     print(f"impute {shape[0]} {dt}: worst error / bound = {worst:.3g}")
+
+
+@pytest.mark.parametrize("R", [1, 5, 16])
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+@pytest.mark.parametrize("shape", TILED_SHAPES, ids=[s[0] for s in TILED_SHAPES])
+def test_heldout_resid_and_impute_across_column_tiles(be, shape, dt, R):
+    dev = be.device
+    X, T, WA, WB, mean = _case(shape, dt, R)
+    xbuf, Xd = _guarded(X, 0, dev)
+    before = _bits(xbuf, dt).copy()
+    Td, WAd, WBd, md = _scores(T, dev), torch.from_numpy(WA).to(dev), torch.from_numpy(WB).to(dev), torch.from_numpy(mean).to(dev)
+    got = be.heldout_resid(Xd, Td, WAd, WBd, md, 0.5, 991, 2, 4099)
+    assert got is not None and torch.equal(got, be.heldout_resid(Xd, Td, WAd, WBd, md, 0.5, 991, 2, 4099))
+    want, bound = ref.heldout_sums(X, T, WA, WB, mean, 0.5, 991, block=0, offset=4099)
+    g = got.cpu().numpy()
+    assert g[R + 1] == want[R + 1] and want[R + 1] > 0
+    assert np.abs(g[:R + 1] - want[:R + 1]).max() <= bound
+    obuf, out = _guarded(np.zeros_like(X), 0, dev)
+    count = be.impute(Xd, out, Td, WAd, WBd, md)
+    wantx, gap, tol = ref.imputed(X, T, WA, WB, mean)
+    assert count is not None and count.item() == float(gap.sum())
+    assert _guards_intact(obuf, 0, X.size) and np.array_equal(_bits(xbuf, dt), before)
+    assert np.array_equal(_bits(out, dt)[~gap], X.view(_DT[dt][2])[~gap])                           # observed: bit for bit
+    assert (np.abs(out.cpu().numpy().astype(np.float64) - wantx)[gap] <= tol[gap]).all()
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+@pytest.mark.parametrize("n", FLAT_SIZES)
+def test_holdout_mask_of_a_flat_tensor(be, n, dt, shift):
+    X = np.random.default_rng(n).normal(size=n).astype(_DT[dt][1])
+    X[np.random.default_rng(n + 1).random(n) < 0.2] = np.nan
+    xbuf, Xd = _guarded(X, shift, be.device)
+    before = _bits(xbuf, dt).copy()
+    obuf, out = _guarded(np.zeros_like(X), shift, be.device)
+    counts = be.holdout_mask(Xd, out, 0.5, 215, 3, 4099)
+    want, wcounts = ref.masked_copy(X, 0.5, 215, block=1, offset=4099)
+    keep = ~np.isnan(want)
+    assert np.array_equal(np.isnan(out.cpu().numpy()), ~keep) and np.array_equal(_bits(out, dt)[keep], want.view(_DT[dt][2])[keep])
+    assert counts.cpu().tolist() == [float(c) for c in wcounts]
+    assert _guards_intact(obuf, shift, X.size) and np.array_equal(_bits(xbuf, dt), before)
 
 
 @pytest.mark.parametrize("dt", ["f32", "f64"])

@@ -386,7 +386,8 @@ def test_kron(be):
 @pytest.mark.parametrize("dt", ["f32", "f64"])
 @pytest.mark.parametrize("masked", [False, True])
 @pytest.mark.parametrize("shape,M", [((37, 10, 8), 4), ((100, 38, 65), 3), ((64, 1, 20), 16), ((300, 16, 16), 17),
-                                     ((130, 128, 128), 16), ((257, 24, 12), 33), ((70, 8, 8), 64), ((1000, 16, 16), 16)])
+                                     ((130, 128, 128), 16), ((257, 24, 12), 33), ((70, 8, 8), 64), ((1000, 16, 16), 16),
+                                     ((37, 10, 8), 70)])                     # more than 64 responses: two tiles of 64, the second ragged
 def test_xcov_mfma(be, shape, M, dt, masked):
     """S = Y^T X_(0) on the f64 matrix cores against NumPy float64 (operand layout of
     v_mfma_f64_16x16x4_f64 checked with asymmetric random data, every M-tile count, ragged rows/cols)."""

@@ -663,7 +663,8 @@ def test_xcov_pipelined_inner_loop_for_coupled_and_masked_blocks(api, monkeypatc
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("I,P,M", [(4096, 16384, 16), (1000, 4096, 32), (777, 1000, 5), (130, 514, 48), (64, 256, 1)])
+@pytest.mark.parametrize("I,P,M", [(4096, 16384, 16), (1000, 4096, 32), (777, 1000, 5), (130, 514, 48), (64, 256, 1),
+                                   (257, 288, 33), (300, 256, 17), (70, 64, 64), (37, 80, 4)])      # the shapes of test_gpu_kernels.py::test_xcov_mfma
 def test_xcov_ssq_kernel_gives_s_and_the_centred_norm_from_one_read(be, dtype, I, P, M):
     rng = np.random.default_rng(I + P + M)
     x = rng.normal(size=(I, P)) * rng.uniform(0.5, 2.0, size=P) + rng.normal(size=P) * 5.0

@@ -471,7 +471,8 @@ def test_rank1_chain_gives_up_loudly_and_the_engine_falls_back_to_launches(api):
 
 # ---- the column statistics out of the read that builds S (second session of round 4) --------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("I,P,M", [(4096, 16384, 16), (1000, 4096, 32), (777, 1000, 5), (130, 514, 48), (64, 256, 1), (333, 65536, 64)])
+@pytest.mark.parametrize("I,P,M", [(4096, 16384, 16), (1000, 4096, 32), (777, 1000, 5), (130, 514, 48), (64, 256, 1), (333, 65536, 64),
+                                   (257, 288, 33), (300, 256, 17), (70, 64, 64), (37, 80, 4)])      # the shapes of test_gpu_kernels.py::test_xcov_mfma
 def test_xcov_stats_kernel_gives_s_and_the_column_statistics_from_one_read(dtype, I, P, M):
     """cmtfpls_xcov_stats_*: S bit for bit the matrix-core pass of cmtfpls_xcov_*, the column sums and sums of squares of tpls.py:61-71
     from the same read; a missing value shows as a NaN in its column's sum."""

@@ -67,6 +67,10 @@ SHAPES = [
     (64, 256, 64, 0),      # ... four response tiles (masked: two passes of two)
     (64, 256, 48, 0),      # three response tiles run as four with the last one masked off
     (65, 64, 16, 1),       # a view one element into its storage: misaligned base, scalar loads
+    # the shapes of tests/test_gpu_workspace_contract.py: 9 row blocks with a short last one at P = 63 (scalar) and 240 (vector, also
+    # misaligned); P = 1320: five column tiles and a partial one, 33 row blocks
+    (517, 63, 1, 0), (517, 63, 17, 0), (517, 240, 1, 0), (517, 240, 17, 0), (517, 240, 1, 1), (517, 240, 17, 1),
+    (2100, 1320, 1, 0), (2100, 1320, 17, 0),
 ]
 
 
