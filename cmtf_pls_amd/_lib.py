@@ -67,6 +67,10 @@ SIGNATURES = {
     "cmtfpls_rank1_tensor_workspace_bytes": (c_size_t, [_P, c_int]),
     "cmtfpls_rank1_tensor_f64": (c_int, [_P, _P, c_int, c_double, _P, c_int, _P, c_int, _P, c_size_t, _P]),
     "cmtfpls_kron_f64": (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    "cmtfpls_rank1_sparse_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cmtfpls_rank1_sparse_form": (c_int, [c_int, c_int]),
+    "cmtfpls_rank1_sparse_f64": (c_int, [_P, c_int, c_int, _P, _P, c_double, c_double, c_double, c_int, _P, _P, c_size_t, _P]),
+    "cmtfpls_soft_normalize_f64": (c_int, [_P, c_int64, c_double, _P, _P]),
     "cmtfpls_xcov_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "cmtfpls_xcov_f32": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
     "cmtfpls_xcov_f64": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P]),

@@ -243,6 +243,22 @@ class HipBackend:
     def normalize(self, v: torch.Tensor) -> None:
         _lib.check(self.lib.cmtfpls_normalize_f64(_ptr(v), v.numel(), None, self._stream()), "normalize")
 
+    # -- sparse loadings: soft-thresholded sweeps on the dense pair (csrc/rank1_sparse.hip) ------------------------
+    def rank1_sparse_form(self, A: int, B: int) -> int:
+        """1: Z staged in LDS once; 2: Z streamed on every half-sweep; 0: outside 2 <= A, B <= 4096, A * B <= 65536."""
+        return int(self.lib.cmtfpls_rank1_sparse_form(int(A), int(B)))
+
+    def rank1_sparsify(self, Z: torch.Tensor, A: int, B: int, wA: torch.Tensor, wB: torch.Tensor, lamA: float, lamB: float,
+                       info: Optional[torch.Tensor] = None, tol_s: float = 1e-10, max_sweeps: int = 200) -> None:
+        """(wA, wB): the dense pair of Z in, the soft-thresholded pair out, every sweep in ONE launch of one workgroup.
+        info (2 doubles, optional): [converged, sweeps run]."""
+        _lib.check(self.lib.cmtfpls_rank1_sparse_f64(_ptr(Z), int(A), int(B), _ptr(wA), _ptr(wB), float(lamA), float(lamB), float(tol_s),
+                                                     int(max_sweeps), _ptr(info), None, 0, self._stream()), "rank1_sparse")
+
+    def soft_normalize(self, v: torch.Tensor, lam: float) -> None:
+        """v <- soft(v, lam) / |soft(v, lam)|_2 in place: the loading of a matrix block with sparsity."""
+        _lib.check(self.lib.cmtfpls_soft_normalize_f64(_ptr(v), v.numel(), float(lam), None, self._stream()), "soft_normalize")
+
     # -- cross-covariance form (exact re-association of the loop, see include/cmtfpls.h) --------
     def xcov(self, X2: torch.Tensor, Y: torch.Tensor, masked: bool, out: Optional[torch.Tensor] = None,
              mixed: bool = False) -> Optional[torch.Tensor]:

@@ -41,7 +41,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_pass,
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, REFIT, _decline_blocks, _decline_coupled_tensor, _device_blocks, _device_pass,
                     _device_passes, _dims, _from_scores, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
                     _route, _tensor_dims, _to_dev, _training_data, _weighted_models, masked_coupled_report, masked_models,
                     masked_models_coupled, masked_models_report)
@@ -122,7 +122,7 @@ def refit(pls, X, Y, idx: np.ndarray, oob: np.ndarray, tol: float, max_iter: int
     coupled = isinstance(X, list)
     R = pls.n_components
     m = type(pls)(R, dtype=pls._dtype, device=pls._device, backend=pls._backend, algorithm=pls._algorithm, graphs=pls._graphs,
-                  matrix_precision="f32" if pls._mixed else "f64", options=pls._options)
+                  matrix_precision="f32" if pls._mixed else "f64", options=pls._options, sparsity=getattr(pls, "sparsity", None))
     m.fit([_take(b, idx) for b in X] if coupled else _take(X, idx), _take(Y, idx), tol=tol, max_iter=max_iter)
     pred = None
     if oob.size:
@@ -245,7 +245,7 @@ def bootstrap(pls, n_resamples: int = 100, resamples=None, random_state=0, level
     masked = None
     ctensor = None                                                # (B1, B2) per block of a ctPLS under tensor_resamples_coupled
     route, detail = _route(pls, X, device_folds)
-    why: Optional[str] = detail if route == OFF else None
+    why: Optional[str] = detail if route in (OFF, REFIT) else None
     if route in (MASKED, MASKED_COUPLED):       # EngineOptions.masked_folds, masked_tensor_folds (8s), masked_folds_coupled (8j)
         masked, mwhy = (masked_models if route == MASKED else masked_models_coupled)(pls, X, Y, counts.astype(np.int32), None, tol,
                                                                                       max_iter, factors=True)

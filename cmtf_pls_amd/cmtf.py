@@ -18,6 +18,7 @@ from .tpls import _EstimatorBase, _project_blocks
 
 class ctPLS(_EstimatorBase):
     """Coupled tensor PLS"""
+    _coupled = True                   # `sparsity`: None, a scalar, or one entry (a scalar or one lambda per non-sample mode) per block
 
     def __getitem__(self, index):
         if index == 0:
@@ -52,7 +53,7 @@ class ctPLS(_EstimatorBase):
 
         st = eng.fit(Xd, Yd, self.n_components, tol, max_iter, coupled=True, verbose=verbose, algorithm=self._algorithm,
                      use_graphs=self._graphs, mixed=self._mixed, on_preprocessed=notice,
-                     owned=[(xd is not X) or not self._copy_X for xd, X in zip(Xd, Xs)])
+                     owned=[(xd is not X) or not self._copy_X for xd, X in zip(Xd, Xs)], sparsity=self.sparsity)
         del Xd
         self._state = st
         self.factor_T = st.T.cpu().numpy()

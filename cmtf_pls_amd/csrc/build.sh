@@ -8,7 +8,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function)
 objs=()
 pids=()
-for src in runtime sweeps small rank1 rank1_tensor xcov mttkrp mixed ceiling solve recon resid contrib selectivity impute synth loo loo_xcov loo_xcov_coupled cv_masked cv_masked_coupled collective project scorecontract kfold press; do
+for src in runtime sweeps small rank1 rank1_sparse rank1_tensor xcov mttkrp mixed ceiling solve recon resid contrib selectivity impute synth loo loo_xcov loo_xcov_coupled cv_masked cv_masked_coupled collective project scorecontract kfold press; do
   "$HIPCC" "${FLAGS[@]}" -c "$HERE/$src.hip" -o "$OUT/$src.o" &
   pids+=($!)
   objs+=("$OUT/$src.o")

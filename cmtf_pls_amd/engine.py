@@ -162,15 +162,24 @@ class NipalsEngine(ProjectionMixin):
 
     def _rank1(self, blk: BlockState, Z: torch.Tensor, wA: torch.Tensor, wB: torch.Tensor,
                info: Optional[torch.Tensor] = None, n_squarings: Optional[int] = None,
-               fac: Optional[torch.Tensor] = None, tol: float = 1e-8) -> None:
+               fac: Optional[torch.Tensor] = None, tol: float = 1e-8, sparse=None) -> None:
         """tpls.py:84-90: Z / norm(Z) for a vector, leading singular pair for a matrix, rank-1 CP
-        (tensorly parafac restated) for a tensor; fills the factored loading (wA, wB)."""
+        (tensorly parafac restated) for a tensor; fills the factored loading (wA, wB).
+        sparse = (lambdas of the block's non-sample modes, sweep info (2 doubles) or None): soft-thresholded loadings --
+        a vector is thresholded before it is normalised, a matrix's dense pair (extracted as always, its info and budget protocol
+        untouched) is sparsified in place."""
         order = len(blk.shape)
         if order == 2:
             wB.copy_(Z)                                   # wA of a matrix block is the constant [1]: set once in FitRun
-            self.be.normalize(wB)
+            if sparse is not None:
+                self.be.soft_normalize(wB, sparse[0][0])
+            else:
+                self.be.normalize(wB)
         elif order == 3:
             self.be.rank1(Z, blk.A, blk.B, wA, wB, info=info, n_squarings=n_squarings)
+            if sparse is not None:
+                self.be.rank1_sparsify(Z, blk.A, blk.B, wA, wB, sparse[0][0], sparse[0][1], sparse[1],
+                                       tol_s=self.opt.sparse_tol, max_sweeps=self.opt.sparse_max_sweeps)
         else:
             if order > MAX_ORDER:
                 raise NotImplementedError(f"X blocks of order > {MAX_ORDER} are not supported")
@@ -191,24 +200,25 @@ class NipalsEngine(ProjectionMixin):
 
     # ------------------------------------------------------------------------------------
     def begin(self, Xs: List[torch.Tensor], Y: torch.Tensor, n_components: int, coupled: bool,
-              algorithm: str = "direct", owned: Optional[List[bool]] = None, allow_raw: bool = True) -> "FitRun":
+              algorithm: str = "direct", owned: Optional[List[bool]] = None, allow_raw: bool = True, sparsity=None) -> "FitRun":
         """Preprocess (centre in place) and allocate the per-fit buffers; see FitRun.  owned[b] = False: block b is the
         CALLER's tensor -- it is cloned before anything writes it, and not at all when the fit only reads it."""
         with self.device_ctx():
-            return FitRun(self, Xs, Y, n_components, coupled, algorithm, owned, allow_raw)
+            return FitRun(self, Xs, Y, n_components, coupled, algorithm, owned, allow_raw, sparsity)
 
     def fit(self, Xs: List[torch.Tensor], Y: torch.Tensor, n_components: int, tol: float, max_iter: int,
             coupled: bool, verbose: int = 0, algorithm: str = "direct", use_graphs: bool = False,
-            mixed: bool = False, on_preprocessed=None, owned: Optional[List[bool]] = None) -> FitState:
+            mixed: bool = False, on_preprocessed=None, owned: Optional[List[bool]] = None, sparsity=None) -> FitState:
         """Xs: device copies (will be centred and deflated in place); Y: (I_local, M) f64 copy.
         algorithm: "direct" = the reference's loop (two X reads per iteration); "xcov" = the same
         iteration re-associated through S = X_(0)^T Y (one X read + one read/write per component)."""
         with self.device_ctx():
-            small = self._fit_small(Xs, Y, n_components, tol, max_iter, coupled, verbose, on_preprocessed)
+            # (a sparse fit takes no form that extracts loadings inside a fused native call: FitRun says so in its report)
+            small = None if sparsity is not None else self._fit_small(Xs, Y, n_components, tol, max_iter, coupled, verbose, on_preprocessed)
             if small is not None:
                 return small
             # (the f32-MFMA S build accumulates in f32 chains: on an uncentred X its error would scale with the means)
-            run = self.begin(Xs, Y, n_components, coupled, algorithm, owned, allow_raw=not mixed)
+            run = self.begin(Xs, Y, n_components, coupled, algorithm, owned, allow_raw=not mixed, sparsity=sparsity)
             if on_preprocessed is not None:                          # the estimators print their missing-value notice
                 on_preprocessed(run.blocks)                          # here, where the reference does (tpls.py:62-63)
             run.tol = tol                                            # also handed to parafac (tpls.py:86)

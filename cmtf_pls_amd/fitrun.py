@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .fitrun_xcov import XcovMixin
+from .sparsity import SWITCHED_OFF, resolve_sparsity, validate_sparse_limits
 from .state import BlockState, FitState, split_trailing, validate_limits
 from .storage import HALF_DTYPES, HALF_ENTRIES, dtype_name, fallback_text, half_route
 
@@ -31,7 +32,7 @@ class FitRun(XcovMixin):
     ``iterate`` directly so that the timed step IS the product's iteration."""
 
     def __init__(self, eng: NipalsEngine, Xs: List[torch.Tensor], Y: torch.Tensor, n_components: int, coupled: bool,
-                 algorithm: str = "direct", owned: Optional[List[bool]] = None, allow_raw: bool = True):
+                 algorithm: str = "direct", owned: Optional[List[bool]] = None, allow_raw: bool = True, sparsity=None):
         be, comm = eng.be, eng.comm
         Xs = list(Xs)
         owned = [True] * len(Xs) if owned is None else list(owned)
@@ -40,6 +41,11 @@ class FitRun(XcovMixin):
         self.algorithm_requested = self.algorithm = algorithm
         self.notes: List[str] = []                                # every declined fast form, in words (report["declined"])
         validate_limits([tuple(X.shape) for X in Xs], n_components)   # before the first sweep touches X
+        # sparse loadings: per block one lambda per non-sample mode, None for the dense model
+        self.sparse = resolve_sparsity(sparsity, [tuple(X.shape) for X in Xs], coupled)
+        validate_sparse_limits([tuple(X.shape) for X in Xs], self.sparse)
+        if self.sparse is not None and not all(hasattr(be, f) for f in ("rank1_sparsify", "soft_normalize")):
+            raise RuntimeError("sparsity needs a backend with rank1_sparsify and soft_normalize")
         self.eng, self.Xs, self.Y, self.R, self.coupled = eng, Xs, Y, n_components, coupled
         R = n_components
         I, M = Y.shape
@@ -168,6 +174,13 @@ class FitRun(XcovMixin):
         self.u_new = be.empty(I)
         self.q = be.empty(M)
         self.n_iter: List[int] = []
+        if self.sparse is not None:
+            # the sweep info of every block's extraction goes to a device buffer of its own; [unconverged, sweeps, most sweeps]
+            # are summed on the device and logged once per component (sparse_log), read back with everything else in result()
+            nbk = len(self.blocks)
+            self.sparse_info = be.zeros(nbk, 2)
+            self.sparse_acc = be.zeros(nbk, 3)
+            self.sparse_log = be.zeros(R, nbk * 3)
         # the pipelined inner loop on S (report["pipeline"]): iterations accepted, enqueued ahead of the host, enqueued for nothing
         # (the loop had converged), host round trips the GPU idled through (no speculation), tails redone with the full budget
         self.pipeline_stats = {"iterations": 0, "ahead": 0, "unused": 0, "waited": 0, "redone": 0}
@@ -185,7 +198,7 @@ class FitRun(XcovMixin):
         # Coupled blocks: normalize(Y^T mean_b t_b) = normalize(sum_b Y^T t_b), so every block's score kernel
         # adds its partial rows and the averaged score itself is only formed once per component.
         self._z_ready = False                     # Zs already hold X x_0 u_0 of the component about to start
-        self._fused = (algorithm == "direct" and M <= 64
+        self._fused = (algorithm == "direct" and M <= 64 and self.sparse is None
                        and all(hasattr(be, f) for f in ("mode0_contract_yq", "score_gram", "q_update")))
         if self._fused:
             self.Gy = be.empty(M, M)
@@ -373,6 +386,21 @@ class FitRun(XcovMixin):
                     print("Comp {}: converged after {} iterations".format(a, it))
                 break
 
+    def _sparse_arg(self, b: int):
+        """What NipalsEngine._rank1 needs for block b of a sparse fit: (its lambdas, its sweep-info buffer); None for a dense fit."""
+        if self.sparse is None:
+            return None
+        return self.sparse[b], (self.sparse_info[b] if len(self.blocks[b].shape) == 3 else None)
+
+    def _sparse_count(self, b: int) -> None:
+        """Add block b's last sweep info to the component's sums, on the device (an iteration's tail that is redone counts twice)."""
+        if self.sparse is None or len(self.blocks[b].shape) != 3:
+            return
+        acc, inf = self.sparse_acc[b], self.sparse_info[b]
+        acc[0:1].add_(1.0 - inf[0:1])
+        acc[1:2].add_(inf[1:2])
+        torch.maximum(acc[2:3], inf[1:2], out=acc[2:3])
+
     def _update_budgets(self, host) -> bool:
         """Adapt the squaring budget of every order-3 block; True if the iteration tail must be redone."""
         retry = False
@@ -523,7 +551,8 @@ class FitRun(XcovMixin):
         def seg_loadings_scores():
             for b, blk in enumerate(self.blocks):
                 self.eng._rank1(blk, self.Zs[b], self.wA[b], self.wB[b], info=self.status[1 + 2 * b: 3 + 2 * b],
-                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol)   # tpls.py:84-90
+                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol, sparse=self._sparse_arg(b))   # tpls.py:84-90
+                self._sparse_count(b)
                 be.score(self.X2[b], blk.A, blk.B, self.wA[b], self.wB[b],
                          blk.rowcnt if blk.has_miss else None, self.Ts[b])        # tpls.py:92-99
             if self.t.data_ptr() != self.Ts.data_ptr():
@@ -595,7 +624,8 @@ class FitRun(XcovMixin):
         def seg_loadings_scores():
             for b, blk in enumerate(self.blocks):
                 self.eng._rank1(blk, self.Zs[b], self.wA[b], self.wB[b], info=self.status[1 + 2 * b: 3 + 2 * b],
-                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol)
+                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol, sparse=self._sparse_arg(b))
+                self._sparse_count(b)
                 if be.score_gram(self.X2[b], blk.A, blk.B, self.wA[b], self.wB[b], blk.rowcnt if blk.has_miss else None,
                                  self.Ts[b], self.Y, self.qpart[b]) is None:
                     # _fused is only chosen for M <= 64, the one shape limit of score_gram: anything else is a bug,
@@ -658,6 +688,9 @@ class FitRun(XcovMixin):
     def finish_component(self, a: int) -> None:
         be, comm = self.eng.be, self.eng.comm
         self.n_iter.append(self._executed)
+        if self.sparse is not None:
+            self.sparse_log[a].copy_(self.sparse_acc.view(-1))     # once per component, device to device
+            self.sparse_acc.zero_()
         ssqs = []
         if self.algorithm == "xcov" and self._s_carry:
             if self._nowrite:
@@ -806,7 +839,12 @@ class FitRun(XcovMixin):
         if nowrite:
             self.eng.comm.allreduce(self.dot_log)
             parts.append(self.dot_log.reshape(-1))
+        if self.sparse is not None:
+            parts.append(self.sparse_log.reshape(-1))                 # (identical on every rank: Z is all-reduced)
         host = torch.cat(parts).cpu().numpy()
+        if self.sparse is not None:
+            self._sparse_host = host[host.size - self.sparse_log.numel():].reshape(self.R, nb, 3)
+            host = host[: host.size - self.sparse_log.numel()]
         R = self.R
         self.coef[...] = host[: R * R].reshape(R, R)
         ssq = host[R * R: R * R + R * (nb + 1)].reshape(R, nb + 1).copy()
@@ -876,7 +914,7 @@ class FitRun(XcovMixin):
             if rep["pipelined"]:
                 rep["pipeline"] = dict(self.pipeline_stats)
             if not rep["pipelined"] and eng.opt.xcov_pipeline:
-                why = ("graph replay requested" if self.use_graphs else "more than 64 responses" if self.M > 64 else
+                why = ("sparse loadings" if self.sparse is not None else "graph replay requested" if self.use_graphs else "more than 64 responses" if self.M > 64 else
                        "a block of order > 3 or a backend without the single-call iteration")
                 self.notes.append("inner loop on S not pipelined: " + why)
             if self.algorithm_requested == "xcov" and not self.raw and eng.opt.xcov_raw and not any_miss and not any("uncentred" in n for n in self.notes):
@@ -898,5 +936,35 @@ class FitRun(XcovMixin):
             }
         rep["rank1_one_launch_chain"] = bool(getattr(eng.be, "rank1_chain_side", 0)) and any(
             len(blk.shape) == 3 and min(blk.A, blk.B) <= int(getattr(eng.be, "rank1_chain_side", 0)) for blk in self.blocks)
+        if self.sparse is not None:
+            rep["sparse"] = self._sparse_report()
         rep["declined"] = list(self.notes)
         return rep
+
+    def _sparse_report(self) -> Dict[str, object]:
+        """fit_report_["sparse"]: the lambdas, the sweep counts of every extraction of the fit, the non-zero entries of every loading
+        column and the form of the kernel (1: Z in LDS, 2: Z streamed; None for a matrix block); the fused forms a sparse fit does
+        not take go to `declined`."""
+        be = self.eng.be
+        done = len(self.n_iter)
+        log = getattr(self, "_sparse_host", None)
+        log = log[:done] if log is not None else np.zeros((0, len(self.blocks), 3))
+        forms = []
+        for blk in self.blocks:
+            if len(blk.shape) != 3:
+                forms.append(None)
+            else:
+                forms.append(int(be.rank1_sparse_form(blk.A, blk.B)) if hasattr(be, "rank1_sparse_form") else None)
+        off = ["small_fit"] + (["fused direct iteration"] if self.algorithm == "direct" else
+                               ["xcov_iterate / xcov_iterate_plan", "xcov_blocks_plan", "pipelined xcov loop"])
+        for name in off:
+            self.notes.append(f"sparse loadings: {name} switched off: {SWITCHED_OFF[name]}")
+        return {
+            "lambda": [tuple(l) for l in self.sparse],
+            "sweeps_max": int(log[:, :, 2].max()) if log.size else 0,
+            "sweeps_total": int(log[:, :, 1].sum()) if log.size else 0,
+            "unconverged": int(log[:, :, 0].sum()) if log.size else 0,
+            "nonzeros": [[[int(v) for v in (L[:, :done] != 0).sum(dim=0).cpu().tolist()] for L in blk.loadings] for blk in self.blocks],
+            "form": forms,
+            "tol": float(self.eng.opt.sparse_tol), "max_sweeps": int(self.eng.opt.sparse_max_sweeps),
+        }

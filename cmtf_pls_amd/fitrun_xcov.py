@@ -47,8 +47,7 @@ class XcovMixin:
         self._executed += 1
 
         blk0 = self.blocks[0]
-        composite = (len(self.blocks) == 1 and len(blk0.shape) == 3 and not blk0.has_miss and self.M <= 64
-                     and self.qn.data_ptr() == self.Tq.data_ptr() and hasattr(be, "xcov_iterate"))
+        composite = self._single_composite()
 
         par = self._parity
         q_cur, q_new = self.qx[par], self.qx[par ^ 1]
@@ -67,7 +66,8 @@ class XcovMixin:
                         be.colscale(self.Zs[b], blk.colcnt, self.n_total)            # missingvals.py:17-19
             for b, blk in enumerate(self.blocks):
                 self.eng._rank1(blk, self.Zs[b], self.wA[b], self.wB[b], info=self.status[1 + 2 * b: 3 + 2 * b],
-                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol)   # tpls.py:84-90
+                                n_squarings=self.sq_budget[b], fac=self.fac[b], tol=self.tol, sparse=self._sparse_arg(b))   # tpls.py:84-90
+                self._sparse_count(b)
                 be.score_s(self.S2[b] if blk.has_miss else self.S[b], blk.A, blk.B, self.wA[b], self.wB[b], self.Tq[b])
             if self.qn.data_ptr() != self.Tq.data_ptr():
                 be.scores_mean(self.Tq, self.qn)                                 # cmtf.py:120 (linear in t)
@@ -91,12 +91,12 @@ class XcovMixin:
 
     def _single_composite(self) -> bool:
         blk0 = self.blocks[0]
-        return (len(self.blocks) == 1 and len(blk0.shape) == 3 and not blk0.has_miss and self.M <= 64
+        return (len(self.blocks) == 1 and len(blk0.shape) == 3 and not blk0.has_miss and self.M <= 64 and self.sparse is None
                 and self.qn.data_ptr() == self.Tq.data_ptr() and hasattr(self.eng.be, "xcov_iterate"))
 
     def _pipeline_ok(self) -> bool:
         be = self.eng.be
-        if self.algorithm != "xcov" or self.use_graphs or not self.eng.opt.xcov_pipeline:
+        if self.algorithm != "xcov" or self.use_graphs or not self.eng.opt.xcov_pipeline or self.sparse is not None:
             return False
         if self.M > 64 or not all(hasattr(be, f) for f in ("status_snapshot", "status_wait")):
             return False

@@ -166,7 +166,7 @@ def refit_fold(pls, X, Y, test: np.ndarray, tol: float, max_iter: int):
         Xtr, Xte = _rows(X, ~test), _rows(X, test)
     Ytr = Y[torch.from_numpy(~test).to(Y.device)] if isinstance(Y, torch.Tensor) else Y[~test]
     m = (ctPLS if coupled else tPLS)(R, dtype=pls._dtype, device=pls._device, backend=pls._backend, algorithm=pls._algorithm,
-                                     graphs=pls._graphs, matrix_precision="f32" if pls._mixed else "f64", options=pls._options)
+                                     graphs=pls._graphs, matrix_precision="f32" if pls._mixed else "f64", options=pls._options, sparsity=getattr(pls, "sparsity", None))
     m.fit(Xtr, Ytr, tol=tol, max_iter=max_iter)
     scores = m.transform(Xte)
     pred = np.stack([_from_scores(scores, m.coef_, m.Y_factors[1].T, m.Y_mean, r) for r in range(1, R + 1)])
@@ -995,6 +995,15 @@ def _masked_declined(entry: str, why: str) -> str:
     return f"the masked form ({entry}) declined: {why}"
 
 
+SPARSE_WHY = ("sparse loadings (sparsity set): the fold kernels extract dense loadings inside their workgroups, "
+              "so every model refits on the regular engine")
+
+
+def is_sparse(pls) -> bool:
+    """A model constructed with `sparsity`: none of the resampling device forms applies to it."""
+    return getattr(pls, "sparsity", None) is not None
+
+
 def _route(pls, X, device_folds: bool, models: bool = True, masked: bool = True, coupled_first: bool = False, coupled_gate=None):
     """Which way a driver takes the fitted data X: (route, detail).  OFF (device_folds is False) and REFIT (no device form for this
     model): every model refits, detail is the report's `why`.  MASKED (kfold.wants_masked) and MASKED_COUPLED
@@ -1004,6 +1013,8 @@ def _route(pls, X, device_folds: bool, models: bool = True, masked: bool = True,
     a ctPLS only when `on` (an EngineOptions switch), else it is REFIT with `why`."""
     if not device_folds:
         return OFF, "device folds switched off"
+    if is_sparse(pls):
+        return REFIT, SPARSE_WHY
     asks = ((MASKED, wants_masked, lambda: masked_forms(pls, X)[int(models)]), (MASKED_COUPLED, wants_masked_coupled, lambda: coupled_form(pls, X)))
     # behaviour: permutation_test asks the coupled masked form first, kfold_run, repeated_kfold and bootstrap the tPLS one (at most one holds)
     for route, wants, entry in (asks[::-1] if coupled_first else asks) if masked else ():
@@ -1054,7 +1065,7 @@ def kfold_run(pls, n_splits: int = 5, folds=None, tol: float = 1e-8, max_iter: i
     R = pls.n_components
     pred = None
     route, detail = _route(pls, X, device_folds, models=False)
-    why = detail if route == OFF else None
+    why = detail if route in (OFF, REFIT) else None
     if route in (MASKED, MASKED_COUPLED):
         pred, rep = (masked_predictions if route == MASKED else masked_predictions_coupled)(pls, X, Y, ids, K, tol, max_iter)
         why = None if pred is not None else _masked_declined(detail, rep)

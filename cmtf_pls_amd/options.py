@@ -119,6 +119,11 @@ class EngineOptions:
     # contrib_rows), impute, get_q2x_heldout and a backend without the entries still upcast; opt-in (report: diagnostics_report_ /
     # contributions_report_ / importance_report_ / r2x_literal_report_ with "half_storage", else "storage_fallback" with the reason)
     half_diagnostics: bool = False
+    # sparse loadings (tPLS / ctPLS `sparsity`): the soft-thresholded sweeps of an order-3 block's extraction stop when
+    # max(|a - wA|_inf, |b - wB|_inf) < sparse_tol, or after sparse_max_sweeps with the last iterate kept (counted in
+    # fit_report_["sparse"]["unconverged"]); a dense model reads neither
+    sparse_tol: float = 1e-10
+    sparse_max_sweeps: int = 200
 
     def but(self, **changes) -> "EngineOptions":
         return replace(self, **changes)

@@ -31,7 +31,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
+from .kfold import (MASKED, MASKED_COUPLED, MAX_FOLDS, OFF, PASSES, REFIT, _decline_blocks, _device_blocks, _device_numerators, _device_pass,
                     _device_passes, _fold_means, _groups, _host, _masked_declined, _masked_run_report, _names, _passes_report,
                     _refit_numerators, _route, _tensor_dims, _to_dev, _training_data, masked_fold_numerators, repeated_fold_ids)
 from .storage import FOLDS_WHY, reports_storage
@@ -102,7 +102,7 @@ def repeated_kfold(pls, n_splits: int = 5, n_repeats: int = 10, folds=None, rand
     G = 0
     masked = None
     route, detail = _route(pls, X, device_folds)
-    why: Optional[str] = detail if route == OFF else None
+    why: Optional[str] = detail if route in (OFF, REFIT) else None
     if route in (MASKED, MASKED_COUPLED):       # EngineOptions.masked_folds, masked_tensor_folds (8s), masked_folds_coupled (8j)
         got = masked_fold_numerators(pls, X, Y, ids, K, None, tol, max_iter, coupled=route == MASKED_COUPLED)
         if got[0] is None:

@@ -9,6 +9,7 @@ Opt-in extras (defaults reproduce the reference): ``dtype`` (storage type of X o
 "xcov" = the same iteration through the cross-covariance S = X_(0)^T Y, one X read per component),
 ``graphs`` (replay each iteration as a HIP graph), ``matrix_precision`` ("f64" | "f32": the opt-in
 f32-MFMA form of the two matrix-core kernels), ``copy_X`` (False: fit a device-resident X in place),
+``sparsity`` (None | lambda | one lambda per non-sample mode: soft-thresholded SPARSE loadings),
 ``device``, ``comm`` (sample-mode sharding: each
 rank passes its own rows), ``options`` (an ``EngineOptions``: which exact form of each step to take where the shape
 allows it), ``n_iter_`` (inner iterations executed per component), ``fit_report_`` / ``projection_report_`` (which
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from .engine import Comm, EngineOptions, NipalsEngine
+from .sparsity import check_sparsity
 from .storage import HALF_DTYPES, _as_torch_dtype, dtype_name, fallback_text, notes_of, read_dtype, reports_storage, to_device_copy, to_device_read
 
 
@@ -54,11 +56,18 @@ def _project_blocks(eng: NipalsEngine, state, Xs, dtypes, mixed: bool) -> torch.
 
 
 class _EstimatorBase(Mapping):
+    _coupled = False
+
     def __init__(self, n_components: int, dtype=None, device=None, comm: Optional[Comm] = None, backend=None,
                  algorithm: str = "direct", graphs: bool = False, matrix_precision: str = "f64", copy_X: bool = True,
-                 options: Optional[EngineOptions] = None):
+                 options: Optional[EngineOptions] = None, sparsity=None):
         super().__init__()
         self.n_components = n_components
+        # sparse loadings: None = the dense model; a scalar lambda in [0, 1) for every non-sample mode; tPLS: one lambda
+        # per non-sample mode; ctPLS: one such entry per block
+        self.sparsity = check_sparsity(sparsity, self._coupled)
+        if self.sparsity is not None and graphs:
+            raise ValueError("graphs=True together with sparsity is not supported: the sparse extraction is not part of a captured iteration")
         self._options = options                   # None: the process default (engine.default_options())
         self._algorithm = algorithm
         self._graphs = graphs                     # replay each iteration's launch sequence as a HIP graph
@@ -215,7 +224,7 @@ class tPLS(_EstimatorBase):
 
         st = eng.fit([Xd], Yd, self.n_components, tol, max_iter, coupled=False, verbose=verbose, algorithm=self._algorithm,
                      use_graphs=self._graphs, mixed=self._mixed, on_preprocessed=notice,
-                     owned=[(Xd is not X) or not self._copy_X])
+                     owned=[(Xd is not X) or not self._copy_X], sparsity=self.sparsity)
         del Xd
         blk = st.blocks[0]
         self._state = st

@@ -26,8 +26,8 @@ import numpy as np
 
 from . import _lib
 from .backend import _int_pairs
-from .kfold import (HALF_LOO_WHY, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
-                    _masked_declined, _size_blocks, _tensor_dims, _training_data, _upload, coupled_form, has_missing, masked_predictions,
+from .kfold import (HALF_LOO_WHY, MASKED_FORM, MASKED_TENSOR_FORM, MAX_BLOCKS, MAX_SIDE, SPARSE_WHY, TENSOR_LDS_CAP, TENSOR_RANK1, _dims, _host,
+                    _masked_declined, _size_blocks, _tensor_dims, _training_data, _upload, coupled_form, has_missing, is_sparse, masked_predictions,
                     masked_predictions_coupled, refit_predictions, wants_masked_coupled, wants_masked_tensor)
 from .storage import FOLDS_WHY, reports_storage
 from .tpls import tPLS
@@ -156,6 +156,8 @@ def _loo_result(pls, out, entry: str, form: str, Y, blocks=None, rank1: bool = F
 
 def _loo_device_coupled(pls, tol: float, max_iter: int):
     """_loo_device for a fitted ctPLS: (Y_pred, None) from a device form (q2y_report_ set), or (None, why)."""
+    if is_sparse(pls):
+        return None, SPARSE_WHY
     Xs, Y = _training_data(pls)
     I = Y.shape[0]
     # EngineOptions.masked_folds_coupled: cmtfpls_cv_masked_coupled_f64; masked_tensor_folds_coupled with a block of order 4:
@@ -205,6 +207,8 @@ def _loo_device(pls_tensor, tol: float, max_iter: int):
     """(Y_pred, None) from a device form, or (None, why): why is None when no form was tried (get_q2y then names the limits)."""
     import torch
 
+    if is_sparse(pls_tensor):
+        return None, SPARSE_WHY
     X = pls_tensor.original_X
     Y = pls_tensor.original_Y
     eng = pls_tensor._get_engine()
@@ -257,7 +261,7 @@ def get_q2y(pls_tensor, device_folds: bool = True):
         # behaviour: this loop is the reference's, and its tPLS is built without the fitted model's graphs, matrix_precision and
         # options, unlike kfold.refit_fold
         refit = tPLS(pls_tensor.n_components, dtype=pls_tensor._dtype, device=pls_tensor._device,
-                     backend=pls_tensor._backend, algorithm=pls_tensor._algorithm)
+                     backend=pls_tensor._backend, algorithm=pls_tensor._algorithm, sparsity=getattr(pls_tensor, "sparsity", None))
         Y_pred = np.zeros(Y.shape)
         keep = np.ones(n, dtype=bool)
         for i in range(n):                                   # LeaveOneOut().split(X, Y)     validate.py:24,27

@@ -131,6 +131,27 @@ size_t cmtfpls_rank1_tensor_workspace_bytes(const int* dims, int n);
 int cmtfpls_rank1_tensor_f64(const double* Z, const int* dims, int n, double tol, double* factors, int ld,
                              double* info, int n_squarings, void* ws, size_t ws_bytes, void* stream);
 int cmtfpls_kron_f64(const double* a, int na, const double* b, int nb, double* out, void* stream);
+/* rank1_sparse: SPARSE loadings at the call site of rank1 (tpls.py:84-90, cmtf.py:98-102; the reference itself only has dense
+ * ones).  soft(v, lam): theta = lam * max_j |v_j|, out_j = sign(v_j) * max(|v_j| - theta, 0), 0 <= lam < 1 -- at least one entry
+ * survives, thresholded entries are exactly 0.0.  In: (wA, wB) = the dense pair of the A x B matrix Z as cmtfpls_rank1_f64 left
+ * it; out: the sparse pair after sweeps of
+ *   a = soft(Z wB, lamA); a /= |a|_2;   b = soft(Z^T a, lamB); b /= |b|_2;   d = max(|a - wA|_inf, |b - wB|_inf); (wA, wB) = (a, b)
+ * stopped when d < tol_s (tol_s = 0: exactly max_sweeps sweeps) or after max_sweeps, the last iterate kept.  info (nullable, 2
+ * doubles) = [converged ? 1 : 0, sweeps run].  A zero a or b gives NaN loadings, as normalising a zero vector does.
+ * ONE launch of ONE workgroup runs every sweep (no wait on any other workgroup); cmtfpls_rank1_sparse_form(A, B), host only: 1 = Z
+ * staged in LDS once (Z, the vectors and the partial sums within 150 KB; 128 x 128 is inside), 2 = Z read from L2 / global memory
+ * on every half-sweep, 0 = outside the limits.  16-byte loads of Z when B is even and Z 16-byte aligned.  Every sum in an order
+ * fixed by the thread index, no atomics: a second call on the same input returns the same bits.
+ * Checked in this order, before any pointer is read: CMTFPLS_EUNSUPPORTED unless 2 <= A, B <= 4096 and A * B <= 65536;
+ * CMTFPLS_EINVAL for a lambda outside [0, 1), max_sweeps < 1 or tol_s < 0.  The workspace size is 0 (everything lives in LDS); ws
+ * may be NULL.
+ * soft_normalize: v <- soft(v, lam) / |soft(v, lam)|_2 in place, the vector case `Z / norm(Z)` (tpls.py:84, cmtf.py:98) with
+ * sparsity; nrm (nullable) receives the norm.  1 <= n <= 2^24 (CMTFPLS_EUNSUPPORTED beyond), lam as above. */
+size_t cmtfpls_rank1_sparse_workspace_bytes(int A, int B);
+int cmtfpls_rank1_sparse_form(int A, int B);
+int cmtfpls_rank1_sparse_f64(const double* Z, int A, int B, double* wA, double* wB, double lamA, double lamB, double tol_s,
+                             int max_sweeps, double* info, void* ws, size_t ws_bytes, void* stream);
+int cmtfpls_soft_normalize_f64(double* v, int64_t n, double lam, double* nrm, void* stream);
 
 /* ---- cross-covariance contraction (not a reference call site: an exact re-association of the loop)
  * xcov: S (M x P, row-major f64) = Y^T X_(0), i.e. S[m, c] = sum_i Y[i*ldy + m] * X[i, c], on the
